@@ -2,16 +2,26 @@
 """bench.py - edges/sec of one full SymGatedGCNModel forward (encoders + 8 layers + scorer).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|10m|parity64|c4shard|c4|c5|c5shard|c5quarter|c4quarter] [--kind banded|uniform]
-                    [--mode infer|train]
+                    [--mode infer|train] [--full] [--dump-outputs DIR]
 
 One "step" = one `model(graph, x, e)` on a synthetic assembly graph already resident in HBM (graph views prebuilt, as a
 caller that scores the same graph repeatedly would have them; the cold numbers - view build, first call - are reported
-separately).  N = 1 runs BASELINE.json configs[1] (c2: N=1e5, E=1e6, H=128) by default and adds two sub-records to the
-line: `target_10m` (the north_star's 10M-edge graph, GPU forward) and `train` (configs[2]'s shape: fwd + BCE + bwd + Adam,
-fp32, replayed from a hipGraph).  N > 1 (launched by torch.distributed.run, one rank per GPU over RCCL) runs ONE graph
-partitioned by destination-node range (gnnome_amd/dist.py): strong scaling; the default graph there is the 10M-edge one
-(at 1M edges a rank has < 1 ms of kernels per forward and the launch / collective host work is what gets timed), and
-rank 0 first times the same graph on its GPU alone (`scaling_reference`).  Prints ONE JSON line on rank 0.
+separately).  N = 1 runs BASELINE.json configs[1] (c2: N=1e5, E=1e6, H=128) by default.  N > 1 (launched by
+torch.distributed.run, one rank per GPU over RCCL) runs ONE graph partitioned by destination-node range (gnnome_amd/dist.py):
+strong scaling; the default graph there is the 10M-edge one (at 1M edges a rank has < 1 ms of kernels per forward and the
+launch / collective host work is what gets timed).  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, print the line.  --full adds everything else:
+the CPU baseline (child process), HIP events on the two big kernels inside the timed region (`roofline`), an untimed per-kernel
+pass (`kernels`, `reference_order`), the host cost of a forward with an empty queue, a fresh graph in a warm process (`cold`),
+the committed PMC / MFMA-busy figures of this build, and the sub-records: at N = 1 `target_10m` (the north_star's 10M-edge graph),
+`h256_shard` and `train` (configs[2]'s shape: fwd + BCE + bwd + Adam, fp32, replayed from a hipGraph); at N > 1 the same graph
+on rank 0's GPU alone (`scaling_reference`) and the halo exchange timed alone (`exchange`, `prediction`).  --no-cpu-baseline,
+--no-extras and --no-kernel-timers switch parts of --full off again.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32): `logits` for a forward;
+`loss` and `parameters` (every parameter after the step, flattened in named_parameters() order) for a training step.  The inputs
+are seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import hashlib
@@ -43,6 +53,7 @@ WORKLOADS = {
     # reference-order fp32 VALU kernels, layers 1-7 through the bf16x6 matrix-core kernels
     "ecoli": (30_000, 300_000, 64),
 }
+DUMP_BYTES_MAX = 60 << 20   # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
 HBM_PEAK = 8.0e12        # B/s, MI355X_MICROARCH.md
 MFMA_F32_PEAK = 157.3e12  # flop/s, v_mfma_f32_32x32x2_f32
 MFMA_BF16_PEAK = 2.5e15   # flop/s dense bf16 (no sparsity), v_mfma_f32_32x32x16_bf16
@@ -68,6 +79,26 @@ def workload_state_dict(workload, hidden):
         return torch.load(os.path.join(ROOT, "tests", "golden", "weights.pt"), map_location="cpu")
     from gnnome_amd.synth import random_state_dict
     return random_state_dict(hidden, seed=1)
+
+
+def host_outputs(**tensors):
+    """Copies of what a step returned, taken right after the timed region (a replayed graph or a placed buffer is overwritten by the next step)."""
+    return {name: t.detach().float().cpu() for name, t in tensors.items()}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, float32.  An array whose share of DUMP_BYTES_MAX is smaller than itself is written as a fixed
+    sample of its rows (numpy seed 0, kept in ascending order), the same rows in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.numpy().astype(np.float32, copy=False)
+        if a.nbytes > share and a.ndim > 0:
+            row_bytes = a.nbytes // a.shape[0]
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max(1, share // row_bytes), replace=False))
+            a = a[keep]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def so_sha16():
@@ -383,10 +414,10 @@ def _memory_record(dev, edges_local, hidden):
             "local_edges": edges_local, "hidden": hidden}
 
 
-def _train_record(gnnome_amd, ops, g, n, e, hidden, dev, steps, warmup, symmetry, dropout, storage="fp32", recompute=False):
+def _train_record(gnnome_amd, ops, g, n, e, hidden, dev, steps, warmup, symmetry, dropout, storage="fp32", recompute=False, outputs=None):
     """configs[2]'s shape: fwd + loss + bwd + Adam on the whole graph, fp32, the step replayed from a hipGraph (a training
     loop over one graph repeats the same launch sequence; ~450 library launches + a few hundred small torch ops cost
-    30-40 ms of host time per step when issued eagerly)."""
+    30-40 ms of host time per step when issued eagerly).  outputs: a dict that receives the last step's loss and parameters."""
     from gnnome_amd.loss import bce_loss, symmetry_loss
     model = gnnome_amd.SymGatedGCNModel(2, 2, hidden, 16, 8, 64, "batch", dropout=dropout).train()
     from gnnome_amd.synth import random_state_dict
@@ -440,6 +471,8 @@ def _train_record(gnnome_amd, ops, g, n, e, hidden, dev, steps, warmup, symmetry
         return static_loss
 
     loss, elapsed, _ = _time_steps(step, steps, warmup, torch.cuda.synchronize)
+    if outputs is not None:
+        outputs.update(host_outputs(loss=loss, parameters=torch.cat([p.detach().reshape(-1) for p in model.parameters()])))
     assert torch.isfinite(loss).all()
     ms = elapsed / steps * 1e3
     passes = 2 if symmetry else 1
@@ -453,7 +486,7 @@ def _train_record(gnnome_amd, ops, g, n, e, hidden, dev, steps, warmup, symmetry
             "hbm_roofline_frac_3xBfwd": passes * 3 * b_fwd / (ms * 1e-3) / HBM_PEAK, "mfma_f32_frac_3xFfwd": passes * 3 * f_fwd / (ms * 1e-3) / MFMA_F32_PEAK}
 
 
-def _partitioned_train_record(gnnome_amd, gdist, ops, g, n, e, hidden, dev, rank, world, plan, runner, model, args, gloo_transport):
+def _partitioned_train_record(gnnome_amd, gdist, ops, g, n, e, hidden, dev, rank, world, plan, runner, model, args, gloo_transport, outputs=None):
     """BASELINE configs[4]'s step on a destination-range partition (SURVEY.md 8e "Training additions"; train.py:138-145,
     328-330): every rank runs the train-mode forward over its rows (halo exchange per layer, BatchNorm statistics merged over
     ranks), computes BCEWithLogits(pos_weight) on the assembled logits, runs the backward (halo gradients returned to their
@@ -477,6 +510,8 @@ def _partitioned_train_record(gnnome_amd, gdist, ops, g, n, e, hidden, dev, rank
         torch.cuda.synchronize()
 
     loss, elapsed, t_host = _time_steps(step, args.steps, args.warmup, barrier)
+    if outputs is not None:
+        outputs.update(host_outputs(loss=loss, parameters=torch.cat([p.detach().reshape(-1) for p in model.parameters()])))
     t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if gloo_transport else dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
@@ -558,10 +593,12 @@ def main():
                                                                   "-8 of ~34 KB per edge at hidden 256)")
     ap.add_argument("--symmetry", action="store_true", help="train: the reference's default step (symmetry loss: two forwards, dropout 0.2)")
     ap.add_argument("--hipgraph", action="store_true", help="replay the forward from a captured hipGraph (infer; at --gpus > 1: one graph per stretch between two collectives)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="SURVEY.md 8d's protocol: E = 1M median of 3 + one E = 10M run (minutes)")
-    ap.add_argument("--no-kernel-timers", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the target_10m / train sub-records (N = 1) and the scaling reference (N > 1)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline (CPU baseline, kernel events and tables, sub-records, exchange probe); see the module docstring")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="with --full: SURVEY.md 8d's protocol: E = 1M median of 3 + one E = 10M run (minutes)")
+    ap.add_argument("--no-kernel-timers", action="store_true", help="with --full: no HIP events in the timed region and no per-kernel pass")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the target_10m / train sub-records (N = 1) and the scaling reference (N > 1)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--tuning", default="", help="A/B measurement only: gnnome_set_tuning pairs 'key=value,key=value' (include/gnnome_hip.h); recorded in the line")
     ap.add_argument("--plan", default="slices", choices=["slices", "global"],
@@ -570,6 +607,10 @@ def main():
                     help="plumbing check of the N>1 path on a 1-GPU box: all ranks share cuda:0, collectives go over gloo "
                          "(host-staged); the numbers it prints are NOT a multi-GPU measurement")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_extras = args.no_kernel_timers = True
     if args.workload is None:
         if args.gpus > 1 and args.mode == "train":
             args.workload, need_recompute = train_workload_for(args.gpus, args.kind, args.one_gpu_gloo)
@@ -672,23 +713,25 @@ def main():
         t2 = time.perf_counter()
         # a FRESH graph in a warm process (the reference builds new graph objects per call when it masks, train.py:96,336):
         # the edge list reversed, so no cache can apply
-        for _ in range(2):   # (the first of the two pays the one-time load of the deferred range check's kernel)
+        fresh_ms = None
+        for _ in range(2 if args.full else 0):   # (the first of the two pays the one-time load of the deferred range check's kernel)
             t3 = time.perf_counter()
             views2 = ops.GraphViews(dst, src, n, validate="lazy")
             ops.degree_features(views2)
             torch.cuda.synchronize()
-            t4 = time.perf_counter()
+            fresh_ms = (time.perf_counter() - t3) * 1e3
             del views2
         cold = {"node_order_ms": order_ms, "graph_views_and_features_ms": (t1 - t0) * 1e3, "first_call_ms": (t2 - t1) * 1e3, "weight_preparation_ms": (t1b - t1) * 1e3,
                 "first_forward_after_preparation_ms": (t2 - t1b) * 1e3,
-                "fresh_graph_warm_process_ms": (t4 - t3) * 1e3,
+                "fresh_graph_warm_process_ms": fresh_ms,
                 "note": "first call = weight preparation (weight_preparation_ms) + allocator growth + kernel code load + one forward "
                         "(first_forward_after_preparation_ms); the first view build pays the process's "
                         "one-time HIP / rocPRIM initialisation, a fresh graph afterwards costs fresh_graph_warm_process_ms"}
 
         if args.mode == "train":
+            outputs = {}
             rec = _train_record(gnnome_amd, ops, g, n, e, hidden, dev, args.steps, args.warmup, args.symmetry, 0.2 if args.symmetry else None,
-                                storage=args.storage, recompute=args.recompute_gate)
+                                storage=args.storage, recompute=args.recompute_gate, outputs=outputs if args.dump_outputs else None)
             rec.update({"n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
                         "data": "synthetic", "config": {"workload": f"{args.workload}: {args.kind} synthetic assembly graph N={n} E={e}, SymGatedGCNModel "
                                                                     f"hidden={hidden} L=8 hs=64, {rec.pop('step')}, random-init weights seed 1",
@@ -697,6 +740,8 @@ def main():
                 rec["cpu_baseline"], err = _run_cpu_child(args, 200)
                 if rec["cpu_baseline"]:
                     rec["gpu_over_cpu"] = rec["value"] / rec["cpu_baseline"]["value"]
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, outputs)
             print(json.dumps(rec))
             return
         if args.hipgraph:
@@ -749,9 +794,13 @@ def main():
         torch.cuda.synchronize()
         cold = {"partition_plan_views_features_ms": (time.perf_counter() - t0) * 1e3, "plan": args.plan}
         if args.mode == "train":
-            rec = _partitioned_train_record(gnnome_amd, gdist, ops, g, n, e, hidden, dev, rank, world, plan, runner, model, args, gloo_transport)
+            outputs = {}
+            rec = _partitioned_train_record(gnnome_amd, gdist, ops, g, n, e, hidden, dev, rank, world, plan, runner, model, args, gloo_transport,
+                                            outputs if args.dump_outputs else None)
             if rank == 0:
                 rec["cold"] = cold
+                if args.dump_outputs:
+                    dump_outputs(args.dump_outputs, outputs)
                 print(json.dumps(rec))
             dist.destroy_process_group()
             return
@@ -769,26 +818,27 @@ def main():
             torch.cuda.synchronize()
         parallelism = f"dst-range x{world}" + (" (hipGraph segments between the collectives)" if args.hipgraph else "") + (" (ALL RANKS ON ONE GPU over gloo: plumbing check, not a measurement)" if args.one_gpu_gloo
                                                else " (RCCL FAILED: host-staged gloo transport)" if gloo_transport else " over RCCL")
-        # what the halo exchange moves: rows this rank sends / receives per layer, and the time of one exchange alone
-        sent, recv = int(sum(plan.send_counts)), int(sum(plan.recv_counts))
-        xchg = gdist.HaloExchange(plan, ops)
-        h_probe = torch.zeros((plan.n_local, hidden), dtype=torch.float32, device=dev)
-        for _ in range(3):
-            xchg.start(h_probe)
-            xchg.finish()
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(10):
-            xchg.start(h_probe)
-            xchg.finish()
-        barrier()
-        extras["exchange"] = {"transport": "gloo (host-staged)" if gloo_transport else "rccl", "rccl_ranks": 0 if gloo_transport else world,
-                              "rank0_rows_sent_per_layer": sent, "rank0_rows_received_per_layer": recv,
-                              "rank0_bytes_sent_per_layer": sent * hidden * 4, "exchanges_per_forward": 8, "ms_per_exchange_alone": (time.perf_counter() - t0) * 100,
-                              "rank0_owned_nodes": plan.n_own, "rank0_halo_nodes": plan.n_local - plan.n_own,
-                              "rank0_local_edges": plan.views.num_edges, "rank0_scored_edges": plan.n_score,
-                              "logits": f"all_gather of {plan.score_pad * 4} B per rank + one index_select"}
-        del h_probe
+        if args.full:
+            # what the halo exchange moves: rows this rank sends / receives per layer, and the time of one exchange alone
+            sent, recv = int(sum(plan.send_counts)), int(sum(plan.recv_counts))
+            xchg = gdist.HaloExchange(plan, ops)
+            h_probe = torch.zeros((plan.n_local, hidden), dtype=torch.float32, device=dev)
+            for _ in range(3):
+                xchg.start(h_probe)
+                xchg.finish()
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(10):
+                xchg.start(h_probe)
+                xchg.finish()
+            barrier()
+            extras["exchange"] = {"transport": "gloo (host-staged)" if gloo_transport else "rccl", "rccl_ranks": 0 if gloo_transport else world,
+                                  "rank0_rows_sent_per_layer": sent, "rank0_rows_received_per_layer": recv,
+                                  "rank0_bytes_sent_per_layer": sent * hidden * 4, "exchanges_per_forward": 8, "ms_per_exchange_alone": (time.perf_counter() - t0) * 100,
+                                  "rank0_owned_nodes": plan.n_own, "rank0_halo_nodes": plan.n_local - plan.n_own,
+                                  "rank0_local_edges": plan.views.num_edges, "rank0_scored_edges": plan.n_score,
+                                  "logits": f"all_gather of {plan.score_pad * 4} B per rank + one index_select"}
+            del h_probe
 
     # HIP events in the timed region go around ONE launch of the dominant kernel per step (the 8 layers launch
     # the same shape): a pair around every launch of every kernel cost ~1.6 ms per step here (56 events, ~28 us
@@ -825,31 +875,35 @@ def main():
     if fwd_timer:
         fwd_timer.close()
         kt = fwd_timer
-    # what a forward costs the HOST when the launch queue is empty (in the timed region above the host runs ahead until the queue is full and
-    # then waits for the GPU: host_enqueue_ms_per_step is the GPU's time there, not Python's)
-    torch.cuda.synchronize()
-    t0h = time.perf_counter()
-    for _ in range(10):
-        step()
-    host_unblocked_ms = (time.perf_counter() - t0h) / 10 * 1e3
-    barrier()
+    outputs = host_outputs(logits=out) if args.dump_outputs and rank == 0 else None
+    host_unblocked_ms = None
+    if args.full:
+        # what a forward costs the HOST when the launch queue is empty (in the timed region above the host runs ahead until the queue is full and
+        # then waits for the GPU: host_enqueue_ms_per_step is the GPU's time there, not Python's)
+        torch.cuda.synchronize()
+        t0h = time.perf_counter()
+        for _ in range(10):
+            step()
+        host_unblocked_ms = (time.perf_counter() - t0h) / 10 * 1e3
+        barrier()
     # untimed diagnostic pass: every kernel family instrumented, for the per-kernel table only
     others = [] if args.no_kernel_timers or world > 1 else ["node_aggregate", "linear", "edge_score", "encode", "linear_ref", "edge_gate_ref",
                                                             "edge_gate_encode"] + (["edge_gate"] if args.workload == "ecoli" else [])
     chunks_timed = engine.PIPELINE_CHUNKS if (world == 1 and n >= engine.PIPELINE_MIN_NODES) else 1
-    with KernelTimer(ops, others) as kd:
-        kd.on = True
-        was_one_call = engine.ONE_CALL_FORWARD
-        if others:
-            engine.PIPELINE_CHUNKS = 1   # the per-kernel table wants every kernel alone on the chip, one launch per layer
-            engine.ONE_CALL_FORWARD = False   # ... and launched call by call, so that each can carry its own pair of events
-        try:
-            for _ in range(min(args.steps, 5)):
-                step()
-        finally:
-            engine.PIPELINE_CHUNKS = chunks_timed if chunks_timed > 1 else engine.PIPELINE_CHUNKS
-            engine.ONE_CALL_FORWARD = was_one_call
-        barrier()
+    if args.full:
+        with KernelTimer(ops, others) as kd:
+            kd.on = True
+            was_one_call = engine.ONE_CALL_FORWARD
+            if others:
+                engine.PIPELINE_CHUNKS = 1   # the per-kernel table wants every kernel alone on the chip, one launch per layer
+                engine.ONE_CALL_FORWARD = False   # ... and launched call by call, so that each can carry its own pair of events
+            try:
+                for _ in range(min(args.steps, 5)):
+                    step()
+            finally:
+                engine.PIPELINE_CHUNKS = chunks_timed if chunks_timed > 1 else engine.PIPELINE_CHUNKS
+                engine.ONE_CALL_FORWARD = was_one_call
+            barrier()
     timed = dominant
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if gloo_transport else dev)
@@ -991,7 +1045,7 @@ def main():
                  "frac": (e * hidden * 4.0 + 3 * e * 4.0) / (sc_ms * 1e-3) / HBM_PEAK},
                 {"kernel": "k_encode (node + edge)", "bound": "hbm", "avg_launch_ms": en_ms, "launches": en_n},
             ]
-        if world == 1 and args.workload in ("c2", "c4shard"):
+        if args.full and world == 1 and args.workload in ("c2", "c4shard"):
             mu = _mfma_util(f"{args.workload}_infer")
             if mu:
                 res["mfma_util"] = mu
@@ -1033,6 +1087,8 @@ def main():
                         res["target_10m"]["north_star_target"] = ">= 10x the CPU path's edges/s on the 10M-edge graph at 1 GPU"
                 else:
                     res["cpu_baseline_error"] = err_cpu[-300:]
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(res))
 
     if world > 1:

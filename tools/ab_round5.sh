@@ -10,7 +10,7 @@ for spec in "c2|" "c4shard|--workload c4shard" "10m|--workload 10m" "parity64|--
   name=${spec%%|*}; args=${spec#*|}
   for rnd in $(seq 1 $R); do
     a=$(cd build/ab_r05 && timeout 600 python bench.py --no-cpu-baseline --no-extras $args 2>/dev/null | ms)
-    b=$(timeout 600 python bench.py --no-cpu-baseline --no-extras $args 2>/dev/null | ms)
+    b=$(timeout 600 python bench.py --full --no-cpu-baseline --no-extras $args 2>/dev/null | ms)
     echo "$name round $rnd: round-5 tree $a ms   this tree $b ms"
   done
 done

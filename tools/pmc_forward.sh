@@ -3,7 +3,7 @@
 OUT=$1; W=${2:-c2}; M=${3:-infer}; R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp; export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 150 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $R/$OUT/$C -o p -- python $R/bench.py --workload $W --mode $M --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timers --no-extras > /dev/null 2>&1 || echo "$C pass failed"
+  timeout 150 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $R/$OUT/$C -o p -- python $R/bench.py --full --workload $W --mode $M --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timers --no-extras > /dev/null 2>&1 || echo "$C pass failed"
 done
 python - "$R/$OUT" <<'PY'
 import csv, sys, collections

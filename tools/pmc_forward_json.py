@@ -27,7 +27,7 @@ def main():
                for name, (f, w, n) in sorted(tot.items(), key=lambda kv: -kv[1][0]) if n and (f + w) / n > 1024}
     res = {"so_sha16": hashlib.sha256(open(so, "rb").read()).hexdigest()[:16], "workload": workload,
            "collected_with": "tools/pmc_forward.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE, one counter per pass, over "
-                             f"`bench.py --workload {workload} --steps 2 --warmup 1`",
+                             f"`bench.py --full --workload {workload} --steps 2 --warmup 1`",
            "corrections": "FETCH_SIZE doubled (gfx950 tallies 128-byte reads at 64 B - MI355X_MICROARCH.md, HBM); WRITE_SIZE as reported",
            "kernels": kernels}
     with open(out, "w") as f:

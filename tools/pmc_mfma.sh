@@ -6,7 +6,7 @@ cd /tmp; export TMPDIR=/tmp
 run() {   # name, bench arguments
   local name=$1; shift
   timeout 240 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $R/$OUT/$name -o p -- \
-      python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timers --no-extras "$@" > /dev/null 2> $R/$OUT/$name.err || echo "$name: pass failed"
+      python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timers --no-extras "$@" > /dev/null 2> $R/$OUT/$name.err || echo "$name: pass failed"
 }
 mkdir -p $R/$OUT
 run c2_infer

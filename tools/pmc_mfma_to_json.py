@@ -29,7 +29,7 @@ def main():
     so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gnnome_amd", "lib", "libgnnome_hip.so")
     res = {"so_sha16": hashlib.sha256(open(so, "rb").read()).hexdigest()[:16],
            "collected_with": "tools/pmc_mfma.sh: rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE, one pass per workload "
-                             "(python bench.py --steps 3 --warmup 1)",
+                             "(python bench.py --full --steps 3 --warmup 1)",
            "mfma_util": "SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs * 1024 SIMDs), both averaged over the kernel's launches", "workloads": {}}
     for d in sorted(glob.glob(os.path.join(src, "*", ""))):
         files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)

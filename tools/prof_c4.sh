@@ -1,3 +1,3 @@
-cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; mkdir -p gpurun_out/pc4
-timeout 400 rocprofv3 --kernel-trace --stats -d gpurun_out/pc4 -o r01 -- python bench.py --workload c4shard --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-timers > gpurun_out/pc4/bench.json 2> gpurun_out/pc4/err.log
-DB=$(find gpurun_out/pc4 -name "*.db" | head -1); python tools/rocpd_summary.py "$DB" | head -14; find gpurun_out/pc4 -name "*.db" -delete
+cd "$(dirname "$0")/.." || exit 1; export TMPDIR=/tmp; O=${1:?usage: tools/prof_c4.sh <outdir>  (relative to the repository root)}; mkdir -p $O
+timeout 400 rocprofv3 --kernel-trace --stats -d $O -o r01 -- python bench.py --full --workload c4shard --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-timers > $O/bench.json 2> $O/err.log
+DB=$(find $O -name "*.db" | head -1); python tools/rocpd_summary.py "$DB" | head -14; find $O -name "*.db" -delete

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/trace; rm -rf $O; mkdir -p $O
-timeout 300 rocprofv3 --hip-trace --memory-copy-trace --kernel-trace --output-format csv -d $O/t -o r -- python bench.py --workload ecoli --steps 20 --warmup 3 --no-cpu-baseline --no-kernel-timers --no-extras > /dev/null 2> $O/err.log
+timeout 300 rocprofv3 --hip-trace --memory-copy-trace --kernel-trace --output-format csv -d $O/t -o r -- python bench.py --full --workload ecoli --steps 20 --warmup 3 --no-cpu-baseline --no-kernel-timers --no-extras > /dev/null 2> $O/err.log
 F=$(find $O/t -name "*hip_api_trace.csv" | head -1)
 python - "$F" <<'PY'
 import csv, sys, collections
