@@ -104,6 +104,9 @@ SIGNATURES = {
     "gnnome_mark_walk_visited": [_p, _p, _p, _l, _p, _p],
     "gnnome_overlap_workspace_bytes": [ctypes.POINTER(_sz)],
     "gnnome_overlap_edit_distance": [_p, _p, _l, _p, _i, _p, _p, _p, _l, _p, _p, _p, _sz, _p],
+    "gnnome_contig_pieces_workspace_bytes": [_l, _l, ctypes.POINTER(_sz)],
+    "gnnome_contig_pieces": [_p, _l, _p, _l, _p, _p, _p, _p, _l, _p, _l, _p, _p, _sz, _p],
+    "gnnome_contig_spell": [_p, _l, _p, _l, _p, _p, _p, _l, _p, _i, _p, _l, _p],
     "gnnome_adjacency_support": [_p, _p, _p, _l, _l, _p, _p],
     "gnnome_bfs_levels": [_p, _p, _l, _p, _p, _p, _p, _p, _p, _p],
     "gnnome_hem_propose": [_p, _p, _p, _p, _p, _l, _i, _p, _p],
@@ -112,7 +115,7 @@ SIGNATURES = {
     "gnnome_edge_loss_f32": [_p, _p, _p, _l, _p, ctypes.c_float, ctypes.c_float, _p, _p, _p, _p, _p, _sz, _p],
 }
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 # the parameter blocks of gnnome_model_forward_f32 (include/gnnome_hip.h), field for field

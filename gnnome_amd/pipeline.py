@@ -1,12 +1,17 @@
 """From a GFA to contig walks on one MI355X - the sequence of inference.py:411-467 with every step on this package's side
-of the boundary (GFA reader, feature preparation, the SymGatedGCN scorer, greedy decode).  What inference.py does after it
-(walks -> FASTA with the read sequences, evaluation with minigraph / paftools) is outside SURVEY.md 8's rows.
+of the boundary (GFA reader, feature preparation, the SymGatedGCN scorer, greedy decode), and assemble_to_fasta goes on to
+inference.py:475-489 (walks -> contigs -> FASTA, gnnome_amd/contigs.py) with N50 / NG50.  The evaluation with minigraph /
+paftools (evaluate.py:139-197) is not here.
 
     model = gnnome_amd.SymGatedGCNModel(2, 2, 64, 16, 8, 64, 'batch'); model.load_state_dict(torch.load('weights/weights.pt')); model.eval()
     walks, scores, g = assemble('asm.gfa', model, len_threshold=10, nb_paths=100)
+    walks, contigs, stats = assemble_to_fasta('asm.gfa', model, '0_assembly.fasta', len_threshold=10, reads='reads.fastq.gz')
 """
+import os
+
 import torch
 
+from . import contigs as contigs_mod
 from . import decode, features, gfa
 from .graph import views_for
 
@@ -35,3 +40,50 @@ def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto"
     prefix = g["prefix_length"].masked_fill(g["prefix_length"] < 0, 0)      # inference.py:461
     dg = decode.DecodeGraph(g["src"], g["dst"], g["num_nodes"], prefix, g["read_length"], device=device).set_scores(scores)
     return decode.decode_contigs(dg, len_threshold, nb_paths=nb_paths, sampler=sampler), scores, g
+
+
+def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, nb_paths=100, similarity="auto", device=None, scores=None,
+                      sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None):
+    """GFA -> scores -> greedy walks -> contigs spelled on the device -> FASTA at out_path (inference.py:411-489).
+    -> (walks, contigs, stats); stats = quick_evaluation's figures as a dict (ref_length from the caller: NG50 and the
+    reconstructed fraction are -1 without it).  Sequences: the GFA's S lines if it carries them, else `reads` (a FASTA / FASTQ
+    path, plain or .gz, or a ReadStore); with neither this raises before any scoring.  Only the reads the walks touch are
+    uploaded.  The prefixes are masked as pipeline.assemble masks them (inference.py:461)."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    gfa_path = None if isinstance(gfa_or_graph, dict) else gfa_or_graph
+    if isinstance(reads, contigs_mod.ReadStore):
+        source = "store"
+    elif gfa_path is not None and contigs_mod.gfa_sequences(gfa_path) is not None:
+        source = "gfa"
+    elif reads is not None:
+        if not os.path.isfile(reads):
+            raise FileNotFoundError(f"reads file {reads} not found")
+        contigs_mod.reads_file_type(reads)
+        source = "file"
+    elif isinstance(gfa_or_graph, dict) and gfa_or_graph.get("read_seqs"):
+        source = "dict"
+    else:
+        raise ValueError("no read sequences: the GFA's S lines say '*' (or a graph dict was passed) and no `reads` was given")
+    g = gfa_or_graph if isinstance(gfa_or_graph, dict) else gfa.read_gfa(gfa_or_graph, similarity=similarity)
+    walks, scores, g = assemble(g, model, len_threshold, nb_paths=nb_paths, similarity=similarity, device=device, scores=scores,
+                                sampler=sampler)
+    touched = sorted({v >> 1 for w in walks for v in w})
+    if source == "store":
+        store = reads
+    elif source == "gfa":
+        store = contigs_mod.ReadStore.from_gfa(gfa_path, keep=touched, device=device)
+    elif source == "file":
+        store = contigs_mod.ReadStore.from_reads_file(reads, g["node_to_read"], g["num_nodes"], keep=touched, device=device)
+    else:
+        store = contigs_mod.ReadStore.from_sequences([g["read_seqs"][2 * r] for r in range(g["num_nodes"] // 2)], keep=touched, device=device)
+    prefix = g["prefix_length"].masked_fill(g["prefix_length"] < 0, 0)
+    dg = decode.DecodeGraph(g["src"], g["dst"], g["num_nodes"], prefix, g["read_length"], device=device)
+    contigs = contigs_mod.spell_contigs(dg, walks, store, line_width=line_width)
+    contigs_mod.write_fasta(contigs, out_path, line_width=line_width)
+    stats = {"num_contigs": len(contigs), "total_length": int(sum(contigs.lengths_host())) if len(contigs) else 0}
+    if len(contigs):
+        n, longest, rec, n50, ng50 = contigs_mod.quick_evaluation(contigs, ref_length)
+        stats.update(longest_contig=longest, reconstructed=rec, n50=n50, ng50=ng50)
+    else:
+        stats.update(longest_contig=0, reconstructed=-1, n50=-1, ng50=-1)
+    return walks, contigs, stats

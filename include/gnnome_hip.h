@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 17
+#define GNNOME_ABI_VERSION 18
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -679,6 +679,37 @@ int gnnome_overlap_edit_distance(const uint8_t* reads, const int64_t* read_off, 
                                  int num_symbols, const int32_t* src, const int32_t* dst, const int32_t* overlap_length,
                                  int64_t num_edges, int32_t* dist_out, float* similarity_out, void* workspace,
                                  size_t workspace_bytes, void* stream);
+
+/* ---- contig spelling: walks -> sequences and FASTA bodies ------------------------------------------------------------------------
+ * Replaces utils/evaluate.py:38-48 (walk_to_sequence) and the byte layout of :51-53 (save_assembly: Biopython's FASTA writer,
+ * 60 columns).  For step j of walk w, node u = walk_nodes[j], read r = u >> 1, len_u = read_off[r+1] - read_off[r]:
+ *   not the walk's last node: p = prefix_length[edges[(u, walk_nodes[j+1])]] with the id as decode's succ_eid gives it (the last
+ *       inserted id of a parallel pair), and the piece is reads[u][:p] under Python's slice rule: min(p, len_u) for p >= 0,
+ *       max(len_u + p, 0) for p < 0 (pipeline.assemble masks p < 0 to 0 first, inference.py:463; the drop-in entry does not)
+ *   the walk's last node: its whole read
+ *   node 2r copies read r; node 2r+1 the first `piece` bytes of its reverse complement, i.e. read r read backwards from its end
+ *   through Bio.Seq's IUPAC complement table in both letter cases, every other byte unchanged (graph_parser.py:183-184, :365)
+ *   reads uint8[T], read_off int64[R+1]: the forward strand only (gnnome_amd/overlap.py pack_reads); num_nodes == 2 R
+ *   walk_nodes int32[S], walk_off int64[W+1]: the walks concatenated
+ * gnnome_contig_pieces: piece_len int64[S].  It first checks every walk and pair and SYNCHRONISES `stream` to report the first
+ *   failure (an empty walk, offsets that do not rise from 0 to S, a node outside [0, num_nodes), a pair that is not an edge - the
+ *   reference raises KeyError) as GNNOME_EINVAL naming the walk and the pair; nothing is written then.  Not capturable.
+ *   workspace: gnnome_contig_pieces_workspace_bytes.  num_walks == 0 is a no-op.
+ * gnnome_contig_spell: piece_off int64[S+1] = the exclusive scan of piece_len (contig w holds unwrapped bytes
+ *   [piece_off[walk_off[w]], piece_off[walk_off[w+1]]) ).  line_width == 0: out = the contigs concatenated in that layout.
+ *   line_width > 0: contig w's FASTA body goes to out + body_off[w] (body_off int64[W], rising, bodies disjoint): '\n' after every
+ *   line_width bytes and after a final partial line; bytes between bodies (where the caller puts header lines) are not written.
+ *   Only bytes below out_bytes are written.  The copy is split into fixed tiles of the output, stores 16-byte vectors where out is
+ *   16-byte aligned, and uses no atomics: equal inputs give equal bytes.  walk_off / piece_off as gnnome_contig_pieces checked and
+ *   produced them. */
+int gnnome_contig_pieces_workspace_bytes(int64_t num_walks, int64_t num_steps, size_t* bytes_host);
+int gnnome_contig_pieces(const int32_t* walk_nodes, int64_t num_steps, const int64_t* walk_off, int64_t num_walks, const int32_t* succ_ptr,
+                         const int32_t* succ_nbr, const int32_t* succ_eid, const int32_t* prefix_length, int64_t num_nodes,
+                         const int64_t* read_off, int64_t num_reads, int64_t* piece_len, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int gnnome_contig_spell(const int32_t* walk_nodes, int64_t num_steps, const int64_t* walk_off, int64_t num_walks, const int64_t* piece_off,
+                        const uint8_t* reads, const int64_t* read_off, int64_t num_reads, const int64_t* body_off, int line_width,
+                        uint8_t* out, int64_t out_bytes, void* stream);
 
 /* ---- Node order (round 4): locality for inputs whose node ids do not follow the layout ---------------------------------------
  * The reference numbers nodes in S-line order of the GFA (graph_parser.py:174-181: read r -> nodes 2r, 2r+1), which need not be
