@@ -146,31 +146,24 @@ def reads_file_type(path):
     raise ValueError(f"{path}: not a reads file by its suffix (fasta / fna / fa / fastq / fnq / fq, optionally .gz)")
 
 
-def read_sequences(path, wanted=None):
-    """{record id: sequence bytes} of a FASTA (multi-line) or FASTQ file, plain or gzip.  The id is the first whitespace-separated
-    token of the header (Biopython's record.id); a repeated id keeps its last record, like the reference's dict.  `wanted`: keep
-    only these ids."""
+def _records(path, sequences=True):
+    """(title, sequence lines | None) of every record of a FASTA (multi-line) or FASTQ file, plain or gzip, in file order.  The title
+    is the header line without its marker and trailing whitespace (Biopython's record.description); sequences=False keeps no
+    sequence (the FASTQ checks still run)."""
     kind = reads_file_type(path)
     opener = gzip.open if str(path).endswith("gz") else open
-    out = {}
-
-    def put(title, chunks):
-        rid = title.split(None, 1)[0] if title.strip() else ""
-        if wanted is None or rid in wanted:
-            out[rid] = "".join(chunks).replace(" ", "").replace("\r", "").encode("ascii")
-
     with opener(path, "rt") as f:
         if kind == "fasta":        # Bio.SeqIO.FastaIO.SimpleFastaParser
             title, chunks = None, []
             for line in f:
                 if line.startswith(">"):
                     if title is not None:
-                        put(title, chunks)
+                        yield title, chunks if sequences else None
                     title, chunks = line[1:].rstrip(), []
-                elif title is not None:
+                elif title is not None and sequences:
                     chunks.append(line.strip())
             if title is not None:
-                put(title, chunks)
+                yield title, chunks if sequences else None
         else:                      # Bio.SeqIO.QualityIO.FastqGeneralIterator: sequence lines up to '+', as many quality characters
             line = f.readline()
             while line:
@@ -179,22 +172,45 @@ def read_sequences(path, wanted=None):
                     continue
                 if not line.startswith("@"):
                     raise ValueError(f"{path}: FASTQ record does not start with '@': {line[:40]!r}")
-                title, chunks = line[1:].rstrip(), []
+                title, chunks, n = line[1:].rstrip(), [], 0
                 line = f.readline()
                 while line and not line.startswith("+"):
-                    chunks.append(line.strip())
+                    n += len(line.strip())
+                    if sequences:
+                        chunks.append(line.strip())
                     line = f.readline()
                 if not line:
                     raise ValueError(f"{path}: FASTQ record {title.split()[0] if title.split() else ''!r} ends before its '+' line")
-                n, q = sum(len(c) for c in chunks), 0
+                q = 0
                 line = f.readline()
                 while line and q < n:
                     q += len(line.strip())
                     line = f.readline()
                 if q != n:
                     raise ValueError(f"{path}: FASTQ record {title!r}: {n} bases but {q} quality values")
-                put(title, chunks)
+                yield title, chunks if sequences else None
+
+
+def _record_id(title):
+    return title.split(None, 1)[0] if title.strip() else ""
+
+
+def read_sequences(path, wanted=None):
+    """{record id: sequence bytes} of a FASTA (multi-line) or FASTQ file, plain or gzip.  The id is the first whitespace-separated
+    token of the header (Biopython's record.id); a repeated id keeps its last record, like the reference's dict.  `wanted`: keep
+    only these ids."""
+    out = {}
+    for title, chunks in _records(path):
+        rid = _record_id(title)
+        if wanted is None or rid in wanted:
+            out[rid] = "".join(chunks).replace(" ", "").replace("\r", "").encode("ascii")
     return out
+
+
+def read_titles(path):
+    """{record id: whole title} of a FASTA or FASTQ file, plain or gzip - the reference's {read.id: read.description for read in
+    SeqIO.parse(...)} (graph_parser.py:121-136).  No sequence is kept; a repeated id keeps its last record."""
+    return {_record_id(title): title for title, _ in _records(path, sequences=False)}
 
 
 class ContigRecord:

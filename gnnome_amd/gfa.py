@@ -28,9 +28,20 @@ from the third-party aligner edlib on the CPU.  Here (`similarity="auto"`, the d
 a GFA with sequences - from the device kernel gnnome_overlap_edit_distance (gnnome_amd/overlap.py: exact edit distances,
 one wavefront per overlap; needs the MI355X, there is no CPU version in this package); a caller-supplied
 `similarity(src_seq, dst_seq, overlap_length)` callable overrides both.  A GFA without sequences and without tags gives
-None - never a guess (hyperparameters.py:17 `use_similarities`: a model trained with them needs them)."""
+None - never a guess (hyperparameters.py:17 `use_similarities`: a model trained with them needs them).
+
+training=True (:120-138, :213-272, :387-400) adds what a training step needs.  The titles of the records in `reads_path` (FASTA or
+FASTQ, plain or .gz, by suffix as contigs.reads_file_type) carry `strand=`, `start=`, `end=` and `chr=` as the simulator writes them
+(generate_data.py:43-60); every S line takes them from its read's title, a unitig with A lines combines its reads (strand: the sum of
+title strand x A-line orientation, >= 0 -> +1; start: min; end: max; chromosome: the most common, ties to the first seen), node 2k gets
+the strand and 2k+1 its opposite.  New keys read_strand, read_start, read_end, read_chr (int64[N]) and y (float32[E], edge-id order),
+the labels of utils/labels.py computed on the device by gnnome_amd.labels (csrc/edge_labels.hip).  `labels` follows `similarity`:
+"auto" labels on the device when there is one, else y is None with a warning; "device" insists; False leaves y None.  A read missing
+from the file, or a title without one of the four fields, raises ValueError naming the read and the file."""
 import gzip
 import re
+import warnings
+from collections import Counter
 
 import torch
 
@@ -39,9 +50,60 @@ _HIFIASM_ID = re.compile(r"(.*):\d-\d*")
 _COMPLEMENT = str.maketrans("ACGTMRWSYKVHDBXNUacgtmrwsykvhdbxnu", "TGCAKYWSRMBDHVXNAtgcakywsrmbdhvxna")
 
 
-def read_gfa(path, similarity="auto", keep_sequences=False):
+_STRAND = re.compile(r"strand=(\+|\-)")
+_START = re.compile(r"start=(\d+)")
+_END = re.compile(r"end=(\d+)")
+_CHR = re.compile(r"chr=([0-9XYM]+)")
+_CHR_CODES = {"X": -1, "Y": -2, "M": -3}
+
+
+def _annotation(titles, rid, reads_path):
+    """(strand, start, end, chromosome) of read `rid` from its title (graph_parser.py:213-228): the first match of each field."""
+    if rid not in titles:
+        raise ValueError(f"read {rid!r} is not in {reads_path}")
+    title = titles[rid]
+    found = [rx.search(title) for rx in (_STRAND, _START, _END, _CHR)]
+    missing = [name for name, m in zip(("strand=", "start=", "end=", "chr="), found) if m is None]
+    if missing:
+        raise ValueError(f"read {rid!r} in {reads_path}: the title {title!r} has no {', '.join(missing)} field")
+    strand, start, end, chrom = (m.group(1) for m in found)
+    try:
+        chrom = _CHR_CODES[chrom] if chrom in _CHR_CODES else int(chrom)
+    except ValueError:
+        raise ValueError(f"read {rid!r} in {reads_path}: chr={chrom} is neither a number nor X, Y or M") from None
+    return (1 if strand == "+" else -1), int(start), int(end), chrom
+
+
+def _node_annotations(node_to_read, num_nodes, reads_path):
+    """read_strand, read_start, read_end, read_chr int64[N] (graph_parser.py:213-272)."""
+    from .contigs import read_titles
+    titles = read_titles(reads_path)
+    cols = [[0] * num_nodes for _ in range(4)]
+    for real in range(0, num_nodes, 2):
+        rid = node_to_read[real]
+        if isinstance(rid, list):   # a unitig: its reads from the A lines, (read id, orientation)
+            if not rid:
+                raise ValueError(f"unitig node {real}: no A lines name its reads, so it has no position in {reads_path}")
+            anns = [_annotation(titles, r, reads_path) for r, _ in rid]
+            strands = [a[0] * (1 if o == "+" else -1) for a, (_, o) in zip(anns, rid)]
+            ann = (1 if sum(strands) >= 0 else -1, min(a[1] for a in anns), max(a[2] for a in anns),
+                   Counter(a[3] for a in anns).most_common()[0][0])
+        else:
+            ann = _annotation(titles, rid, reads_path)
+        strand, start, end, chrom = ann
+        for col, a, b in zip(cols, (strand, start, end, chrom), (-strand, start, end, chrom)):
+            col[real], col[real + 1] = a, b
+    return [torch.tensor(c, dtype=torch.int64) for c in cols]
+
+
+def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, training=False, labels="auto"):
     """-> dict(src, dst int64[E]; num_nodes; overlap_length, prefix_length int64[E]; read_length int64[N];
-    overlap_similarity float32[E] | None; read_to_node, node_to_read, read_to_node2; read_seqs | None)."""
+    overlap_similarity float32[E] | None; read_to_node, node_to_read, read_to_node2; read_seqs | None);
+    training=True adds read_strand, read_start, read_end, read_chr int64[N] and y float32[E] | None (see the module docstring)."""
+    if training and reads_path is None:
+        raise ValueError("read_gfa(training=True) needs reads_path: the FASTA / FASTQ whose titles carry the read positions")
+    if labels not in ("auto", "device", False, None):
+        raise ValueError(f"labels={labels!r}: expected 'auto', 'device' or False")
     opener = gzip.open if str(path).endswith(".gz") else open
     with opener(path, "rt") as f:
         lines = f.readlines()
@@ -137,8 +199,23 @@ def read_gfa(path, similarity="auto", keep_sequences=False):
             try:
                 out["overlap_similarity"] = overlap_similarity(forward, src_t, dst_t, ol_t).cpu()
             except (RuntimeError, ValueError, OSError) as ex:
-                import warnings
                 warnings.warn(f"read_gfa: overlap similarities not computed on the device ({ex}); overlap_similarity is None")
+    if training:
+        keys = ("read_strand", "read_start", "read_end", "read_chr")
+        out.update(zip(keys, _node_annotations(node_to_read, node_idx, reads_path)))
+        out["y"] = None
+        if labels == "device":
+            from .labels import process_graph
+            out["y"] = process_graph(out)[1].cpu()
+        elif labels == "auto":
+            if torch.cuda.is_available():
+                from .labels import process_graph
+                try:
+                    out["y"] = process_graph(out)[1].cpu()
+                except (RuntimeError, OSError) as ex:
+                    warnings.warn(f"read_gfa: edge labels not computed on the device ({ex}); y is None")
+            else:
+                warnings.warn("read_gfa: no GPU, so the edge labels (y) were not computed; y is None")
     return out
 
 

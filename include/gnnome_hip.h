@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 18
+#define GNNOME_ABI_VERSION 19
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -710,6 +710,31 @@ int gnnome_contig_pieces(const int32_t* walk_nodes, int64_t num_steps, const int
 int gnnome_contig_spell(const int32_t* walk_nodes, int64_t num_steps, const int64_t* walk_off, int64_t num_walks, const int64_t* piece_off,
                         const uint8_t* reads, const int64_t* read_off, int64_t num_reads, const int64_t* body_off, int line_width,
                         uint8_t* out, int64_t out_bytes, void* stream);
+
+/* ---- ground-truth edge labels from read positions --------------------------------------------------------------------------------
+ * Replaces utils/labels.py (process_graph / process_graph_combo: create_correct_graphs[_combo] + get_gt_for_single_strand), which
+ * graph_parser.py:387-400 runs on the networkx graph when training=True.  Per node: read_strand int32[N] in {-1, +1}, read_start /
+ * read_end int64[N], read_chr int32[N] the raw chromosome code (X = -1, Y = -2, M = -3); the entry groups by chromosome itself.
+ *   An edge (u, v) is a class edge of problem (c, s) when chr[u] == chr[v] == c, strand[u] == strand[v] == s and start[u] < start[v]
+ *   < end[u] (s = +1) or start[v] < start[u] < end[v] (s = -1).  Per problem, over its class edges and their endpoints V:
+ *     s = +1: final = argmax_V end, reached = argmin_V end; while nodes are alive: a = argmin_alive start, F = reachable from a in
+ *       G[alive], h = argmax_F end, C = the nodes that reach h in G[F]; if |C| >= 2 and not end[h] < end[reached]: reached = h, the
+ *       class edges inside C are labelled 1, stop if h == final; alive -= F.
+ *     s = -1: final = argmin_V start, reached = argmax_V start, a = argmax_alive end, h = argmin_F start, reject when start[h] >
+ *       start[reached].
+ *   Every argmin / argmax takes the SMALLEST NODE ID among equal keys (the reference takes a networkx view's or a Python set's order).
+ *   y float32[E] in edge-id order: 1.0 for the labelled edges, 0.0 for every other; all of y is written.  A problem with no class edges
+ *   contributes nothing (the reference raises ValueError there).
+ *   stats: NULL, or int64[1 + 8 * stats_rows]: stats[0] = P, the number of problems; row p < stats_rows (problems by chromosome code
+ *   ascending, strand -1 before +1) at stats + 1 + 8 p = {chr, strand, nodes |V|, class edges, passes, accepted components, forward
+ *   queue pops, backward queue pops}.
+ *   N and E below 2^31.  The entry checks node ids in [0, N) and strands in {-1, +1} in a first pass and SYNCHRONISES `stream` to
+ *   report the first failure as GNNOME_EINVAL (y is not written then); not capturable.  The loop is one wavefront per problem (one
+ *   launch; problems share nothing); y is a function of the inputs alone.  workspace: gnnome_edge_labels_workspace_bytes. */
+int gnnome_edge_labels_workspace_bytes(int64_t num_nodes, int64_t num_edges, size_t* bytes_host);
+int gnnome_edge_labels(const int32_t* src, const int32_t* dst, int64_t num_edges, int64_t num_nodes, const int32_t* read_strand,
+                       const int64_t* read_start, const int64_t* read_end, const int32_t* read_chr, float* y, int64_t* stats,
+                       int64_t stats_rows, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Node order (round 4): locality for inputs whose node ids do not follow the layout ---------------------------------------
  * The reference numbers nodes in S-line order of the GFA (graph_parser.py:174-181: read r -> nodes 2r, 2r+1), which need not be
