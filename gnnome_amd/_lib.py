@@ -109,6 +109,8 @@ SIGNATURES = {
     "gnnome_contig_spell": [_p, _l, _p, _l, _p, _p, _p, _l, _p, _i, _p, _l, _p],
     "gnnome_edge_labels_workspace_bytes": [_l, _l, ctypes.POINTER(_sz)],
     "gnnome_edge_labels": [_p, _p, _l, _l, _p, _p, _p, _p, _p, _p, _l, _p, _sz, _p],
+    "gnnome_cluster_inputs_workspace_bytes": [_l, _l, ctypes.POINTER(_sz)],
+    "gnnome_cluster_inputs_f32": [_p, _p, _l, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p, _l, _p, _p, _l, _p, _p, _p, _p, _p, _sz, _p],
     "gnnome_adjacency_support": [_p, _p, _p, _l, _l, _p, _p],
     "gnnome_bfs_levels": [_p, _p, _l, _p, _p, _p, _p, _p, _p, _p],
     "gnnome_hem_propose": [_p, _p, _p, _p, _p, _l, _i, _p, _p],
@@ -117,7 +119,7 @@ SIGNATURES = {
     "gnnome_edge_loss_f32": [_p, _p, _p, _l, _p, ctypes.c_float, ctypes.c_float, _p, _p, _p, _p, _p, _sz, _p],
 }
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 # the parameter blocks of gnnome_model_forward_f32 (include/gnnome_hip.h), field for field

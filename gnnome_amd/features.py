@@ -135,4 +135,38 @@ def mask_graph_strandwise(graph, fraction, device=None, keep_half=None):
     return induced_subgraph(graph, keep_half.to(device).repeat_interleave(2), device)
 
 
+class ClusterInputs:
+    """One cluster's model inputs (features.cluster_inputs): contiguous views of the packed buffers.
+    x[N',2] = [z(in) | z(out)], x_rev[N',2] = [z(out) | z(in)] (None unless asked for), e[E',2], y[E'] (None without labels)."""
+    __slots__ = ("x", "x_rev", "e", "y")
+
+    def __init__(self, x, x_rev, e, y):
+        self.x, self.x_rev, self.e, self.y = x, x_rev, e, y
+
+
+def cluster_inputs(parts, full_in_deg, full_out_deg, e, y, outer_nid=None, outer_eid=None, need_rev=True):
+    """partition_degree_features(full_in_deg, full_out_deg, sub.nid, reverse) for both orientations plus the gathers e[sub.eid] and
+    y[sub.eid] (train.py:125-135, 148-186), for every cluster of `parts` in one call of gnnome_cluster_inputs_f32 -> {part id:
+    ClusterInputs} in the order of `parts` (a dict as cluster_partition returns it, or a sequence -> a list).  `outer_nid` / `outer_eid`:
+    the ids of the graph the clusters were cut from inside the full graph (MaskedGraph.nid / .eid of the strand-wise mask): degrees,
+    e and y are then those of the FULL graph, composed through the mask without an intermediate gather.  The statistics are per
+    cluster, mean and unbiased std from fp64 sums, as the torch expression gives them (NaN for a one-node cluster, no clamping).
+    Synchronises once; a bad ptr or id raises naming the cluster, and nothing is written."""
+    from .partition import pack_clusters
+    keys = list(parts.keys()) if isinstance(parts, dict) else None
+    subs = list(parts.values()) if keys is not None else list(parts)
+    dev = e.device
+    node_ptr, nid, edge_ptr, eid = pack_clusters(subs, dev)
+    f32 = lambda t: None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()   # noqa: E731
+    x, xr, es, ys = ops.cluster_inputs(node_ptr, nid, edge_ptr, eid, f32(full_in_deg), f32(full_out_deg), f32(e), f32(y),
+                                       None if outer_nid is None else torch.as_tensor(outer_nid).to(dev).long(),
+                                       None if outer_eid is None else torch.as_tensor(outer_eid).to(dev).long(), need_rev=need_rev)
+    out, n0, e0 = [], 0, 0
+    for s in subs:
+        n1, e1 = n0 + int(s.nid.numel()), e0 + int(s.eid.numel())
+        out.append(ClusterInputs(x[n0:n1], None if xr is None else xr[n0:n1], es[e0:e1], None if ys is None else ys[e0:e1]))
+        n0, e0 = n1, e1
+    return dict(zip(keys, out)) if keys is not None else out
+
+
 degree_features_hip, edge_features_hip = degree_features, edge_features   # earlier names

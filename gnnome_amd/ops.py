@@ -1337,3 +1337,44 @@ def edge_loss(logits, logits_rev, labels, pos_weight, alpha=0.0, need_grad=True,
     _call("gnnome_edge_loss_f32", a.device, _ptr(a), _ptr(b), _ptr(y), E, _ptr(pw), float(alpha), 1.0 / max(E, 1), _ptr(loss),
           _ptr(da), _ptr(db), _ptr(tfpn), _ptr(ws), ws.numel())
     return loss, da, db, tfpn
+
+
+def _ids(t, name, device):
+    if t is None:
+        return None
+    t = torch.as_tensor(t)
+    if t.dtype != torch.int64 or t.dim() != 1 or t.device != device:
+        raise ValueError(f"{name}: expected a 1-d int64 tensor on {device}")
+    return t.contiguous()
+
+
+def cluster_inputs(node_ptr, nid, edge_ptr, eid, in_deg, out_deg, e, y, outer_nid=None, outer_eid=None, need_rev=True):
+    """gnnome_cluster_inputs_f32 (include/gnnome_hip.h) over a packed cluster layout -> (x_org[ΣN',2], x_rev[ΣN',2] | None,
+    e_sub[ΣE',2], y_sub[ΣE'] | None).  Checks every ptr and id first and synchronises once; a bad one raises naming its cluster."""
+    dev = e.device
+    node_ptr, nid, edge_ptr, eid = (_ids(t, n, dev) for t, n in ((node_ptr, "node_ptr"), (nid, "nid"), (edge_ptr, "edge_ptr"), (eid, "eid")))
+    outer_nid, outer_eid = _ids(outer_nid, "outer_nid", dev), _ids(outer_eid, "outer_eid", dev)
+    in_deg, out_deg = _dense(in_deg, "cluster_inputs.in_deg"), _dense(out_deg, "cluster_inputs.out_deg")
+    e = _dense(e, "cluster_inputs.e")
+    k = node_ptr.numel() - 1
+    if k < 0 or edge_ptr.numel() != k + 1:
+        raise ValueError("cluster_inputs: node_ptr and edge_ptr need k + 1 entries each")
+    if in_deg.dim() != 1 or out_deg.shape != in_deg.shape or e.dim() != 2 or e.shape[1] != 2:
+        raise ValueError("cluster_inputs: in_deg / out_deg float32[N], e float32[E,2]")
+    if y is not None:
+        y = _dense(y, "cluster_inputs.y")
+        if y.shape != (e.shape[0],):
+            raise ValueError("cluster_inputs: y float32[E]")
+    tn, te = nid.numel(), eid.numel()
+    x_org = torch.empty((tn, 2), dtype=torch.float32, device=dev)
+    x_rev = torch.empty((tn, 2), dtype=torch.float32, device=dev) if need_rev else None
+    e_sub = torch.empty((te, 2), dtype=torch.float32, device=dev)
+    y_sub = torch.empty(te, dtype=torch.float32, device=dev) if y is not None else None
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().gnnome_cluster_inputs_workspace_bytes(max(k, 0), tn, ctypes.byref(need)), "cluster_inputs_workspace_bytes")
+    ws = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+    _call("gnnome_cluster_inputs_f32", dev, _ptr(node_ptr), _ptr(nid), k, tn, _ptr(edge_ptr), _ptr(eid), te,
+          _ptr(outer_nid), 0 if outer_nid is None else outer_nid.numel(), _ptr(outer_eid), 0 if outer_eid is None else outer_eid.numel(),
+          _ptr(in_deg), _ptr(out_deg), in_deg.numel(), _ptr(e), _ptr(y), e.shape[0], _ptr(x_org), _ptr(x_rev), _ptr(e_sub), _ptr(y_sub),
+          _ptr(ws), ws.numel())
+    return x_org, x_rev, e_sub, y_sub

@@ -403,3 +403,20 @@ def cluster_partition(graph, num_clusters, extra_cached_hops=1, device=None, met
         sub = induced_subgraph((src, dst, n), keep, device)
         parts[p] = ClusterGraph(sub, inner[sub.nid])
     return parts
+
+
+def pack_clusters(parts, device=None):
+    """The packed layout of gnnome_cluster_inputs_f32 from cluster_partition's dict (or any sequence of objects with int64 `nid` /
+    `eid`): (node_ptr int64[k+1], nid int64[ΣN'], edge_ptr int64[k+1], eid int64[ΣE']) - the clusters' nid / eid concatenated in
+    dict order.  The sizes are known on the host: no synchronisation."""
+    subs = list(parts.values()) if isinstance(parts, dict) else list(parts)
+    if not subs:
+        raise ValueError("pack_clusters: no clusters")
+    device = device or subs[0].nid.device
+    n_sizes = [0] + [int(s.nid.numel()) for s in subs]
+    e_sizes = [0] + [int(s.eid.numel()) for s in subs]
+    node_ptr = torch.tensor(n_sizes, dtype=torch.int64).cumsum_(0).to(device, non_blocking=True)
+    edge_ptr = torch.tensor(e_sizes, dtype=torch.int64).cumsum_(0).to(device, non_blocking=True)
+    nid = torch.cat([s.nid.to(device=device, dtype=torch.int64) for s in subs])
+    eid = torch.cat([s.eid.to(device=device, dtype=torch.int64) for s in subs])
+    return node_ptr, nid, edge_ptr, eid

@@ -1,0 +1,439 @@
+"""The training loop: train.py:188-450 of the reference on this package, from a dataset of labelled graphs to a trained model.
+
+    records = trainer.train(train_set, valid_set, out="run", seed=1)        # -> one record per epoch
+    python -m gnnome_amd.trainer --train DIR --valid DIR --name run [--overfit] [--resume] [--dropout P] [--seed S] [--gpu I]
+
+Per epoch, as the reference: shuffle the training graphs; if `masking`, keep a random fraction of the reads
+(features.mask_graph_strandwise); train on the whole graph if `num_nodes_per_cluster >= N`, otherwise on the
+`N // num_nodes_per_cluster + 1` clusters of partition.cluster_partition, shuffled; each step runs the symmetry loss (or BCE),
+zero_grad / backward / step.  Then validation under torch.no_grad() and model.eval() (masked as well), the model saved at a new
+minimum of the validation loss (of the training loss under `overfit`), ReduceLROnPlateau stepped, a checkpoint written.
+
+Where the inputs come from (train.py:125-186, utils/data_utils.py:31-41): degrees are the FULL graph's stored degrees, e is the full
+graph's z-scored edge features computed once per graph at load, labels are y[eid] composed through the mask.  All clusters of a graph
+get their inputs from ONE call of gnnome_cluster_inputs_f32 (features.cluster_inputs); the whole-graph mode is the same call with one
+cluster.  Loss and the confusion counts come out of one pass of the edge-loss kernel and stay on the device in a [steps, 5] log that
+is copied to the host once per epoch: the loop itself adds no host synchronisation per step.
+
+Deliberate deviations from the reference:
+  * clusters without edges are skipped and counted in the epoch record (the reference divides by zero there);
+  * the first overfit epoch saves the model (the reference's min([]) raises at that point);
+  * the checkpoint also holds the scheduler state and the random state (and the order of the training graphs), and resume restores
+    them, so a resumed run reproduces the run that was not interrupted;
+  * the epoch records are returned and appended as JSON lines next to the checkpoint, in place of wandb.
+"""
+import argparse
+import json
+import os
+import random
+import re
+import time
+import types
+from datetime import datetime
+
+import numpy as np
+import torch
+from torch.optim.lr_scheduler import ReduceLROnPlateau
+
+from . import features, metrics, ops
+from .models import SymGatedGCNModel
+from .partition import cluster_partition
+
+# configs/hyperparameters.py, the keys the loop reads
+DEFAULT_HYPERPARAMETERS = {
+    "seed": 1,
+    "dim_latent": 64,
+    "num_gnn_layers": 8,
+    "node_features": 2,
+    "edge_features": 2,
+    "hidden_ne_features": 16,
+    "hidden_edge_scores": 64,
+    "normalization": "batch",
+    "dropout": 0.2,
+    "num_epochs": 5,
+    "lr": 1e-4,
+    "use_symmetry_loss": True,
+    "alpha": 0.1,
+    "num_nodes_per_cluster": 1000,
+    "k_extra_hops": 1,
+    "patience": 2,
+    "decay": 0.95,
+    "masking": True,
+    "mask_frac_low": 80,
+    "mask_frac_high": 100,
+}
+
+CHECKPOINT_KEYS = ("epoch", "model_state_dict", "optim_state_dict", "loss_train", "loss_valid", "scheduler_state_dict", "rng_state")
+METRIC_KEYS = ("loss", "fp_rate", "fn_rate", "acc", "precision", "recall", "f1", "acc_inv", "precision_inv", "recall_inv", "f1_inv")
+
+
+def hyperparameters_with(overrides=None):
+    """configs/hyperparameters.py's values, updated by `overrides` (the reference's key names; an unknown key raises)."""
+    hp = dict(DEFAULT_HYPERPARAMETERS)
+    for k, v in (overrides or {}).items():
+        if k not in hp:
+            raise KeyError(f"unknown hyperparameter {k!r}")
+        hp[k] = v
+    return hp
+
+
+def set_seed(seed):
+    """utils/utils.py:10-30: Python, numpy, torch and the device generators."""
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    if torch.cuda.is_available():
+        torch.cuda.manual_seed_all(seed)
+
+
+def plan(num_nodes, num_nodes_per_cluster):
+    """train.py:316-320: -> (whole graph?, num_clusters).  The whole graph if num_nodes_per_cluster >= N, otherwise N // npc + 1 clusters."""
+    if num_nodes_per_cluster >= num_nodes:
+        return True, 1
+    return False, num_nodes // num_nodes_per_cluster + 1
+
+
+def pos_weight_of(graphs):
+    """train.py:239: 1 / mean over the training graphs of #(round(y) == 1) / #(round(y) == 0).  `graphs`: (name, y) pairs."""
+    ratios = []
+    for name, y in graphs:
+        r = torch.round(torch.as_tensor(y).float())
+        pos, neg = int((r == 1).sum()), int((r == 0).sum())
+        if neg == 0:
+            raise ValueError(f"graph {name}: no negative edges (round(y) == 0), the positive-class weight is undefined")
+        ratios.append(pos / neg)
+    if not ratios:
+        raise ValueError("no training graphs")
+    mean = sum(ratios) / len(ratios)
+    if mean == 0:
+        raise ValueError("no positive edges in the training graphs, the positive-class weight is undefined")
+    return 1.0 / mean
+
+
+def compute_fp_fn_rates(TP, TN, FP, FN):
+    """train.py:23-27."""
+    fp_rate = FP / (FP + TN) if (FP + TN) != 0 else 0.0
+    fn_rate = FN / (FN + TP) if (FN + TP) != 0 else 0.0
+    return fp_rate, fn_rate
+
+
+def compute_metrics(TP, TN, FP, FN, loss):
+    """train.py:30-54 from the four counts (the reference counts them from the logits first)."""
+    acc, precision, recall, f1 = metrics.calculate_metrics(TP, TN, FP, FN)
+    acc_inv, precision_inv, recall_inv, f1_inv = metrics.calculate_metrics_inverse(TP, TN, FP, FN)
+    fp_rate, fn_rate = compute_fp_fn_rates(TP, TN, FP, FN)
+    return {"loss": loss, "fp_rate": fp_rate, "fn_rate": fn_rate, "acc": acc, "precision": precision, "recall": recall, "f1": f1,
+            "acc_inv": acc_inv, "precision_inv": precision_inv, "recall_inv": recall_inv, "f1_inv": f1_inv}
+
+
+def average_epoch_metrics(step_metrics):
+    """train.py:57-59 over a list of compute_metrics dicts -> {key: mean} (plain floats)."""
+    if not step_metrics:
+        return {}
+    return {k: float(np.mean([m[k] for m in step_metrics])) for k in step_metrics[0]}
+
+
+def metrics_from_log(log):
+    """[steps, 5] rows (loss, TP, TN, FP, FN) on the host -> the per-step compute_metrics dicts."""
+    rows = log.tolist() if hasattr(log, "tolist") else log
+    return [compute_metrics(int(tp), int(tn), int(fp), int(fn), float(loss)) for loss, tp, tn, fp, fn in rows]
+
+
+# ---- datasets --------------------------------------------------------------------------------------------------------------
+
+def _dataset_files(path):
+    found = []
+    for name in os.listdir(path):
+        m = re.fullmatch(r"(\d+)\.(pt|dgl)", name)
+        if m:
+            found.append((int(m.group(1)), m.group(2), os.path.join(path, name)))
+    return sorted(found)
+
+
+def load_dataset(ds):
+    """A list of graph dicts (as gfa.read_gfa / dgl_io return them, each with y) -> [(name, dict)]; or a directory of <idx>.pt files
+    (torch.save of such a dict; trainer.process writes them), sorted by idx, and of <idx>.dgl files when DGL can be imported."""
+    if isinstance(ds, (str, os.PathLike)):
+        out = []
+        try:
+            import dgl  # noqa: F401
+            have_dgl = True
+        except ImportError:
+            have_dgl = False
+        for idx, kind, path in _dataset_files(ds):
+            if kind == "pt":
+                out.append((path, torch.load(path, map_location="cpu", weights_only=False)))
+            elif have_dgl:
+                from .dgl_io import load_dgl_file
+                out.append((path, load_dgl_file(path)))
+        if not out:
+            raise ValueError(f"{ds}: no <idx>.pt graphs" + ("" if have_dgl else " (.dgl files need DGL, which is not installed)"))
+        return out
+    return [(f"graph {i}", g) for i, g in enumerate(ds)]
+
+
+class _Graph:
+    """One dataset graph on the device, prepared once at load: the full graph's views, stored degrees, z-scored e and labels."""
+
+    def __init__(self, name, g, device):
+        y = g.get("y") if isinstance(g, dict) else None
+        if y is None:
+            raise ValueError(f"graph {name}: no labels (y); build training graphs with gfa.read_gfa(..., training=True) or trainer.process")
+        self.name = name
+        self.num_nodes = int(g["num_nodes"])
+        src = torch.as_tensor(g["src"]).to(device=device, dtype=torch.int32).contiguous()
+        dst = torch.as_tensor(g["dst"]).to(device=device, dtype=torch.int32).contiguous()
+        self.views = ops.GraphViews(src, dst, self.num_nodes)
+        self.num_edges = int(src.numel())
+        self.y = torch.as_tensor(y).to(device=device, dtype=torch.float32).contiguous()
+        if self.y.numel() != self.num_edges:
+            raise ValueError(f"graph {name}: {self.y.numel()} labels for {self.num_edges} edges")
+        if g.get("e") is not None:
+            self.e = torch.as_tensor(g["e"]).to(device=device, dtype=torch.float32).contiguous()
+        else:
+            if g.get("overlap_length") is None or g.get("overlap_similarity") is None:
+                raise ValueError(f"graph {name}: needs overlap_length and overlap_similarity (or e) for the edge features")
+            self.e = features.edge_features(torch.as_tensor(g["overlap_length"]).to(device).float(),
+                                            torch.as_tensor(g["overlap_similarity"]).to(device).float())
+        if g.get("in_deg") is not None and g.get("out_deg") is not None:
+            self.in_deg = torch.as_tensor(g["in_deg"]).to(device=device, dtype=torch.float32).contiguous()
+            self.out_deg = torch.as_tensor(g["out_deg"]).to(device=device, dtype=torch.float32).contiguous()
+        else:
+            self.in_deg, self.out_deg = (t.contiguous() for t in features.stored_degrees(self.views))
+
+
+def process(gfa, reads, out_path, device=None):
+    """One training graph file: gfa.read_gfa(gfa, reads_path=reads, training=True) with the labels computed on the device and the
+    stored degrees (graph_parser.py: ndata in_deg / out_deg) added, written with torch.save to `out_path` (<dir>/<idx>.pt)."""
+    from .gfa import read_gfa
+    g = read_gfa(gfa, reads_path=reads, training=True, labels="device")
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    views = ops.GraphViews(g["src"].to(device=device, dtype=torch.int32), g["dst"].to(device=device, dtype=torch.int32), g["num_nodes"])
+    g["in_deg"], g["out_deg"] = (t.cpu() for t in features.stored_degrees(views))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    torch.save(g, out_path)
+    return g
+
+
+# ---- the step --------------------------------------------------------------------------------------------------------------
+
+class _LossAndCounts(torch.autograd.Function):
+    """loss.symmetry_loss / loss.bce_loss that also leaves (loss, TP, TN, FP, FN) of the org logits in a row of the device log:
+    one edge-loss kernel gives all of them (ops.edge_loss(..., need_counts=True))."""
+
+    @staticmethod
+    def forward(ctx, org, rev, labels, pos_weight, alpha, row):
+        need = org.requires_grad or (rev is not None and rev.requires_grad)
+        loss, d_org, d_rev, tfpn = ops.edge_loss(org.detach().float().contiguous(), None if rev is None else rev.detach().float().contiguous(),
+                                                labels, pos_weight, alpha, need_grad=need, need_counts=True)
+        row[0].copy_(loss[0])
+        row[1:5].copy_(tfpn)
+        ctx.save_for_backward(d_org, d_rev)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        d_org, d_rev = ctx.saved_tensors
+        return (None if d_org is None else g * d_org), (None if d_rev is None else g * d_rev), None, None, None, None
+
+
+def _graph_steps(gr, hp, device, training, trace, phase, epoch):
+    """Mask, plan, partition and build the inputs of one graph -> the list of (views, ClusterInputs, record) steps, and the
+    number of clusters skipped for having no edges."""
+    fraction, outer_nid, outer_eid, work = None, None, None, gr.views
+    if hp["masking"]:
+        fraction = random.randint(hp["mask_frac_low"], hp["mask_frac_high"]) / 100
+        work = features.mask_graph_strandwise(gr.views, fraction, device)   # torch.rand on the device, as train.py:92
+        outer_nid, outer_eid = work.nid, work.eid
+    n = work.num_nodes if isinstance(work, ops.GraphViews) else work.num_nodes()
+    whole, num_clusters = plan(n, hp["num_nodes_per_cluster"])
+    if whole:
+        views = work if isinstance(work, ops.GraphViews) else work.views
+        parts = [types.SimpleNamespace(nid=torch.arange(n, device=device), eid=torch.arange(views.num_edges, device=device),
+                                       views=views, src=None, dst=None)]
+    else:
+        parts = list(cluster_partition(work, num_clusters, extra_cached_hops=hp["k_extra_hops"], device=device).values())
+    inputs = features.cluster_inputs(parts, gr.in_deg, gr.out_deg, gr.e, gr.y, outer_nid=outer_nid, outer_eid=outer_eid,
+                                     need_rev=hp["use_symmetry_loss"])
+    steps = list(zip(parts, inputs))
+    if training and not whole:
+        random.shuffle(steps)                                                  # train.py:336
+    kept = [s for s in steps if s[0].eid.numel() > 0]
+    if trace is not None:
+        for sub, _ in kept:
+            nid, eid = sub.nid, sub.eid
+            if outer_nid is not None:
+                nid, eid = outer_nid[nid], outer_eid[eid]
+            v = sub.views
+            src = sub.src if sub.src is not None else _edge_src_dst(v)[0]
+            dst = sub.dst if sub.dst is not None else _edge_src_dst(v)[1]
+            trace.append({"phase": phase, "epoch": epoch, "graph": gr.name, "fraction": fraction, "whole": whole,
+                          "nid": nid.cpu(), "eid": eid.cpu(), "src": src.cpu(), "dst": dst.cpu(), "num_nodes": int(sub.nid.numel())})
+    return [(sub.views, ci) for sub, ci in kept], len(steps) - len(kept)
+
+
+def _edge_src_dst(views):
+    src = torch.empty(views.num_edges, dtype=torch.int32, device=views.device)
+    dst = torch.empty_like(src)
+    src[views.srt_eid.long()], dst[views.srt_eid.long()] = views.srt_src, views.srt_dst
+    return src, dst
+
+
+def _run_epoch_phase(model, optimizer, graphs, hp, pos_weight, device, training, trace, epoch):
+    phase = "train" if training else "valid"
+    logs, skipped, first_grads = [], 0, trace is not None and training and not any(t.get("grads") is not None for t in trace)
+    alpha = float(hp["alpha"]) if hp["use_symmetry_loss"] else 0.0
+    n_trace0 = len(trace) if trace is not None else 0
+    for gr in graphs:
+        if training:
+            model.train()
+        steps, skip = _graph_steps(gr, hp, device, training, trace, phase, epoch)
+        skipped += skip
+        log = torch.zeros((len(steps), 5), dtype=torch.float64, device=device)
+        for i, (views, ci) in enumerate(steps):
+            org = model(views, ci.x, ci.e).squeeze(-1)
+            rev = model(views.reversed(), ci.x_rev, ci.e).squeeze(-1) if hp["use_symmetry_loss"] else None
+            loss = _LossAndCounts.apply(org, rev, ci.y, pos_weight, alpha, log[i])
+            if training:
+                optimizer.zero_grad()
+                loss.backward()
+                if first_grads:
+                    trace[n_trace0]["grads"] = {k: p.grad.detach().cpu().clone() for k, p in model.named_parameters()}
+                    first_grads = False
+                optimizer.step()
+        logs.append(log)
+    log = torch.cat(logs).cpu() if logs else torch.zeros((0, 5), dtype=torch.float64)   # the one copy to the host of the phase
+    if trace is not None:
+        for rec, row in zip(trace[n_trace0:], log.tolist()):
+            rec.update(loss=row[0], tp=int(row[1]), tn=int(row[2]), fp=int(row[3]), fn=int(row[4]))
+    step_metrics = metrics_from_log(log)
+    if not step_metrics:
+        raise ValueError(f"{phase}: no step with edges in this epoch")
+    return average_epoch_metrics(step_metrics), len(step_metrics), skipped
+
+
+def _rng_state(train_order):
+    return {"python": random.getstate(), "numpy": np.random.get_state(), "torch": torch.get_rng_state(),
+            "cuda": torch.cuda.get_rng_state_all() if torch.cuda.is_available() else [], "train_order": list(train_order)}
+
+
+def _set_rng_state(st):
+    random.setstate(st["python"])
+    np.random.set_state(st["numpy"])
+    torch.set_rng_state(st["torch"].cpu())
+    if st.get("cuda"):
+        torch.cuda.set_rng_state_all([t.cpu() for t in st["cuda"]])
+
+
+def train(train_set, valid_set, out=None, hyperparameters=None, overfit=False, dropout=None, seed=None, resume=False, device=None,
+          models_dir="models", checkpoints_dir="checkpoints", trace=None):
+    """train.py:188-450 (see the module docstring) -> the list of epoch records.  `hyperparameters`: overrides of
+    configs/hyperparameters.py by the reference's key names.  `trace` (for tests): a list that receives the initial state dict and
+    one dict per step (graph, mask fraction, the step's full-graph node and edge ids, its edges, loss and counts; the first training
+    step's gradients) - it copies to the host per step."""
+    hp = hyperparameters_with(hyperparameters)
+    seed = hp["seed"] if seed is None else seed
+    dropout = hp["dropout"] if dropout is None else dropout
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if device.type != "cuda":
+        raise ValueError("the training step runs on the MI355X: device must be a HIP device")
+    torch.cuda.set_device(device)
+    set_seed(seed)
+    if out is None:
+        out = datetime.now().strftime("%Y-%b-%d-%H-%M-%S")
+    ds_train = [_Graph(n, g, device) for n, g in load_dataset(train_set)]
+    ds_valid = ds_train if overfit else [_Graph(n, g, device) for n, g in load_dataset(valid_set)]
+    pos_weight = torch.tensor([pos_weight_of([(g.name, g.y) for g in ds_train])], device=device)
+
+    model = SymGatedGCNModel(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_ne_features"], hp["num_gnn_layers"],
+                             hp["hidden_edge_scores"], hp["normalization"], dropout=dropout).to(device)
+    optimizer = torch.optim.Adam(model.parameters(), lr=hp["lr"])
+    scheduler = ReduceLROnPlateau(optimizer, mode="min", factor=hp["decay"], patience=hp["patience"])
+    if trace is not None:
+        trace.append({"initial_state": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, "pos_weight": float(pos_weight)})
+
+    out = f"{out}_seed{seed}"
+    os.makedirs(models_dir, exist_ok=True)
+    os.makedirs(checkpoints_dir, exist_ok=True)
+    model_path = os.path.join(models_dir, f"model_{out}.pt")
+    ckpt_path = os.path.join(checkpoints_dir, f"ckpt_{out}.pt")
+    start_epoch, loss_train, loss_valid = 0, [], []
+    order = list(range(len(ds_train)))
+    if resume:
+        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)   # load_state_dict moves to the device
+        model_path = os.path.join(models_dir, f"model_{out}_resumed-{hp['num_epochs']}.pt")
+        ckpt_path = os.path.join(checkpoints_dir, f"ckpt_{out}_resumed-{hp['num_epochs']}.pt")
+        start_epoch = ckpt["epoch"] + 1
+        model.load_state_dict(ckpt["model_state_dict"])
+        optimizer.load_state_dict(ckpt["optim_state_dict"])
+        loss_train.append(ckpt["loss_train"])
+        loss_valid.append(ckpt["loss_valid"])
+        if "scheduler_state_dict" in ckpt:
+            scheduler.load_state_dict(ckpt["scheduler_state_dict"])
+        if "rng_state" in ckpt:
+            _set_rng_state(ckpt["rng_state"])
+            order = list(ckpt["rng_state"]["train_order"])
+    log_path = os.path.splitext(ckpt_path)[0] + ".jsonl"
+
+    records = []
+    for epoch in range(start_epoch, hp["num_epochs"]):
+        t0 = time.perf_counter()
+        random.shuffle(order)                                                          # train.py:294 shuffles the list in place
+        train_mean, n_steps, n_skip = _run_epoch_phase(model, optimizer, [ds_train[i] for i in order], hp, pos_weight, device, True,
+                                                       trace, epoch)
+        loss_train.append(train_mean["loss"])
+        lr = optimizer.param_groups[0]["lr"]
+        rec = {"epoch": epoch, **{f"train/{k}": v for k, v in train_mean.items()}, "train/steps": n_steps, "train/skipped_clusters": n_skip}
+        if overfit:
+            if len(loss_train) == 1 or loss_train[-1] < min(loss_train[:-1]):     # the first epoch saves (the reference's min([]) raises)
+                torch.save(model.state_dict(), model_path)
+                rec["saved"] = True
+            scheduler.step(train_mean["loss"])
+            best = (min(loss_train), 0.0)
+        else:
+            model.eval()
+            with torch.no_grad():
+                valid_mean, v_steps, v_skip = _run_epoch_phase(model, None, ds_valid, hp, pos_weight, device, False, trace, epoch)
+            loss_valid.append(valid_mean["loss"])
+            rec.update({f"valid/{k}": v for k, v in valid_mean.items()})
+            rec.update({"valid/steps": v_steps, "valid/skipped_clusters": v_skip})
+            if len(loss_valid) == 1 or loss_valid[-1] < min(loss_valid[:-1]):
+                torch.save(model.state_dict(), model_path)
+                rec["saved"] = True
+            scheduler.step(valid_mean["loss"])
+            best = (min(loss_train), min(loss_valid))
+        rec["lr"] = lr
+        rec["seconds"] = time.perf_counter() - t0
+        # after scheduler.step: the checkpoint's scheduler state is the one the next epoch starts from
+        torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optim_state_dict": optimizer.state_dict(),
+                    "loss_train": best[0], "loss_valid": best[1], "scheduler_state_dict": scheduler.state_dict(),
+                    "rng_state": _rng_state(order)}, ckpt_path)
+        with open(log_path, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+        records.append(rec)
+    return records
+
+
+def main(argv=None):
+    """train.py:498-509."""
+    p = argparse.ArgumentParser(description="Train a SymGatedGCN model on a dataset of labelled graphs")
+    p.add_argument("--train", type=str, required=True, help="directory of <idx>.pt training graphs (trainer.process)")
+    p.add_argument("--valid", type=str, required=True, help="directory of <idx>.pt validation graphs")
+    p.add_argument("--asm", type=str, default=None, help="assembler used (accepted for the reference's command line; not read)")
+    p.add_argument("--name", type=str, default=None, help="name for the model")
+    p.add_argument("--overfit", action="store_true", help="overfit on the training data")
+    p.add_argument("--resume", action="store_true", help="resume from the checkpoint of the run with this name and seed")
+    p.add_argument("--dropout", type=float, default=None, help="dropout rate for the model")
+    p.add_argument("--seed", type=int, default=None, help="random seed")
+    p.add_argument("--gpu", type=int, default=None, help="index of the GPU to train on")
+    p.add_argument("--models-dir", type=str, default="models")
+    p.add_argument("--checkpoints-dir", type=str, default="checkpoints")
+    a = p.parse_args(argv)
+    device = torch.device("cuda", a.gpu if a.gpu is not None else torch.cuda.current_device())
+    for rec in train(a.train, a.valid, out=a.name, overfit=a.overfit, dropout=a.dropout, seed=a.seed, resume=a.resume, device=device,
+                     models_dir=a.models_dir, checkpoints_dir=a.checkpoints_dir):
+        print(json.dumps(rec))
+
+
+if __name__ == "__main__":
+    main()

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 19
+#define GNNOME_ABI_VERSION 20
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -735,6 +735,29 @@ int gnnome_edge_labels_workspace_bytes(int64_t num_nodes, int64_t num_edges, siz
 int gnnome_edge_labels(const int32_t* src, const int32_t* dst, int64_t num_edges, int64_t num_nodes, const int32_t* read_strand,
                        const int64_t* read_start, const int64_t* read_end, const int32_t* read_chr, float* y, int64_t* stats,
                        int64_t stats_rows, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Every cluster's model inputs at once (mini-batch training) -------------------------------------------------------------
+ * train.py:125-135 (get_partition_ne_features, both orientations) and the gathers of train.py:148-186 (get_bce_loss_partition,
+ * get_symmetry_loss_partition: e[sub_g.edata['_ID']], y[sub_g.edata['_ID']]) for all k clusters of a graph in one call.
+ * Packed layout: cluster c owns node positions [node_ptr[c], node_ptr[c+1]) of nid and edge positions [edge_ptr[c], edge_ptr[c+1])
+ * of eid (int64 each; node_ptr[0] = edge_ptr[0] = 0, node_ptr[k] = total_nodes, edge_ptr[k] = total_edges).  outer_nid / outer_eid
+ * (NULL: none) compose one more id map - cluster -> masked graph -> full graph: position p stands for node outer_nid[nid[p]] of the
+ * full graph (outer_nodes entries; nid indexes it) - so a masked graph's clusters need no intermediate gather.
+ * in_deg / out_deg float32[num_nodes]: the FULL graph's stored degrees; e float32[num_edges,2]; y float32[num_edges] (NULL with y_sub).
+ * Outputs, packed the same way: x_org float32[total_nodes,2] = [z(in) | z(out)], x_rev (NULL: skip) = [z(out) | z(in)],
+ * e_sub float32[total_edges,2], y_sub float32[total_edges]; z = (d - mean) / std over the cluster's own nodes in fp32, mean and
+ * UNBIASED std from fixed-order fp64 sums (no float atomics; the bits do not depend on the launch), rounded to fp32 as torch's CPU
+ * statistics are.  A one-node cluster (std NaN) and a cluster of equal degrees (std 0) give torch's NaN / inf: nothing is clamped.
+ * Any mix of cluster sizes, from one cluster of the whole graph to many of a few nodes.  The entry checks both ptrs and every id in a
+ * first pass and SYNCHRONISES `stream` once: the first failure is GNNOME_EINVAL naming the cluster, and no output is written then;
+ * not capturable.  workspace: gnnome_cluster_inputs_workspace_bytes(k, total_nodes). */
+int gnnome_cluster_inputs_workspace_bytes(int64_t num_clusters, int64_t total_nodes, size_t* bytes_host);
+int gnnome_cluster_inputs_f32(const int64_t* node_ptr, const int64_t* nid, int64_t num_clusters, int64_t total_nodes,
+                              const int64_t* edge_ptr, const int64_t* eid, int64_t total_edges, const int64_t* outer_nid,
+                              int64_t outer_nodes, const int64_t* outer_eid, int64_t outer_edges, const float* in_deg,
+                              const float* out_deg, int64_t num_nodes, const float* e, const float* y, int64_t num_edges,
+                              float* x_org, float* x_rev, float* e_sub, float* y_sub, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* ---- Node order (round 4): locality for inputs whose node ids do not follow the layout ---------------------------------------
  * The reference numbers nodes in S-line order of the GFA (graph_parser.py:174-181: read r -> nodes 2r, 2r+1), which need not be
