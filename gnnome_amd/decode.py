@@ -52,13 +52,16 @@ class DecodeGraph:
         self.succ_nbr = dst[order].int().contiguous()
         self.succ_ptr = torch.searchsorted(src[order].contiguous(), torch.arange(num_nodes + 1, device=device)).int()
         # the reference's `edges` dict maps a (u, v) PAIR to one id - the last one inserted (graph_parser.py:77-80);
-        # with parallel edges every slot of the pair therefore carries that id
+        # with parallel edges every slot of the pair therefore carries that id, and so does a start edge: get_contig_length
+        # (inference.py:29-36) looks the sampled (src, dst) up like every other step of the contig.  pair_eid: edge id -> that id
+        self.pair_eid = torch.arange(e, dtype=torch.int32, device=device)
         if e:
             key = src[order] * num_nodes + dst[order]
             uniq, inv = torch.unique(key, return_inverse=True)
             if uniq.numel() != e:
                 last = torch.zeros(uniq.numel(), dtype=torch.long, device=device).scatter_reduce(0, inv, order, "amax", include_self=False)
                 self.succ_eid = last[inv].int()
+                self.pair_eid[order] = self.succ_eid
         self.prefix_length = _i32_checked(prefix_length, "prefix_length").to(device).contiguous()
         self.read_length = _i32_checked(read_length, "read_length").to(device).contiguous()
         if self.prefix_length.numel() != e or self.read_length.numel() != num_nodes:
@@ -105,6 +108,7 @@ def greedy_walks(dg, visited, cand_eid, capacity=None):
     cand_eid = torch.as_tensor(cand_eid).to(dev).int().contiguous()
     p = int(cand_eid.numel())
     cs, cd = dg.src[cand_eid.long()].contiguous(), dg.dst[cand_eid.long()].contiguous()
+    cand_eid = dg.pair_eid[cand_eid.long()].contiguous()   # the kernel reads the start edge's prefix length through this id
     cap = int(capacity or (dg.num_nodes // 2 + 2))
     mk = lambda dt, *shape: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
     walks_f, walks_b = mk(torch.int32, p, cap), mk(torch.int32, p, cap)

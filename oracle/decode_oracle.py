@@ -96,18 +96,23 @@ def sample_edges(prob_edges, nb_paths):
 
 
 def get_contigs_greedy(src, dst, num_nodes, scores, prefix_length, read_length, len_threshold, nb_paths=50, sampler=None,
-                       trace=None):
-    """-> list of walks.  `sampler(prob, k)`: indices into the remaining edges (default: sample_edges)."""
+                       trace=None, use_labels=False):
+    """-> list of walks.  `sampler(prob, k)`: indices into the remaining edges (default: sample_edges).  use_labels: `scores`
+    are the 0 / 1 labels g.edata['y'], floored at 1e-9 and taken as the probabilities themselves (inference.py:178-181, :207-208)."""
     sampler = sampler or sample_edges
     succs, preds, edges = neighbor_dicts(src, dst, num_nodes)
-    logProbs = torch.log(torch.sigmoid(scores.float()))
+    if use_labels:
+        labels = scores.float()
+        logProbs = torch.log(labels.masked_fill(labels < 1e-9, 1e-9))
+    else:
+        logProbs = torch.log(torch.sigmoid(scores.float()))
     src_l, dst_l = src.tolist(), dst.tolist()
     all_contigs, visited = [], set()
     while True:
         remaining = [k for k in range(len(src_l)) if src_l[k] not in visited and dst_l[k] not in visited]
         if not remaining:
             break
-        prob_edges = torch.sigmoid(scores.float()[remaining])
+        prob_edges = scores.float()[remaining] if use_labels else torch.sigmoid(scores.float()[remaining])
         idx_edges = sampler(prob_edges, nb_paths)
         results = {}
         for idx in torch.as_tensor(idx_edges).tolist():

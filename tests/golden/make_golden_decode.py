@@ -1,6 +1,6 @@
-"""Generate tests/golden/g9_decode.pt from the REFERENCE's own decode functions.  Build container only:
+"""Generate tests/golden/g9_decode.pt and g15_decode_outer.pt from the REFERENCE's own decode functions.  Build container only:
 
-    python tests/golden/make_golden_decode.py        # needs /root/reference (read-only)
+    python tests/golden/make_golden_decode.py [g9] [outer]     # needs /root/reference (read-only); no argument = both
 
 inference.py imports DGL, so its functions are compiled one at a time from the file's syntax tree (as
 make_golden_closure.py does for train.py) and executed here with torch in scope - the reference's text runs, none of it
@@ -8,6 +8,12 @@ is stored.  Taken: greedy_forwards (:70-114), greedy_backwards_rc (:117-158), ru
 sample_edges (:54-67), with the module constants they read (RANDOM, early_stopping, p_threshold: inference.py:26-28).
 Inputs: small strand-symmetric synthetic graphs (gnnome_amd.synth conventions) with the successor / predecessor / edge
 dicts built as graph_parser.py:31-37, :55-58, :77-80 build them.  The fixture is data only.
+
+g15_decode_outer.pt pins the OUTER loop: get_contigs_greedy (:167-361) with get_subgraph (:40-51) and get_contig_length
+(:30-37), compiled the same way and run over a graph double (_graph_double.py: the few DGL calls they make, with the
+pair -> id and subgraph rules stated there) on simple graphs of tests/decode_graphs.py - hubs of 64 successors and more,
+tied scores, self-loops, jumped-over nodes.  Stored: the graphs, and per run the seed, len_threshold, nb_paths and the
+walks returned.  Checked here before saving: some run samples a self-loop and some chosen walk jumps over a node.
 """
 import ast
 import math
@@ -113,5 +119,70 @@ def main():
                 "torch": torch.__version__}, os.path.join(HERE, "g9_decode.pt"))
 
 
+def outer():
+    import contextlib
+    import io
+    import pickle
+    import tempfile
+    import types
+    from concurrent.futures import ThreadPoolExecutor
+    from datetime import datetime
+
+    sys.path.insert(1, os.path.join(ROOT, "tests"))
+    sys.path.insert(1, HERE)
+    from _graph_double import Graph, dgl
+    from decode_graphs import adversarial_graph
+
+    scope = {"torch": torch, "math": math, "os": os, "pickle": pickle, "dgl": dgl, "datetime": datetime,
+             "ThreadPoolExecutor": ThreadPoolExecutor, "utils": types.SimpleNamespace(timedelta_to_str=str),
+             "RANDOM": False, "early_stopping": False, "p_threshold": 0.06, "DEBUG": False}
+    names = ["get_contig_length", "get_subgraph", "sample_edges", "greedy_forwards", "greedy_backwards_rc", "run_greedy_both_ways",
+             "get_contigs_greedy"]
+    get_contigs_greedy = reference_functions(os.path.join(REF, "inference.py"), names, scope)[-1]
+    drawn = []
+    inner_sample = scope["sample_edges"]
+
+    def watching_sample(prob_edges, nb_paths):       # the reference's draw, unchanged; only remembered
+        idx = inner_sample(prob_edges, nb_paths)
+        drawn.append(idx.clone())
+        return idx
+    scope["sample_edges"] = watching_sample
+
+    cases, loops_sampled, jumped = [], 0, 0
+    for name, kw, runs in [
+            ("hub64_ties", dict(seed=901, hubs=("d64", "mid"), reads=50, self_loops=4), [(1, 0, 8), (2, 40_000, 8), (3, 10 ** 9, 4)]),
+            ("hub65_wide", dict(seed=902, hubs=("d65", "wide"), reads=60, self_loops=4), [(4, 0, 1), (5, 0, 30), (6, 60_000, 30)]),
+            ("small_hubs", dict(seed=903, hubs=("d2", "d3", "d4", "mid"), reads=40, self_loops=6), [(7, 0, 100), (8, 20_000, 5)])]:
+        g = adversarial_graph(parallel=0.0, **kw)
+        succs, preds, edges = dicts(g["src"], g["dst"], g["num_nodes"])
+        assert len(edges) == g["src"].numel(), "simple graphs only"
+        graph = Graph(g["src"], g["dst"], g["num_nodes"], {"read_length": g["read_length"]},
+                      {"score": g["scores"], "prefix_length": g["prefix_length"]})
+        out = []
+        for seed, threshold, nb_paths in runs:
+            torch.manual_seed(seed)
+            del drawn[:]
+            with tempfile.TemporaryDirectory() as tmp, contextlib.redirect_stdout(io.StringIO()):
+                walks = get_contigs_greedy(graph, succs, preds, edges, threshold, nb_paths=nb_paths, checkpoint_dir=tmp)
+            walks = [[int(x) for x in w] for w in walks]
+            out.append({"seed": seed, "len_threshold": threshold, "nb_paths": nb_paths, "walks": walks})
+            # properties of the run, recomputed from what it returned: was a self-loop among the FIRST iteration's start edges
+            # (all edges remain then), does a chosen walk jump over a node
+            first = drawn[0].tolist()
+            loops_sampled += sum(int(g["src"][k]) == int(g["dst"][k]) for k in first)
+            jumped += sum(bool(set(succs[a]) & set(preds[b])) for w in walks for a, b in zip(w[:-1], w[1:]))
+            print(name, "seed", seed, "threshold", threshold, "paths", nb_paths, "->", len(walks), "walks, lengths", [len(w) for w in walks][:12])
+        cases.append({"name": name, "src": g["src"].to(torch.int16), "dst": g["dst"].to(torch.int16), "num_nodes": g["num_nodes"],
+                      "scores": g["scores"], "prefix_length": g["prefix_length"].to(torch.int32),
+                      "read_length": g["read_length"].to(torch.int32), "max_out_degree": max(len(v) for v in succs.values()), "runs": out})
+    assert loops_sampled >= 1 and jumped >= 1, (loops_sampled, jumped)
+    print("self-loop start edges in first iterations:", loops_sampled, " steps that jump over a node:", jumped)
+    torch.save({"cases": cases, "made_with": "tests/golden/make_golden_decode.py outer (reference functions via ast, _graph_double.py)",
+                "torch": torch.__version__}, os.path.join(HERE, "g15_decode_outer.pt"))
+
+
 if __name__ == "__main__":
-    main()
+    if not sys.argv[1:] or "g9" in sys.argv[1:]:
+        main()
+    if not sys.argv[1:] or "outer" in sys.argv[1:]:
+        outer()
