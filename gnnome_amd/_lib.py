@@ -117,9 +117,15 @@ SIGNATURES = {
     "gnnome_kway_gains": [_p, _p, _p, _p, _l, _p, _p, _p],
     "gnnome_greedy_growing_host": [_p, _p, _p, _p, _l, _i, _p],
     "gnnome_edge_loss_f32": [_p, _p, _p, _l, _p, ctypes.c_float, ctypes.c_float, _p, _p, _p, _p, _p, _sz, _p],
+    "gnnome_gfa_tile_sizes": [ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    "gnnome_gfa_mark": [_p, _l, _p, _p, _p],
+    "gnnome_gfa_classify": [_p, _l, _p, _p, _l, _p, _l, _p, _p, _p, _p, _p],
+    "gnnome_gfa_names_insert": [_p, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p],
+    "gnnome_gfa_links": [_p, _l, _p, _p, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p, _p],
+    "gnnome_gfa_pack": [_p, _l, _p, _p, _l, _p, _l, _p],
 }
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 # the parameter blocks of gnnome_model_forward_f32 (include/gnnome_hip.h), field for field

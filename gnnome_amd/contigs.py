@@ -102,6 +102,19 @@ class ReadStore:
             seqs.append(found[rid])
         return cls.from_sequences(seqs, keep=mask, device=device)
 
+    @classmethod
+    def from_packed(cls, data, off, keep=None):
+        """From reads already packed on the device - gfa.read_gfa_device's g["reads"]: (uint8[total], int64[R+1]).  keep: read indices
+        (or a bool mask) to store; the others become zero-length slots and `missing` is set, as in the other constructors.  The
+        restriction is one gnnome_gfa_pack over the kept lengths; nothing visits the host."""
+        if keep is None:
+            return cls(data, off)
+        from .gfa import _pack
+        mask = _keep_mask(keep, int(off.numel()) - 1)
+        lengths = (off[1:] - off[:-1]) * torch.from_numpy(mask).to(off.device)
+        kept, kept_off = _pack(_lib.load(), data, off[:-1], lengths, data.device)
+        return cls(kept, kept_off, ~mask)
+
     def sequence(self, node):
         """Node `node` as a str (host; for checks)."""
         r = node >> 1

@@ -37,12 +37,19 @@ title strand x A-line orientation, >= 0 -> +1; start: min; end: max; chromosome:
 the strand and 2k+1 its opposite.  New keys read_strand, read_start, read_end, read_chr (int64[N]) and y (float32[E], edge-id order),
 the labels of utils/labels.py computed on the device by gnnome_amd.labels (csrc/edge_labels.hip).  `labels` follows `similarity`:
 "auto" labels on the device when there is one, else y is None with a warning; "device" insists; False leaves y None.  A read missing
-from the file, or a title without one of the four fields, raises ValueError naming the read and the file."""
+from the file, or a title without one of the four fields, raises ValueError naming the read and the file.
+
+read_gfa_device / read_gfa(parser="device" | "auto") is a second implementation of the same statement on the MI355X
+(csrc/gfa_parse.hip): the file's bytes go to the device once and come back as the same dict, tensors on the device, plus
+"reads" - the S-line sequences packed as overlap.pack_reads packs them.  What it declines (GfaDeviceError names the line) is
+listed at _DECLINED; parser="auto" then runs the host parser, which returns or raises as it always did."""
 import gzip
+import os
 import re
 import warnings
 from collections import Counter
 
+import numpy as np
 import torch
 
 _HIFIASM_ID = re.compile(r"(.*):\d-\d*")
@@ -96,14 +103,44 @@ def _node_annotations(node_to_read, num_nodes, reads_path):
     return [torch.tensor(c, dtype=torch.int64) for c in cols]
 
 
-def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, training=False, labels="auto"):
+def _add_training(out, reads_path, labels):
+    """read_strand, read_start, read_end, read_chr and y into `out` (the module docstring's training=True)."""
+    keys = ("read_strand", "read_start", "read_end", "read_chr")
+    out.update(zip(keys, _node_annotations(out["node_to_read"], out["num_nodes"], reads_path)))
+    out["y"] = None
+    if labels == "device":
+        from .labels import process_graph
+        out["y"] = process_graph(out)[1].cpu()
+    elif labels == "auto":
+        if torch.cuda.is_available():
+            from .labels import process_graph
+            try:
+                out["y"] = process_graph(out)[1].cpu()
+            except (RuntimeError, OSError) as ex:
+                warnings.warn(f"read_gfa: edge labels not computed on the device ({ex}); y is None")
+        else:
+            warnings.warn("read_gfa: no GPU, so the edge labels (y) were not computed; y is None")
+
+
+def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, training=False, labels="auto", parser="host"):
     """-> dict(src, dst int64[E]; num_nodes; overlap_length, prefix_length int64[E]; read_length int64[N];
     overlap_similarity float32[E] | None; read_to_node, node_to_read, read_to_node2; read_seqs | None);
-    training=True adds read_strand, read_start, read_end, read_chr int64[N] and y float32[E] | None (see the module docstring)."""
+    training=True adds read_strand, read_start, read_end, read_chr int64[N] and y float32[E] | None (see the module docstring).
+    parser: "host" (this function's own loop), "device" (read_gfa_device, its tensors moved to the CPU: the same dict key for key,
+    or GfaDeviceError where the device parser declines the file), "auto" (the device when there is one, the host parser whenever
+    the device parser reports anything at all)."""
     if training and reads_path is None:
         raise ValueError("read_gfa(training=True) needs reads_path: the FASTA / FASTQ whose titles carry the read positions")
     if labels not in ("auto", "device", False, None):
         raise ValueError(f"labels={labels!r}: expected 'auto', 'device' or False")
+    if parser not in ("host", "device", "auto"):
+        raise ValueError(f"parser={parser!r}: expected 'host', 'device' or 'auto'")
+    if parser == "device" or (parser == "auto" and not callable(similarity) and torch.cuda.is_available()):
+        try:
+            return _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels)
+        except Exception:   # noqa: BLE001 ("auto": whatever the device parser reports, the host parser answers)
+            if parser == "device":
+                raise
     opener = gzip.open if str(path).endswith(".gz") else open
     with opener(path, "rt") as f:
         lines = f.readlines()
@@ -201,21 +238,7 @@ def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, tra
             except (RuntimeError, ValueError, OSError) as ex:
                 warnings.warn(f"read_gfa: overlap similarities not computed on the device ({ex}); overlap_similarity is None")
     if training:
-        keys = ("read_strand", "read_start", "read_end", "read_chr")
-        out.update(zip(keys, _node_annotations(node_to_read, node_idx, reads_path)))
-        out["y"] = None
-        if labels == "device":
-            from .labels import process_graph
-            out["y"] = process_graph(out)[1].cpu()
-        elif labels == "auto":
-            if torch.cuda.is_available():
-                from .labels import process_graph
-                try:
-                    out["y"] = process_graph(out)[1].cpu()
-                except (RuntimeError, OSError) as ex:
-                    warnings.warn(f"read_gfa: edge labels not computed on the device ({ex}); y is None")
-            else:
-                warnings.warn("read_gfa: no GPU, so the edge labels (y) were not computed; y is None")
+        _add_training(out, reads_path, labels)
     return out
 
 
@@ -237,3 +260,282 @@ def write_similarity_tags(gfa_in, gfa_out, similarity):
                 if key in similarity:
                     raw = raw.rstrip("\n") + f"\tSI:f:{similarity[key]:.9g}\n"
             o.write(raw)
+
+
+# ---- the device parser (csrc/gfa_parse.hip) ---------------------------------------------------------------------------------------
+
+TOKENISE_TILE = 4096    # bytes one workgroup of gnnome_gfa_mark covers (gnnome_gfa_tile_sizes reports the library's own)
+PACK_TILE = 16384       # output bytes one workgroup of gnnome_gfa_pack writes
+TAG_SLOT = 32           # bytes of the slot an SI:f: value is packed into (the value itself: at most 31)
+_REC = 8
+_NONZERO_CHUNK = 1 << 30
+
+# What the device parser declines, by the code gnnome_gfa_classify / _names_insert / _links leave on the line
+_DECLINED = {
+    1: "an S line with fewer than 4 fields",
+    2: "the length after LN:i: is not 1-18 plain digits",
+    3: "an L line without 6, 7 or 8 fields",
+    4: "a 7-field link whose segment name has no :<digit>- suffix",
+    5: "the overlap in front of the CIGAR letter is not 1-18 plain digits",
+    6: "an SI:f: value longer than 31 bytes",
+    7: "an SI:f: value that is not plain decimal text",
+    8: "an A line of a unitig's run with fewer than 5 fields",
+    9: "a second S line with this segment name",
+    10: "an L line naming an unknown segment",
+    11: "an L line naming a segment that is defined on a later line",
+    12: "a byte >= 0x80",
+    13: "a carriage return that no line feed follows",
+    14: "field descriptors that do not belong to this buffer",
+    15: "the name table is full",
+}
+
+
+class GfaDeviceError(ValueError):
+    """The device parser declines the file: .line (1-based) and .reason; read_gfa's host parser takes any GFA."""
+
+    def __init__(self, path, line, reason):
+        super().__init__(f"{path}: line {line}: {reason} - not served by the device parser (read_gfa(parser='host') or 'auto')")
+        self.line, self.reason = line, reason
+
+
+def assemble_edges(u, v, overlap, tag, num_nodes):
+    """Events in file order -> (src, dst, overlap_length, tag) of the edges, on the events' device (torch sorts and segment firsts /
+    lasts only, so it runs on CPU tensors as well).  Event 2j is line j's (sr, dr), 2j+1 its (sv, dv).  A repeated (u, v) is one edge
+    at the position of its FIRST event with the overlap and tag of its LAST (networkx's adjacency dicts, graph_parser.py:323-340);
+    the edges come by u, then by first event (dgl.from_networkx, :407).  `tag`: any per-event tensor."""
+    T = int(u.numel())
+    if T == 0:
+        return u, v, overlap, tag
+    ks, order = torch.sort(u * int(num_nodes) + v, stable=True)   # ties keep file order
+    start = torch.ones(T, dtype=torch.bool, device=u.device)
+    start[1:] = ks[1:] != ks[:-1]
+    first_pos = torch.nonzero(start).squeeze(1)
+    last_pos = torch.cat([first_pos[1:] - 1, first_pos.new_tensor([T - 1])])
+    first_ev, last_ev = order[first_pos], order[last_pos]
+    by = torch.argsort(u[first_ev] * T + first_ev)                # distinct keys
+    first_ev, last_ev = first_ev[by], last_ev[by]
+    return u[first_ev], v[first_ev], overlap[last_ev], tag[last_ev]
+
+
+def _positions(marks, bit):
+    """int64 positions of the bytes that carry `bit`, in rising order (nonzero in pieces: a file may exceed 2^31 bytes)."""
+    n = int(marks.numel())
+    parts = [torch.nonzero(marks[a:a + _NONZERO_CHUNK] & bit).squeeze(1) + a for a in range(0, n, _NONZERO_CHUNK)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=marks.device)
+
+
+def _pack(lib, src, src_beg, lengths, device):
+    """(uint8[total], int64[R+1]): src[src_beg[r] : src_beg[r] + lengths[r]] for every r, concatenated (gnnome_gfa_pack)."""
+    from .ops import _on, _ptr, _stream
+    R = int(lengths.numel())
+    off = torch.zeros(R + 1, dtype=torch.int64, device=device)
+    torch.cumsum(lengths, 0, out=off[1:])
+    total = int(off[-1]) if R else 0
+    out = torch.empty(total, dtype=torch.uint8, device=device)
+    src_beg = src_beg.contiguous()
+    if total:
+        with _on(device):
+            _lib_check(lib.gnnome_gfa_pack(_ptr(src), int(src.numel()), _ptr(src_beg), _ptr(off), R, _ptr(out), total, _stream(device)),
+                       "gfa_pack")
+    return out, off
+
+
+def _lib_check(rc, what):
+    from . import _lib
+    _lib.check(rc, what)
+
+
+def _texts(lib, buf, beg, end, device):
+    """The fields [beg, end) as a list of str: one blob, the fields joined by '\\n', one copy to the host, one split."""
+    k = int(beg.numel())
+    if k == 0:
+        return []
+    blob, off = _pack(lib, buf, beg, end - beg + 1, device)   # one byte more than the field: the whitespace behind it
+    blob[off[1:] - 1] = 10
+    return blob.cpu().numpy().tobytes().decode("ascii").split("\n")[:-1]
+
+
+def _read_bytes(path):
+    if str(path).endswith(".gz"):
+        with gzip.open(path, "rb") as f:
+            return np.frombuffer(f.read(), dtype=np.uint8).copy()
+    with open(path, "rb") as f:
+        data = np.empty(os.fstat(f.fileno()).st_size, dtype=np.uint8)
+        got = 0
+        while got < data.size:
+            k = f.readinto(memoryview(data)[got:])
+            if not k:
+                break
+            got += k
+        return data[:got]
+
+
+def _parse_on_device(data, device, path="<bytes>", table_capacity=None):
+    """uint8 bytes of a GFA (numpy or tensor) -> the device-side parse: dict(num_nodes, src, dst, overlap_length, tag_begin, tag_length
+    per edge, read_length, buf, seg / arun records for the names, reads).  Raises GfaDeviceError for what _DECLINED lists."""
+    from . import _lib
+    from .ops import _on, _ptr, _stream
+    lib = _lib.load()
+    buf = (torch.from_numpy(data) if isinstance(data, np.ndarray) else data).to(device).contiguous()
+    n = int(buf.numel())
+    i64 = dict(dtype=torch.int64, device=device)
+    i32 = dict(dtype=torch.int32, device=device)
+    marks = torch.empty(n, dtype=torch.uint8, device=device)
+    bad_pos = torch.full((2,), torch.iinfo(torch.int64).max, **i64)
+    first_bad = torch.full((1,), torch.iinfo(torch.int32).max, **i32)
+    with _on(device):
+        _lib.check(lib.gnnome_gfa_mark(_ptr(buf), n, _ptr(marks), _ptr(bad_pos), _stream(device)), "gfa_mark")
+    fs, fe, ls = _positions(marks, 1), _positions(marks, 2), _positions(marks, 4)
+    del marks
+    F, L = int(fs.numel()), int(ls.numel())
+    ff = torch.empty(L + 1, **i64)
+    ff[:L] = torch.searchsorted(fs, ls)
+    ff[L] = F
+    kind = torch.zeros(L, **i32)
+    rec = torch.empty(L, _REC, **i64)
+    err = torch.zeros(L, **i32)
+    with _on(device):
+        _lib.check(lib.gnnome_gfa_classify(_ptr(buf), n, _ptr(fs), _ptr(fe), F, _ptr(ff), L, _ptr(kind), _ptr(rec), _ptr(err),
+                                           _ptr(first_bad), _stream(device)), "gfa_classify")
+    nf = ff[1:] - ff[:-1]
+    del fs, fe
+    s_line = torch.nonzero(kind == 1).squeeze(1)
+    l_line = torch.nonzero(kind == 2).squeeze(1)
+    R, M = int(s_line.numel()), int(l_line.numel())
+    srec, lrec = rec[s_line].contiguous(), rec[l_line].contiguous()
+    cap = int(table_capacity) if table_capacity is not None else max(2, 1 << (2 * R).bit_length())
+    table = torch.full((cap,), -1, **i32)
+    ev_u, ev_v = torch.empty(2 * M, **i64), torch.empty(2 * M, **i64)
+    with _on(device):
+        _lib.check(lib.gnnome_gfa_names_insert(_ptr(buf), n, _ptr(srec), _ptr(s_line), R, _ptr(table), cap, _ptr(err), L, _ptr(first_bad),
+                                               _stream(device)), "gfa_names_insert")
+        _lib.check(lib.gnnome_gfa_links(_ptr(buf), n, _ptr(lrec), _ptr(l_line), M, _ptr(srec), _ptr(s_line), R, _ptr(table), cap, _ptr(err),
+                                        L, _ptr(first_bad), _ptr(ev_u), _ptr(ev_v), _stream(device)), "gfa_links")
+    # A lines: one belongs to a segment when the nearest line above that is not an A line is a utg* S line (gfa.py's inner loop)
+    line_id = torch.arange(L, **i64)
+    is_a = kind == 3
+    above = torch.cummax(torch.where(is_a, line_id.new_full((), -1), line_id), 0)[0] if L else line_id
+    owner_ok = above >= 0
+    above = above.clamp(min=0)
+    in_run = is_a & owner_ok & (kind[above] == 1) & ((rec[above, 5] & 2) != 0) if L else is_a
+    a_line = torch.nonzero(in_run).squeeze(1)
+    a_short = a_line[nf[a_line] < 5]
+    big = torch.iinfo(torch.int64).max
+    report = torch.stack([first_bad[0].long(), a_short.min() if a_short.numel() else first_bad.new_tensor(big, dtype=torch.int64),
+                          bad_pos[0], bad_pos[1]]).cpu().tolist()     # the one synchronisation that reports
+    bad_line, a_bad, hi_pos, cr_pos = report
+    cands = []
+    for pos, code in ((hi_pos, 12), (cr_pos, 13)):
+        if pos != big:
+            cands.append((int(torch.searchsorted(ls, ls.new_tensor([pos]), right=True)) - 1, 0, code))
+    if bad_line != torch.iinfo(torch.int32).max:
+        cands.append((bad_line, 1, int(err[bad_line])))
+    if a_bad != big:
+        cands.append((a_bad, 2, 8))
+    if cands:
+        line, _, code = min(cands)
+        raise GfaDeviceError(path, line + 1, _DECLINED.get(code, f"code {code}"))
+    valid = ev_u >= 0
+    ev = torch.nonzero(valid).squeeze(1)
+    u, v = ev_u[ev], ev_v[ev]
+    ol_ev = lrec[:, 4][ev >> 1] if M else ev
+    src, dst, ol, last = assemble_edges(u, v, ol_ev, ev >> 1, 2 * R)
+    ln = srec[:, 4]
+    out = {"num_nodes": 2 * R, "src": src, "dst": dst, "overlap_length": ol, "read_length": torch.repeat_interleave(ln, 2),
+           "tag_begin": lrec[last, 6] if M else last, "tag_length": lrec[last, 7] if M else last,
+           "buf": buf, "lib": lib, "seg_rec": srec, "arun_rec": rec[a_line], "reads": None}
+    out["arun_owner"] = (torch.cumsum((kind == 1).long(), 0) - 1)[above[a_line]] if L else a_line
+    if R and not bool((srec[:, 5] & 1).any()):
+        out["reads"] = _pack(lib, buf, srec[:, 2], srec[:, 3] - srec[:, 2], device)
+    elif R == 0:
+        out["reads"] = (torch.zeros(0, dtype=torch.uint8, device=device), torch.zeros(1, **i64))
+    return out
+
+
+def _names(p, device):
+    """read_to_node, node_to_read, read_to_node2 from the parse (host dicts; per-item Python only over the utg* segments)."""
+    lib, buf, srec, arec = p["lib"], p["buf"], p["seg_rec"], p["arun_rec"]
+    names = _texts(lib, buf, srec[:, 0], srec[:, 1], device)
+    R = len(names)
+    pairs = list(zip(range(0, 2 * R, 2), range(1, 2 * R, 2)))
+    read_to_node = dict(zip(names, pairs))
+    node_to_read = dict(zip(range(2 * R), (nm for nm in names for _ in (0, 1))))
+    read_to_node2 = {}
+    utg = torch.nonzero((srec[:, 5] & 2) != 0).squeeze(1).cpu().tolist() if R else []
+    if utg:
+        a_reads = _texts(lib, buf, arec[:, 0], arec[:, 1], device)
+        a_orient = _texts(lib, buf, arec[:, 2], arec[:, 3], device)
+        owner = p["arun_owner"].cpu().numpy()
+        count = np.bincount(owner, minlength=R) if owner.size else np.zeros(R, dtype=np.int64)
+        first = np.concatenate([[0], np.cumsum(count)])
+        read_to_node2 = dict(zip(a_reads, (pairs[k] for k in owner.tolist())))
+        items = list(zip(a_reads, a_orient))
+        for k in utg:
+            node_to_read[2 * k] = node_to_read[2 * k + 1] = items[first[k]:first[k + 1]]
+    return read_to_node, node_to_read, read_to_node2
+
+
+def _tag_values(p, device):
+    """float32[E] from the SI:f: text of every edge: 32-byte slots gathered on the device, ONE vectorised cast on the host."""
+    E = int(p["src"].numel())
+    buf, beg, length = p["buf"], p["tag_begin"], p["tag_length"]
+    col = torch.arange(TAG_SLOT, dtype=torch.int64, device=device)
+    idx = (beg[:, None] + col[None, :]).clamp(max=int(buf.numel()) - 1)
+    slots = torch.where(col[None, :] < length[:, None], buf[idx], buf.new_zeros(()))
+    values = np.frombuffer(slots.cpu().numpy().tobytes(), dtype=f"S{TAG_SLOT}").astype(np.float64).astype(np.float32)
+    assert values.size == E
+    return torch.from_numpy(values).to(device)
+
+
+def read_gfa_device(path, similarity="auto", device=None, keep_names=True):
+    """read_gfa's dict from the device parser, every tensor on `device` (same keys, dtypes and edge order; read_seqs is None), plus
+    "reads": (uint8[total], int64[R+1]) on the device - the S-line sequences, forward strand, in S-line order as overlap.pack_reads
+    lays them out - or None when an S line says '*'.  similarity: "auto", "device", None or False (SI:f: tags when every edge carries
+    one; else, with sequences and similarity not None / False, overlap.edit_distances on g["reads"] - "device" insists, "auto" warns
+    and leaves None); a callable belongs to read_gfa's host parser.  keep_names=False leaves read_to_node, node_to_read and
+    read_to_node2 None (for a caller that only scores).  Raises GfaDeviceError for the inputs _DECLINED lists."""
+    if callable(similarity):
+        raise ValueError("read_gfa_device takes no similarity callable (it would need every read on the host): use read_gfa(path, "
+                         "similarity=callable), the host parser")
+    if similarity not in ("auto", "device", None, False):
+        raise ValueError(f"similarity={similarity!r}: expected 'auto', 'device', None or False")
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    p = _parse_on_device(_read_bytes(path), device, path=str(path))
+    src, dst, ol = p["src"], p["dst"], p["overlap_length"]
+    out = {"src": src, "dst": dst, "num_nodes": p["num_nodes"], "overlap_length": ol,
+           "prefix_length": (p["read_length"][src] - ol) if src.numel() else ol.clone(), "read_length": p["read_length"],
+           "read_to_node": None, "node_to_read": None, "read_to_node2": None, "read_seqs": None, "overlap_similarity": None,
+           "reads": p["reads"]}
+    if keep_names:
+        out["read_to_node"], out["node_to_read"], out["read_to_node2"] = _names(p, device)
+    if src.numel() and bool((p["tag_length"] >= 0).all()):
+        out["overlap_similarity"] = _tag_values(p, device)
+    elif similarity not in (None, False) and p["reads"] is not None and p["num_nodes"]:
+        from .overlap import edit_distances
+        if similarity == "device":
+            out["overlap_similarity"] = edit_distances(p["reads"], src, dst, ol, device)[1]
+        else:
+            try:
+                out["overlap_similarity"] = edit_distances(p["reads"], src, dst, ol, device)[1]
+            except (RuntimeError, ValueError, OSError) as ex:
+                warnings.warn(f"read_gfa_device: overlap similarities not computed on the device ({ex}); overlap_similarity is None")
+    return out
+
+
+def _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels):
+    """read_gfa(parser="device"): read_gfa_device's dict on the CPU, with read_seqs and the training keys built on the host."""
+    g = read_gfa_device(path, similarity=similarity)
+    reads = g.pop("reads")
+    out = {k: (t.cpu() if torch.is_tensor(t) else t) for k, t in g.items()}
+    if keep_sequences:
+        if reads is None:
+            raise GfaDeviceError(path, 1, "keep_sequences with S lines that say '*'")
+        text, off = reads[0].cpu().numpy().tobytes().decode("ascii"), reads[1].cpu().tolist()
+        seqs = {}
+        for r in range(len(off) - 1):
+            seqs[2 * r] = text[off[r]:off[r + 1]]
+            seqs[2 * r + 1] = seqs[2 * r].translate(_COMPLEMENT)[::-1]
+        out["read_seqs"] = seqs
+    if training:
+        _add_training(out, reads_path, labels)
+    return out

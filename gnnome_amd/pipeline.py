@@ -31,10 +31,25 @@ def score_graph(g, model, device=None):
         return model(views, x, e).squeeze(1)
 
 
-def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto", device=None, scores=None, sampler=None):
-    """-> (walks, scores, graph dict).  `scores` overrides the model (inference.py:426-432: saved predictions / labels)."""
+def _read(path, similarity, parser, device):
+    """The graph dict of a GFA by `parser`: "host" = gfa.read_gfa; "device" = gfa.read_gfa_device, tensors and packed reads left on the
+    device; "auto" = the device parser, and the host parser whenever that one reports anything."""
+    if parser not in ("host", "device", "auto"):
+        raise ValueError(f"parser={parser!r}: expected 'host', 'device' or 'auto'")
+    if parser == "device" or (parser == "auto" and not callable(similarity) and torch.cuda.is_available()):
+        try:
+            return gfa.read_gfa_device(path, similarity=similarity, device=device)
+        except Exception:   # noqa: BLE001
+            if parser == "device":
+                raise
+    return gfa.read_gfa(path, similarity=similarity)
+
+
+def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto", device=None, scores=None, sampler=None, parser="host"):
+    """-> (walks, scores, graph dict).  `scores` overrides the model (inference.py:426-432: saved predictions / labels).
+    parser: how a GFA path is read (gfa.read_gfa's parser=; with "device" the graph's tensors stay on the device)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
-    g = gfa_or_graph if isinstance(gfa_or_graph, dict) else gfa.read_gfa(gfa_or_graph, similarity=similarity)
+    g = gfa_or_graph if isinstance(gfa_or_graph, dict) else _read(gfa_or_graph, similarity, parser, device)
     if scores is None:
         scores = score_graph(g, model, device)
     prefix = g["prefix_length"].masked_fill(g["prefix_length"] < 0, 0)      # inference.py:461
@@ -43,16 +58,25 @@ def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto"
 
 
 def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, nb_paths=100, similarity="auto", device=None, scores=None,
-                      sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None):
+                      sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, parser="host"):
     """GFA -> scores -> greedy walks -> contigs spelled on the device -> FASTA at out_path (inference.py:411-489).
     -> (walks, contigs, stats); stats = quick_evaluation's figures as a dict (ref_length from the caller: NG50 and the
     reconstructed fraction are -1 without it).  Sequences: the GFA's S lines if it carries them, else `reads` (a FASTA / FASTQ
     path, plain or .gz, or a ReadStore); with neither this raises before any scoring.  Only the reads the walks touch are
-    uploaded.  The prefixes are masked as pipeline.assemble masks them (inference.py:461)."""
+    uploaded.  The prefixes are masked as pipeline.assemble masks them (inference.py:461).  parser="device" / "auto": the GFA is read
+    once, by gfa.read_gfa_device, and its sequences are the packed reads that parse left on the device, restricted to the touched ones."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     gfa_path = None if isinstance(gfa_or_graph, dict) else gfa_or_graph
+    if gfa_path is not None and parser != "host":
+        gfa_or_graph = _read(gfa_path, similarity, parser, device)
+        if "reads" in gfa_or_graph:     # device-parsed: nothing below opens the GFA again
+            gfa_path = None
+    elif parser not in ("host", "device", "auto"):
+        raise ValueError(f"parser={parser!r}: expected 'host', 'device' or 'auto'")
     if isinstance(reads, contigs_mod.ReadStore):
         source = "store"
+    elif isinstance(gfa_or_graph, dict) and gfa_or_graph.get("reads") is not None:
+        source = "packed"
     elif gfa_path is not None and contigs_mod.gfa_sequences(gfa_path) is not None:
         source = "gfa"
     elif reads is not None:
@@ -70,6 +94,8 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
     touched = sorted({v >> 1 for w in walks for v in w})
     if source == "store":
         store = reads
+    elif source == "packed":
+        store = contigs_mod.ReadStore.from_packed(*g["reads"], keep=touched)
     elif source == "gfa":
         store = contigs_mod.ReadStore.from_gfa(gfa_path, keep=touched, device=device)
     elif source == "file":

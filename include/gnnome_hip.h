@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 20
+#define GNNOME_ABI_VERSION 21
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -837,6 +837,50 @@ int gnnome_kway_gains(const int32_t* ptr, const int32_t* adj, const int32_t* wgt
  * part.  label_host[v] in [0, num_parts).  (train.py:333: dgl.metis_partition -> METIS 5.1.0 InitKWayPartitioning; see csrc/partition.hip.) */
 int gnnome_greedy_growing_host(const int32_t* ptr_host, const int32_t* adj_host, const int32_t* wgt_host, const int32_t* vwgt_host,
                                int64_t num_vertices, int num_parts, int32_t* label_host);
+
+/* ---- GFA ingestion: parse, resolve names, pack the reads ----------------------------------------------------------------------------
+ * Replaces the line loop of graph_parser.py:159-340 (only_from_gfa) as gnnome_amd/gfa.py read_gfa states it; the file's bytes are on the
+ * device (buf uint8[num_bytes]).  Whitespace is str.split()'s in ASCII (0x09-0x0d, 0x1c-0x20); a line ends at '\n'.  Compaction of the
+ * marks, the scans and the sorts between these entries are torch operators (gnnome_amd/gfa.py read_gfa_device).  Nothing here produces a
+ * float; no float atomics.
+ * gnnome_gfa_tile_sizes: bytes per workgroup of gnnome_gfa_mark and output bytes per workgroup of gnnome_gfa_pack (host, no launch).
+ * gnnome_gfa_mark (graph_parser.py:160, :167: strip().split() of every line, elementwise): marks uint8[num_bytes], bit 0 = first byte of a
+ *   field, bit 1 = last byte of a field, bit 2 = first byte of a line (also of an empty one).  bad_pos int64[2], preset to INT64_MAX by the
+ *   caller: lowered (atomicMin) to the first byte >= 0x80 and to the first '\r' that no '\n' follows.
+ * gnnome_gfa_classify (:167-208 S and A lines, :276-300 L lines): one thread per line.  field_start / field_end int64[num_fields] = the
+ *   positions of bits 0 / 1 in rising order; line_field int64[num_lines+1] = the index of the first field at or after every line start,
+ *   line_field[num_lines] = num_fields.  kind int32[L]: 0 other or blank, 1 S, 2 L, 3 A.  rec int64[L,8], byte ranges as [begin, end):
+ *     S: name, sequence (field 3), LN = int(field4[5:]), bit 0 the sequence is "*" | bit 1 the name starts with "utg", -, -
+ *     L: name 1, name 2 (after every SI:f: field is dropped when one stands at index >= 6, and, with 7 fields left, without the hifiasm
+ *        suffix: everything from the LAST ":<digit>-" on), overlap = int(cigar[:-1]), orientation case 0 "++" 1 "+-" 2 "-+" 3 anything
+ *        else, begin and length of the first SI:f: value (-1, -1 without one)
+ *     A: field 5 (the read), field 4 (its orientation); -1 with fewer than 5 fields
+ *   err int32[L]: 0, or why the line cannot be served: 1 S line with < 4 fields, 2 LN not 1-18 plain digits, 3 L line without 6, 7 or 8
+ *   fields, 4 a 7-field name without a suffix, 5 overlap not 1-18 plain digits, 6 a tag value above 31 bytes, 7 a tag value that is not
+ *   plain decimal text (6 and 7 only where the overlap is not zero), 14 descriptors that gnnome_gfa_mark did not produce.
+ *   first_bad int32[1], preset to INT32_MAX: lowered to the smallest line with a code, by this entry and the next two.
+ * gnnome_gfa_names_insert (:174-175 read_to_node): seg_rec int64[R,8] / seg_line int64[R] = rec and line number of the S lines in file
+ *   order; table int32[capacity] preset to -1, capacity a power of two above R.  Linear probing; a slot is claimed with a 32-bit
+ *   compare-and-swap and every probe compares length and bytes, so hash collisions cost probes and change no answer.  A slot ends up with
+ *   the SMALLEST S index of its name; every later S line of that name gets code 9 (15: no free slot).  Independent of arrival order.
+ * gnnome_gfa_links (:302-321): link_rec / link_line of the L lines; for link m without a code and with overlap != 0, both names are looked
+ *   up (code 10: unknown, 11: defined on a later line) and event_u / event_v int64[2M] receive (sr, dr) at 2m and (sv, dv) at 2m+1;
+ *   -1 where the link contributes nothing.
+ * gnnome_gfa_pack (:183-184, and overlap.pack_reads): out[out_off[r] : out_off[r+1]] = src[src_beg[r] : ...] for r < num_items, out_off
+ *   int64[num_items+1] rising from 0 to out_bytes (a scan of the lengths; a keep mask enters as zero lengths).  Fixed tiles of the
+ *   OUTPUT, a binary search for the tile's first item, 16-byte stores where aligned; reads outside src are skipped, not made. */
+int gnnome_gfa_tile_sizes(int* tokenise_tile_host, int* pack_tile_host);
+int gnnome_gfa_mark(const uint8_t* buf, int64_t num_bytes, uint8_t* marks, int64_t* bad_pos, void* stream);
+int gnnome_gfa_classify(const uint8_t* buf, int64_t num_bytes, const int64_t* field_start, const int64_t* field_end, int64_t num_fields,
+                        const int64_t* line_field, int64_t num_lines, int32_t* kind, int64_t* rec, int32_t* err, int32_t* first_bad,
+                        void* stream);
+int gnnome_gfa_names_insert(const uint8_t* buf, int64_t num_bytes, const int64_t* seg_rec, const int64_t* seg_line, int64_t num_segments,
+                            int32_t* table, int64_t capacity, int32_t* err, int64_t num_lines, int32_t* first_bad, void* stream);
+int gnnome_gfa_links(const uint8_t* buf, int64_t num_bytes, const int64_t* link_rec, const int64_t* link_line, int64_t num_links,
+                     const int64_t* seg_rec, const int64_t* seg_line, int64_t num_segments, const int32_t* table, int64_t capacity,
+                     int32_t* err, int64_t num_lines, int32_t* first_bad, int64_t* event_u, int64_t* event_v, void* stream);
+int gnnome_gfa_pack(const uint8_t* src, int64_t src_bytes, const int64_t* src_beg, const int64_t* out_off, int64_t num_items, uint8_t* out,
+                    int64_t out_bytes, void* stream);
 
 #ifdef __cplusplus
 }
