@@ -23,7 +23,9 @@
 // their lists are cut into kHubChunks fixed chunks that a first launch reduces to per-chunk partial sums, one wave per
 // chunk (k_hub_partials), and the node's own wave then adds the partials IN CHUNK ORDER instead of walking the list: the
 // result is still a function of the graph alone (bit-reproducible), only a different - fixed - association than the
-// single-wave sum.  Up to kHubCap hubs per call take this path; any further ones fall back to the single wave.
+// single-wave sum.  Up to kHubCap hubs per graph take this path: the kHubCap LOWEST node ids among the hubs, whatever order the threads
+// of k_find_hubs meet them in (the list is a sorted insertion, see there); any further hubs keep the single wave.  Which association a
+// node's sums get is therefore a function of the graph too.
 #include "common.h"
 
 #include <algorithm>
@@ -43,8 +45,8 @@ constexpr int kRecItems = 20;         // neighbours per direction that fit a nod
 struct HubScratch {
     const void *key_in = nullptr, *key_out = nullptr;   // the CSR arrays the hub list was last built from
     int64_t key_n = -1;
-    int* count = nullptr;       // [1]
-    int* nodes = nullptr;       // [kHubCap]
+    int* count = nullptr;       // [1 + kHubCap]: the number of hubs, then the hub list - ONE allocation, cleared by one memset
+    int* nodes = nullptr;       // = count + 1: [kHubCap] keys, hub_key(id) of the lowest hub ids in ascending id order, 0 = empty (hub_node_at)
     float* partials = nullptr;  // [kHubCap][kHubChunks][4][H]
     // The hub count of the graph the list was last built for, read back WITHOUT a host sync: an asynchronous copy into pinned memory
     // behind k_find_hubs, polled with hipEventQuery on later calls.  Once it is known to be zero - every assembly graph without a
@@ -106,8 +108,8 @@ static HubScratch* hub_scratch(hipStream_t s, bool* capturing_unallocated, const
     }
     HubScratch& h = g_hub_table[std::make_pair(dev, s)];
     if (h.partials == nullptr) {
-        if (h.count == nullptr && hipMalloc(&h.count, sizeof(int)) != hipSuccess) return nullptr;
-        if (h.nodes == nullptr && hipMalloc(&h.nodes, sizeof(int) * kHubCap) != hipSuccess) return nullptr;
+        if (h.count == nullptr && hipMalloc(&h.count, sizeof(int) * (1 + kHubCap)) != hipSuccess) return nullptr;
+        h.nodes = h.count + 1;
         if (hipMalloc(&h.partials, sizeof(float) * (size_t)kHubCap * kHubChunks * 4 * kHubMaxH) != hipSuccess) return nullptr;
         if (hipHostMalloc(&h.host_count, sizeof(int), hipHostMallocDefault) != hipSuccess) h.host_count = nullptr;   // (optional: without it the count stays unknown)
         if (h.host_count && hipEventCreateWithFlags(&h.ready, hipEventDisableTiming) != hipSuccess) h.ready = nullptr;
@@ -115,14 +117,29 @@ static HubScratch* hub_scratch(hipStream_t s, bool* capturing_unallocated, const
     return &h;
 }
 
+// The hub list holds KEYS: hub_key(id) = INT_MAX - id > 0, so that a cleared list (all zero, the same memset that clears the count) is an
+// empty one and a lower id is a larger key.
+__device__ __forceinline__ int hub_key(int node) { return 0x7fffffff - node; }
+__device__ __forceinline__ int hub_node_at(const int* __restrict__ nodes, int slot) { return 0x7fffffff - nodes[slot]; }
+
+// count = the number of hubs; nodes[0 .. min(count, kHubCap)) = the keys of the LOWEST hub ids in ascending id order.  Every hub thread
+// walks the list from slot 0 with atomicMax, leaving the larger key in the slot and carrying the smaller one on: slot 0 is offered every
+// key and ends with the largest, slot 1 is offered every other key, and so on - the final list does not depend on the order in which
+// the threads arrive.  (It used to be nodes[atomicAdd(count, 1)] = i: beyond kHubCap hubs, WHICH ones were listed - and so which
+// association their sums got - depended on scheduling.)  A key below the last slot's current value can never enter (slots only grow).
 __global__ __launch_bounds__(256) void k_find_hubs(const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ out_ptr, int64_t n,
                                                    int* __restrict__ count, int* __restrict__ nodes) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int cnt = (in_ptr[i + 1] - in_ptr[i]) + (out_ptr[i + 1] - out_ptr[i]);
     if (cnt > kHubThreshold) {
-        const int slot = atomicAdd(count, 1);
-        if (slot < kHubCap) nodes[slot] = (int)i;
+        atomicAdd(count, 1);
+        int key = hub_key((int)i);
+        if (key < __hip_atomic_load(nodes + kHubCap - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        for (int slot = 0; slot < kHubCap && key != 0; ++slot) {
+            const int old = atomicMax(nodes + slot, key);
+            key = min(old, key);
+        }
     }
 }
 
@@ -310,7 +327,7 @@ __global__ __launch_bounds__(kAggThreads) void k_hub_partials(const float* __res
     const int group = lane / LPR, c = (lane % LPR) * 4;
     const int nh = min(*hub_count, kHubCap);
     for (int h = 0; h < nh; ++h) {
-        const int64_t node = hub_nodes[h];
+        const int64_t node = hub_node_at(hub_nodes, h);
         if (node >= n_out) continue;
         const int ib = in_ptr[node], din = in_ptr[node + 1] - ib;
         const int ob = out_ptr[node], cnt = din + out_ptr[node + 1] - ob;
@@ -364,7 +381,7 @@ __global__ __launch_bounds__(kAggThreads, (WPS > 0 ? WPS : 1)) void k_node_aggre
     if (HUBFIN) {
         hub_slot = blockIdx.x * (kAggThreads / 64) + wave;
         if (hub_slot >= min(*hub_count, kHubCap)) return;
-        node = hub_nodes[hub_slot];
+        node = hub_node_at(hub_nodes, hub_slot);
     } else {
         node = node0 + (int64_t)xcd_remap(blockIdx.x, total_blocks) * (kAggThreads / 64) + wave;
     }
@@ -386,7 +403,7 @@ __global__ __launch_bounds__(kAggThreads, (WPS > 0 ? WPS : 1)) void k_node_aggre
     } else if (cnt > kHubThreshold && hub_nodes != nullptr) {   // wave-uniform: is this node on the hub list?
         const int nh = min(*hub_count, kHubCap);
         bool listed = false;
-        for (int base = 0; base < nh; base += 64) listed |= __ballot(base + lane < nh && hub_nodes[base + lane] == (int)node) != 0;
+        for (int base = 0; base < nh; base += 64) listed |= __ballot(base + lane < nh && hub_nodes[base + lane] == hub_key((int)node)) != 0;
         if (listed) return;
     }
     f32x4 a1 = {0.f, 0.f, 0.f, 0.f};
@@ -510,7 +527,7 @@ __global__ __launch_bounds__(kAggThreads) void k_node_aggregate_pair(
         ob = out_ptr[node], cnt = din + out_ptr[node + 1] - ob;
         if (cnt > kHubThreshold && hub_nodes != nullptr) {   // a listed hub is left to the HUBFIN launch of the kernel above
             const int nh = min(*hub_count, kHubCap);
-            for (int k = 0; k < nh; ++k) valid = valid && hub_nodes[k] != (int)node;
+            for (int k = 0; k < nh; ++k) valid = valid && hub_nodes[k] != hub_key((int)node);
         }
     }
     if (!valid) cnt = din = 0;
@@ -664,7 +681,7 @@ static int launch_agg(const float* e, int64_t n_out, const float* A1h, const flo
         // same addresses - costs speed only: the kernels re-read every count, a listed node that is no hub takes the normal
         // path, an unlisted hub the single-wave path, and the partials are recomputed at every call.
         if (!same_graph(hub)) {
-            GN_HIP(hipMemsetAsync(hub->count, 0, sizeof(int), s));
+            GN_HIP(hipMemsetAsync(hub->count, 0, sizeof(int) * (1 + kHubCap), s));   // the count and the list (0 = an empty slot)
             hipLaunchKernelGGL(k_find_hubs, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, in_ptr, out_ptr, n_out, hub->count, hub->nodes);
             hub->key_in = in_ptr, hub->key_out = out_ptr, hub->key_n = n_out;
             hub->known = -1, hub->pending = false;

@@ -164,11 +164,11 @@ def node_aggregate_raw(e, A1h, A2h, A3h, views, mode, num_nodes, rows_alloc=None
     s, d = views.srt_src.long(), views.srt_dst.long()
     n_tab, H = A2h.shape
     sig = torch.sigmoid(e)
-    zeros = torch.zeros((n_tab, H), dtype=torch.float32)
+    zeros = torch.zeros((n_tab, H), dtype=e.dtype, device=e.device)   # (float64 inputs, on any device: the contract at high precision, tests/test_aggregate_adversarial.py)
     rows = num_nodes if rows_alloc is None else max(rows_alloc, num_nodes)
 
     def cut(t):  # the kernel computes rows < num_nodes only
-        out = torch.zeros((rows, H), dtype=torch.float32)
+        out = torch.zeros((rows, H), dtype=e.dtype, device=e.device)
         out[:num_nodes] = t[:num_nodes]
         return out
 

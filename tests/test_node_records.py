@@ -11,6 +11,7 @@ from gnnome_amd.graph import views_for
 from gnnome_amd.synth import make_graph
 
 pytestmark = pytest.mark.gpu
+PROB_TOL = 1e-4   # the model-level bar: max |sigmoid(logit) - sigmoid(reference logit)| (tests/test_hip_parity.py)
 
 
 def dev():
@@ -86,6 +87,11 @@ def test_model_forward_uses_the_records_where_they_pay_and_keeps_its_bits():
                 built = views._records is not None
                 assert built == (limit >= max(hidden, 64)), (hidden, norm, limit)     # (48 runs at the built width 64)
             assert torch.equal(outs[0], outs[64]) and torch.equal(outs[0], outs[256])
-            assert torch.equal(m(views_for((g["src"], g["dst"], n), dev()).reversed(), x, ed), m(ops.GraphViews(g["dst"].to(dev()), g["src"].to(dev()), n), x, ed)) or True
+            # reversed views against views built from the swapped endpoints: the same graph, its lists in another order - not the same bits, the same
+            # edge probabilities at the model-level bar
+            rev = m(views_for((g["src"], g["dst"], n), dev()).reversed(), x, ed)
+            swapped = m(ops.GraphViews(g["dst"].to(dev()), g["src"].to(dev()), n), x, ed)
+            diff = (torch.sigmoid(rev) - torch.sigmoid(swapped)).abs().max().item()
+            assert diff < PROB_TOL, (hidden, norm, diff)
     finally:
         ops.NODE_RECORDS_MAX_HIDDEN = old
