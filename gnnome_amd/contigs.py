@@ -373,13 +373,16 @@ def spell_contigs(dg, walks, reads, line_width=0):
     walk_off = walk_off.to(dev, torch.int64).contiguous()
     W, S = int(walk_off.numel()) - 1, int(nodes.numel())
     piece_len = torch.empty(S, dtype=torch.int64, device=dev)
+    nbr, eid, pre = dg.succ_nbr, dg.succ_eid, dg.prefix_length
+    if dg.num_edges == 0:   # every walk a single node: the arrays are empty and never read, but the C entry declines a null pointer
+        nbr = eid = pre = torch.zeros(1, dtype=torch.int32, device=dev)
     need = ctypes.c_size_t(0)
     _lib.check(lib.gnnome_contig_pieces_workspace_bytes(W, S, ctypes.byref(need)), "contig_pieces_workspace_bytes")
     ws = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
     with _on(dev):
-        _lib.check(lib.gnnome_contig_pieces(_ptr(nodes), S, _ptr(walk_off), W, _ptr(dg.succ_ptr), _ptr(dg.succ_nbr), _ptr(dg.succ_eid),
-                                            _ptr(dg.prefix_length), dg.num_nodes, _ptr(reads.off), reads.num_reads, _ptr(piece_len),
-                                            _ptr(ws), ws.numel(), _stream(dev)), "contig_pieces")
+        _lib.check(lib.gnnome_contig_pieces(_ptr(nodes), S, _ptr(walk_off), W, _ptr(dg.succ_ptr), _ptr(nbr), _ptr(eid), _ptr(pre), dg.num_nodes,
+                                            _ptr(reads.off), reads.num_reads, _ptr(piece_len), _ptr(ws), ws.numel(), _stream(dev)),
+                   "contig_pieces")
     piece_off = torch.zeros(S + 1, dtype=torch.int64, device=dev)
     torch.cumsum(piece_len, 0, out=piece_off[1:])
     plan = {"device": dev, "nodes": nodes, "walk_off": walk_off, "piece_off": piece_off, "reads": reads,

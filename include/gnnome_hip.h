@@ -694,12 +694,18 @@ int gnnome_overlap_edit_distance(const uint8_t* reads, const int64_t* read_off, 
  * gnnome_contig_pieces: piece_len int64[S].  It first checks every walk and pair and SYNCHRONISES `stream` to report the first
  *   failure (an empty walk, offsets that do not rise from 0 to S, a node outside [0, num_nodes), a pair that is not an edge - the
  *   reference raises KeyError) as GNNOME_EINVAL naming the walk and the pair; nothing is written then.  Not capturable.
+ *   "First" is the smallest item in this order: the W walks' offsets (item w: walk_off[w] < walk_off[w+1], walk_off[0] == 0,
+ *   walk_off[W] == S), then the S steps in walk order (item W + j: the nodes in range, the pair an edge) - so any bad offset is
+ *   reported before any bad step.  Offsets are only compared and nodes range-checked before use: nothing is read out of bounds.
+ *   succ_nbr / succ_eid / prefix_length must be pointers even for a graph without edges (they are not read then).
  *   workspace: gnnome_contig_pieces_workspace_bytes.  num_walks == 0 is a no-op.
  * gnnome_contig_spell: piece_off int64[S+1] = the exclusive scan of piece_len (contig w holds unwrapped bytes
  *   [piece_off[walk_off[w]], piece_off[walk_off[w+1]]) ).  line_width == 0: out = the contigs concatenated in that layout.
  *   line_width > 0: contig w's FASTA body goes to out + body_off[w] (body_off int64[W], rising, bodies disjoint): '\n' after every
  *   line_width bytes and after a final partial line; bytes between bodies (where the caller puts header lines) are not written.
- *   Only bytes below out_bytes are written.  The copy is split into fixed tiles of the output, stores 16-byte vectors where out is
+ *   An empty contig has a body of zero bytes in either layout (its FASTA record is the header line alone, as Biopython writes it),
+ *   so body_off may repeat where bodies are empty.  Only bytes below out_bytes are written: a smaller out_bytes cuts the image there,
+ *   mid-line or mid-body, and every byte from out + out_bytes on is left alone.  The copy is split into fixed tiles of the output, stores 16-byte vectors where out is
  *   16-byte aligned, and uses no atomics: equal inputs give equal bytes.  walk_off / piece_off as gnnome_contig_pieces checked and
  *   produced them. */
 int gnnome_contig_pieces_workspace_bytes(int64_t num_walks, int64_t num_steps, size_t* bytes_host);

@@ -1,6 +1,6 @@
 """Contig spelling (gnnome_amd/contigs.py, csrc/contig_spell.hip): walks -> sequences -> FASTA, N50 / NG50 (utils/evaluate.py:38-105).
 
-The checker is evaluate.py:38-48 restated in plain Python below (`spell_checker`): reads[src][:prefix] for every step but the
+The checker is evaluate.py:38-48 restated in plain Python (`spell_checker`, tests/contig_cases.py): reads[src][:prefix] for every step but the
 last, the whole read for the last node, node 2r+1 the reverse complement of read r, prefixes under Python's slice rule."""
 import ctypes
 import gzip
@@ -11,27 +11,8 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from contig_cases import _COMP, node_seq, spell_checker   # the statement: shared with test_contigs_adversarial.py
 from gnnome_amd import _lib, contigs, gfa
-
-_COMP = str.maketrans("ACGTMRWSYKVHDBXNUacgtmrwsykvhdbxnu", "TGCAKYWSRMBDHVXNAtgcakywsrmbdhvxna")   # Bio.Seq's IUPAC table
-
-
-def node_seq(seqs, u):
-    s = seqs[u >> 1]
-    return s if u % 2 == 0 else s.translate(_COMP)[::-1]
-
-
-def spell_checker(walks, src, dst, prefix, seqs):
-    """evaluate.py:38-48: edges[(u, v)] is the LAST edge id inserted for the pair (graph_parser.py:77-80)."""
-    edges = {}
-    for i, (u, v) in enumerate(zip(src, dst)):
-        edges[(u, v)] = i
-    out = []
-    for w in walks:
-        pieces = [node_seq(seqs, a)[:prefix[edges[(a, b)]]] for a, b in zip(w[:-1], w[1:])]
-        out.append("".join(pieces) + node_seq(seqs, w[-1]))
-    return out
-
 
 # ---------------------------------------------------------------------------------------------------------------- CPU
 
