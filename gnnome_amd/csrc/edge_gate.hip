@@ -15,6 +15,7 @@
 // segments).  Bound: fp32 MFMA (2*H^2 flop per edge against 8*H bytes per edge; AI = H/4 flop/B vs a
 // machine balance of ~20-25 flop/B, so H >= 128 is matrix-bound, H = 64 HBM-bound).
 #include "gemm_tile.h"
+#include "lds_handover.h"
 
 namespace gnnome {
 
@@ -221,33 +222,11 @@ __device__ __forceinline__ void gate_ws_sweep(f32x16& acc, const float* ap, cons
 //            in the next iteration's epilogue) (4 per tile)
 // A wave's DS instructions execute in order, so a counter bump issued after the data accesses is ordered behind
 // them without any s_waitcnt - in particular a compute wave never waits for its e' stores here, which a
-// workgroup-scope release fence (vmcnt(0)) would make it do every tile.
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
-__device__ __forceinline__ void flag_wait(unsigned addr, unsigned want, int nap = 3) {
-    unsigned v, spins = 0;
-    for (;;) {
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-        if (__builtin_amdgcn_readfirstlane(v) >= want) break;
-        if (++spins > (1u << 26)) __builtin_trap();  // a lost hand-over must end the launch, not hang the queue
-        // consumers (nap 3) poll tightly: their wait is on the critical path.  Producers run a whole slot ahead and
-        // poll rarely (nap 0 = 64 x 64 cycles): their ds_reads compete with the compute waves' operand reads.
-        if (nap == 0) {
-            __builtin_amdgcn_s_sleep(64);
-        } else if (nap == 1) {
-            __builtin_amdgcn_s_sleep(16);
-        } else if (nap == 2) {
-            __builtin_amdgcn_s_sleep(4);
-        } else {
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-}
-__device__ __forceinline__ void flag_bump(unsigned addr, int lane) {
-    if (lane == 0) asm volatile("ds_add_u32 %0, %1" ::"v"(addr), "v"(1u) : "memory");
-}
-
+// workgroup-scope release fence (vmcnt(0)) would make it do every tile.  (lds_handover.h has flag_wait / flag_bump.)
+// The compute waves poll tightly (nap 0): their wait is on the critical path.  The load waves run a whole slot ahead and
+// poll rarely (s_sleep 64 unless the experiment knob's bits 1-2 say 16 / 4 / 1): their ds_reads compete with the compute
+// waves' operand reads.
+//
 // MODE 0: the gate.  MODE 1: raw gate x = B1h[src] + B2h[dst] + e W3^T (train mode), with per-workgroup shifted
 // column sums for the BatchNorm batch statistics written to `stats` ([gridDim.x * RB][2H]; `scale` = the centre).
 // MODE 2: C += A W^T on [E,H] rows (the backward's d e_in = d e' + dxe W3): G = the old rows of C, passed as B1h
@@ -321,7 +300,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_ws(
         if (!FLAGS) __syncthreads();  // iteration -1: the load waves hand over tile 0
         if (xp & 1) __builtin_amdgcn_s_setprio(3);
         for (int i = 0; i < n; ++i) {
-            if (FLAGS) flag_wait(full0 + 4 * (i & 3), 2u * ((unsigned)(i >> 2) + 1u));
+            if (FLAGS) flag_wait(full0 + 4 * (i & 3), 2u * ((unsigned)(i >> 2) + 1u), 0);
             const float* As = Aring + (i & 3) * SLOT;
             // previous tile (i-1): its G rows and its e rows (the residual) are still in the ring
             const float* Gp = Gring + ((i - 1) & 3) * SLOT + lane_lds;
@@ -452,7 +431,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_ws(
         if (FLAGS) {
             // this group's tiles: group, group + 4, ...; each waits only for its own slot to be free
             for (int r = group; r < n; r += 4) {
-                flag_wait(done0 + 4 * group, 4u * (unsigned)(r >> 2), (xp >> 1) & 3);
+                flag_wait(done0 + 4 * group, 4u * (unsigned)(r >> 2), 3 - ((xp >> 1) & 3));
                 float* As = Aring + group * SLOT;
                 float* Gs = Gring + group * SLOT;
 #pragma unroll

@@ -24,10 +24,10 @@
 //     writes e' with 16-byte stores - every global access of the kernel is a full-row, 16-byte-per-lane one - then
 //     refills the slot with the tile it fetched in the meantime.
 #include "common.h"
+#include "lds_handover.h"
+#include "operand_planes.h"
 
 namespace gnnome {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 template <int CB, int RB>
 struct GateBF {
@@ -38,52 +38,6 @@ struct GateBF {
     static constexpr int kSlotFloats = TM * LDK;
     static constexpr int kLdsFloats = RING * 2 * kSlotFloats;        // e tiles + G tiles, fp32
 };
-
-__device__ __forceinline__ unsigned lds_addr_bf(const void* p) {
-    return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
-__device__ __forceinline__ void flag_wait_bf(unsigned addr, unsigned want, int nap) {
-    unsigned v, spins = 0;
-    for (;;) {
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-        if (__builtin_amdgcn_readfirstlane(v) >= want) break;
-        if (++spins > (1u << 26)) __builtin_trap();  // a lost hand-over must end the launch, not hang the queue
-        if (nap == 0) {
-            __builtin_amdgcn_s_sleep(1);
-        } else if (nap == 1) {
-            __builtin_amdgcn_s_sleep(4);
-        } else if (nap == 2) {
-            __builtin_amdgcn_s_sleep(16);
-        } else {
-            __builtin_amdgcn_s_sleep(64);
-        }
-    }
-}
-__device__ __forceinline__ void flag_bump_bf(unsigned addr, int lane) {
-    if (lane == 0) asm volatile("ds_add_u32 %0, %1" ::"v"(addr), "v"(1u) : "memory");
-}
-
-// exact three-way bf16 split of eight floats (one lane's share of a 32x32x16 MFMA operand: 8 consecutive k)
-__device__ __forceinline__ void split3(const f32x4 lo4, const f32x4 hi4, uint4& p1, uint4& p2, uint4& p3) {
-    unsigned h[8], m[8], l[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = j < 4 ? lo4[j] : hi4[j - 4];
-        h[j] = __float_as_uint(x) & 0xFFFF0000u;
-        const float r = x - __uint_as_float(h[j]);      // exact
-        m[j] = __float_as_uint(r) & 0xFFFF0000u;
-        l[j] = __float_as_uint(r - __uint_as_float(m[j]));   // exact, <= 8 significant bits: a bf16 (low half zero)
-    }
-    // pack pairs: element 2j in the low half, 2j+1 in the high half (v_perm_b32: bytes 3,2 of each source)
-    p1 = make_uint4(__builtin_amdgcn_perm(h[1], h[0], 0x07060302u), __builtin_amdgcn_perm(h[3], h[2], 0x07060302u),
-                    __builtin_amdgcn_perm(h[5], h[4], 0x07060302u), __builtin_amdgcn_perm(h[7], h[6], 0x07060302u));
-    p2 = make_uint4(__builtin_amdgcn_perm(m[1], m[0], 0x07060302u), __builtin_amdgcn_perm(m[3], m[2], 0x07060302u),
-                    __builtin_amdgcn_perm(m[5], m[4], 0x07060302u), __builtin_amdgcn_perm(m[7], m[6], 0x07060302u));
-    p3 = make_uint4(__builtin_amdgcn_perm(l[1], l[0], 0x07060302u), __builtin_amdgcn_perm(l[3], l[2], 0x07060302u),
-                    __builtin_amdgcn_perm(l[5], l[4], 0x07060302u), __builtin_amdgcn_perm(l[7], l[6], 0x07060302u));
-}
-
-__device__ __forceinline__ bf16x8 as_bf(const uint4 v) { return __builtin_bit_cast(bf16x8, v); }
 
 // MODE 0: y = relu((acc + G) * scale + shift) + e      (the gate, gated_gcn_full.py:97,104-110)
 // MODE 1: y = acc + G, G = B1h[src] + B2h[dst]          (raw gate of the training step) + shifted column sums (scale = centre)
@@ -107,7 +61,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_bf(GateBfArgs a) {
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned full0 = lds_addr_bf(&flags[0]), done0 = lds_addr_bf(&flags[RING]);
+    const unsigned full0 = lds_addr(&flags[0]), done0 = lds_addr(&flags[RING]);
     // interleaved tile order: in round r the whole chip works on one contiguous window of gridDim.x tiles, each XCD
     // (blocks b % 8) on a contiguous sub-window (see edge_gate.hip)
     const int per_xcd = gridDim.x / kXcds;
@@ -135,7 +89,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_bf(GateBfArgs a) {
 #pragma unroll
         for (int q = 0; q < KS; ++q) {
             const float* wp = a.W3 + (int64_t)col * a.ldw + 16 * q + 8 * half;
-            split3(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q], w3[q]);
+            bf16_split8(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q], w3[q]);
         }
         const int lrow = 32 * rb + 4 * half;   // accumulator element r sits in tile row lrow + crow(r)
         const int lane_lds = lrow * LDK + col;
@@ -147,7 +101,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_bf(GateBfArgs a) {
         for (int i = 0; i < n; ++i) {
             const int slot = i % RING;
             if (a.prof) t0 = __builtin_readcyclecounter();
-            flag_wait_bf(full0 + 4 * slot, 2u * ((unsigned)(i / RING) + 1u), 0);
+            flag_wait(full0 + 4 * slot, 2u * ((unsigned)(i / RING) + 1u), 0);
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_wait += t1 - t0; t0 = t1; }
             const float* As = Aring + slot * SLOT;
             const float* ap = As + (32 * rb + cl) * LDK + 8 * half;   // + 16 q
@@ -159,7 +113,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_bf(GateBfArgs a) {
             // Software pipeline, one basic block: while the 6 MFMAs of step q run, the fragment of step q+1 is split
             // (44 VALU operations, dealt out 8 per MFMA by the sched_group_barriers) and the one of step q+2 is read.
             uint4 a1, a2, a3;
-            split3(*reinterpret_cast<const f32x4*>(ap), *reinterpret_cast<const f32x4*>(ap + 4), a1, a2, a3);
+            bf16_split8(*reinterpret_cast<const f32x4*>(ap), *reinterpret_cast<const f32x4*>(ap + 4), a1, a2, a3);
             f32x4 x0 = *reinterpret_cast<const f32x4*>(ap + (KS > 1 ? 16 : 0)), x1 = *reinterpret_cast<const f32x4*>(ap + (KS > 1 ? 20 : 4));
             if (a.prof) { asm volatile("" ::"v"(a1.x), "v"(x0[0])); t1 = __builtin_readcyclecounter(); t_pro += t1 - t0; t0 = t1; }
 #pragma unroll
@@ -167,14 +121,14 @@ __global__ __launch_bounds__(768) void k_edge_gate_bf(GateBfArgs a) {
                 const int q2 = q + 2 < KS ? q + 2 : KS - 1;
                 const f32x4 n0 = *reinterpret_cast<const f32x4*>(ap + 16 * q2), n1 = *reinterpret_cast<const f32x4*>(ap + 16 * q2 + 4);
                 uint4 b1 = a1, b2 = a2, b3 = a3;
-                if (q + 1 < KS) split3(x0, x1, b1, b2, b3);
+                if (q + 1 < KS) bf16_split8(x0, x1, b1, b2, b3);
                 // smallest terms first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(a3), as_bf(w1[q]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(a1), as_bf(w3[q]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(a2), as_bf(w2[q]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(a2), as_bf(w1[q]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(a1), as_bf(w2[q]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(a1), as_bf(w1[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a3), as_bf16x8(w1[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a1), as_bf16x8(w3[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a2), as_bf16x8(w2[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a2), as_bf16x8(w1[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a1), as_bf16x8(w2[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a1), as_bf16x8(w1[q]), acc, 0, 0, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // the two LDS reads of step q+2 first
 #pragma unroll
                 for (int k = 0; k < 6; ++k) {
@@ -192,7 +146,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_bf(GateBfArgs a) {
             // x = acc + G, in place in the G tile (rows past the end of the edge list are never stored)
 #pragma unroll
             for (int r = 0; r < 16; ++r) Gp[crow(r) * LDK] = acc[r];
-            flag_bump_bf(done0 + 4 * slot, lane);
+            flag_bump(done0 + 4 * slot, lane);
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_x += t1 - t0; }
         }
         if (a.prof && wave == 0 && lane == 0) {
@@ -335,10 +289,10 @@ __global__ __launch_bounds__(768) void k_edge_gate_bf(GateBfArgs a) {
                 *reinterpret_cast<f32x4*>(As + (r0 + p * RSTEP) * LDK + 4 * c4) = av[p];
                 *reinterpret_cast<f32x4*>(Gs + (r0 + p * RSTEP) * LDK + 4 * c4) = MODE >= 2 ? g1[p] : g1[p] + g2[p];
             }
-            flag_bump_bf(full0 + 4 * group, lane);
+            flag_bump(full0 + 4 * group, lane);
             if (r + RING < n) issue_early(r + RING);
             // epilogue + store of tile r once the four compute waves have added their products into the G tile
-            flag_wait_bf(done0 + 4 * group, 4u * ((unsigned)(r / RING) + 1u), a.xp & 3);
+            flag_wait(done0 + 4 * group, 4u * ((unsigned)(r / RING) + 1u), a.xp & 3);
             const int valid = tile_valid(r);
             // (re-read per tile, L1-resident: eight registers fewer across the fetch phase)
             f32x4 sc4 = {0.f, 0.f, 0.f, 0.f}, sh4 = {0.f, 0.f, 0.f, 0.f};
@@ -429,45 +383,6 @@ long long* gate_profile_buffer() { return g_gate_prof; }
 // fp16x3 arithmetic (round 4; the derivation and the error model are in edge_tile_f16.hip's header and tests/test_f16x3_model.py): an fp32
 // operand as TWO fp16 planes, x1 = RN16(x) and x2 = RN16((x - x1) * 2048), three products instead of bf16x6's six, the two small ones in
 // a second accumulator that is folded in with 2^-11 once per tile.
-typedef _Float16 h2_pl __attribute__((ext_vector_type(2)));
-typedef _Float16 h8_pl __attribute__((ext_vector_type(8)));
-typedef float f32x2_pl __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split4_h(const f32x4 x, uint2& p1, uint2& p2) {
-    h2_pl a[2], b[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const f32x2_pl v = {x[2 * j], x[2 * j + 1]};
-        a[j] = __builtin_convertvector(v, h2_pl);
-        const f32x2_pl big = v * 2048.f;
-        const f32x2_pl r = {__builtin_fmaf((float)a[j][0], -2048.f, big[0]), __builtin_fmaf((float)a[j][1], -2048.f, big[1])};   // exact
-        b[j] = __builtin_convertvector(r, h2_pl);
-    }
-    p1 = make_uint2(__builtin_bit_cast(unsigned, a[0]), __builtin_bit_cast(unsigned, a[1]));
-    p2 = make_uint2(__builtin_bit_cast(unsigned, b[0]), __builtin_bit_cast(unsigned, b[1]));
-}
-__device__ __forceinline__ void split8_h(const f32x4 lo, const f32x4 hi, uint4& p1, uint4& p2) {
-    uint2 a1, a2, b1, b2;
-    split4_h(lo, a1, a2);
-    split4_h(hi, b1, b2);
-    p1 = make_uint4(a1.x, a1.y, b1.x, b1.y);
-    p2 = make_uint4(a2.x, a2.y, b2.x, b2.y);
-}
-__device__ __forceinline__ h8_pl as_h8(const uint4 v) { return __builtin_bit_cast(h8_pl, v); }
-
-__device__ __forceinline__ void split4_planes(const f32x4 x, uint2& p1, uint2& p2, uint2& p3) {
-    unsigned h[4], m[4], l[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h[j] = __float_as_uint(x[j]) & 0xFFFF0000u;
-        const float r = x[j] - __uint_as_float(h[j]);        // exact
-        m[j] = __float_as_uint(r) & 0xFFFF0000u;
-        l[j] = __float_as_uint(r - __uint_as_float(m[j]));   // exact, a bf16
-    }
-    p1 = make_uint2(__builtin_amdgcn_perm(h[1], h[0], 0x07060302u), __builtin_amdgcn_perm(h[3], h[2], 0x07060302u));
-    p2 = make_uint2(__builtin_amdgcn_perm(m[1], m[0], 0x07060302u), __builtin_amdgcn_perm(m[3], m[2], 0x07060302u));
-    p3 = make_uint2(__builtin_amdgcn_perm(l[1], l[0], 0x07060302u), __builtin_amdgcn_perm(l[3], l[2], 0x07060302u));
-}
-
 // MODE 0: the inference gate.  MODE 1: raw gate + shifted column sums (training forward; a.scale = the centres).  MODE 3: the
 // BatchNorm backward + data gradient of k_edge_gate_bf's mode 3 (A computed by the load waves from the old C rows and the rows at
 // e_in, written to bnb.a_out; C += A W^T).  X16: xe / dxe stored as bf16 (see common.h).  Modes 1 and 3 hold no e rows for a residual.
@@ -501,8 +416,8 @@ __global__ __launch_bounds__(768) void k_edge_gate_pl(GateBfArgs a) {
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned full0 = lds_addr_bf(&flags[0]), rd0 = lds_addr_bf(&flags[RING]), done0 = lds_addr_bf(&flags[2 * RING]),
-                   drained0 = lds_addr_bf(&flags[3 * RING]);
+    const unsigned full0 = lds_addr(&flags[0]), rd0 = lds_addr(&flags[RING]), done0 = lds_addr(&flags[2 * RING]),
+                   drained0 = lds_addr(&flags[3 * RING]);
     const int per_xcd = gridDim.x / kXcds;
     int first = (int)(blockIdx.x % kXcds) * per_xcd + (int)(blockIdx.x / kXcds);
     int stride = (int)gridDim.x;
@@ -546,9 +461,9 @@ __global__ __launch_bounds__(768) void k_edge_gate_pl(GateBfArgs a) {
         for (int q = 0; q < KS; ++q) {
             const float* wp = a.W3 + (int64_t)(H * cbk + col) * a.ldw + 16 * q + 8 * half;
             if (F16)
-                split8_h(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q]);
+                f16_split8(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q]);
             else
-                split3(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q], w3[q]);
+                bf16_split8(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q], w3[q]);
         }
         auto crow = [](int r) { return (r & 3) + 8 * (r >> 2); };
         const int lane_x = 4 * half * LDK + col;   // accumulator element r sits in tile row 4 half + crow(r)
@@ -559,7 +474,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_pl(GateBfArgs a) {
             const int slot = i % RING;
             const unsigned use = (unsigned)(i / RING) + 1u;
             if (a.prof) t0 = __builtin_readcyclecounter();
-            flag_wait_bf(full0 + 4 * slot, 2u * use, 0);
+            flag_wait(full0 + 4 * slot, 2u * use, 0);
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_wait += t1 - t0; t0 = t1; }
             const unsigned char* ap = ring + slot * SLOTB + cl * PLD + 16 * half;   // + 32 q, + PLANE * plane
             f32x16 acc, accC;
@@ -586,33 +501,33 @@ __global__ __launch_bounds__(768) void k_edge_gate_pl(GateBfArgs a) {
                 if (F16) __builtin_amdgcn_sched_barrier(0);
                 const uint4 c1 = f1[q], c2 = f2[q], c3 = F16 ? c1 : f3[F16 ? 0 : q];
                 if (F16) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(c1), as_h8(w1[q]), acc, 0, 0, 0);
-                    accC = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(c1), as_h8(w2[q]), accC, 0, 0, 0);
-                    accC = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(c2), as_h8(w1[q]), accC, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(c1), as_f16x8(w1[q]), acc, 0, 0, 0);
+                    accC = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(c1), as_f16x8(w2[q]), accC, 0, 0, 0);
+                    accC = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(c2), as_f16x8(w1[q]), accC, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 } else {
                     // smallest terms first
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c3), as_bf(w1[q]), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c1), as_bf(w3[F16 ? 0 : q]), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c2), as_bf(w2[q]), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c2), as_bf(w1[q]), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c1), as_bf(w2[q]), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c1), as_bf(w1[q]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c3), as_bf16x8(w1[q]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(w3[F16 ? 0 : q]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c2), as_bf16x8(w2[q]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c2), as_bf16x8(w1[q]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(w2[q]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(w1[q]), acc, 0, 0, 0);
                 }
             }
             if (F16) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] += accC[r] * (1.0f / 2048.f);
+                for (int r = 0; r < 16; ++r) acc[r] += accC[r] * kLoInv;
             }
             if (a.prof) { asm volatile("" ::"v"(acc[0])); t1 = __builtin_readcyclecounter(); t_loop += t1 - t0; t0 = t1; }
             // every compute wave has read the planes -> the slot becomes the x tile
-            flag_bump_bf(rd0 + 4 * slot, lane);
-            flag_wait_bf(rd0 + 4 * slot, 4u * use, 0);
+            flag_bump(rd0 + 4 * slot, lane);
+            flag_wait(rd0 + 4 * slot, 4u * use, 0);
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_rd += t1 - t0; t0 = t1; }
             float* X = reinterpret_cast<float*>(ring + slot * SLOTB) + lane_x;
 #pragma unroll
             for (int r = 0; r < 16; ++r) X[crow(r) * LDK] = acc[r];
-            flag_bump_bf(done0 + 4 * slot, lane);
+            flag_bump(done0 + 4 * slot, lane);
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_x += t1 - t0; }
         }
         if (a.prof && wave == 0 && lane == 0) {   // same record as k_edge_gate_bf; slot 1 = waiting for the other compute waves
@@ -701,7 +616,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_pl(GateBfArgs a) {
             if (a.prof) { t0 = __builtin_readcyclecounter(); asm volatile("" ::"v"(av[0][0]), "v"(g1[NP - 1][0])); t1 = __builtin_readcyclecounter(); t_top += t1 - t0; t0 = t1; }
             // The slot is free once BOTH waves of the group have read the previous x tile out of it: the planes of a row do not
             // lie where its x row lay, so one wave's plane stores would land on x rows the other wave has yet to read.
-            flag_wait_bf(drained0 + 4 * group, 2u * (use - 1u), 0);
+            flag_wait(drained0 + 4 * group, 2u * (use - 1u), 0);
             if (MODE == 3) {
                 // A = BatchNorm backward of (dy = the old C rows, x = the xe rows) for this lane's four columns, written out as dxe
                 const f32x4 ka = *reinterpret_cast<const f32x4*>(norm_lds + 4 * c4), k1 = *reinterpret_cast<const f32x4*>(norm_lds + H + 4 * c4);
@@ -732,9 +647,9 @@ __global__ __launch_bounds__(768) void k_edge_gate_pl(GateBfArgs a) {
                 uint2 p1, p2, p3;
                 unsigned char* d = S + (r0 + p * RSTEP) * PLD + 8 * c4;
                 if (F16) {
-                    split4_h(av[p], p1, p2);
+                    f16_split4(av[p], p1, p2);
                 } else {
-                    split4_planes(av[p], p1, p2, p3);
+                    bf16_split4(av[p], p1, p2, p3);
                     *reinterpret_cast<uint2*>(d + 2 * PLANE) = p3;
                 }
                 *reinterpret_cast<uint2*>(d) = p1;
@@ -745,7 +660,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_pl(GateBfArgs a) {
                 // behind that epilogue's own stores (one in-order counter for loads and stores) and stall on their completion
                 if (MODE != 4) asm volatile("" : "+v"(gk[p]));
             }
-            flag_bump_bf(full0 + 4 * group, lane);
+            flag_bump(full0 + 4 * group, lane);
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_split += t1 - t0; t0 = t1; }
             if (r + RING < n) issue_early(r + RING);
             // MODE 4 (round 4): the A rows of this group's NEXT tile are requested here, ahead of the wait for the compute waves and of the epilogue's
@@ -753,7 +668,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_pl(GateBfArgs a) {
             // 2040 cycles per own tile waiting for rows requested after the epilogue); the other modes hold too many registers across the epilogue
             constexpr bool kFetchAhead = MODE == 4;
             if (kFetchAhead && r + RING < n && !(a.xp & 32)) fetch_e(r + RING);
-            flag_wait_bf(done0 + 4 * group, 4u * use, a.xp & 3);
+            flag_wait(done0 + 4 * group, 4u * use, a.xp & 3);
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_done += t1 - t0; t0 = t1; }
             const int valid = tile_valid(r);
             // MODE 0: scale, shift; MODE 1: sc4 = the centres; MODE 3: unused
@@ -805,7 +720,7 @@ __global__ __launch_bounds__(768) void k_edge_gate_pl(GateBfArgs a) {
                     }
                 }
             }
-            flag_bump_bf(drained0 + 4 * group, lane);
+            flag_bump(drained0 + 4 * group, lane);
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_epi += t1 - t0; }
             if (r + RING < n) {   // (woven into the epilogue piece by piece, the e-row fetch made the epilogue 1200 cycles longer and
                                   //  arrived no earlier: loads and stores share one in-order counter)
@@ -903,7 +818,7 @@ __global__ __launch_bounds__(640) void k_edge_gate_enc16(GateBfArgs a) {
     __shared__ unsigned flags[2 * RING];   // full[RING], done[RING]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned full0 = lds_addr_bf(&flags[0]), done0 = lds_addr_bf(&flags[RING]);
+    const unsigned full0 = lds_addr(&flags[0]), done0 = lds_addr(&flags[RING]);
     const int per_xcd = gridDim.x / kXcds;
     const int first = (int)(blockIdx.x % kXcds) * per_xcd + (int)(blockIdx.x / kXcds);
     const int stride = (int)gridDim.x;
@@ -926,9 +841,9 @@ __global__ __launch_bounds__(640) void k_edge_gate_enc16(GateBfArgs a) {
         uint4 u1, u2, u3, v1, v2, v3;
         {
             const float* p = a.enc.W23 + col * 16 + 8 * half;
-            split3(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4), u1, u2, u3);
+            bf16_split8(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4), u1, u2, u3);
             const float* q = a.enc.W2 + col * 16 + 8 * half;
-            split3(*reinterpret_cast<const f32x4*>(q), *reinterpret_cast<const f32x4*>(q + 4), v1, v2, v3);
+            bf16_split8(*reinterpret_cast<const f32x4*>(q), *reinterpret_cast<const f32x4*>(q + 4), v1, v2, v3);
         }
         auto crow = [](int r) { return (r & 3) + 8 * (r >> 2); };
         const int lane_x = 4 * half * LDK + col;
@@ -936,7 +851,7 @@ __global__ __launch_bounds__(640) void k_edge_gate_enc16(GateBfArgs a) {
         for (int i = 0; i < n; ++i) {
             const int slot = i % RING;
             const unsigned use = (unsigned)(i / RING) + 1u;
-            flag_wait_bf(full0 + 4 * slot, 2u * use, 0);
+            flag_wait(full0 + 4 * slot, 2u * use, 0);
             const unsigned char* tp = ring + slot * SLOTB + cl * TPLD + 16 * half;
             const uint4 c1 = *reinterpret_cast<const uint4*>(tp), c2 = *reinterpret_cast<const uint4*>(tp + TPLANE),
                         c3 = *reinterpret_cast<const uint4*>(tp + 2 * TPLANE);
@@ -944,25 +859,25 @@ __global__ __launch_bounds__(640) void k_edge_gate_enc16(GateBfArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) ax[r] = ae[r] = 0.f;
             // smallest terms first; the two products alternate
-            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c3), as_bf(u1), ax, 0, 0, 0);
-            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c3), as_bf(v1), ae, 0, 0, 0);
-            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c1), as_bf(u3), ax, 0, 0, 0);
-            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c1), as_bf(v3), ae, 0, 0, 0);
-            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c2), as_bf(u2), ax, 0, 0, 0);
-            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c2), as_bf(v2), ae, 0, 0, 0);
-            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c2), as_bf(u1), ax, 0, 0, 0);
-            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c2), as_bf(v1), ae, 0, 0, 0);
-            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c1), as_bf(u2), ax, 0, 0, 0);
-            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c1), as_bf(v2), ae, 0, 0, 0);
-            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c1), as_bf(u1), ax, 0, 0, 0);
-            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(c1), as_bf(v1), ae, 0, 0, 0);
+            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c3), as_bf16x8(u1), ax, 0, 0, 0);
+            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c3), as_bf16x8(v1), ae, 0, 0, 0);
+            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(u3), ax, 0, 0, 0);
+            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(v3), ae, 0, 0, 0);
+            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c2), as_bf16x8(u2), ax, 0, 0, 0);
+            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c2), as_bf16x8(v2), ae, 0, 0, 0);
+            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c2), as_bf16x8(u1), ax, 0, 0, 0);
+            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c2), as_bf16x8(v1), ae, 0, 0, 0);
+            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(u2), ax, 0, 0, 0);
+            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(v2), ae, 0, 0, 0);
+            ax = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(u1), ax, 0, 0, 0);
+            ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(v1), ae, 0, 0, 0);
             float* X = reinterpret_cast<float*>(ring + slot * SLOTB + 3 * TPLANE) + lane_x;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 X[crow(r) * LDK] = ax[r] + bxc;          // (+ b23 / + b2 here, one column per lane, rather than as two more float4
                 X[TILEF + crow(r) * LDK] = ae[r] + bec;  //  constants in the store waves: the same two additions, the same bits)
             }
-            flag_bump_bf(done0 + 4 * slot, lane);
+            flag_bump(done0 + 4 * slot, lane);
         }
     } else {
         // ------------------------------------------------------------------ load / store wave
@@ -1016,7 +931,7 @@ __global__ __launch_bounds__(640) void k_edge_gate_enc16(GateBfArgs a) {
                     t[j] = fmaxf(__builtin_fmaf(raw1, w1s[2 * hu + 1], raw0 * w1s[2 * hu]) + b1s[hu], 0.f);
                 }
                 uint2 p1, p2, p3;
-                split4_planes(t, p1, p2, p3);
+                bf16_split4(t, p1, p2, p3);
                 unsigned char* d = S + trow * TPLD + 8 * jq;
                 *reinterpret_cast<uint2*>(d) = p1;
                 *reinterpret_cast<uint2*>(d + TPLANE) = p2;
@@ -1027,10 +942,10 @@ __global__ __launch_bounds__(640) void k_edge_gate_enc16(GateBfArgs a) {
                 gk[p] = g1[p] + g2[p];
                 asm volatile("" : "+v"(gk[p]));   // summed here, not in the epilogue (see k_edge_gate_pl)
             }
-            flag_bump_bf(full0 + 4 * group, lane);
+            flag_bump(full0 + 4 * group, lane);
             if (r + RING < n) issue_late();                       // tile r + RING: its indices arrived during the previous iteration
             if (r + 2 * RING < n) issue_early(r + 2 * RING);
-            flag_wait_bf(done0 + 4 * group, 4u * use, a.xp & 3);
+            flag_wait(done0 + 4 * group, 4u * use, a.xp & 3);
             const int valid = tile_valid(r);
             const f32x4 sc4 = *reinterpret_cast<const f32x4*>(consts + 4 * c4), sh4 = *reinterpret_cast<const f32x4*>(consts + H + 4 * c4);
             float* out = a.e_out + (int64_t)tile_of(r) * TM * H;

@@ -35,85 +35,15 @@
 // 2.36 ms (k_edge_gate_stream) -> 1.98 ms per launch at the 2.5M-edge shard; the matrix-pipe floor of this form is 1.25 ms.
 // e_out must not alias e_in (the two column halves of a row are written by different workgroups while both read whole rows).
 #include "common.h"
+#include "lds_handover.h"
+#include "operand_planes.h"
 
 #include <type_traits>
 
 namespace gnnome {
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 constexpr bool kResidualFromPlanes = true;   // the epilogue's residual rebuilt from the LDS planes (true; 5724 cycles per tile) or fetched again (false; 5949)
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p; }
-__device__ __forceinline__ void flag_wait(unsigned addr, unsigned want) {
-    unsigned v, spins = 0;
-    for (;;) {
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-        if (__builtin_amdgcn_readfirstlane(v) >= want) break;
-        if (++spins > (1u << 26)) __builtin_trap();   // a lost hand-over must end the launch, not hang the queue
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-__device__ __forceinline__ void flag_bump(unsigned addr, int lane) {
-    if (lane == 0) asm volatile("ds_add_u32 %0, %1" ::"v"(addr), "v"(1u) : "memory");
-}
-// exact three-way bf16 split (see edge_gate_bf.hip): eight floats -> one MFMA operand per plane
-__device__ __forceinline__ void split8(const f32x4 lo4, const f32x4 hi4, uint4& p1, uint4& p2, uint4& p3) {
-    unsigned h[8], m[8], l[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = j < 4 ? lo4[j] : hi4[j - 4];
-        h[j] = __float_as_uint(x) & 0xFFFF0000u;
-        const float r = x - __uint_as_float(h[j]);
-        m[j] = __float_as_uint(r) & 0xFFFF0000u;
-        l[j] = __float_as_uint(r - __uint_as_float(m[j]));
-    }
-    p1 = make_uint4(__builtin_amdgcn_perm(h[1], h[0], 0x07060302u), __builtin_amdgcn_perm(h[3], h[2], 0x07060302u),
-                    __builtin_amdgcn_perm(h[5], h[4], 0x07060302u), __builtin_amdgcn_perm(h[7], h[6], 0x07060302u));
-    p2 = make_uint4(__builtin_amdgcn_perm(m[1], m[0], 0x07060302u), __builtin_amdgcn_perm(m[3], m[2], 0x07060302u),
-                    __builtin_amdgcn_perm(m[5], m[4], 0x07060302u), __builtin_amdgcn_perm(m[7], m[6], 0x07060302u));
-    p3 = make_uint4(__builtin_amdgcn_perm(l[1], l[0], 0x07060302u), __builtin_amdgcn_perm(l[3], l[2], 0x07060302u),
-                    __builtin_amdgcn_perm(l[5], l[4], 0x07060302u), __builtin_amdgcn_perm(l[7], l[6], 0x07060302u));
-}
-__device__ __forceinline__ void split4(const f32x4 x, uint2& p1, uint2& p2, uint2& p3) {
-    unsigned h[4], m[4], l[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h[j] = __float_as_uint(x[j]) & 0xFFFF0000u;
-        const float r = x[j] - __uint_as_float(h[j]);
-        m[j] = __float_as_uint(r) & 0xFFFF0000u;
-        l[j] = __float_as_uint(r - __uint_as_float(m[j]));
-    }
-    p1 = make_uint2(__builtin_amdgcn_perm(h[1], h[0], 0x07060302u), __builtin_amdgcn_perm(h[3], h[2], 0x07060302u));
-    p2 = make_uint2(__builtin_amdgcn_perm(m[1], m[0], 0x07060302u), __builtin_amdgcn_perm(m[3], m[2], 0x07060302u));
-    p3 = make_uint2(__builtin_amdgcn_perm(l[1], l[0], 0x07060302u), __builtin_amdgcn_perm(l[3], l[2], 0x07060302u));
-}
-__device__ __forceinline__ bf16x8_t as_bf8(const uint4 v) { return __builtin_bit_cast(bf16x8_t, v); }
-
-// fp16x3 planes (edge_tile_f16.hip's header): x1 = RN16(x), x2 = RN16((x - x1) 2048); and, for the one-accumulator form of mode 3, x1 2048
-typedef _Float16 pl_h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 pl_h8 __attribute__((ext_vector_type(8)));
-typedef float pl_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ pl_h8 as_h8(const uint4 v) { return __builtin_bit_cast(pl_h8, v); }
-__device__ __forceinline__ void split2h(const pl_f2 v, unsigned& p1, unsigned& p2, unsigned& p1x) {
-    const pl_h2 a = __builtin_convertvector(v, pl_h2);
-    const pl_f2 af = {(float)a[0], (float)a[1]};
-    const pl_f2 r = {__builtin_fmaf(af[0], -2048.f, v[0] * 2048.f), __builtin_fmaf(af[1], -2048.f, v[1] * 2048.f)};   // exact
-    p1 = __builtin_bit_cast(unsigned, a);
-    p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, pl_h2));
-    p1x = __builtin_bit_cast(unsigned, __builtin_convertvector(af * 2048.f, pl_h2));   // exact: |x| < 32 (the caller's scale), subnormal a1 included
-}
-__device__ __forceinline__ void split4h3(const f32x4 x, uint2& p1, uint2& p2, uint2& p1x) {
-    split2h(pl_f2{x[0], x[1]}, p1.x, p2.x, p1x.x);
-    split2h(pl_f2{x[2], x[3]}, p1.y, p2.y, p1x.y);
-}
-__device__ __forceinline__ void split8h(const f32x4 lo4, const f32x4 hi4, uint4& p1, uint4& p2) {
-    unsigned unused;
-    split2h(pl_f2{lo4[0], lo4[1]}, p1.x, p2.x, unused);
-    split2h(pl_f2{lo4[2], lo4[3]}, p1.y, p2.y, unused);
-    split2h(pl_f2{hi4[0], hi4[1]}, p1.z, p2.z, unused);
-    split2h(pl_f2{hi4[2], hi4[3]}, p1.w, p2.w, unused);
-}
 
 // MODE 0: e' = relu((e W3^T + B1h[src] + B2h[dst]) * scale + shift) + e    (gated_gcn_full.py:97,104-110)
 // MODE 1: xe = e W3^T + B1h[src] + B2h[dst] and its shifted column sums (training forward; a.scale = the centres, a.stats out)
@@ -190,8 +120,8 @@ __global__ __launch_bounds__(512) void k_edge_gate_pl256(GateBfArgs a) {
 #pragma unroll
         for (int q = 0; q < KS; ++q) {
             const float* wp = a.W3 + (int64_t)col * a.ldw + 64 * (q >> 2) + 32 * half + 8 * (q & 3);
-            if (F16) split8h(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q]);
-            else split8(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q], w3[q]);
+            if (F16) f16_split8(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q]);
+            else bf16_split8(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q], w3[q]);
         }
         auto crow = [](int r) { return (r & 3) + 8 * (r >> 2); };
         const int lane_x = 4 * half * LDK + 32 * wave + cl;   // accumulator element r sits in tile row 4 half + crow(r)
@@ -202,7 +132,7 @@ __global__ __launch_bounds__(512) void k_edge_gate_pl256(GateBfArgs a) {
             const int slot = i & 1;
             const unsigned use = (unsigned)(i >> 1) + 1u;
             if (a.prof) t0 = __builtin_readcyclecounter();
-            flag_wait(full0 + 4 * slot, 2u * use);
+            flag_wait(full0 + 4 * slot, 2u * use, 0);
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_wait += t1 - t0; t0 = t1; }
             const unsigned char* ap = ring + slot * SLOTB + cl * PLD + 64 * half;   // + 128 b + 16 q (step 4 b + q), + PLANE * plane
             f32x16 acc;
@@ -221,21 +151,21 @@ __global__ __launch_bounds__(512) void k_edge_gate_pl256(GateBfArgs a) {
                     continue;
                 }
                 if (F16) {   // planes of A: c1 = a1, c2 = a2 2^11, c3 = a1 2^11; smallest terms first
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(c2), as_h8(w1[q]), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(c1), as_h8(w2[q]), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(c3), as_h8(w1[q]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(c2), as_f16x8(w1[q]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(c1), as_f16x8(w2[q]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(c3), as_f16x8(w1[q]), acc, 0, 0, 0);
                     c1 = n1;
                     c2 = n2;
                     c3 = n3;
                     continue;
                 }
                 // smallest terms first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(c3), as_bf8(w1[q]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(c1), as_bf8(w3[q]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(c2), as_bf8(w2[q]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(c2), as_bf8(w1[q]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(c1), as_bf8(w2[q]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(c1), as_bf8(w1[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c3), as_bf16x8(w1[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(w3[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c2), as_bf16x8(w2[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c2), as_bf16x8(w1[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(w2[q]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(c1), as_bf16x8(w1[q]), acc, 0, 0, 0);
                 c1 = n1;
                 c2 = n2;
                 c3 = n3;
@@ -243,7 +173,7 @@ __global__ __launch_bounds__(512) void k_edge_gate_pl256(GateBfArgs a) {
             if (a.prof) { asm volatile("" ::"v"(acc[0])); t1 = __builtin_readcyclecounter(); t_loop += t1 - t0; t0 = t1; }
             // the x buffer of this slot must have been read out by its group's epilogue of the tile before last (the group publishes
             // the next tile's planes BEFORE that epilogue, so this is a real wait - normally long satisfied)
-            flag_wait(drained0 + 4 * slot, 2u * (use - 1u));
+            flag_wait(drained0 + 4 * slot, 2u * (use - 1u), 0);
             float* X = xt + slot * XT + lane_x;
 #pragma unroll
             for (int r = 0; r < 16; ++r) X[crow(r) * LDK] = acc[r];
@@ -372,8 +302,8 @@ __global__ __launch_bounds__(512) void k_edge_gate_pl256(GateBfArgs a) {
 #pragma unroll
             for (int p = 0; p < NPF; ++p) {
                 uint2 p1, p2, p3;
-                if (F16) split4h3(av[p] * row_scale, p1, p2, p3);
-                else split4(av[p], p1, p2, p3);
+                if (F16) f16_split4x(av[p] * row_scale, p1, p2, p3);
+                else bf16_split4(av[p], p1, p2, p3);
                 unsigned char* d = S + (16 * r0f + p) * PLD + 8 * c4f;
                 *reinterpret_cast<uint2*>(d) = p1;
                 *reinterpret_cast<uint2*>(d + PLANE) = p2;
@@ -398,7 +328,7 @@ __global__ __launch_bounds__(512) void k_edge_gate_pl256(GateBfArgs a) {
         for (int r = group; r < n; r += 2) {
             const unsigned use = (unsigned)(r >> 1) + 1u;
             if (a.prof) t0 = __builtin_readcyclecounter();
-            flag_wait(done0 + 4 * group, 4u * use);   // x(r) is ready; the planes slot is free (all four compute waves have read it)
+            flag_wait(done0 + 4 * group, 4u * use, 0);   // x(r) is ready; the planes slot is free (all four compute waves have read it)
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_done += t1 - t0; t0 = t1; }
             if (MODE == 0 && kResidualFromPlanes) {
                 // the residual e[row, this half] is NOT fetched a second time: the planes of tile r are still in the slot, and the

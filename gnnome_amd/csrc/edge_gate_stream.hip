@@ -43,7 +43,7 @@ __global__ __launch_bounds__(512) void k_edge_gate_stream(const float* __restric
     for (int it = 0; it < P::kWPieces; ++it) {   // split the W3 chunk once
         const int f = tid + P::NT * it, row = f / (K / 4), c4 = f % (K / 4);
         uint2 p1, p2, p3;
-        tile_split4(*reinterpret_cast<const f32x4*>(W3 + (int64_t)(col0 + row) * ldw + 4 * c4), p1, p2, p3);
+        bf16_split4(*reinterpret_cast<const f32x4*>(W3 + (int64_t)(col0 + row) * ldw + 4 * c4), p1, p2, p3);
         unsigned char* dst = Wp + row * PLD + 8 * c4;
         *reinterpret_cast<uint2*>(dst) = p1;
         *reinterpret_cast<uint2*>(dst + PB) = p2;
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(512) void k_edge_gate_stream(const float* __restric
     }
     __syncthreads();   // the only barrier
 
-    auto bf = [](const uint4 v) { return __builtin_bit_cast(tile_bf16x8, v); };
+    auto bf = [](const uint4 v) { return as_bf16x8(v); };
     // k numbering of the matrix-core steps (the same for both operands, see the A fragments below): step 4 b + q of the lower /
     // upper half wave takes k in [64 b + 32 half + 8 q, + 8)
     const unsigned char* wp = Wp + cl * PLD + 64 * half;   // + 128 b + 16 q
@@ -119,8 +119,8 @@ __global__ __launch_bounds__(512) void k_edge_gate_stream(const float* __restric
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 uint2 l1, l2, l3, h1, h2, h3;
-                tile_split4(x[2 * q], l1, l2, l3);
-                tile_split4(x[2 * q + 1], h1, h2, h3);
+                bf16_split4(x[2 * q], l1, l2, l3);
+                bf16_split4(x[2 * q + 1], h1, h2, h3);
                 const uint4 a1 = make_uint4(l1.x, l1.y, h1.x, h1.y), a2 = make_uint4(l2.x, l2.y, h2.x, h2.y),
                             a3 = make_uint4(l3.x, l3.y, h3.x, h3.y);
                 const unsigned char* w = wp + 128 * b + 16 * q;

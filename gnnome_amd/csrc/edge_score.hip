@@ -116,37 +116,9 @@ __global__ __launch_bounds__(kGemmThreads) void k_edge_score(
 // wave-private LDS tile, adds Ps[src] + Qd[dst] there row-wise (16-byte gathers, 16 lanes per row), and runs the 64 -> 32 -> 1
 // tail from that tile.  One barrier per launch; 8 waves per workgroup, one workgroup per CU.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void score_split8(const f32x4 lo4, const f32x4 hi4, uint4& p1, uint4& p2, uint4& p3) {
-    uint2 l1, l2, l3, h1, h2, h3;
-    tile_split4(lo4, l1, l2, l3);
-    tile_split4(hi4, h1, h2, h3);
-    p1 = make_uint4(l1.x, l1.y, h1.x, h1.y);
-    p2 = make_uint4(l2.x, l2.y, h2.x, h2.y);
-    p3 = make_uint4(l3.x, l3.y, h3.x, h3.y);
-}
-
-// fp16x3 (round 4; see edge_tile_f16.hip's header): two fp16 planes per operand, three f16 MFMAs per k step, the two small products in a second
+// fp16x3 (round 4; operand_planes.h): two fp16 planes per operand, three f16 MFMAs per k step, the two small products in a second
 // accumulator folded in with 2^-11.  F16 = true also runs the 64 -> 32 product on the f16 matrix cores (it was 32 exact-fp32 MFMAs = 2048 matrix-pipe
 // cycles per 32-edge tile, now 12 f16 MFMAs = 384) and lets W1e fit LDS at K = 256 (two planes: 68 KB), so that width streams too.
-typedef _Float16 sc_h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 sc_h8 __attribute__((ext_vector_type(8)));
-typedef float sc_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void score_split8h(const f32x4 lo, const f32x4 hi, uint4& p1, uint4& p2) {
-    unsigned a[4], b[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const sc_f2 v = j < 2 ? sc_f2{lo[2 * j], lo[2 * j + 1]} : sc_f2{hi[2 * j - 4], hi[2 * j - 3]};
-        const sc_h2 x1 = __builtin_convertvector(v, sc_h2);
-        const sc_f2 big = v * 2048.f;
-        const sc_f2 r = {__builtin_fmaf((float)x1[0], -2048.f, big[0]), __builtin_fmaf((float)x1[1], -2048.f, big[1])};   // exact
-        const sc_h2 x2 = __builtin_convertvector(r, sc_h2);
-        a[j] = __builtin_bit_cast(unsigned, x1);
-        b[j] = __builtin_bit_cast(unsigned, x2);
-    }
-    p1 = make_uint4(a[0], a[1], a[2], a[3]);
-    p2 = make_uint4(b[0], b[1], b[2], b[3]);
-}
-
 template <int K, bool F16 = false>
 __global__ __launch_bounds__(512) void k_edge_score_ws(
     const float* __restrict__ e, int64_t E, const float* __restrict__ Ps, const float* __restrict__ Qd, int ldn,
@@ -167,9 +139,9 @@ __global__ __launch_bounds__(512) void k_edge_score_ws(
         uint4 p1, p2, p3;
         unsigned char* dst = Wp + row * PLD + 16 * c8;
         if (F16) {
-            score_split8h(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), p1, p2);
+            f16_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), p1, p2);
         } else {
-            score_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), p1, p2, p3);
+            bf16_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), p1, p2, p3);
             *reinterpret_cast<uint4*>(dst + 2 * PB) = p3;
         }
         *reinterpret_cast<uint4*>(dst) = p1;
@@ -184,12 +156,12 @@ __global__ __launch_bounds__(512) void k_edge_score_ws(
 #pragma unroll
         for (int q = 0; q < HS / 16; ++q) {
             const float* wr = W2s + cl * LDZ + 16 * q + 8 * half;
-            score_split8h(*reinterpret_cast<const f32x4*>(wr), *reinterpret_cast<const f32x4*>(wr + 4), w2a[q], w2b[q]);
+            f16_split8(*reinterpret_cast<const f32x4*>(wr), *reinterpret_cast<const f32x4*>(wr + 4), w2a[q], w2b[q]);
         }
     }
-    auto h8 = [](const uint4 v) { return __builtin_bit_cast(sc_h8, v); };
+    auto h8 = [](const uint4 v) { return as_f16x8(v); };
 
-    auto bf = [](const uint4 v) { return __builtin_bit_cast(tile_bf16x8, v); };
+    auto bf = [](const uint4 v) { return as_bf16x8(v); };
     float* Zs = Zall + wave * 32 * LDZ;
     const unsigned char* wp = Wp + cl * PLD + 16 * half;
     const int t0 = blockIdx.x * tiles_per_group, t_end = min(num_tiles, t0 + tiles_per_group);
@@ -231,7 +203,7 @@ __global__ __launch_bounds__(512) void k_edge_score_ws(
                 uint4 a1, a2, a3;
                 const unsigned char* w = wp + 32 * (hq + q);
                 if (F16) {
-                    score_split8h(x[q][0], x[q][1], a1, a2);
+                    f16_split8(x[q][0], x[q][1], a1, a2);
                     const uint4 u1 = *reinterpret_cast<const uint4*>(w), u2 = *reinterpret_cast<const uint4*>(w + PB);
                     const uint4 v1 = *reinterpret_cast<const uint4*>(w + 32 * PLD), v2 = *reinterpret_cast<const uint4*>(w + 32 * PLD + PB);
                     acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(a1), h8(u1), acc0, 0, 0, 0);
@@ -242,7 +214,7 @@ __global__ __launch_bounds__(512) void k_edge_score_ws(
                     acc1c = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(a2), h8(v1), acc1c, 0, 0, 0);
                     continue;
                 }
-                score_split8(x[q][0], x[q][1], a1, a2, a3);
+                bf16_split8(x[q][0], x[q][1], a1, a2, a3);
                 const uint4 u1 = *reinterpret_cast<const uint4*>(w), u2 = *reinterpret_cast<const uint4*>(w + PB),
                             u3 = *reinterpret_cast<const uint4*>(w + 2 * PB);
                 const uint4 v1 = *reinterpret_cast<const uint4*>(w + 32 * PLD), v2 = *reinterpret_cast<const uint4*>(w + 32 * PLD + PB),
@@ -276,8 +248,8 @@ __global__ __launch_bounds__(512) void k_edge_score_ws(
         if (F16) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                acc0[r] += acc0c[r] * (1.0f / 2048.f);
-                acc1[r] += acc1c[r] * (1.0f / 2048.f);
+                acc0[r] += acc0c[r] * kLoInv;
+                acc1[r] += acc1c[r] * kLoInv;
             }
         }
         // e W1e^T -> the wave's LDS tile (accumulator layout), then relu(. + G) row-wise in place
@@ -309,13 +281,13 @@ __global__ __launch_bounds__(512) void k_edge_score_ws(
 #pragma unroll
             for (int q = 0; q < HS / 16; ++q) {
                 uint4 z1, z2;
-                score_split8h(*reinterpret_cast<const f32x4*>(zq + 16 * q), *reinterpret_cast<const f32x4*>(zq + 16 * q + 4), z1, z2);
+                f16_split8(*reinterpret_cast<const f32x4*>(zq + 16 * q), *reinterpret_cast<const f32x4*>(zq + 16 * q + 4), z1, z2);
                 acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(z1), h8(w2a[q]), acc2, 0, 0, 0);
                 acc2c = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(z1), h8(w2b[q]), acc2c, 0, 0, 0);
                 acc2c = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(z2), h8(w2a[q]), acc2c, 0, 0, 0);
             }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc2[r] += acc2c[r] * (1.0f / 2048.f);
+            for (int r = 0; r < 16; ++r) acc2[r] += acc2c[r] * kLoInv;
         } else {
             const float* zp = Zs + cl * LDZ + 4 * half;
             const float* w2p = W2s + cl * LDZ + 4 * half;

@@ -40,6 +40,8 @@
 // operand beyond fp16's range leaves the matrix cores as inf / NaN; the epilogue keeps it that way through the relu (fmaxf would
 // turn NaN into 0): the output row is NaN, never silently wrong.
 #include "common.h"
+#include "lds_handover.h"
+#include "operand_planes.h"
 
 #include <type_traits>
 
@@ -47,62 +49,6 @@
 
 namespace gnnome {
 namespace {
-
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr float kLoScale = 2048.f, kLoInv = 1.0f / 2048.f;
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p; }
-__device__ __forceinline__ void flag_wait(unsigned addr, unsigned want) {
-    unsigned v, spins = 0;
-    for (;;) {
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-        if (__builtin_amdgcn_readfirstlane(v) >= want) break;
-        if (++spins > (1u << 26)) __builtin_trap();   // a lost hand-over must end the launch, not hang the queue
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-__device__ __forceinline__ void flag_bump(unsigned addr, int lane) {
-    if (lane == 0) asm volatile("ds_add_u32 %0, %1" ::"v"(addr), "v"(1u) : "memory");
-}
-// one row piece of LDS-DMA: the wave's 64 lanes x 16 bytes land at lds .. lds + 1023 (lane-linear); the source is row + voff (voff = 16 lane)
-__device__ __forceinline__ void dma_row(const float* row, unsigned voff, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(row), "s"(lds) : "memory", "m0");
-}
-
-// the two fp16 planes of eight floats (see the header): p1 = RN16(x), p2 = RN16((x - p1) * 2048)
-__device__ __forceinline__ void split8h(const f32x4 lo, const f32x4 hi, h8_t& p1, h8_t& p2) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const f32x2 v = j < 2 ? f32x2{lo[2 * j], lo[2 * j + 1]} : f32x2{hi[2 * j - 4], hi[2 * j - 3]};
-        const h2_t a = __builtin_convertvector(v, h2_t);
-        const f32x2 big = v * kLoScale;
-        const f32x2 r = {__builtin_fmaf((float)a[0], -kLoScale, big[0]), __builtin_fmaf((float)a[1], -kLoScale, big[1])};   // exact
-        const h2_t b = __builtin_convertvector(r, h2_t);
-        p1[2 * j] = a[0];
-        p1[2 * j + 1] = a[1];
-        p2[2 * j] = b[0];
-        p2[2 * j + 1] = b[1];
-    }
-}
-
-// four floats -> the two planes' four halves each
-__device__ __forceinline__ void split4h(const f32x4 x, uint2& p1, uint2& p2) {
-    h2_t a[2], b[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const f32x2 v = {x[2 * j], x[2 * j + 1]};
-        a[j] = __builtin_convertvector(v, h2_t);
-        const f32x2 big = v * kLoScale;
-        const f32x2 r = {__builtin_fmaf((float)a[j][0], -kLoScale, big[0]), __builtin_fmaf((float)a[j][1], -kLoScale, big[1])};   // exact
-        b[j] = __builtin_convertvector(r, h2_t);
-    }
-    p1 = make_uint2(__builtin_bit_cast(unsigned, a[0]), __builtin_bit_cast(unsigned, a[1]));
-    p2 = make_uint2(__builtin_bit_cast(unsigned, b[0]), __builtin_bit_cast(unsigned, b[1]));
-}
-__device__ __forceinline__ h8_t as_h8(const uint4 v) { return __builtin_bit_cast(h8_t, v); }
 
 // MODE 0: e' = relu((e W3^T + B1h[src] + B2h[dst]) * scale + shift) + e    (gated_gcn_full.py:97,104-110)
 // MODE 1: xe = e W3^T + B1h[src] + B2h[dst] and its shifted column sums (training forward; a.scale = the centres, a.stats out)
@@ -171,12 +117,12 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
     if (ENC && wave < 4) {
         // ------------------------------------------------------------------ compute wave, folded encoder: t in registers, two K = 16 products
         const int cl = lane & 31, half = lane >> 5, col = colh + 32 * wave + cl;
-        h8_t wxa, wxb, wea, web;   // this lane's B fragments (column col, k = 8 half .. + 7) of W23 and of W2
+        f16x8 wxa, wxb, wea, web;   // this lane's B fragments (column col, k = 8 half .. + 7) of W23 and of W2
         {
             const float* p23 = a.enc.W23 + col * 16 + 8 * half;
             const float* p2 = a.enc.W2 + col * 16 + 8 * half;
-            split8h(f32x4{p23[0], p23[1], p23[2], p23[3]}, f32x4{p23[4], p23[5], p23[6], p23[7]}, wxa, wxb);
-            split8h(f32x4{p2[0], p2[1], p2[2], p2[3]}, f32x4{p2[4], p2[5], p2[6], p2[7]}, wea, web);
+            f16_split8(f32x4{p23[0], p23[1], p23[2], p23[3]}, f32x4{p23[4], p23[5], p23[6], p23[7]}, wxa, wxb);
+            f16_split8(f32x4{p2[0], p2[1], p2[2], p2[3]}, f32x4{p2[4], p2[5], p2[6], p2[7]}, wea, web);
         }
         const float b2c = a.enc.b2[col];
         float w1a[8], w1b[8], b1v[8];   // hidden units 8 half .. + 7 of the edge encoder's first layer (in_features = 2)
@@ -205,8 +151,8 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
                 tl[k] = fmaxf(__builtin_fmaf(r1, w1b[k], r0 * w1a[k]) + b1v[k], 0.f);
                 th[k] = fmaxf(__builtin_fmaf(r1, w1b[4 + k], r0 * w1a[4 + k]) + b1v[4 + k], 0.f);
             }
-            h8_t ta, tb;
-            split8h(tl, th, ta, tb);
+            f16x8 ta, tb;
+            f16_split8(tl, th, ta, tb);
             f32x16 z;
 #pragma unroll
             for (int r = 0; r < 16; ++r) z[r] = 0.f;
@@ -216,7 +162,7 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
             f32x16 em = __builtin_amdgcn_mfma_f32_32x32x16_f16(ta, wea, z, 0, 0, 0);
             f32x16 ec = __builtin_amdgcn_mfma_f32_32x32x16_f16(ta, web, z, 0, 0, 0);
             ec = __builtin_amdgcn_mfma_f32_32x32x16_f16(tb, wea, ec, 0, 0, 0);
-            flag_wait(drained0, 4u * (unsigned)j);   // x(j - 1) and e0(j - 1) have been read by all four epilogue waves
+            flag_wait(drained0, 4u * (unsigned)j, 0);   // x(j - 1) and e0(j - 1) have been read by all four epilogue waves
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 X[crow(r) * LDK] = xm[r] + xc[r] * kLoInv;
@@ -229,11 +175,11 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
     } else if (!ENC && wave < 4) {
         // ------------------------------------------------------------------ compute wave: DMA in, planes in place, 32 rows x 32 columns of MFMA
         const int cl = lane & 31, half = lane >> 5, col = colh + 32 * wave + cl;
-        h8_t w1[KS], w2[KS];
+        f16x8 w1[KS], w2[KS];
 #pragma unroll
         for (int q = 0; q < KS; ++q) {   // step q: k in [16 q + 8 half, + 8)
             const float* wp = a.W3 + (int64_t)col * a.ldw + 16 * q + 8 * half;
-            split8h(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q]);
+            f16_split8(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), w1[q], w2[q]);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the W loads: from here on this wave's only vector-memory traffic is its DMA)
         const unsigned ring0 = lds_addr(ring), voff = 16u * (unsigned)lane;
@@ -248,7 +194,7 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
             d_left = valid - 1 - trow;   // rows that follow trow inside the tile
             d_lds = ring0 + (unsigned)((r % NS) * SLOTB + 8 * wave * RSB);
         };
-        auto dma_piece = [&]() {
+        auto dma_next = [&]() {
             dma_row(d_row, voff, d_lds);
             if (d_left > 0) d_row += lda, --d_left;
             d_lds += RSB;
@@ -258,7 +204,7 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
         auto row_read = [&](int r, int p) { return *reinterpret_cast<const f32x4*>(ring + (r % NS) * SLOTB + (8 * wave + p) * RSB + 16 * lane); };
         auto row_write = [&](int r, int p, const f32x4 x) {
             uint2 p1, p2;
-            split4h(x, p1, p2);
+            f16_split4(x, p1, p2);
             unsigned char* d = ring + (r % NS) * SLOTB + (8 * wave + p) * RSB + 8 * lane;
             *reinterpret_cast<uint2*>(d) = p1;
             *reinterpret_cast<uint2*>(d + 2 * H) = p2;
@@ -267,7 +213,7 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
         for (int r = 0; r < 3; ++r) {
             dma_begin(r);
 #pragma unroll
-            for (int p = 0; p < 8; ++p) dma_piece();
+            for (int p = 0; p < 8; ++p) dma_next();
         }
         asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         if (EPI_CONV) {
@@ -291,8 +237,8 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
             if (a.prof) t0 = __builtin_readcyclecounter();
             if (!(PROBE & 1)) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // this wave's rows of tile j + 1 have landed (tile j + 2's may be in flight)
             if (EPI_CONV) flag_bump(landed0 + 4 * ((j + 1) % NS), lane);
-            flag_wait(full0 + 4 * slot, 4u * ((unsigned)(j / NS) + 1u));   // tile j's planes are complete; (!EPI_CONV:) every compute wave is through with tile j - 1
-            if (EPI_CONV) flag_wait(done0, 4u * (unsigned)j);              // every compute wave is through with tile j - 1: its slot may be refilled
+            flag_wait(full0 + 4 * slot, 4u * ((unsigned)(j / NS) + 1u), 0);   // tile j's planes are complete; (!EPI_CONV:) every compute wave is through with tile j - 1
+            if (EPI_CONV) flag_wait(done0, 4u * (unsigned)j, 0);              // every compute wave is through with tile j - 1: its slot may be refilled
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_wait += t1 - t0; t0 = t1; }
             const unsigned char* ap = ring + slot * SLOTB + cl * RSB + 16 * half;   // + 32 q: the lane's eight halves of step q; + 2 H: the second plane
             dma_begin(j + 3);   // tile j + 3 goes into the slot tile j - 1 has left
@@ -317,7 +263,7 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
                     f2[q + PD] = *reinterpret_cast<const uint4*>(ap + 32 * (q + PD) + 2 * H);
                 }
                 if ((q & 1) == 0) {
-                    if (!(PROBE & 1)) dma_piece();
+                    if (!(PROBE & 1)) dma_next();
                     if (!(PROBE & 2) && !EPI_CONV) raw = row_read(j + 1, q >> 1);        // tile j + 1, this wave's row q / 2 ...
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -328,15 +274,15 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
                 if (PROBE & 4) {
                     accM[q] += __uint_as_float(c1.x ^ c2.y ^ __builtin_bit_cast(uint4, w1[q]).x ^ __builtin_bit_cast(uint4, w2[q]).y);
                 } else {
-                    accM = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(c1), w1[q], accM, 0, 0, 0);
-                    accC = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(c1), w2[q], accC, 0, 0, 0);
-                    accC = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(c2), w1[q], accC, 0, 0, 0);
+                    accM = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(c1), w1[q], accM, 0, 0, 0);
+                    accC = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(c1), w2[q], accC, 0, 0, 0);
+                    accC = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(c2), w1[q], accC, 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (!EPI_CONV) flag_bump(full0 + 4 * ((j + 1) % NS), lane);   // my rows of tile j + 1 are planes, my reads of tile j are issued
             if (a.prof) { asm volatile("" ::"v"(accM[0])); t1 = __builtin_readcyclecounter(); t_loop += t1 - t0; t0 = t1; }
-            flag_wait(drained0, 4u * (unsigned)j);   // x(j - 1) has been read by all four epilogue waves
+            flag_wait(drained0, 4u * (unsigned)j, 0);   // x(j - 1) has been read by all four epilogue waves
 #pragma unroll
             for (int r = 0; r < 16; ++r) X[crow(r) * LDK] = accM[r] + accC[r] * kLoInv;
             flag_bump(done0, lane);
@@ -393,7 +339,7 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
         };
         // EPI_CONV: rows 8 ew .. 8 ew + 7 of tile ordinal r become planes in place (all 64 lanes read a row before any of them writes it)
         auto to_planes = [&](int r) {
-            flag_wait(landed0 + 4 * (r % NS), 4u * ((unsigned)(r / NS) + 1u));
+            flag_wait(landed0 + 4 * (r % NS), 4u * ((unsigned)(r / NS) + 1u), 0);
             unsigned char* rows = ring + (r % NS) * SLOTB + 8 * ew * RSB;
             f32x4 t[8];
 #pragma unroll
@@ -401,7 +347,7 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
 #pragma unroll
             for (int p = 0; p < 8; ++p) {
                 uint2 p1, p2;
-                split4h(t[p], p1, p2);
+                f16_split4(t[p], p1, p2);
                 *reinterpret_cast<uint2*>(rows + p * RSB + 8 * lane) = p1;
                 *reinterpret_cast<uint2*>(rows + p * RSB + 8 * lane + 2 * H) = p2;
             }
@@ -416,7 +362,7 @@ __global__ __launch_bounds__(512) void k_edge_tile_f16(GateBfArgs a) {
             constexpr int S = decltype(set)::value, S2 = (S + 2) % 3;
             if (a.prof) t0 = __builtin_readcyclecounter();
             if (EPI_CONV && i + 1 < n) to_planes(i + 1);   // (while the compute waves are busy with tile i)
-            flag_wait(done0, 4u * ((unsigned)i + 1u));
+            flag_wait(done0, 4u * ((unsigned)i + 1u), 0);
             if (a.prof) { t1 = __builtin_readcyclecounter(); t_done += t1 - t0; t0 = t1; }
             f32x4 x[NP];
 #pragma unroll

@@ -4,8 +4,7 @@
 // A workgroup is 4 waves (256 threads) and owns a 128-row x (32*NB)-column output tile
 // C = A[128,K] * W[32*NB,K]^T.  Wave w owns rows [32w, 32w+32) and all NB column blocks, one accumulator
 // (16 VGPRs) per block.  The product runs on the bf16 matrix cores as the fp32-faithful three-way split
-// ("bf16x6": x = x1 + x2 + x3 exactly, six of the nine partial products, what is dropped is of the size of one fp32
-// rounding - edge_gate_bf.hip and DESIGN.md explain and measure it).
+// ("bf16x6", operand_planes.h).
 //
 // K is streamed through LDS in chunks of KC = 32:
 //   * A rows are staged as fp32 ([128][36]: 4-float pad, conflict-free ds_read_b128 fragments); a wave's 32 rows are its
@@ -17,6 +16,7 @@
 // 32 nb + (l & 31).
 #pragma once
 #include "common.h"
+#include "operand_planes.h"
 
 namespace gnnome {
 
@@ -31,28 +31,7 @@ constexpr int kGemmThreads = 256;
 template <int NB>
 constexpr int tile_lds_floats() { return kTileM * kLdk + 32 * NB * kWRowFloats; }
 
-typedef __bf16 tile_bf16x8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ int cd_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-
-__device__ __forceinline__ unsigned tile_pack_hi(unsigned odd, unsigned even) {   // (even >> 16) | (odd & 0xFFFF0000)
-    return __builtin_amdgcn_perm(odd, even, 0x07060302u);
-}
-
-// exact three-way bf16 split of one float4 -> three 8-byte groups
-__device__ __forceinline__ void tile_split4(const f32x4 x, uint2& p1, uint2& p2, uint2& p3) {
-    unsigned h[4], m[4], l[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h[j] = __float_as_uint(x[j]) & 0xFFFF0000u;
-        const float r = x[j] - __uint_as_float(h[j]);        // exact
-        m[j] = __float_as_uint(r) & 0xFFFF0000u;
-        l[j] = __float_as_uint(r - __uint_as_float(m[j]));   // exact, a bf16
-    }
-    p1 = make_uint2(tile_pack_hi(h[1], h[0]), tile_pack_hi(h[3], h[2]));
-    p2 = make_uint2(tile_pack_hi(m[1], m[0]), tile_pack_hi(m[3], m[2]));
-    p3 = make_uint2(tile_pack_hi(l[1], l[0]), tile_pack_hi(l[3], l[2]));
-}
 
 // Global -> registers for one 32-wide K chunk of `ROWS` rows (ROWS % 32 == 0).  Thread t fetches the
 // 16-byte piece (t & 7) of rows (t >> 3) + 32*it: 8 lanes cover one 128-byte row segment.
@@ -86,7 +65,7 @@ struct ChunkRegs {
 #pragma unroll
         for (int it = 0; it < kIters; ++it) {
             uint2 p1, p2, p3;
-            tile_split4(v[it], p1, p2, p3);
+            bf16_split4(v[it], p1, p2, p3);
             unsigned char* dst = base + (r0 + 32 * it) * kWRowBytes + 8 * c4;
             *reinterpret_cast<uint2*>(dst) = p1;
             *reinterpret_cast<uint2*>(dst + ROWS * kWRowBytes) = p2;
@@ -101,13 +80,13 @@ __device__ __forceinline__ void mma_chunk(f32x16 (&acc)[NB], const float* As, co
     constexpr int PB = 32 * NB * kWRowBytes;   // bytes per W plane
     const float* ap = As + (32 * wave + (lane & 31)) * kLdk + 8 * (lane >> 5);
     const unsigned char* wp = reinterpret_cast<const unsigned char*>(Ws) + (lane & 31) * kWRowBytes + 16 * (lane >> 5);
-    auto bf = [](const uint4 v) { return __builtin_bit_cast(tile_bf16x8, v); };
+    auto bf = [](const uint4 v) { return as_bf16x8(v); };
 #pragma unroll
     for (int q = 0; q < kKC / 16; ++q) {
         const f32x4 x0 = *reinterpret_cast<const f32x4*>(ap + 16 * q), x1 = *reinterpret_cast<const f32x4*>(ap + 16 * q + 4);
         uint2 l1, l2, l3, h1, h2, h3;
-        tile_split4(x0, l1, l2, l3);
-        tile_split4(x1, h1, h2, h3);
+        bf16_split4(x0, l1, l2, l3);
+        bf16_split4(x1, h1, h2, h3);
         const uint4 a1 = make_uint4(l1.x, l1.y, h1.x, h1.y), a2 = make_uint4(l2.x, l2.y, h2.x, h2.y),
                     a3 = make_uint4(l3.x, l3.y, h3.x, h3.y);
 #pragma unroll

@@ -157,31 +157,11 @@ __global__ __launch_bounds__(64 * CB * RB) void k_linear_ws(const float* __restr
 
 // ---------------------------------------------------------------------------------------------------
 // The same weight-stationary walk with the product on the bf16 matrix cores as an fp32-faithful three-way split
-// (edge_gate_bf.hip explains the arithmetic: x = x1 + x2 + x3 exactly, six of the nine partial products, what is
+// (bf16x6, operand_planes.h: x = x1 + x2 + x3 exactly, six of the nine partial products, what is
 // dropped is of the size of one fp32 rounding).  The W chunk is split ONCE per workgroup into three bf16 planes in
 // LDS; every wave splits its A fragment in registers (~44 VALU operations per K = 16) - with two waves per SIMD one
 // wave's split runs under the other's MFMAs.  6 x 32 cycles per K = 16 instead of 8 x 64.
 // ---------------------------------------------------------------------------------------------------
-typedef __bf16 lin_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void lin_split8(const f32x4 lo4, const f32x4 hi4, uint4& p1, uint4& p2, uint4& p3) {
-    unsigned h[8], m[8], l[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = j < 4 ? lo4[j] : hi4[j - 4];
-        h[j] = __float_as_uint(x) & 0xFFFF0000u;
-        const float r = x - __uint_as_float(h[j]);           // exact
-        m[j] = __float_as_uint(r) & 0xFFFF0000u;
-        l[j] = __float_as_uint(r - __uint_as_float(m[j]));   // exact, a bf16
-    }
-    p1 = make_uint4(__builtin_amdgcn_perm(h[1], h[0], 0x07060302u), __builtin_amdgcn_perm(h[3], h[2], 0x07060302u),
-                    __builtin_amdgcn_perm(h[5], h[4], 0x07060302u), __builtin_amdgcn_perm(h[7], h[6], 0x07060302u));
-    p2 = make_uint4(__builtin_amdgcn_perm(m[1], m[0], 0x07060302u), __builtin_amdgcn_perm(m[3], m[2], 0x07060302u),
-                    __builtin_amdgcn_perm(m[5], m[4], 0x07060302u), __builtin_amdgcn_perm(m[7], m[6], 0x07060302u));
-    p3 = make_uint4(__builtin_amdgcn_perm(l[1], l[0], 0x07060302u), __builtin_amdgcn_perm(l[3], l[2], 0x07060302u),
-                    __builtin_amdgcn_perm(l[5], l[4], 0x07060302u), __builtin_amdgcn_perm(l[7], l[6], 0x07060302u));
-}
-
 template <int K, int CB, int RB>
 struct LinBF {
     static constexpr int TM = 32 * RB, NC = 32 * CB, NW = CB * RB, NT = 64 * NW, LDK = K + 4, LDY = NC + 4, PLD = 2 * K + 16;
@@ -219,7 +199,7 @@ __global__ __launch_bounds__(64 * CB * RB) void k_linear_bf(const float* __restr
         const int f = tid + NT * it, row = f / (K / 8), c8 = f % (K / 8);
         const float* src = W + (int64_t)(col0 + row) * ldw + 8 * c8;
         uint4 p1, p2, p3;
-        lin_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), p1, p2, p3);
+        bf16_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), p1, p2, p3);
         unsigned char* dst = Wp + row * PLD + 16 * c8;
         *reinterpret_cast<uint4*>(dst) = p1;
         *reinterpret_cast<uint4*>(dst + PB) = p2;
@@ -268,8 +248,8 @@ __global__ __launch_bounds__(64 * CB * RB) void k_linear_bf(const float* __restr
             const uint4 w1 = *reinterpret_cast<const uint4*>(wp + 32 * q), w2 = *reinterpret_cast<const uint4*>(wp + 32 * q + PB),
                         w3 = *reinterpret_cast<const uint4*>(wp + 32 * q + 2 * PB);
             uint4 a1, a2, a3;
-            lin_split8(x0, x1, a1, a2, a3);
-            auto bf = [](const uint4 v) { return __builtin_bit_cast(lin_bf16x8, v); };
+            bf16_split8(x0, x1, a1, a2, a3);
+            auto bf = [](const uint4 v) { return as_bf16x8(v); };
             // the 2^-16 terms into one chain, the leading ones into the other
             acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf(a3), bf(w1), acc2, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf(a2), bf(w1), acc, 0, 0, 0);
@@ -349,7 +329,7 @@ __global__ __launch_bounds__(64 * NW) void k_linear_bf2(const float* __restrict_
         const int f = tid + P::NT * it, row = f / (K / 8), c8 = f % (K / 8);
         const float* src = W + (int64_t)(col0 + row) * ldw + 8 * c8;
         uint4 p1, p2, p3;
-        lin_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), p1, p2, p3);
+        bf16_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), p1, p2, p3);
         unsigned char* dst = Wp + row * PLD + 16 * c8;
         *reinterpret_cast<uint4*>(dst) = p1;
         *reinterpret_cast<uint4*>(dst + PB) = p2;
@@ -358,7 +338,7 @@ __global__ __launch_bounds__(64 * NW) void k_linear_bf2(const float* __restrict_
     const float b0 = bias != nullptr ? bias[col0 + cl] : 0.f, b1 = bias != nullptr ? bias[col0 + 32 + cl] : 0.f;
     __syncthreads();   // the only barrier
 
-    auto bf = [](const uint4 v) { return __builtin_bit_cast(lin_bf16x8, v); };
+    auto bf = [](const uint4 v) { return as_bf16x8(v); };
     const unsigned char* wp = Wp + cl * PLD + 16 * half;   // + 32 * 32 rows for the second column block, + 32 q, + plane * PB
     for (int t = t0; t < t_end; ++t) {
         const int64_t row0 = (int64_t)t * P::TM + 32 * wave;
@@ -391,7 +371,7 @@ __global__ __launch_bounds__(64 * NW) void k_linear_bf2(const float* __restrict_
 #pragma unroll
             for (int q = 0; q < HS; ++q) {
                 uint4 a1, a2, a3;
-                lin_split8(x[q][0], x[q][1], a1, a2, a3);
+                bf16_split8(x[q][0], x[q][1], a1, a2, a3);
                 const unsigned char* w = wp + 32 * (hq + q);
 #pragma unroll
                 for (int cb = 0; cb < 2; ++cb) {
@@ -511,7 +491,7 @@ __global__ __launch_bounds__(256, 2) void k_linear_as(const float* __restrict__ 
     const int cl = lane & 31, half = lane >> 5;
     const int64_t row0 = (int64_t)blockIdx.x * P::TM + 32 * wave;
     const bool live = row0 < M;   // a wave past the end still stages W and meets the barriers
-    auto bf = [](const uint4 v) { return __builtin_bit_cast(lin_bf16x8, v); };
+    auto bf = [](const uint4 v) { return as_bf16x8(v); };
 
     uint4 a1[KS], a2[KS], a3[KS];
     {
@@ -524,7 +504,7 @@ __global__ __launch_bounds__(256, 2) void k_linear_as(const float* __restrict__ 
             x[q][1] = *reinterpret_cast<const f32x4*>(ap + 16 * q + 4);
         }
 #pragma unroll
-        for (int q = 0; q < KS; ++q) lin_split8(x[q][0], x[q][1], a1[q], a2[q], a3[q]);
+        for (int q = 0; q < KS; ++q) bf16_split8(x[q][0], x[q][1], a1[q], a2[q], a3[q]);
     }
     f32x4 wr[NP][2];
     auto fetch_w = [&](int chunk) {   // eight consecutive k of one W row per piece
@@ -545,7 +525,7 @@ __global__ __launch_bounds__(256, 2) void k_linear_as(const float* __restrict__ 
         for (int it = 0; it < NP; ++it) {
             const int f = tid + 256 * it, row = f / (K / 8), c8 = f % (K / 8);
             uint4 p1, p2, p3;
-            lin_split8(wr[it][0], wr[it][1], p1, p2, p3);
+            bf16_split8(wr[it][0], wr[it][1], p1, p2, p3);
             unsigned char* dst = Wp + row * PLD + 16 * c8;
             *reinterpret_cast<uint4*>(dst) = p1;
             *reinterpret_cast<uint4*>(dst + PB) = p2;

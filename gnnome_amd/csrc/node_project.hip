@@ -34,26 +34,13 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "lds_handover.h"
+#include "operand_planes.h"
 
 #pragma clang diagnostic ignored "-Winline-asm"
 
 namespace gnnome {
 namespace {
-
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr float kLoScale = 2048.f, kLoInv = 1.0f / 2048.f;
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p; }
-
-// 1 KB of LDS-DMA: lane l's 16 bytes at src + voff (voff = 16 l) land at lds + 16 l.  No "memory" clobber: between the two barriers that bracket
-// it nothing reads the slot it fills, and with the clobber hipcc may not move the NEXT k steps' ds_reads above it - it then waits out one LDS
-// latency per k step (measured: 224 cycles per step against 96 of MFMA).  asm volatile keeps it ordered with the barriers and the waits.
-__device__ __forceinline__ void dma_piece(const void* src, unsigned voff, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds) : "m0");
-}
 
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -90,22 +77,6 @@ __device__ __forceinline__ void quad_transpose(f32x4& E0, f32x4& E1, f32x4& E2, 
 #undef GN_SWAP
 }
 
-// the two fp16 planes of eight floats: p1 = RN16(x), p2 = RN16((x - p1) * 2048)   (x - p1 is exact in fp32)
-__device__ __forceinline__ void split8(const f32x4 lo, const f32x4 hi, h8_t& p1, h8_t& p2) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const f32x2 v = j < 2 ? f32x2{lo[2 * j], lo[2 * j + 1]} : f32x2{hi[2 * j - 4], hi[2 * j - 3]};
-        const h2_t a = __builtin_convertvector(v, h2_t);
-        const f32x2 big = v * kLoScale;
-        const f32x2 r = {__builtin_fmaf((float)a[0], -kLoScale, big[0]), __builtin_fmaf((float)a[1], -kLoScale, big[1])};
-        const h2_t b = __builtin_convertvector(r, h2_t);
-        p1[2 * j] = a[0];
-        p1[2 * j + 1] = a[1];
-        p2[2 * j] = b[0];
-        p2[2 * j + 1] = b[1];
-    }
-}
-
 }  // namespace (the helpers above stay private to this file; the kernels carry plain gnnome:: names for the profilers' tables)
 
 // Which output column of its 32-column block the MFMA's row index i = 8 a + 4 h + t stands for: 16 h + 4 a + t.  With W as the A operand, lane
@@ -123,8 +94,8 @@ __global__ __launch_bounds__(256) void k_weight_planes(const float* __restrict__
     if (cb * 32 >= Nout) return;
     const int col = 32 * cb + frag_col(lane & 31), k = 16 * s + 8 * (lane >> 5);
     const float* w = W + (int64_t)col * ldw + k;
-    h8_t p1, p2;
-    split8(*reinterpret_cast<const f32x4*>(w), *reinterpret_cast<const f32x4*>(w + 4), p1, p2);
+    f16x8 p1, p2;
+    f16_split8(*reinterpret_cast<const f32x4*>(w), *reinterpret_cast<const f32x4*>(w + 4), p1, p2);
     uint4* dst = planes + ((int64_t)cb * ksteps + s) * 128 + lane;
     dst[0] = __builtin_bit_cast(uint4, p1);
     dst[64] = __builtin_bit_cast(uint4, p2);
@@ -196,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void k_node_project(const float* __restrict
         }
     }
 
-    h8_t a1[KS], a2[KS];
+    f16x8 a1[KS], a2[KS];
     float* crow[4];
     constexpr bool PREFETCH_ROWS = K <= 128 && !(PROBE & 16);
     f32x4 raw[2 * KS];
@@ -233,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void k_node_project(const float* __restrict
 #pragma unroll
             for (int q = 1; q < KS / 4; ++q) landed8(raw + 8 * q, false);
 #pragma unroll
-            for (int s = 0; s < KS; ++s) split8(raw[2 * s], raw[2 * s + 1], a1[s], a2[s]);
+            for (int s = 0; s < KS; ++s) f16_split8(raw[2 * s], raw[2 * s + 1], a1[s], a2[s]);
             ahead = false;
             // where this lane's four 16-byte pieces of a column block go (see frag_col): rows 4 g + r of the wave's 32, columns 16 h + 4 a .. + 3
 #pragma unroll
@@ -267,11 +238,11 @@ __global__ __launch_bounds__(256, 2) void k_node_project(const float* __restrict
         const unsigned char* slot = ring + (n & 1) * GB + 16 * lane;
         // W fragments two k steps ahead of the MFMAs that take them (hipcc by itself requests a step's pair only after the previous step's MFMAs)
         constexpr int AHEAD = 2;
-        h8_t wq1[16], wq2[16];
+        f16x8 wq1[16], wq2[16];
 #pragma unroll
         for (int st = 0; st < AHEAD; ++st) {
-            wq1[st] = *reinterpret_cast<const h8_t*>(slot + (2 * st) * 1024);
-            wq2[st] = *reinterpret_cast<const h8_t*>(slot + (2 * st + 1) * 1024);
+            wq1[st] = *reinterpret_cast<const f16x8*>(slot + (2 * st) * 1024);
+            wq2[st] = *reinterpret_cast<const f16x8*>(slot + (2 * st + 1) * 1024);
         }
 #pragma unroll
         for (int b = 0; b < BPG; ++b) {
@@ -286,10 +257,10 @@ __global__ __launch_bounds__(256, 2) void k_node_project(const float* __restrict
                 constexpr int EVERY = KS / NP;
                 if (!(PROBE & 4) && step % EVERY == 0 && step / EVERY < NP) dma_piece(next_src + (step / EVERY) * 1024, voff, next_slot + (step / EVERY) * 1024);
                 if (step + AHEAD < SPG) {
-                    wq1[step + AHEAD] = *reinterpret_cast<const h8_t*>(slot + (2 * (step + AHEAD)) * 1024);
-                    wq2[step + AHEAD] = *reinterpret_cast<const h8_t*>(slot + (2 * (step + AHEAD) + 1) * 1024);
+                    wq1[step + AHEAD] = *reinterpret_cast<const f16x8*>(slot + (2 * (step + AHEAD)) * 1024);
+                    wq2[step + AHEAD] = *reinterpret_cast<const f16x8*>(slot + (2 * (step + AHEAD) + 1) * 1024);
                 }
-                const h8_t w1 = wq1[step], w2 = wq2[step];
+                const f16x8 w1 = wq1[step], w2 = wq2[step];
                 if (!(PROBE & 2)) {
                     accM = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, a1[s], accM, 0, 0, 0);
                     accC = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, a2[s], accC, 0, 0, 0);

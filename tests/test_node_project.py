@@ -122,3 +122,36 @@ def test_linear_planes_rejects_what_it_is_not_built_for():
     W = torch.randn(640, 128, device=dev()) / 11.0
     with ops.bf16x6_arithmetic():
         assert torch.isfinite(ops.linear(A, W, None)).all()
+
+
+def _split_test_weights(nout, k, seed):
+    """Distinct values of both signs with magnitudes log-uniform over 2^-30 .. 6e4, and the split's edge cases written over some of them."""
+    rng = np.random.default_rng(seed)
+    mag = np.exp2(rng.uniform(-30.0, np.log2(6.0e4), size=nout * k))
+    W = (mag * rng.choice([-1.0, 1.0], size=nout * k)).astype(np.float32)
+    special = np.array([0.0, -0.0, 65504.0, -65504.0,
+                        2.0 ** -14,                  # the smallest fp16 normal
+                        3.0e-6, -2.0 ** -24,         # RN16(x) is subnormal
+                        0.125 + 2.0 ** -26,          # (x - x1) * 2048 = 2^-15: the second plane is subnormal
+                        -(3.0 + 2.0 ** -22)],        # a one-bit residual far below the first plane's last place
+                       dtype=np.float32)
+    W[rng.choice(nout * k, size=special.size, replace=False)] = special
+    assert np.unique(W.view(np.uint32)).size == W.size
+    return W.reshape(nout, k)
+
+
+@pytest.mark.parametrize("nout,k", [(64, 64), (32, 256)])
+def test_weight_planes_are_the_fp16_split_bit_for_bit(nout, k):
+    """ops.weight_planes shows the fp16 split itself (csrc/operand_planes.h): per (column block, k step) the (plane 1, plane 2) pairs
+    are exactly x1 = RN16(x), x2 = RN16((x - x1) * 2048) of that 32 x 16 block of W.  (The kernel's fma(x1, -2048, x * 2048) is the same
+    value: x - x1 and both products are exact in fp32.)  Sorting the 32-bit keys removes only the documented lane / column permutation
+    inside a block (node_project.hip's header); pairing and values are compared exactly and no element is left out."""
+    W = _split_test_weights(nout, k, seed=nout * 1000 + k)
+    got = ops.weight_planes(torch.from_numpy(W).to(dev())).cpu().numpy().view(np.uint16).reshape(nout // 32, k // 16, 2, 512)
+    got_key = np.sort(got[:, :, 0].astype(np.uint32) << 16 | got[:, :, 1].astype(np.uint32), axis=-1)
+    x = W.reshape(nout // 32, 32, k // 16, 16).transpose(0, 2, 1, 3).reshape(nout // 32, k // 16, 512)
+    x1 = x.astype(np.float16)
+    x2 = ((x - x1) * np.float32(2048.0)).astype(np.float16)
+    assert x2.dtype == np.float16 and (x - x1).dtype == np.float32
+    want_key = np.sort(x1.view(np.uint16).astype(np.uint32) << 16 | x2.view(np.uint16).astype(np.uint32), axis=-1)
+    assert np.array_equal(got_key, want_key)
