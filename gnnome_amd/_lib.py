@@ -123,9 +123,14 @@ SIGNATURES = {
     "gnnome_gfa_names_insert": [_p, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p],
     "gnnome_gfa_links": [_p, _l, _p, _p, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p, _p],
     "gnnome_gfa_pack": [_p, _l, _p, _p, _l, _p, _l, _p],
+    "gnnome_reads_records_fasta": [_p, _l, _p, _p, _l, _p, _p, _l, _p, _p, _p, _p, _p, _p],
+    "gnnome_reads_records_fastq": [_p, _l, _p, _p, _l, _p, _p, _l, _p, _l, _p, _p, _p, _p],
+    "gnnome_reads_names_insert": [_p, _l, _p, _l, _p, _l, _p, _p, _p],
+    "gnnome_reads_match": [_p, _l, _p, _i, _l, _p, _l, _p, _l, _p, _l, _p, _p],
+    "gnnome_reads_annotations": [_p, _l, _p, _i, _l, _p, _p, _l, _p, _p, _p, _l, _p, _p],
 }
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 # the parameter blocks of gnnome_model_forward_f32 (include/gnnome_hip.h), field for field

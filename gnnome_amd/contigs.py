@@ -77,10 +77,14 @@ class ReadStore:
         return cls.from_sequences(seqs, keep=keep, device=device)
 
     @classmethod
-    def from_reads_file(cls, path, node_to_read, num_nodes, keep=None, device=None):
+    def from_reads_file(cls, path, node_to_read, num_nodes, keep=None, device=None, parser="host"):
         """For a GFA whose S lines say '*': read r is the record of the FASTA / FASTQ file (plain or .gz) whose id is
         node_to_read[2r] (graph_parser.py:341-366; read_gfa's "node_to_read").  A unitig segment with A-lines maps to several
-        reads and has no single record: that raises, as in the reference (there a TypeError)."""
+        reads and has no single record: that raises, as in the reference (there a TypeError).  parser: "host" (the per-record loop
+        below), "device" (reads.read_reads_device: the same data, off and missing, the same errors, or ReadsDeviceError where the
+        device reader declines the file), "auto" (the device when there is one, the host loop whenever it reports anything at all)."""
+        if parser not in ("host", "device", "auto"):
+            raise ValueError(f"parser={parser!r}: expected 'host', 'device' or 'auto'")
         num_reads = int(num_nodes) // 2
         ids = []
         for r in range(num_reads):
@@ -90,6 +94,14 @@ class ReadStore:
                                  f"of {path}; use a GFA that carries the unitig sequences on its S lines")
             ids.append(rid)
         mask = _keep_mask(keep, num_reads)
+        if parser == "device" or (parser == "auto" and torch.cuda.is_available()):
+            from .reads import read_store_arrays
+            try:
+                data, off = read_store_arrays(path, ids, mask, device or _default_device())
+                return cls(data, off, None if mask is None else ~mask)
+            except Exception:   # noqa: BLE001 ("auto": whatever the device reader reports, the host loop answers)
+                if parser == "device":
+                    raise
         wanted = set(ids) if mask is None else {rid for rid, m in zip(ids, mask) if m}
         found = read_sequences(path, wanted)
         seqs = []

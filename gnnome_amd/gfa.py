@@ -103,10 +103,21 @@ def _node_annotations(node_to_read, num_nodes, reads_path):
     return [torch.tensor(c, dtype=torch.int64) for c in cols]
 
 
-def _add_training(out, reads_path, labels):
-    """read_strand, read_start, read_end, read_chr and y into `out` (the module docstring's training=True)."""
+def _add_training(out, reads_path, labels, reads_parser="host"):
+    """read_strand, read_start, read_end, read_chr and y into `out` (the module docstring's training=True).  reads_parser: who reads
+    the titles - "host" (_node_annotations), "device" (reads.node_annotations_device) or "auto"."""
     keys = ("read_strand", "read_start", "read_end", "read_chr")
-    out.update(zip(keys, _node_annotations(out["node_to_read"], out["num_nodes"], reads_path)))
+    cols = None
+    if reads_parser == "device" or (reads_parser == "auto" and torch.cuda.is_available()):
+        from .reads import node_annotations_device
+        try:
+            cols = node_annotations_device(out["node_to_read"], out["num_nodes"], reads_path)
+        except Exception:   # noqa: BLE001 ("auto": whatever the device reader reports, the host code answers)
+            if reads_parser == "device":
+                raise
+    if cols is None:
+        cols = _node_annotations(out["node_to_read"], out["num_nodes"], reads_path)
+    out.update(zip(keys, cols))
     out["y"] = None
     if labels == "device":
         from .labels import process_graph
@@ -122,22 +133,27 @@ def _add_training(out, reads_path, labels):
             warnings.warn("read_gfa: no GPU, so the edge labels (y) were not computed; y is None")
 
 
-def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, training=False, labels="auto", parser="host"):
+def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, training=False, labels="auto", parser="host",
+             reads_parser="host"):
     """-> dict(src, dst int64[E]; num_nodes; overlap_length, prefix_length int64[E]; read_length int64[N];
     overlap_similarity float32[E] | None; read_to_node, node_to_read, read_to_node2; read_seqs | None);
     training=True adds read_strand, read_start, read_end, read_chr int64[N] and y float32[E] | None (see the module docstring).
     parser: "host" (this function's own loop), "device" (read_gfa_device, its tensors moved to the CPU: the same dict key for key,
     or GfaDeviceError where the device parser declines the file), "auto" (the device when there is one, the host parser whenever
-    the device parser reports anything at all)."""
+    the device parser reports anything at all).  reads_parser: who reads the titles of `reads_path` for training=True - "host"
+    (contigs.read_titles and a regex per read), "device" (gnnome_amd/reads.py: the same four tensors, the same ValueError for a read
+    that is absent or lacks a field, or ReadsDeviceError where the device reader declines the file) or "auto" likewise."""
     if training and reads_path is None:
         raise ValueError("read_gfa(training=True) needs reads_path: the FASTA / FASTQ whose titles carry the read positions")
     if labels not in ("auto", "device", False, None):
         raise ValueError(f"labels={labels!r}: expected 'auto', 'device' or False")
     if parser not in ("host", "device", "auto"):
         raise ValueError(f"parser={parser!r}: expected 'host', 'device' or 'auto'")
+    if reads_parser not in ("host", "device", "auto"):
+        raise ValueError(f"reads_parser={reads_parser!r}: expected 'host', 'device' or 'auto'")
     if parser == "device" or (parser == "auto" and not callable(similarity) and torch.cuda.is_available()):
         try:
-            return _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels)
+            return _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels, reads_parser)
         except Exception:   # noqa: BLE001 ("auto": whatever the device parser reports, the host parser answers)
             if parser == "device":
                 raise
@@ -238,7 +254,7 @@ def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, tra
             except (RuntimeError, ValueError, OSError) as ex:
                 warnings.warn(f"read_gfa: overlap similarities not computed on the device ({ex}); overlap_similarity is None")
     if training:
-        _add_training(out, reads_path, labels)
+        _add_training(out, reads_path, labels, reads_parser)
     return out
 
 
@@ -522,7 +538,7 @@ def read_gfa_device(path, similarity="auto", device=None, keep_names=True):
     return out
 
 
-def _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels):
+def _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels, reads_parser="host"):
     """read_gfa(parser="device"): read_gfa_device's dict on the CPU, with read_seqs and the training keys built on the host."""
     g = read_gfa_device(path, similarity=similarity)
     reads = g.pop("reads")
@@ -537,5 +553,5 @@ def _read_gfa_through_device(path, similarity, keep_sequences, reads_path, train
             seqs[2 * r + 1] = seqs[2 * r].translate(_COMPLEMENT)[::-1]
         out["read_seqs"] = seqs
     if training:
-        _add_training(out, reads_path, labels)
+        _add_training(out, reads_path, labels, reads_parser)
     return out

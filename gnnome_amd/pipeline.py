@@ -58,13 +58,14 @@ def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto"
 
 
 def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, nb_paths=100, similarity="auto", device=None, scores=None,
-                      sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, parser="host"):
+                      sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, parser="host", reads_parser="host"):
     """GFA -> scores -> greedy walks -> contigs spelled on the device -> FASTA at out_path (inference.py:411-489).
     -> (walks, contigs, stats); stats = quick_evaluation's figures as a dict (ref_length from the caller: NG50 and the
     reconstructed fraction are -1 without it).  Sequences: the GFA's S lines if it carries them, else `reads` (a FASTA / FASTQ
     path, plain or .gz, or a ReadStore); with neither this raises before any scoring.  Only the reads the walks touch are
     uploaded.  The prefixes are masked as pipeline.assemble masks them (inference.py:461).  parser="device" / "auto": the GFA is read
-    once, by gfa.read_gfa_device, and its sequences are the packed reads that parse left on the device, restricted to the touched ones."""
+    once, by gfa.read_gfa_device, and its sequences are the packed reads that parse left on the device, restricted to the touched ones.
+    reads_parser: how a `reads` file is read (ReadStore.from_reads_file's parser=)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     gfa_path = None if isinstance(gfa_or_graph, dict) else gfa_or_graph
     if gfa_path is not None and parser != "host":
@@ -99,7 +100,8 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
     elif source == "gfa":
         store = contigs_mod.ReadStore.from_gfa(gfa_path, keep=touched, device=device)
     elif source == "file":
-        store = contigs_mod.ReadStore.from_reads_file(reads, g["node_to_read"], g["num_nodes"], keep=touched, device=device)
+        store = contigs_mod.ReadStore.from_reads_file(reads, g["node_to_read"], g["num_nodes"], keep=touched, device=device,
+                                                      parser=reads_parser)
     else:
         store = contigs_mod.ReadStore.from_sequences([g["read_seqs"][2 * r] for r in range(g["num_nodes"] // 2)], keep=touched, device=device)
     prefix = g["prefix_length"].masked_fill(g["prefix_length"] < 0, 0)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 21
+#define GNNOME_ABI_VERSION 22
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -887,6 +887,51 @@ int gnnome_gfa_links(const uint8_t* buf, int64_t num_bytes, const int64_t* link_
                      int32_t* err, int64_t num_lines, int32_t* first_bad, int64_t* event_u, int64_t* event_v, void* stream);
 int gnnome_gfa_pack(const uint8_t* src, int64_t src_bytes, const int64_t* src_beg, const int64_t* out_off, int64_t num_items, uint8_t* out,
                     int64_t out_bytes, void* stream);
+
+/* ---- FASTA / FASTQ reads files: records, wanted ids, sequences, positions ------------------------------------------------------------
+ * Replaces the per-record loops of graph_parser.py:121-136 (the titles of the reads file), :213-272 (strand, start, end and chromosome
+ * from those titles, per node) and :341-366 (the sequences of a GFA whose S lines say '*'), as gnnome_amd/contigs.py _records /
+ * read_sequences / read_titles and gnnome_amd/gfa.py _annotation state them.  The file's bytes are on the device (buf uint8[num_bytes],
+ * .gz decompressed on the host) and are tokenised by gnnome_gfa_mark unchanged; field_start / field_end / line_field are what
+ * gnnome_gfa_classify takes, line_start int64[num_lines] the positions of mark bit 2.  Compactions, scans, sorts and the unitig
+ * combination are torch operators (gnnome_amd/reads.py); the bases are copied by gnnome_gfa_pack, one item per sequence line.  Nothing
+ * here produces a float; no float atomics.  err int32[num_lines] preset to 0 and first_bad int32[1] preset to INT32_MAX are shared by
+ * the entries: a line this path does not serve gets a code (1 a sequence or quality line with more than one field, 2 a FASTQ record
+ * that is not in the four-line form, 3 a number of more than 18 digits in a title, 4 a chr= value that mixes digits and letters) and
+ * first_bad is lowered (atomicMin) to the smallest such line.
+ * gnnome_reads_records_fasta: one thread per line.  kind int32[L]: 0 blank, 1 header (the line's first BYTE is '>'), 2 any other
+ *   line with a field.  rec int64[L,4], byte ranges as [begin, end): header: id (the first whitespace-separated token of line[1:], empty
+ *   when nothing follows the marker), title (line[1:].rstrip()); other: its first field, -, -.  first_header int64[1] on the device: the
+ *   line of the first header (num_lines without one); a line of kind 2 with more than one field gets code 1 only below it.
+ * gnnome_reads_records_fastq: one thread per record over nonblank int64[num_nonblank], the lines with a field, in file order; record k
+ *   is lines 4k..4k+3 of them and must be: first byte '@'; first byte not '+', one field; first byte '+'; one field as long as the
+ *   sequence.  rec int64[ceil(num_nonblank / 4), 6]: id, title, sequence; all 0 for a record that breaks the form, whose first
+ *   offending line gets code 2 (1 for the field count); a trailing group of fewer than 4 lines gets code 2 at its first line.
+ * gnnome_reads_names_insert: names uint8[names_bytes] = the wanted names one after the other, name r = names[name_off[r] : name_off[r+1]],
+ *   name_off int64[R+1]; table int32[capacity] preset to -1, capacity a power of two (>= 2).  Linear probing, 32-bit compare-and-swap,
+ *   every probe compares length and bytes.  Names with equal bytes share a slot (two nodes may name one read).  slot_of int32[R]: the
+ *   slot of every name, -1 when the table had no room, in which case full int32[1] (preset to 0) becomes 1.
+ * gnnome_reads_match: record k's id = buf[rec[k*rec_stride] : rec[k*rec_stride+1]) is looked up; where a wanted name has its bytes,
+ *   match[slot] (int32[capacity], preset to -1) is raised to k with an integer atomicMax: a repeated id keeps its last record.
+ * gnnome_reads_annotations: one thread per entry of which int64[num_which] (a record index, or -1: no record).  The title
+ *   buf[rec[k*rec_stride+2] : rec[k*rec_stride+3]) is searched for the first match of strand=(\+|\-), start=(\d+), end=(\d+) and
+ *   chr=([0-9XYM]+) as re.search finds them (substring matches; an occurrence the pattern does not match is passed over).  ann
+ *   int64[num_which,4] = +1 / -1, start, end, chromosome (X, Y, M: -1, -2, -3); missing int32[num_which]: bit 0 strand, 1 start, 2 end,
+ *   3 chr has no match (15 for which = -1).  Codes 3 and 4 go to line rec_line[k] (int64[num_records], the record's header line). */
+int gnnome_reads_records_fasta(const uint8_t* buf, int64_t num_bytes, const int64_t* field_start, const int64_t* field_end,
+                               int64_t num_fields, const int64_t* line_field, const int64_t* line_start, int64_t num_lines,
+                               const int64_t* first_header, int32_t* kind, int64_t* rec, int32_t* err, int32_t* first_bad, void* stream);
+int gnnome_reads_records_fastq(const uint8_t* buf, int64_t num_bytes, const int64_t* field_start, const int64_t* field_end,
+                               int64_t num_fields, const int64_t* line_field, const int64_t* line_start, int64_t num_lines,
+                               const int64_t* nonblank, int64_t num_nonblank, int64_t* rec, int32_t* err, int32_t* first_bad, void* stream);
+int gnnome_reads_names_insert(const uint8_t* names, int64_t names_bytes, const int64_t* name_off, int64_t num_names, int32_t* table,
+                              int64_t capacity, int32_t* slot_of, int32_t* full, void* stream);
+int gnnome_reads_match(const uint8_t* buf, int64_t num_bytes, const int64_t* rec, int rec_stride, int64_t num_records,
+                       const uint8_t* names, int64_t names_bytes, const int64_t* name_off, int64_t num_names, const int32_t* table,
+                       int64_t capacity, int32_t* match, void* stream);
+int gnnome_reads_annotations(const uint8_t* buf, int64_t num_bytes, const int64_t* rec, int rec_stride, int64_t num_records,
+                             const int64_t* rec_line, const int64_t* which, int64_t num_which, int64_t* ann, int32_t* missing, int32_t* err,
+                             int64_t num_lines, int32_t* first_bad, void* stream);
 
 #ifdef __cplusplus
 }
