@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import contigs as contigs_mod
-from . import decode, features, gfa
+from . import decode, features, gfa, metrics
 from .graph import views_for
 
 
@@ -115,3 +115,24 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
     else:
         stats.update(longest_contig=0, reconstructed=-1, n50=-1, ng50=-1)
     return walks, contigs, stats
+
+
+def edge_report(g, model=None, scores=None, device=None):
+    """The quality figures of a scorer on a labelled graph (a dict with `y`, e.g. read_gfa(training=True)): the confusion counts at
+    0.5, the eight figures utils/metrics.py:15-46 derives from them and the two average precisions (:67-80).  `scores` (logits, one
+    per edge) overrides the model, as in assemble."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    if g.get("y") is None:
+        raise ValueError("edge_report: the graph carries no labels y (read_gfa(training=True), or labels.process_graph)")
+    if scores is None:
+        if model is None:
+            raise ValueError("edge_report: neither a model nor scores")
+        scores = score_graph(g, model, device)
+    scores = torch.as_tensor(scores).detach().reshape(-1).float().to(device)
+    y = torch.as_tensor(g["y"]).reshape(-1).float().to(device)
+    TP, TN, FP, FN = metrics.calculate_tfpn(scores, y)
+    acc, precision, recall, f1 = metrics.calculate_metrics(TP, TN, FP, FN)
+    acc_inv, precision_inv, recall_inv, f1_inv = metrics.calculate_metrics_inverse(TP, TN, FP, FN)
+    return {"TP": TP, "TN": TN, "FP": FP, "FN": FN, "acc": acc, "precision": precision, "recall": recall, "f1": f1,
+            "acc_inv": acc_inv, "precision_inv": precision_inv, "recall_inv": recall_inv, "f1_inv": f1_inv,
+            "aps": metrics.get_aps(scores, y, device=device), "aps_inverse": metrics.get_aps_inverse(scores, y, device=device)}

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 22
+#define GNNOME_ABI_VERSION 23
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -932,6 +932,39 @@ int gnnome_reads_match(const uint8_t* buf, int64_t num_bytes, const int64_t* rec
 int gnnome_reads_annotations(const uint8_t* buf, int64_t num_bytes, const int64_t* rec, int rec_stride, int64_t num_records,
                              const int64_t* rec_line, const int64_t* which, int64_t num_which, int64_t* ann, int32_t* missing, int32_t* err,
                              int64_t num_lines, int32_t* first_bad, void* stream);
+
+/* ---- Precision-recall curve and average precision of the edge scores -----------------------------------------------------------------
+ * Replaces the scikit-learn calls of utils/metrics.py:51-80 (precision_recall_curve, average_precision_score) for either class, as
+ * gnnome_amd/metrics.py states them.  With v the score of an edge and `positive` its class bit: sort by v descending; idx = the last
+ * position of every run of equal v; tp[j] = positives at positions <= idx[j], fp[j] = 1 + idx[j] - tp[j], thresholds[j] = v at idx[j].
+ * The sort between the first two entries is the caller's (torch.sort, descending, of the keys as int32).  Every count is an exact
+ * integer scan in three launches (per-tile sums, ONE workgroup over the tile sums, per-tile downsweep): no kernel waits on another
+ * workgroup, the tiles are fixed, and the only atomics are integer minima of the check words.  1 <= num_edges < 2^31.
+ * The workspace is shared by the four entries of one curve and must not be touched between them.
+ * gnnome_pr_curve_tile_size: sorted positions per tile of the scan and terms per tile of the AP sum (host, no launch).
+ * gnnome_pr_curve_keys (utils/metrics.py:52, :59-60, :68, :76-77): p = preds (apply_sigmoid = 0) or 1 / (1 + expf(-preds)) in float32
+ *   (apply_sigmoid = 1), also written to probs_out when that is not NULL; v = p, positive = (label == 1), or with inverse != 0
+ *   v = 1.0f - p in float32, positive = (label == 0); keys uint32[E] = (bits(v) << 1) | positive (v in [0, 1]: 30 bits, monotone in
+ *   v).  The check words are preset here: the smallest edge id with p NaN or outside [0, 1], and with a label other than 0 or 1.
+ * gnnome_pr_curve_scan (utils/metrics.py:54, :62, :70, :79): sorted_keys uint32[E] descending.  SYNCHRONISES `stream` once and fills
+ *   result_host int64[4] (HOST memory): the number of thresholds M, the number of positives P, the two check words (-1: none).
+ * gnnome_pr_curve_emit (utils/metrics.py:54-55, :62-63): any output may be NULL.  thresholds float32[M], tp, fp int64[M] at j (descending
+ *   threshold); precision, recall float64[M+1] in scikit-learn's order: (double)tp / (double)(tp + fp) and (double)tp / (double)P at
+ *   M-1-j, and (1, 0) at M; last int64[1] = the first j with tp[j] = P, where scikit-learn 0.24.2 cuts the curve (it keeps j = last..0).
+ *   num_thresholds and num_positives are what gnnome_pr_curve_scan returned (P >= 1).
+ * gnnome_pr_curve_ap (utils/metrics.py:70, :79): ap float64[1] = max(0, -sum over r < M of (recall[r+1] - recall[r]) * precision[r]),
+ *   each term one IEEE subtraction and one IEEE multiplication (no fma), summed per tile and then over the tiles in fixed trees. */
+int gnnome_pr_curve_tile_size(int* tile_host);
+int gnnome_pr_curve_workspace_bytes(int64_t num_edges, size_t* bytes_host);
+int gnnome_pr_curve_keys(const float* preds, const float* labels, int64_t num_edges, int apply_sigmoid, int inverse, uint32_t* keys,
+                         float* probs_out, void* workspace, size_t workspace_bytes, void* stream);
+int gnnome_pr_curve_scan(const uint32_t* sorted_keys, int64_t num_edges, void* workspace, size_t workspace_bytes, int64_t* result_host,
+                         void* stream);
+int gnnome_pr_curve_emit(const uint32_t* sorted_keys, int64_t num_edges, int64_t num_thresholds, int64_t num_positives, float* thresholds,
+                         int64_t* tp, int64_t* fp, double* precision, double* recall, int64_t* last, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int gnnome_pr_curve_ap(const double* precision, const double* recall, int64_t num_thresholds, double* ap, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
