@@ -104,6 +104,8 @@ SIGNATURES = {
     "gnnome_mark_walk_visited": [_p, _p, _p, _l, _p, _p],
     "gnnome_overlap_workspace_bytes": [ctypes.POINTER(_sz)],
     "gnnome_overlap_edit_distance": [_p, _p, _l, _p, _i, _p, _p, _p, _l, _p, _p, _p, _sz, _p],
+    "gnnome_overlap_long_workspace_bytes": [_l, ctypes.POINTER(_sz)],
+    "gnnome_overlap_edit_distance_long": [_p, _p, _l, _p, _i, _p, _p, _p, _l, _l, _p, _p, _p, _sz, _p],
     "gnnome_contig_pieces_workspace_bytes": [_l, _l, ctypes.POINTER(_sz)],
     "gnnome_contig_pieces": [_p, _l, _p, _l, _p, _p, _p, _p, _l, _p, _l, _p, _p, _sz, _p],
     "gnnome_contig_spell": [_p, _l, _p, _l, _p, _p, _p, _l, _p, _i, _p, _l, _p],

@@ -360,6 +360,164 @@ int launch_class(const uint8_t* reads, const int64_t* read_off, const uint8_t* s
     return GNNOME_OK;
 }
 
+// The strip pass (gnnome_overlap_edit_distance_long only): what is still marked kNeedFull after the banded pass and the ten class
+// kernels - a query longer than one wavefront's 65 536 rows, or one whose match masks do not fit LDS at its class - is cut into
+// horizontal STRIPS of H = B * 2048 query rows (64 lanes x B blocks x 32 rows) and one wave runs the strips of an overlap one
+// after another, each with the skewed wavefront of k_overlap_edit_distance<B>.  What a strip adds to that kernel:
+//   * carry in: row 0 of strip s > 0 is not row 0 of the NW matrix; lane 0's horizontal input for column c is the horizontal
+//     delta the LAST row of strip s - 1 produced for column c (strip 0: +1, as before);
+//   * carry out: every strip but the last is full (H rows, no padding), its last row is lane 63's; lane 63 stores its hout per
+//     column, one byte (hout + 1), into this workgroup's slot of the carry buffer;
+//   * the match masks are rebuilt per strip, for that strip's rows only (each lane writes and reads only its own LDS words);
+//   * score starts at D[bottom row of this lane in this strip][column 0] = strip_base + (lane + 1) * B * 32, and only the LAST
+//     strip has padding rows to take off.
+// The carry slot holds max_columns bytes (rounded up to 128); an overlap whose target is longer keeps its mark (-> -1), so no
+// index exceeds the slot: reads and writes are at columns < n <= max_columns.
+// Ordering of the slot's accesses - all by ONE wave, which is the whole workgroup:
+//   * write in strip s, read in strip s + 1: __threadfence() between the strips, an agent-scope release + acquire.  By the
+//     MI355X microarchitecture guide's fence table ("Workgroup dispatch, XCD placement & inter-workgroup visibility") it lowers to
+//     s_waitcnt vmcnt(0) + buffer_wbl2 sc1 (the wave's carry stores have been performed and are in L2) and buffer_inv sc1 (this CU's
+//     L1 holds no line any more), so the next strip's loads are issued after the stores are done and can only be served with
+//     what L2 holds: a stale line has nowhere to come from.  Nobody else touches this slot during the launch, and a CU's L1
+//     goes stale only through another CU's stores (same section; programming guide, Guideline 16), so wavefront-scope program
+//     order would do - but a workgroup-scope fence is dropped entirely for a one-wave workgroup, and ~3.5 us per strip boundary is
+//     nothing next to a strip (>= 60 us at B = 16 and the shortest target).  The loads are per-lane vector loads through a pointer that
+//     is neither const nor __restrict__, so they cannot be moved to the scalar cache (Guideline 16, pitfall 6).
+//   * read and write of column c inside one strip (the slot is read for strip s while strip s writes it): column c is loaded at
+//     step <= max(c - 64, 0), consumed by lane 0 (readlane, i.e. after the wave has waited for the load) at step c, and written
+//     by lane 63 at step c + 63 - the store is issued after the loaded value has arrived in registers.
+template <int B>
+__global__ __launch_bounds__(64) void k_overlap_strips(const uint8_t* __restrict__ reads, const int64_t* __restrict__ read_off,
+                                                       const uint8_t* __restrict__ symtab, int nsym, const int32_t* __restrict__ src,
+                                                       const int32_t* __restrict__ dst, const int32_t* __restrict__ ol, int64_t E,
+                                                       int64_t max_columns, int64_t slot_bytes, uint8_t* carry_all, int* __restrict__ ticket,
+                                                       int32_t* __restrict__ dist_out) {
+    extern __shared__ uint32_t lds[];
+    constexpr int H = B * 2048;                                     // query rows per strip
+    uint32_t* peq = lds;                                            // [nsym][B][64]
+    uint8_t* st = reinterpret_cast<uint8_t*>(lds + nsym * B * 64);  // [512]
+    uint8_t* carry = carry_all + (int64_t)blockIdx.x * slot_bytes;  // [max_columns]: hout + 1 of the previous strip's last row
+    const int lane = threadIdx.x;
+    for (int i = lane; i < 512; i += 64) st[i] = (uint8_t)min((int)symtab[i], nsym - 1);
+    __syncthreads();
+    for (;;) {
+        int first = 0;
+        if (lane == 0) first = atomicAdd(ticket, 64);
+        first = __builtin_amdgcn_readfirstlane(first);
+        if (first >= E) break;
+        const int64_t cand = (int64_t)first + lane;
+        int mine_m = 0, mine_n = 0;
+        bool take = false;
+        if (cand < E && dist_out[cand] == kNeedFull) {   // (the mark first: an edge with an endpoint out of range never reaches read_off)
+            int ulen, vlen;
+            overlap_shape(read_off, src[cand], dst[cand], ol[cand], mine_m, mine_n, ulen, vlen);
+            take = mine_m > 0 && mine_n > 0 && mine_n <= max_columns;   // (a target longer than the carry slot keeps its mark: reported)
+        }
+        unsigned long long todo = __ballot(take);
+        while (todo) {
+            const int who = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int64_t ed = (int64_t)first + who;
+            const int m = __builtin_amdgcn_readfirstlane(__shfl(mine_m, who)), n = __builtin_amdgcn_readfirstlane(__shfl(mine_n, who));
+            const int u = src[ed], v = dst[ed];
+            const int64_t uo = read_off[u >> 1], vo = read_off[v >> 1];
+            const int ulen = (int)(read_off[(u >> 1) + 1] - uo), vlen = (int)(read_off[(v >> 1) + 1] - vo);
+            const bool urc = u & 1, vrc = v & 1;
+            const uint8_t* stu = st + (urc ? 256 : 0);
+            const uint8_t* stv = st + (vrc ? 256 : 0);
+            const int strips = (m + H - 1) / H;
+            const int row0 = lane * B * 32;   // first row of this lane inside a strip
+            for (int s = 0; s < strips; ++s) {
+                const int strip_base = s * H;
+                const int ms = min(H, m - strip_base);   // rows of this strip: H in every strip but the last
+                const bool last = s == strips - 1;
+                // ---- match masks of this lane's rows in this strip.  query[r] = read_src[ulen - m + r]
+                for (int i = 0; i < nsym * B; ++i) peq[i * 64 + lane] = 0;
+                for (int k = 0; k < B; ++k) {
+                    const int base = row0 + k * 32;
+                    if (base >= ms) break;
+                    const int cnt = min(32, ms - base);
+                    for (int bit = 0; bit < cnt; ++bit) {
+                        const int p = ulen - m + strip_base + base + bit;
+                        const uint8_t byte = urc ? reads[uo + (ulen - 1 - p)] : reads[uo + p];
+                        peq[(stu[byte] * B + k) * 64 + lane] |= 1u << bit;
+                    }
+                }
+                uint32_t Pv[B], Mv[B];
+#pragma unroll
+                for (int k = 0; k < B; ++k) Pv[k] = 0xFFFFFFFFu, Mv[k] = 0u;
+                int score = strip_base + (lane + 1) * B * 32;   // D[bottom row of this lane][column 0]
+                const int nl = (ms + B * 32 - 1) / (B * 32);
+                const int steps = n + nl - 1;
+                // lane 0's input for column j, as it travels between the lanes: (hin + 1) | symbol << 2; hin = +1 in strip 0, else the carry
+                auto column_in = [&](int j) -> uint32_t {
+                    if (j >= n) return 0u;
+                    const uint32_t h1 = s > 0 ? (uint32_t)carry[j] : 2u;
+                    return h1 | ((uint32_t)stv[vrc ? reads[vo + (vlen - 1 - j)] : reads[vo + j]] << 2);
+                };
+                uint32_t tbuf = column_in(lane), tnext = column_in(64 + lane);
+                uint32_t out_prev = 0;
+                for (int t = 0; t < steps; ++t) {
+                    if ((t & 63) == 0 && t > 0) {
+                        tbuf = tnext;
+                        tnext = column_in(t + 64 + lane);
+                    }
+                    const uint32_t fresh = (uint32_t)__builtin_amdgcn_readlane((int)tbuf, t & 63);
+                    uint32_t in = (uint32_t)__shfl_up((int)out_prev, 1);
+                    if (lane == 0) in = fresh;
+                    const int c = t - lane;
+                    uint32_t out = in;
+                    if (c >= 0 && c < n && lane < nl) {
+                        int h = (int)(in & 3u) - 1;
+                        const uint32_t sy = in >> 2;
+                        const uint32_t* pe = peq + (sy * B) * 64 + lane;
+#pragma unroll
+                        for (int k = 0; k < B; ++k) h = myers_block(Pv[k], Mv[k], pe[k * 64], h);
+                        score += h;
+                        out = (uint32_t)(h + 1) | (sy << 2);
+                        if (!last && lane == 63) carry[c] = (uint8_t)(h + 1);   // (c < n <= max_columns: inside the slot)
+                    }
+                    out_prev = out;
+                }
+                if (!last) {
+                    __threadfence();   // this strip's carry stores before the next strip's carry loads (see above)
+                } else if (lane == (ms - 1) / (B * 32)) {
+                    // ---- D[m][n]: the owner of the last query row removes the padding rows below it
+                    int excess = 0;
+#pragma unroll
+                    for (int k = 0; k < B; ++k) {
+                        const int base = row0 + k * 32;
+                        if (base + 32 > ms) {
+                            const uint32_t mask = base >= ms ? 0xFFFFFFFFu : (0xFFFFFFFFu << (ms - base));
+                            excess += __popc(Pv[k] & mask) - __popc(Mv[k] & mask);
+                        }
+                    }
+                    dist_out[ed] = score - excess;
+                    atomicAdd(ticket + 1, 1);   // workspace int 13: overlaps the strip pass settled (statistics only)
+                }
+            }
+        }
+    }
+}
+
+constexpr size_t kLongHeader = 128;   // the 16 ints of the short entry, padded so that the carry slots start on a 128-byte line
+constexpr int kStripWavesPerCU = 4;   // one per SIMD: the masks of one wave take up to 155 KB of a CU's 160 KB
+
+inline size_t strip_slot_bytes(int64_t max_columns) { return (size_t)((std::max<int64_t>(max_columns, 1) + 127) / 128 * 128); }
+
+template <int B>
+int launch_strips(const uint8_t* reads, const int64_t* read_off, const uint8_t* symtab, int nsym, const int32_t* src, const int32_t* dst,
+                  const int32_t* ol, int64_t E, int64_t max_columns, uint8_t* carry, int* ticket, int32_t* dist, int grid, hipStream_t s) {
+    const size_t lds = (size_t)nsym * B * 64 * 4 + 512;
+    GN_REQUIRE(lds <= 160 * 1024, "overlap_edit_distance_long: %d symbols x %d blocks per lane need %zu bytes of LDS", nsym, B, lds);
+    if (lds > 64 * 1024)
+        GN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_overlap_strips<B>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_overlap_strips<B>), dim3((unsigned)grid), dim3(64), lds, s, reads, read_off, symtab, nsym, src, dst, ol, E, max_columns,
+                       (int64_t)strip_slot_bytes(max_columns), carry, ticket, dist);
+    GN_LAUNCH_CHECK();
+    return GNNOME_OK;
+}
+
 __global__ void k_similarity(const int32_t* __restrict__ dist, const int32_t* __restrict__ ol, int64_t E, float* __restrict__ sim) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= E) return;
@@ -377,11 +535,13 @@ extern "C" int gnnome_overlap_workspace_bytes(size_t* bytes_host) {
     return GNNOME_OK;
 }
 
-extern "C" int gnnome_overlap_edit_distance(const uint8_t* reads, const int64_t* read_off, int64_t num_reads, const uint8_t* symtab,
-                                            int num_symbols, const int32_t* src, const int32_t* dst, const int32_t* overlap_length,
-                                            int64_t num_edges, int32_t* dist_out, float* similarity_out, void* workspace,
-                                            size_t workspace_bytes, void* stream) {
-    using namespace gnnome;
+namespace gnnome {
+namespace {
+
+// both entries: prepare, the banded pass, the ten class kernels, [max_columns >= 0: the strip pass], finish, similarities
+int overlap_passes(const uint8_t* reads, const int64_t* read_off, int64_t num_reads, const uint8_t* symtab, int num_symbols, const int32_t* src,
+                   const int32_t* dst, const int32_t* overlap_length, int64_t num_edges, int32_t* dist_out, float* similarity_out,
+                   void* workspace, size_t workspace_bytes, int64_t max_columns, void* stream) {
     GN_REQUIRE(num_edges >= 0 && num_reads >= 0, "overlap_edit_distance: negative size");
     if (num_edges == 0) return GNNOME_OK;
     GN_REQUIRE(reads && read_off && symtab && src && dst && overlap_length && dist_out && workspace, "overlap_edit_distance: null pointer");
@@ -425,6 +585,20 @@ extern "C" int gnnome_overlap_edit_distance(const uint8_t* reads, const int64_t*
     GN_CLASS(0, 1);
 #undef GN_CLASS
     if (rc != GNNOME_OK) return rc;
+    if (max_columns >= 0) {
+        // the strip pass: what is still marked.  One carry slot per workgroup; as many workgroups as the workspace has slots for
+        const size_t slot = strip_slot_bytes(max_columns);
+        GN_REQUIRE(workspace_bytes >= kLongHeader + slot, "overlap_edit_distance_long: workspace too small for one carry slot of %zu bytes", slot);
+        const int64_t slots = (int64_t)((workspace_bytes - kLongHeader) / slot);
+        const int sgrid = (int)std::min<int64_t>({(num_edges + 63) / 64, (int64_t)persistent_grid() * kStripWavesPerCU, slots});
+        uint8_t* carry = reinterpret_cast<uint8_t*>(workspace) + kLongHeader;
+        // the largest existing class whose masks fit LDS for this alphabet: 32 blocks per lane up to 19 symbols, 16 up to 32
+        if ((size_t)num_symbols * 32 * 64 * 4 + 512 <= 160 * 1024)
+            rc = launch_strips<32>(reads, read_off, symtab, num_symbols, src, dst, overlap_length, num_edges, max_columns, carry, tickets + 12, dist_out, sgrid, s);
+        else
+            rc = launch_strips<16>(reads, read_off, symtab, num_symbols, src, dst, overlap_length, num_edges, max_columns, carry, tickets + 12, dist_out, sgrid, s);
+        if (rc != GNNOME_OK) return rc;
+    }
     hipLaunchKernelGGL(k_overlap_finish, dim3(eb), dim3(256), 0, s, num_edges, dist_out);
     GN_LAUNCH_CHECK();
     if (similarity_out) {
@@ -432,4 +606,34 @@ extern "C" int gnnome_overlap_edit_distance(const uint8_t* reads, const int64_t*
         GN_LAUNCH_CHECK();
     }
     return GNNOME_OK;
+}
+
+}  // namespace
+}  // namespace gnnome
+
+extern "C" int gnnome_overlap_edit_distance(const uint8_t* reads, const int64_t* read_off, int64_t num_reads, const uint8_t* symtab,
+                                            int num_symbols, const int32_t* src, const int32_t* dst, const int32_t* overlap_length,
+                                            int64_t num_edges, int32_t* dist_out, float* similarity_out, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    return gnnome::overlap_passes(reads, read_off, num_reads, symtab, num_symbols, src, dst, overlap_length, num_edges, dist_out, similarity_out,
+                                  workspace, workspace_bytes, -1, stream);
+}
+
+extern "C" int gnnome_overlap_long_workspace_bytes(int64_t max_columns, size_t* bytes_host) {
+    using namespace gnnome;
+    GN_REQUIRE(bytes_host, "overlap_long_workspace_bytes: null pointer");
+    GN_REQUIRE(max_columns >= 0 && max_columns < (1ll << 31), "overlap_long_workspace_bytes: max_columns %lld outside [0, 2^31)", (long long)max_columns);
+    // (sized for the largest device, not the current one: the entry launches as many strip waves as there are slots, up to 4 per CU)
+    *bytes_host = kLongHeader + (size_t)kNumCUs * kStripWavesPerCU * strip_slot_bytes(max_columns);
+    return GNNOME_OK;
+}
+
+extern "C" int gnnome_overlap_edit_distance_long(const uint8_t* reads, const int64_t* read_off, int64_t num_reads, const uint8_t* symtab,
+                                                 int num_symbols, const int32_t* src, const int32_t* dst, const int32_t* overlap_length,
+                                                 int64_t num_edges, int64_t max_columns, int32_t* dist_out, float* similarity_out,
+                                                 void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(max_columns >= 0 && max_columns < (1ll << 31), "overlap_edit_distance_long: max_columns %lld outside [0, 2^31)", (long long)max_columns);
+    return overlap_passes(reads, read_off, num_reads, symtab, num_symbols, src, dst, overlap_length, num_edges, dist_out, similarity_out, workspace,
+                          workspace_bytes, max_columns, stream);
 }

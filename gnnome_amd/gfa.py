@@ -26,7 +26,8 @@ overlap_similarity (:101-117, :372-376) is 1 - editDistance(suffix, prefix) / ov
 from the third-party aligner edlib on the CPU.  Here (`similarity="auto"`, the default) it comes, in this order, from
 `SI:f:` tags on the `L` lines where the GFA carries them (our own extension, written by `write_similarity_tags`), else - for
 a GFA with sequences - from the device kernel gnnome_overlap_edit_distance (gnnome_amd/overlap.py: exact edit distances,
-one wavefront per overlap; needs the MI355X, there is no CPU version in this package); a caller-supplied
+one wavefront per overlap; needs the MI355X, there is no CPU version in this package; an overlap longer than 65 536 bases is
+refused unless long_overlaps=True, which aligns it strip by strip - overlap.edit_distances); a caller-supplied
 `similarity(src_seq, dst_seq, overlap_length)` callable overrides both.  A GFA without sequences and without tags gives
 None - never a guess (hyperparameters.py:17 `use_similarities`: a model trained with them needs them).
 
@@ -134,7 +135,7 @@ def _add_training(out, reads_path, labels, reads_parser="host"):
 
 
 def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, training=False, labels="auto", parser="host",
-             reads_parser="host"):
+             reads_parser="host", long_overlaps=False):
     """-> dict(src, dst int64[E]; num_nodes; overlap_length, prefix_length int64[E]; read_length int64[N];
     overlap_similarity float32[E] | None; read_to_node, node_to_read, read_to_node2; read_seqs | None);
     training=True adds read_strand, read_start, read_end, read_chr int64[N] and y float32[E] | None (see the module docstring).
@@ -142,7 +143,9 @@ def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, tra
     or GfaDeviceError where the device parser declines the file), "auto" (the device when there is one, the host parser whenever
     the device parser reports anything at all).  reads_parser: who reads the titles of `reads_path` for training=True - "host"
     (contigs.read_titles and a regex per read), "device" (gnnome_amd/reads.py: the same four tensors, the same ValueError for a read
-    that is absent or lacks a field, or ReadsDeviceError where the device reader declines the file) or "auto" likewise."""
+    that is absent or lacks a field, or ReadsDeviceError where the device reader declines the file) or "auto" likewise.
+    long_overlaps: handed to the device similarity call (overlap.edit_distances): True aligns overlaps beyond 65 536 bases strip by
+    strip, False (the default) refuses them - similarity="device" raises, "auto" warns and leaves None."""
     if training and reads_path is None:
         raise ValueError("read_gfa(training=True) needs reads_path: the FASTA / FASTQ whose titles carry the read positions")
     if labels not in ("auto", "device", False, None):
@@ -153,7 +156,7 @@ def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, tra
         raise ValueError(f"reads_parser={reads_parser!r}: expected 'host', 'device' or 'auto'")
     if parser == "device" or (parser == "auto" and not callable(similarity) and torch.cuda.is_available()):
         try:
-            return _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels, reads_parser)
+            return _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels, reads_parser, long_overlaps)
         except Exception:   # noqa: BLE001 ("auto": whatever the device parser reports, the host parser answers)
             if parser == "device":
                 raise
@@ -246,11 +249,11 @@ def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, tra
         out["overlap_similarity"] = torch.tensor(sims, dtype=torch.float32)
     elif similarity not in (None, False) and not no_seqs and (similarity == "device" or torch.cuda.is_available()):
         from .overlap import overlap_similarity   # the MI355X kernel
-        if similarity == "device":              # "device" insists: a missing library, > 32 symbols or an overlap beyond 65 536 bases raise
-            out["overlap_similarity"] = overlap_similarity(forward, src_t, dst_t, ol_t).cpu()
+        if similarity == "device":              # "device" insists: a missing library, > 32 symbols or (without long_overlaps) an overlap beyond 65 536 bases raise
+            out["overlap_similarity"] = overlap_similarity(forward, src_t, dst_t, ol_t, long_overlaps=long_overlaps).cpu()
         else:                                   # "auto": what cannot be aligned here is reported and left to the caller, as before the kernel existed
             try:
-                out["overlap_similarity"] = overlap_similarity(forward, src_t, dst_t, ol_t).cpu()
+                out["overlap_similarity"] = overlap_similarity(forward, src_t, dst_t, ol_t, long_overlaps=long_overlaps).cpu()
             except (RuntimeError, ValueError, OSError) as ex:
                 warnings.warn(f"read_gfa: overlap similarities not computed on the device ({ex}); overlap_similarity is None")
     if training:
@@ -503,12 +506,13 @@ def _tag_values(p, device):
     return torch.from_numpy(values).to(device)
 
 
-def read_gfa_device(path, similarity="auto", device=None, keep_names=True):
+def read_gfa_device(path, similarity="auto", device=None, keep_names=True, long_overlaps=False):
     """read_gfa's dict from the device parser, every tensor on `device` (same keys, dtypes and edge order; read_seqs is None), plus
     "reads": (uint8[total], int64[R+1]) on the device - the S-line sequences, forward strand, in S-line order as overlap.pack_reads
     lays them out - or None when an S line says '*'.  similarity: "auto", "device", None or False (SI:f: tags when every edge carries
     one; else, with sequences and similarity not None / False, overlap.edit_distances on g["reads"] - "device" insists, "auto" warns
-    and leaves None); a callable belongs to read_gfa's host parser.  keep_names=False leaves read_to_node, node_to_read and
+    and leaves None; long_overlaps is handed to it: True aligns overlaps beyond 65 536 bases strip by strip, False refuses them); a
+    callable belongs to read_gfa's host parser.  keep_names=False leaves read_to_node, node_to_read and
     read_to_node2 None (for a caller that only scores).  Raises GfaDeviceError for the inputs _DECLINED lists."""
     if callable(similarity):
         raise ValueError("read_gfa_device takes no similarity callable (it would need every read on the host): use read_gfa(path, "
@@ -529,18 +533,18 @@ def read_gfa_device(path, similarity="auto", device=None, keep_names=True):
     elif similarity not in (None, False) and p["reads"] is not None and p["num_nodes"]:
         from .overlap import edit_distances
         if similarity == "device":
-            out["overlap_similarity"] = edit_distances(p["reads"], src, dst, ol, device)[1]
+            out["overlap_similarity"] = edit_distances(p["reads"], src, dst, ol, device, long_overlaps=long_overlaps)[1]
         else:
             try:
-                out["overlap_similarity"] = edit_distances(p["reads"], src, dst, ol, device)[1]
+                out["overlap_similarity"] = edit_distances(p["reads"], src, dst, ol, device, long_overlaps=long_overlaps)[1]
             except (RuntimeError, ValueError, OSError) as ex:
                 warnings.warn(f"read_gfa_device: overlap similarities not computed on the device ({ex}); overlap_similarity is None")
     return out
 
 
-def _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels, reads_parser="host"):
+def _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels, reads_parser="host", long_overlaps=False):
     """read_gfa(parser="device"): read_gfa_device's dict on the CPU, with read_seqs and the training keys built on the host."""
-    g = read_gfa_device(path, similarity=similarity)
+    g = read_gfa_device(path, similarity=similarity, long_overlaps=long_overlaps)
     reads = g.pop("reads")
     out = {k: (t.cpu() if torch.is_tensor(t) else t) for k, t in g.items()}
     if keep_sequences:

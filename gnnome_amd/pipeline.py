@@ -31,25 +31,28 @@ def score_graph(g, model, device=None):
         return model(views, x, e).squeeze(1)
 
 
-def _read(path, similarity, parser, device):
+def _read(path, similarity, parser, device, long_overlaps=False):
     """The graph dict of a GFA by `parser`: "host" = gfa.read_gfa; "device" = gfa.read_gfa_device, tensors and packed reads left on the
-    device; "auto" = the device parser, and the host parser whenever that one reports anything."""
+    device; "auto" = the device parser, and the host parser whenever that one reports anything.  long_overlaps goes to the reader's
+    device similarity call (gfa.read_gfa)."""
     if parser not in ("host", "device", "auto"):
         raise ValueError(f"parser={parser!r}: expected 'host', 'device' or 'auto'")
     if parser == "device" or (parser == "auto" and not callable(similarity) and torch.cuda.is_available()):
         try:
-            return gfa.read_gfa_device(path, similarity=similarity, device=device)
+            return gfa.read_gfa_device(path, similarity=similarity, device=device, long_overlaps=long_overlaps)
         except Exception:   # noqa: BLE001
             if parser == "device":
                 raise
-    return gfa.read_gfa(path, similarity=similarity)
+    return gfa.read_gfa(path, similarity=similarity, long_overlaps=long_overlaps)
 
 
-def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto", device=None, scores=None, sampler=None, parser="host"):
+def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto", device=None, scores=None, sampler=None, parser="host",
+             long_overlaps=False):
     """-> (walks, scores, graph dict).  `scores` overrides the model (inference.py:426-432: saved predictions / labels).
-    parser: how a GFA path is read (gfa.read_gfa's parser=; with "device" the graph's tensors stay on the device)."""
+    parser: how a GFA path is read (gfa.read_gfa's parser=; with "device" the graph's tensors stay on the device).
+    long_overlaps: gfa.read_gfa's keyword - True lets a GFA with overlaps beyond 65 536 bases (ultra-long ONT reads) through."""
     device = device or torch.device("cuda", torch.cuda.current_device())
-    g = gfa_or_graph if isinstance(gfa_or_graph, dict) else _read(gfa_or_graph, similarity, parser, device)
+    g = gfa_or_graph if isinstance(gfa_or_graph, dict) else _read(gfa_or_graph, similarity, parser, device, long_overlaps)
     if scores is None:
         scores = score_graph(g, model, device)
     prefix = g["prefix_length"].masked_fill(g["prefix_length"] < 0, 0)      # inference.py:461
@@ -58,18 +61,19 @@ def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto"
 
 
 def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, nb_paths=100, similarity="auto", device=None, scores=None,
-                      sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, parser="host", reads_parser="host"):
+                      sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, parser="host", reads_parser="host",
+                      long_overlaps=False):
     """GFA -> scores -> greedy walks -> contigs spelled on the device -> FASTA at out_path (inference.py:411-489).
     -> (walks, contigs, stats); stats = quick_evaluation's figures as a dict (ref_length from the caller: NG50 and the
     reconstructed fraction are -1 without it).  Sequences: the GFA's S lines if it carries them, else `reads` (a FASTA / FASTQ
     path, plain or .gz, or a ReadStore); with neither this raises before any scoring.  Only the reads the walks touch are
     uploaded.  The prefixes are masked as pipeline.assemble masks them (inference.py:461).  parser="device" / "auto": the GFA is read
     once, by gfa.read_gfa_device, and its sequences are the packed reads that parse left on the device, restricted to the touched ones.
-    reads_parser: how a `reads` file is read (ReadStore.from_reads_file's parser=)."""
+    reads_parser: how a `reads` file is read (ReadStore.from_reads_file's parser=).  long_overlaps: as in assemble."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     gfa_path = None if isinstance(gfa_or_graph, dict) else gfa_or_graph
     if gfa_path is not None and parser != "host":
-        gfa_or_graph = _read(gfa_path, similarity, parser, device)
+        gfa_or_graph = _read(gfa_path, similarity, parser, device, long_overlaps)
         if "reads" in gfa_or_graph:     # device-parsed: nothing below opens the GFA again
             gfa_path = None
     elif parser not in ("host", "device", "auto"):
@@ -89,7 +93,7 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
         source = "dict"
     else:
         raise ValueError("no read sequences: the GFA's S lines say '*' (or a graph dict was passed) and no `reads` was given")
-    g = gfa_or_graph if isinstance(gfa_or_graph, dict) else gfa.read_gfa(gfa_or_graph, similarity=similarity)
+    g = gfa_or_graph if isinstance(gfa_or_graph, dict) else gfa.read_gfa(gfa_or_graph, similarity=similarity, long_overlaps=long_overlaps)
     walks, scores, g = assemble(g, model, len_threshold, nb_paths=nb_paths, similarity=similarity, device=device, scores=scores,
                                 sampler=sampler)
     touched = sorted({v >> 1 for w in walks for v in w})

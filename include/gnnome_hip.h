@@ -679,6 +679,26 @@ int gnnome_overlap_edit_distance(const uint8_t* reads, const int64_t* read_off, 
                                  int num_symbols, const int32_t* src, const int32_t* dst, const int32_t* overlap_length,
                                  int64_t num_edges, int32_t* dist_out, float* similarity_out, void* workspace,
                                  size_t workspace_bytes, void* stream);
+/* The same, for overlaps of any length (graph_parser.py:101-117 has no limit: edlib aligns what it is given).  gnnome_overlap_edit_distance_long
+ * runs the passes of gnnome_overlap_edit_distance and then, before anything is reported as -1, a STRIP pass over what is left: a query
+ * longer than 65 536 bases, or one whose match masks exceed LDS at its length, is cut into strips of B * 2048 rows (B = 32 up to 19
+ * symbols, 16 up to 32), one wavefront runs the strips of an overlap one after another and hands the last row's horizontal deltas, one byte
+ * per target column, from strip to strip through its slot of the workspace (csrc/overlap_similarity.hip, k_overlap_strips).  Cost per
+ * overlap: ceil(m / (B * 2048)) strips of (n + 63) * B block steps each; exact like every other pass.
+ *   max_columns  the largest target length min(overlap_length, len(read dst)) over the edges, >= 0: it sizes the carry slots.  An overlap
+ *                whose target is longer than max_columns is not aligned by the strip pass (-1 unless an earlier pass settled it)
+ *   workspace    gnnome_overlap_long_workspace_bytes(max_columns) bytes: the 16 ints of the short entry, padded to 128 bytes, then one slot
+ *                of max_columns bytes (rounded up to 128) per strip wave, four per CU of the largest device.  A smaller workspace is accepted
+ *                down to one slot; the strip pass then launches as many waves as there are whole slots
+ *   workspace ints 0-11 as in the short entry (11: overlaps the banded pass settled), 12 the strip pass's ticket counter,
+ *                13 the overlaps the strip pass settled (statistics only)
+ * Everything else - arguments, the -1 report for endpoints out of range, similarity_out - as gnnome_overlap_edit_distance, whose own
+ * behaviour and 16-int workspace are unchanged. */
+int gnnome_overlap_long_workspace_bytes(int64_t max_columns, size_t* bytes_host);
+int gnnome_overlap_edit_distance_long(const uint8_t* reads, const int64_t* read_off, int64_t num_reads, const uint8_t* symtab,
+                                      int num_symbols, const int32_t* src, const int32_t* dst, const int32_t* overlap_length,
+                                      int64_t num_edges, int64_t max_columns, int32_t* dist_out, float* similarity_out, void* workspace,
+                                      size_t workspace_bytes, void* stream);
 
 /* ---- contig spelling: walks -> sequences and FASTA bodies ------------------------------------------------------------------------
  * Replaces utils/evaluate.py:38-48 (walk_to_sequence) and the byte layout of :51-53 (save_assembly: Biopython's FASTA writer,
