@@ -130,6 +130,8 @@ SIGNATURES = {
     "gnnome_reads_names_insert": [_p, _l, _p, _l, _p, _l, _p, _p, _p],
     "gnnome_reads_match": [_p, _l, _p, _i, _l, _p, _l, _p, _l, _p, _l, _p, _p],
     "gnnome_reads_annotations": [_p, _l, _p, _i, _l, _p, _p, _l, _p, _p, _p, _l, _p, _p],
+    "gnnome_maf_lines": [_p, _l, _p, _p, _l, _p, _l, _p, _p, _p, _p, _p],
+    "gnnome_maf_text_check": [_p, _l, _p, _p, _l, _p, _l, _p, _p],
     "gnnome_pr_curve_tile_size": [ctypes.POINTER(_i)],
     "gnnome_pr_curve_workspace_bytes": [_l, ctypes.POINTER(_sz)],
     "gnnome_pr_curve_keys": [_p, _p, _l, _i, _i, _p, _p, _p, _sz, _p],
@@ -138,7 +140,7 @@ SIGNATURES = {
     "gnnome_pr_curve_ap": [_p, _p, _l, _p, _p, _sz, _p],
 }
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 # the parameter blocks of gnnome_model_forward_f32 (include/gnnome_hip.h), field for field

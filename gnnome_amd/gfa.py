@@ -36,7 +36,9 @@ FASTQ, plain or .gz, by suffix as contigs.reads_file_type) carry `strand=`, `sta
 (generate_data.py:43-60); every S line takes them from its read's title, a unitig with A lines combines its reads (strand: the sum of
 title strand x A-line orientation, >= 0 -> +1; start: min; end: max; chromosome: the most common, ties to the first seen), node 2k gets
 the strand and 2k+1 its opposite.  New keys read_strand, read_start, read_end, read_chr (int64[N]) and y (float32[E], edge-id order),
-the labels of utils/labels.py computed on the device by gnnome_amd.labels (csrc/edge_labels.hip).  `labels` follows `similarity`:
+the labels of utils/labels.py computed on the device by gnnome_amd.labels (csrc/edge_labels.hip).  With `maf=` (the MAF file pbsim3
+writes next to its FASTQ, and `maf_chr=`) the four columns come from the alignment blocks instead of the titles - gnnome_amd/maf.py, the
+step generate_data.py:43-60 does with Biopython - and reads_path is not needed.  `labels` follows `similarity`:
 "auto" labels on the device when there is one, else y is None with a warning; "device" insists; False leaves y None.  A read missing
 from the file, or a title without one of the four fields, raises ValueError naming the read and the file.
 
@@ -104,12 +106,16 @@ def _node_annotations(node_to_read, num_nodes, reads_path):
     return [torch.tensor(c, dtype=torch.int64) for c in cols]
 
 
-def _add_training(out, reads_path, labels, reads_parser="host"):
+def _add_training(out, reads_path, labels, reads_parser="host", maf=None, maf_chr=None, maf_parser="host"):
     """read_strand, read_start, read_end, read_chr and y into `out` (the module docstring's training=True).  reads_parser: who reads
-    the titles - "host" (_node_annotations), "device" (reads.node_annotations_device) or "auto"."""
+    the titles - "host" (_node_annotations), "device" (reads.node_annotations_device) or "auto".  With `maf` the four columns come from
+    maf.node_annotations(maf, maf_chr, parser=maf_parser) and no title is read."""
     keys = ("read_strand", "read_start", "read_end", "read_chr")
     cols = None
-    if reads_parser == "device" or (reads_parser == "auto" and torch.cuda.is_available()):
+    if maf is not None:
+        from .maf import node_annotations
+        cols = node_annotations(out["node_to_read"], out["num_nodes"], maf, maf_chr, parser=maf_parser)
+    elif reads_parser == "device" or (reads_parser == "auto" and torch.cuda.is_available()):
         from .reads import node_annotations_device
         try:
             cols = node_annotations_device(out["node_to_read"], out["num_nodes"], reads_path)
@@ -135,7 +141,7 @@ def _add_training(out, reads_path, labels, reads_parser="host"):
 
 
 def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, training=False, labels="auto", parser="host",
-             reads_parser="host", long_overlaps=False):
+             reads_parser="host", long_overlaps=False, maf=None, maf_chr=None, maf_parser="host"):
     """-> dict(src, dst int64[E]; num_nodes; overlap_length, prefix_length int64[E]; read_length int64[N];
     overlap_similarity float32[E] | None; read_to_node, node_to_read, read_to_node2; read_seqs | None);
     training=True adds read_strand, read_start, read_end, read_chr int64[N] and y float32[E] | None (see the module docstring).
@@ -145,9 +151,15 @@ def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, tra
     (contigs.read_titles and a regex per read), "device" (gnnome_amd/reads.py: the same four tensors, the same ValueError for a read
     that is absent or lacks a field, or ReadsDeviceError where the device reader declines the file) or "auto" likewise.
     long_overlaps: handed to the device similarity call (overlap.edit_distances): True aligns overlaps beyond 65 536 bases strip by
-    strip, False (the default) refuses them - similarity="device" raises, "auto" warns and leaves None."""
-    if training and reads_path is None:
-        raise ValueError("read_gfa(training=True) needs reads_path: the FASTA / FASTQ whose titles carry the read positions")
+    strip, False (the default) refuses them - similarity="device" raises, "auto" warns and leaves None.
+    maf, maf_chr, maf_parser: for training=True, a pbsim3 MAF file (or a list of (path, chr) pairs, maf_chr None) as the source of the
+    four read_* columns instead of the titles (gnnome_amd/maf.py; maf_parser "host", "device" or "auto" as there); reads_path is then not
+    needed and no title is read.  Without `maf` nothing changes."""
+    if training and reads_path is None and maf is None:
+        raise ValueError("read_gfa(training=True) needs reads_path: the FASTA / FASTQ whose titles carry the read positions "
+                         "(or maf=: the simulator's MAF file)")
+    if maf_parser not in ("host", "device", "auto"):
+        raise ValueError(f"maf_parser={maf_parser!r}: expected 'host', 'device' or 'auto'")
     if labels not in ("auto", "device", False, None):
         raise ValueError(f"labels={labels!r}: expected 'auto', 'device' or False")
     if parser not in ("host", "device", "auto"):
@@ -156,7 +168,8 @@ def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, tra
         raise ValueError(f"reads_parser={reads_parser!r}: expected 'host', 'device' or 'auto'")
     if parser == "device" or (parser == "auto" and not callable(similarity) and torch.cuda.is_available()):
         try:
-            return _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels, reads_parser, long_overlaps)
+            return _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels, reads_parser, long_overlaps,
+                                            maf, maf_chr, maf_parser)
         except Exception:   # noqa: BLE001 ("auto": whatever the device parser reports, the host parser answers)
             if parser == "device":
                 raise
@@ -257,7 +270,7 @@ def read_gfa(path, similarity="auto", keep_sequences=False, reads_path=None, tra
             except (RuntimeError, ValueError, OSError) as ex:
                 warnings.warn(f"read_gfa: overlap similarities not computed on the device ({ex}); overlap_similarity is None")
     if training:
-        _add_training(out, reads_path, labels, reads_parser)
+        _add_training(out, reads_path, labels, reads_parser, maf, maf_chr, maf_parser)
     return out
 
 
@@ -542,7 +555,8 @@ def read_gfa_device(path, similarity="auto", device=None, keep_names=True, long_
     return out
 
 
-def _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels, reads_parser="host", long_overlaps=False):
+def _read_gfa_through_device(path, similarity, keep_sequences, reads_path, training, labels, reads_parser="host", long_overlaps=False,
+                             maf=None, maf_chr=None, maf_parser="host"):
     """read_gfa(parser="device"): read_gfa_device's dict on the CPU, with read_seqs and the training keys built on the host."""
     g = read_gfa_device(path, similarity=similarity, long_overlaps=long_overlaps)
     reads = g.pop("reads")
@@ -557,5 +571,5 @@ def _read_gfa_through_device(path, similarity, keep_sequences, reads_path, train
             seqs[2 * r + 1] = seqs[2 * r].translate(_COMPLEMENT)[::-1]
         out["read_seqs"] = seqs
     if training:
-        _add_training(out, reads_path, labels, reads_parser)
+        _add_training(out, reads_path, labels, reads_parser, maf, maf_chr, maf_parser)
     return out

@@ -156,6 +156,14 @@ def read_reads_device(path, names, device=None, sequences=True, titles=False, ma
     mask over the names, the others enter as zero lengths, as in ReadStore.from_packed).  titles: the four title fields of that record.
     max_bytes: files above it are declined before anything is uploaded (default: a sixth of the free device memory; a file is not
     streamed in pieces).  Raises ReadsDeviceError for what _DECLINED lists."""
+    res = _read_uploaded(path, names, device, sequences, titles, max_bytes, keep, table_capacity)
+    if isinstance(res, ReadsDeviceError):
+        raise res       # from here: the traceback of a decline holds no frame with the reader's device tensors, so a kept error pins none
+    return res
+
+
+def _read_uploaded(path, names, device, sequences, titles, max_bytes, keep, table_capacity):
+    """read_reads_device's work.  What is declined once the bytes are on the device is RETURNED as a ReadsDeviceError, not raised."""
     from .ops import _on, _ptr, _stream
     kind_of_file = reads_file_type(path)
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -247,9 +255,9 @@ def read_reads_device(path, names, device=None, sequences=True, titles=False, ma
         cands.append((bad_line, 1, int(err[bad_line])))
     if cands:
         line, _, code = min(cands)
-        raise ReadsDeviceError(path, line + 1, _DECLINED.get(code, f"code {code}"))
+        return ReadsDeviceError(path, line + 1, _DECLINED.get(code, f"code {code}"))
     if table_full:
-        raise ReadsDeviceError(path, 0, _DECLINED[7])
+        return ReadsDeviceError(path, 0, _DECLINED[7])
     if sequences:
         keep_dev = None if keep is None else torch.from_numpy(np.ascontiguousarray(keep, dtype=bool)).to(device)
         src_beg, lengths, first = pack_items(res.last, keep_dev, seq_first, item_beg, item_len)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 23
+#define GNNOME_ABI_VERSION 24
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -952,6 +952,28 @@ int gnnome_reads_match(const uint8_t* buf, int64_t num_bytes, const int64_t* rec
 int gnnome_reads_annotations(const uint8_t* buf, int64_t num_bytes, const int64_t* rec, int rec_stride, int64_t num_records,
                              const int64_t* rec_line, const int64_t* which, int64_t num_which, int64_t* ann, int32_t* missing, int32_t* err,
                              int64_t num_lines, int32_t* first_bad, void* stream);
+
+/* ---- pbsim3 MAF files: the read positions of the training labels -----------------------------------------------------------------------
+ * Replaces the Biopython AlignIO loop of generate_data.py:43-60 (change_description_pbsim: start and size of the reference line of every
+ * alignment block, the strand of its read line), as gnnome_amd/maf.py states it.  The file's bytes are on the device and are tokenised by
+ * gnnome_gfa_mark unchanged; field_start / field_end / line_field are what gnnome_gfa_classify takes.  Grouping the s lines under the
+ * nearest a line, "exactly two" and "equal text lengths" are torch scans (gnnome_amd/maf.py); the wanted names go through
+ * gnnome_reads_names_insert / gnnome_reads_match with the block records (rec_stride 8).  err int32[num_lines] preset to 0 and first_bad
+ * int32[1] preset to INT32_MAX as for the reads entries; the codes: 1 an s line without exactly 7 fields, 2 a start, size or srcSize that
+ * is not plain digits, 3 one of more than 18 digits, 4 a strand other than + or -, 5 a line that is neither blank, a comment, a track
+ * line, an a line nor an s line, 9 a text whose bytes other than '-' are not `size` many (6-8 are set by the torch scans).
+ * gnnome_maf_lines (generate_data.py:43-60, the fields AlignIO reads from an s line): one thread per line.  kind int32[L]: 0 blank,
+ *   1 comment (first field begins with '#', or is "track"), 2 a (first field "a"), 3 s (first field "s"), 4 other.  rec int64[L,8], for
+ *   an s line without a code: name begin, name end, start, size, strand (+1 / -1), text begin, text end, 1; all 0 otherwise.
+ * gnnome_maf_text_check (generate_data.py:43-60, the size the reference trusts instead of len(seq)): one wavefront per record of rec
+ *   int64[num_records,8] (the s lines' records, compacted; rec_line int64[num_records] their lines).  A record whose last word is 1 and
+ *   whose text range lies inside [0, num_bytes) has the bytes of its text that are not '-' counted (16-byte loads where aligned, byte
+ *   loads at the ragged ends, a wave reduction); a count other than `size` gives its line code 9. */
+int gnnome_maf_lines(const uint8_t* buf, int64_t num_bytes, const int64_t* field_start, const int64_t* field_end, int64_t num_fields,
+                     const int64_t* line_field, int64_t num_lines, int32_t* kind, int64_t* rec, int32_t* err, int32_t* first_bad,
+                     void* stream);
+int gnnome_maf_text_check(const uint8_t* buf, int64_t num_bytes, const int64_t* rec, const int64_t* rec_line, int64_t num_records,
+                          int32_t* err, int64_t num_lines, int32_t* first_bad, void* stream);
 
 /* ---- Precision-recall curve and average precision of the edge scores -----------------------------------------------------------------
  * Replaces the scikit-learn calls of utils/metrics.py:51-80 (precision_recall_curve, average_precision_score) for either class, as
