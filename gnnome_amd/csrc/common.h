@@ -11,7 +11,7 @@ namespace gnnome {
 void set_error(const char* fmt, ...);
 
 // Tuning knobs (gnnome_set_tuning): variant selection for A/B measurements; 0 = the shipped default.
-enum { kTuneGateVariant = 0, kTuneGateAblation = 1, kTuneLinearVariant = 2, kTuneGateTileOrder = 3, kTuneGateExperiment = 4, kTuneAggLdsKiB = 5, kTuneAggHubs = 6, kTuneAggVariant = 7, kTuneRefVariant = 8, kTuneOverlapBand = 9, kTuneArith = 10, kTuneCount = 16 };
+enum { kTuneGateVariant = 0, kTuneGateAblation = 1, kTuneLinearVariant = 2, kTuneGateTileOrder = 3, kTuneGateExperiment = 4, kTuneAggLdsKiB = 5, kTuneAggHubs = 6, kTuneAggVariant = 7, kTuneRefVariant = 8, kTuneOverlapBand = 9, kTuneArith = 10, kTuneAggAddr64 = 11, kTuneCount = 16 };
 int tuning(int key);
 
 // Layer 0 only: the e tile is not loaded but COMPUTED by the load waves from the raw edge features,
@@ -154,6 +154,22 @@ __device__ __forceinline__ int xcd_remap(int bid, int n) {
 // v_exp_f32 + v_rcp_f32 (each within 1 ulp); an IEEE division here costs ~10 more VALU operations per element and the
 // aggregation kernels evaluate this E*H*2 times per layer
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+
+// sigmoidf_ of four elements, the same bits per element: __expf(-x) is v_exp_f32(x * -log2(e)), and the product and the "1 +" around the
+// two transcendentals are done on element pairs, v_pk_mul_f32 / v_pk_add_f32 (2 + 2 instructions instead of 4 + 4; IEEE per element
+// either way).  packed_: an empty asm that takes the pair as ONE 64-bit operand - without it the optimiser splits a two-element
+// product whose results are only read one by one back into two v_mul_f32.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 packed_(f32x2 v) {
+    asm("" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ f32x4 sigmoid4_(const f32x4 x) {
+    const f32x2 t0 = packed_(packed_(f32x2{x[0], x[1]}) * -1.4426950408889634f), t1 = packed_(packed_(f32x2{x[2], x[3]}) * -1.4426950408889634f);
+    const f32x2 d0 = packed_(packed_(f32x2{__builtin_amdgcn_exp2f(t0[0]), __builtin_amdgcn_exp2f(t0[1])}) + 1.0f);
+    const f32x2 d1 = packed_(packed_(f32x2{__builtin_amdgcn_exp2f(t1[0]), __builtin_amdgcn_exp2f(t1[1])}) + 1.0f);
+    return f32x4{__builtin_amdgcn_rcpf(d0[0]), __builtin_amdgcn_rcpf(d0[1]), __builtin_amdgcn_rcpf(d1[0]), __builtin_amdgcn_rcpf(d1[1])};
+}
 
 // relu that keeps NaN a NaN (fmaxf(NaN, 0) = 0): a node row whose sums went non-finite - an fp16x3 operand beyond 65504 upstream - must stay loud
 // all the way to the logits, where engine.forward_in_range looks.  Same value as fmaxf(t, 0) for every t that is not NaN.

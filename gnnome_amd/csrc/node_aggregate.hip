@@ -312,6 +312,120 @@ __device__ __forceinline__ void accumulate_items_split(const float* __restrict__
     }
 }
 
+// The default item loop: accumulate_items_split's sums - every item in the same lane group, added in the same order, every element through
+// the same operations: bit-identical - with less vector-instruction issue per item (profiles/aggregation_issue_audit.md):
+//   - the node, and with it the list bounds and every loop counter, is wave-uniform BY CONSTRUCTION (the caller passes scalars): the loops
+//     run on the scalar unit instead of as exec-mask loops over VGPR counters;
+//   - sigmoid4_: the products and adds around v_exp_f32 / v_rcp_f32 packed on element pairs;
+//   - the e rows of an in-edge step are contiguous from a uniform address: a scalar base and a per-lane constant;
+//   - the other row addresses without per-lane 64-bit arithmetic - a uniform base plus a 32-bit byte offset, multiplied out once per lane
+//     and step instead of once per lane and item - whenever the step's e rows lie below 4 GiB and its table rows below
+//     a32_rows = 2^32 / (ldn * 4) (0: never - gnnome_set_tuning(11, 1), for tests).  The entry point knows neither the edge count nor
+//     the tables' row count (a partition's halo rows lie beyond num_nodes_out), so the choice is made from the indices themselves - one
+//     compare and a wave vote per step - and is wave-uniform;
+//   - the cross-lane read of an item's offsets is a v_readlane where a lane group is the whole wave (H = 256).
+// As in accumulate_items_split, the in-edge e rows of a step are requested BEFORE the wave waits for its index loads: everything that
+// depends on them is derived inside the step from a copy the compiler cannot hoist (opaque_).
+__device__ __forceinline__ int opaque_(int v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+template <int H, int U = (H == 256 ? 8 : 4)>
+__device__ __forceinline__ void accumulate_items_lean(const float* __restrict__ e, const float* __restrict__ A2h, const float* __restrict__ A3h,
+                                                      int ldn, const int32_t* __restrict__ srt_src, const int32_t* __restrict__ out_pos,
+                                                      const int32_t* __restrict__ out_dst, int ib, int din, int ob, int lo, int hi, int lane,
+                                                      int group, int c, f32x4& nf, f32x4& df, f32x4& nb, f32x4& db, uint32_t a32_rows) {
+    constexpr int LPR = H / 4, G = 64 / LPR;
+    constexpr uint32_t kPosLimit = (uint32_t)((1ull << 32) / (H * 4));
+    const uint32_t lc = (uint32_t)c * 4, lg = (uint32_t)group * (H * 4) + lc;
+    // the value lane `it` holds: `it` is uniform inside a lane group, so with one group (H = 256) it is a scalar read
+    auto pick = [&](uint32_t v, int it) -> uint32_t {
+        if (G == 1) return (uint32_t)__builtin_amdgcn_readlane((int)v, __builtin_amdgcn_readfirstlane(it));
+        return (uint32_t)__builtin_amdgcn_ds_bpermute(it << 2, (int)v);
+    };
+    auto row32 = [&](const float* tb, uint32_t off) -> f32x4 {
+        return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(tb) + (size_t)(uint32_t)(off + lc));
+    };
+    auto row64 = [&](const float* tb, uint32_t idx, int stride) -> f32x4 { return *reinterpret_cast<const f32x4*>(tb + (int64_t)(int)idx * stride + c); };
+    for (int base = lo; base < hi; base += 64) {
+        const int j = base + lane;   // lane l owns item base + l
+        int my_p = 0, my_n = 0;
+        if (j < din) {
+            my_n = srt_src[ib + j];
+        } else if (j < hi) {
+            my_p = out_pos[ob + j - din];
+            my_n = out_dst[ob + j - din];
+        }
+        const int m = min(64, hi - base);
+        const int m_in = min(m, max(din - base, 0));   // items [0, m_in) of this batch are in-edges
+        for (int j0 = 0; j0 < m_in; j0 += G * U) {
+            const char* xb = reinterpret_cast<const char*>(e + (int64_t)(ib + base + j0) * H);
+            f32x4 x[U], a[U];
+            bool live[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                live[u] = j0 + u * G + group < m_in;
+                x[u] = *reinterpret_cast<const f32x4*>(xb + (size_t)(live[u] ? lg + (uint32_t)(u * G * H * 4) : lc));   // (a dead slot reads item j0)
+            }
+            const uint32_t nn = (uint32_t)opaque_(my_n);
+            if (__ballot(nn >= a32_rows) == 0) {
+                const uint32_t no = nn * (uint32_t)(ldn * 4);
+#pragma unroll
+                for (int u = 0; u < U; ++u) a[u] = row32(A2h, pick(no, live[u] ? j0 + u * G + group : j0));
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) a[u] = row64(A2h, pick(nn, live[u] ? j0 + u * G + group : j0), ldn);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (live[u]) {
+                    const f32x4 s = sigmoid4_(x[u]);
+                    nf += s * a[u];
+                    df += s;
+                }
+            }
+        }
+        if (m_in < m) {
+            const uint32_t pp = (uint32_t)my_p, nn = (uint32_t)my_n;
+            const bool fit = __ballot(pp >= kPosLimit || nn >= a32_rows) == 0;
+            const uint32_t po = pp * (uint32_t)(H * 4), no = nn * (uint32_t)(ldn * 4);
+            for (int j0 = m_in / (G * U) * (G * U); j0 < m; j0 += G * U) {
+                f32x4 x[U], a[U];
+                bool live[U];
+                int it[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int item = j0 + u * G + group;
+                    live[u] = item >= m_in && item < m;
+                    it[u] = live[u] ? item : m_in;   // (m_in < m here: a valid out-item)
+                }
+                if (fit) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        x[u] = row32(e, pick(po, it[u]));
+                        a[u] = row32(A3h, pick(no, it[u]));
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        x[u] = row64(e, pick(pp, it[u]), H);
+                        a[u] = row64(A3h, pick(nn, it[u]), ldn);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (live[u]) {
+                        const f32x4 s = sigmoid4_(x[u]);
+                        nb += s * a[u];
+                        db += s;
+                    }
+                }
+            }
+        }
+    }
+}
+
 // First launch of the hub path: wave (blockIdx.x * 4 + wave) reduces chunk c of EVERY split hub to (sum s*A2h, sum s,
 // sum s*A3h, sum s) partials; chunk boundaries are a function of the node's item count only.
 template <int H>
@@ -373,9 +487,12 @@ __global__ __launch_bounds__(kAggThreads, (WPS > 0 ? WPS : 1)) void k_node_aggre
     const float* __restrict__ h_in, int ldh, float* __restrict__ h_out, const float* __restrict__ scale,
     const float* __restrict__ shift, int total_blocks, float* __restrict__ aux0, float* __restrict__ aux1,
     float* __restrict__ aux2, float* __restrict__ aux3, const int* __restrict__ hub_count, const int* __restrict__ hub_nodes,
-    const float* __restrict__ hub_partials, int64_t node0, int norm_width, const int32_t* __restrict__ records = nullptr) {
+    const float* __restrict__ hub_partials, int64_t node0, int norm_width, const int32_t* __restrict__ records = nullptr,
+    uint32_t a32_rows = 0) {
     constexpr int LPR = H / 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // SPLIT == 6 (the default item loop, accumulate_items_lean): the wave index read as a scalar, so that the node and everything loaded
+    // through it (list bounds, counts) live in scalar registers
+    const int lane = threadIdx.x & 63, wave = SPLIT == 6 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     int64_t node;
     int hub_slot = -1;
     if (HUBFIN) {
@@ -431,7 +548,9 @@ __global__ __launch_bounds__(kAggThreads, (WPS > 0 ? WPS : 1)) void k_node_aggre
             accumulate_items_split<H, U, false, false, true>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db);
         else if (SPLIT == 3)   // variant 8: the split loop without branches around dead items
             accumulate_items_split<H, U, true>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db);
-        else if (SPLIT == 1)
+        else if (SPLIT == 6)
+            accumulate_items_lean<H, U>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db, a32_rows);
+        else if (SPLIT == 1)   // the item loop up to round 6, kept as tuning variant 16: the oracle of tests/test_aggregate_issue_forms.py
             accumulate_items_split<H, U>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db, recv, rec_small);
         else
             accumulate_items<H, U>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db);
@@ -700,8 +819,16 @@ static int launch_agg(const float* e, int64_t n_out, const float* A1h, const flo
 #define GN_AGG_LAUNCH_S(NORM_, MODE_, FIN_, U_, WPS_, GRID_, SPLIT_)                                                                           \
     hipLaunchKernelGGL((k_node_aggregate<H, NORM_, MODE_, FIN_, U_, WPS_, SPLIT_>), dim3((unsigned)(GRID_)), dim3(kAggThreads), (FIN_) ? 0 : dyn, s, e, \
                        (FIN_) ? n_out : node_end, A1h, A2h, A3h, ldn, in_ptr, ss, out_ptr, out_pos, od, h_in, ldh, h_out, scale, shift,   \
-                       (int)blocks, aux0, aux1, aux2, aux3, hub_count, hub_nodes, hub_partials, (FIN_) ? (int64_t)0 : node0, norm_width)
-#define GN_AGG_LAUNCH(NORM_, MODE_, FIN_, U_, WPS_, GRID_) GN_AGG_LAUNCH_S(NORM_, MODE_, FIN_, U_, WPS_, GRID_, 1)
+                       (int)blocks, aux0, aux1, aux2, aux3, hub_count, hub_nodes, hub_partials, (FIN_) ? (int64_t)0 : node0, norm_width, nullptr, a32_rows)
+    // the regular launch of every mode: accumulate_items_lean (SPLIT 6); tuning variant 16 keeps the split loop it replaced (SPLIT 1) - the same bits
+#define GN_AGG_LAUNCH(NORM_, MODE_, FIN_, U_, WPS_, GRID_)                                \
+    do {                                                                                  \
+        constexpr int kLoop = (!(FIN_) && (WPS_) == 0 && (U_) == UD) ? 6 : 1;             \
+        if (kLoop == 6 && prev_loop)                                                      \
+            GN_AGG_LAUNCH_S(NORM_, MODE_, FIN_, U_, WPS_, GRID_, 1);                      \
+        else                                                                              \
+            GN_AGG_LAUNCH_S(NORM_, MODE_, FIN_, U_, WPS_, GRID_, kLoop);                  \
+    } while (0)
     // The regular launches run the split item loop (accumulate_items_split: 0.2207 -> 0.2103 ms per launch at configs[1], whole forward
     // 4.89 -> 4.78 ms, the same bits, the same 782 MB fetched); variant 6 keeps the single loop for A/B.  (A single loop with a
     // wave-uniform fast path for steps of in-edges only - one round fewer, the overlap only when a node has >= G U in-edges - measured
@@ -714,6 +841,9 @@ static int launch_agg(const float* e, int64_t n_out, const float* A1h, const flo
     // H = 256 (one 1 KB row per load instruction): 2 since round 4 - measured inside the 2.5M-edge forward 1.036 (U = 8) / 0.980 (2) / 0.969 ms (1) per launch,
     // the same bits (one lane group: the items are added in list order whatever U)
     constexpr int UD = H == 256 ? 2 : 4;
+    const bool prev_loop = tuning(kTuneAggVariant) == 16;
+    // table rows below this index are addressed with 32-bit byte offsets (accumulate_items_lean); gnnome_set_tuning(11, 1): none are
+    const uint32_t a32_rows = tuning(kTuneAggAddr64) == 1 ? 0u : (uint32_t)((1ull << 32) / ((uint64_t)ldn * 4));
     constexpr int kFinGrid = kHubCap / (kAggThreads / 64);
     if (mode == 1) {
         GN_AGG_LAUNCH(GNNOME_NORM_AFFINE, 1, false, UD, 0, blocks);
@@ -765,6 +895,8 @@ static int launch_agg(const float* e, int64_t n_out, const float* A1h, const flo
                 }
                 break;
             default:
+                // the record form keeps accumulate_items_split: with the lean loop the 1M-edge H = 64 forward measured 2.30-2.31 ms against
+                // 2.27-2.29 (profiles/ab_aggregation_issue_diet.txt) - the record's readlanes already make that kernel's bounds scalar
                 if (g_node_records != nullptr && node_begin == 0 && node_end == n_out)
                     hipLaunchKernelGGL((k_node_aggregate<H, GNNOME_NORM_AFFINE, 0, false, UD, 0, 1, true>), dim3((unsigned)blocks), dim3(kAggThreads), dyn, s, e, node_end,
                                        A1h, A2h, A3h, ldn, in_ptr, ss, out_ptr, out_pos, od, h_in, ldh, h_out, scale, shift, (int)blocks, aux0, aux1, aux2, aux3,

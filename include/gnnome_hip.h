@@ -71,7 +71,10 @@ const char* gnnome_last_error(void);
  *   key 9 overlap edit distance: 0 banded (Ukkonen) pass first, the full matrix for what exceeds the band; 1 full matrix only
  *   key 10 forward arithmetic : 0 fp16x3 on the f16 matrix cores for the forward's dense products at H = 128 / 256 (round 4; see
  *                             gnnome_linear_f32), 1 bf16x6 everywhere (round 3's arithmetic; the plane-form kernels at H = 256)
- *   key 7 also: 9 / 10 two nodes per wave (U = 4 / 2), 11-13 persistent contiguous chunks (measured negatives) */
+ *   key 7 also: 9 / 10 two nodes per wave (U = 4 / 2), 11-13 persistent contiguous chunks (measured negatives),
+ *                             16 the item loop before the lean one (accumulate_items_split; the same bits, every mode)
+ *   key 11 aggregation addressing: 1 = row addresses in 64 bits per item at every size (default: 32-bit byte offsets wherever a step's
+ *                             rows lie below 4 GiB; the same bits) */
 int gnnome_set_tuning(int key, int value);
 
 /* Measurement only: when set to a device buffer of 256 x 8 int64, every launch of the edge-tile kernel leaves, per
