@@ -8,6 +8,7 @@
 //     P      = torch.ops.gnnome_hip.linear(h, Wcat, bcat)                                                   # gated_gcn_full.py:91-96
 //     e_new  = torch.ops.gnnome_hip.edge_gate(e, B1h, B2h, srt_src, srt_dst, W3, scale, shift, norm_kind)   # :97, 104-110
 //     h_new  = torch.ops.gnnome_hip.node_aggregate(e_new, A1h, A2h, A3h, in_ptr, srt_src, out_ptr, out_pos, out_dst, h, scale, shift, norm_kind)
+//     h_new  = torch.ops.gnnome_hip.node_aggregate_in(e_new, A1h, A2h, in_ptr, srt_src, h, scale, shift, norm_kind)   # GatedGCN, :212-225
 //     logits = torch.ops.gnnome_hip.edge_score(e, Ps, Qd, srt_src, srt_dst, srt_eid, W1e, W2, b2, W3, b3)   # score_predictor.py:12-24
 //
 // Built by gnnome_amd/csrc/Makefile (target torch_ext: g++ against this interpreter's torch headers, linked to libgnnome_hip.so beside it);
@@ -182,6 +183,26 @@ Tensor node_aggregate(const Tensor& e, const Tensor& A1h, const Tensor& A2h, con
     return out;
 }
 
+// ---- the in-edge gated aggregation + node update of GatedGCN (gnnome_node_aggregate_in_f32; gated_gcn_full.py:212-225) -------------------------
+Tensor node_aggregate_in(const Tensor& e, const Tensor& A1h, const Tensor& A2h, const Tensor& in_ptr, const Tensor& srt_src, const Tensor& h_in,
+                         const Tensor& scale, const Tensor& shift, int64_t norm_kind) {
+    const int ldn = rows_ld(A1h, "node_aggregate_in.A1h"), l2 = rows_ld(A2h, "node_aggregate_in.A2h");
+    const int ldh = rows_ld(h_in, "node_aggregate_in.h_in");
+    TORCH_CHECK(ldn == l2, "node_aggregate_in: A1h and A2h are column blocks of one projection (equal row strides)");
+    const int64_t N = h_in.size(0), H = h_in.size(1), E = srt_src.numel();
+    TORCH_CHECK(e.dim() == 2 && e.size(0) == E && e.size(1) == H && A1h.size(0) == N && A1h.size(1) == H && A2h.size(1) == H &&
+                    in_ptr.numel() == N + 1 && scale.numel() == H && shift.numel() == H,
+                "node_aggregate_in: shapes e[E,H] A1h[N,H] A2h[rows,H] in_ptr[N+1] srt_src[E] h_in[N,H] scale,shift[H]");
+    Guard guard(h_in.device());
+    Tensor out = at::empty({N, H}, h_in.options());
+    ok(gnnome_node_aggregate_in_f32(f32_dense(e, "node_aggregate_in.e"), (int)H, N, f32(A1h, "A1h"), f32(A2h, "A2h"), ldn,
+                                    i32(in_ptr, "node_aggregate_in.in_ptr"), i32(srt_src, "node_aggregate_in.srt_src"), f32(h_in, "h_in"), ldh,
+                                    out.data_ptr<float>(), (int)norm_kind, f32_dense(scale, "node_aggregate_in.scale"),
+                                    f32_dense(shift, "node_aggregate_in.shift"), stream_of(h_in)),
+       "gnnome_node_aggregate_in_f32");
+    return out;
+}
+
 // ---- the edge scorer (gnnome_edge_score_f32; score_predictor.py:12-24), logits in edge-id order -------------------------------------------------
 Tensor edge_score(const Tensor& e, const Tensor& Ps, const Tensor& Qd, const Tensor& srt_src, const Tensor& srt_dst, const Tensor& srt_eid,
                   const Tensor& W1e, const Tensor& W2, const Tensor& b2, const Tensor& W3, const Tensor& b3) {
@@ -220,6 +241,10 @@ Tensor node_aggregate_meta(const Tensor&, const Tensor&, const Tensor&, const Te
                            const Tensor&, const Tensor& h_in, const Tensor&, const Tensor&, int64_t) {
     return at::empty_like(h_in);
 }
+Tensor node_aggregate_in_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor& h_in, const Tensor&,
+                              const Tensor&, int64_t) {
+    return at::empty_like(h_in);
+}
 Tensor edge_score_meta(const Tensor& e, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
                        const Tensor&, const Tensor&, const Tensor&) {
     return at::empty({e.size(0)}, e.options());
@@ -235,6 +260,8 @@ TORCH_LIBRARY(gnnome_hip, m) {
     m.def("edge_gate(Tensor e, Tensor B1h, Tensor B2h, Tensor srt_src, Tensor srt_dst, Tensor W3, Tensor scale, Tensor shift, int norm_kind=0) -> Tensor");
     m.def("node_aggregate(Tensor e, Tensor A1h, Tensor A2h, Tensor A3h, Tensor in_ptr, Tensor srt_src, Tensor out_ptr, Tensor out_pos, Tensor out_dst, "
           "Tensor h_in, Tensor scale, Tensor shift, int norm_kind=0) -> Tensor");
+    m.def("node_aggregate_in(Tensor e, Tensor A1h, Tensor A2h, Tensor in_ptr, Tensor srt_src, Tensor h_in, Tensor scale, Tensor shift, "
+          "int norm_kind=0) -> Tensor");
     m.def("edge_score(Tensor e, Tensor Ps, Tensor Qd, Tensor srt_src, Tensor srt_dst, Tensor srt_eid, Tensor W1e, Tensor W2, Tensor b2, Tensor W3, "
           "Tensor b3) -> Tensor");
     m.def("abi_version() -> int", []() -> int64_t { return gnnome_abi_version(); });   // the libgnnome_hip.so this extension is bound to
@@ -247,6 +274,7 @@ TORCH_LIBRARY_IMPL(gnnome_hip, CUDA, m) {   // the CUDA dispatch key is the HIP 
     m.impl("linear_ref", &linear_ref);
     m.impl("edge_gate", &edge_gate);
     m.impl("node_aggregate", &node_aggregate);
+    m.impl("node_aggregate_in", &node_aggregate_in);
     m.impl("edge_score", &edge_score);
 }
 
@@ -257,5 +285,6 @@ TORCH_LIBRARY_IMPL(gnnome_hip, Meta, m) {
     m.impl("linear_ref", &linear_meta);
     m.impl("edge_gate", &edge_gate_meta);
     m.impl("node_aggregate", &node_aggregate_meta);
+    m.impl("node_aggregate_in", &node_aggregate_in_meta);
     m.impl("edge_score", &edge_score_meta);
 }

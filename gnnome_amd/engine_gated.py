@@ -1,0 +1,338 @@
+"""Host logic of the one-direction GatedGCN path (models/full_graph.py:33-53, layers/gated_gcn_full.py:145-230): weight
+preparation and the kernel sequences of GatedGCNModel, beside engine.py (the symmetric model), which stays as it is.
+
+Eval mode, per layer (N nodes, E edges, H hidden; e in DESTINATION-SORTED order across the whole stack):
+    P    = h Wcat^T + bcat      [N,4H] = A1h|A2h|B1h|B2h, one GEMM         gnnome_linear_planes_f32 / gnnome_linear_f32
+    e'   = relu(bn_e(B1h[src] + B2h[dst] + B_3 e)) + e                      the symmetric model's fused gate, unchanged
+    h'   = relu(bn_h(A1h + fwd)) + h                                        gnnome_node_aggregate_in_f32 (csrc/node_aggregate_in.hip)
+then the symmetric model's scorer.  There is no A_3 block in the projection and no out-edge half in the aggregation.
+Only the matrix-core arithmetic is served: `arithmetic="reference"` raises.
+
+directed=False (full_graph.py:47-51): the stack runs on the doubled edge list src|dst -> dst|src (the reverse copy of edge k
+has id E + k), fed with the encoded e twice; the ORIGINAL graph is scored with the rows of the first E edge ids.  The doubled
+views and the two row maps are kept with the graph's own cached views (GraphViews._derived; graph.views_for), so they are built once
+per graph object.
+
+Train mode goes through the symmetric model's training step (train._TrainStep): an adapter presents the model under the
+symmetric model's attribute names, SHARING the Parameter objects, and gives every layer a zero A_3 (plain zero tensors, no
+Parameters: never updated, absent from state_dict).  That is exact for every real parameter and for dh, because A3h = 0
+makes bwd = +0, d bwd / d sigma = 0 and A_3^T dA3h = 0.  It COSTS WHAT THE SYMMETRIC STEP COSTS - the out-edge pass and the
+fifth projection block are computed on zeros; a one-direction backward kernel is not built.
+"""
+import torch
+import torch.nn.functional as F
+
+from . import engine
+from . import ops as hip_ops
+from .graph import views_for
+from .ops import GraphViews
+
+ARITHMETIC_MODES = ("auto", "fast")   # both: the matrix-core kernels; the reference-order route is not served for this model
+
+
+def built_width(width, built=engine.BUILT_HIDDEN, what="hidden_features"):
+    """GatedGCN runs at the built widths only (zero-padding is not served for this model)."""
+    if width not in built:
+        raise ValueError(f"{what}={width}: GatedGCN is built for {what} in {tuple(built)}")
+    return width
+
+
+def check_arithmetic(module):
+    mode = getattr(module, "arithmetic", "auto")
+    if mode not in ARITHMETIC_MODES:
+        raise ValueError(f"arithmetic={mode!r}: GatedGCN serves {ARITHMETIC_MODES} (the matrix-core kernels); the reference-order "
+                         "route is built for SymGatedGCN only")
+    return mode
+
+
+class GatedLayerWeights:
+    """What engine.gate / the aggregation read of one layer (engine.LayerWeights' names; ref is always False here)."""
+    __slots__ = ("Wcat", "bcat", "W3", "b3", "norm", "scale_e", "shift_e", "scale_h", "shift_h", "ref", "planes")
+
+
+def prepare_layer(conv, device, arithmetic=None):
+    def dev(t):
+        return t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+    check_arithmetic(conv)
+    hidden = built_width(conv.B_3.weight.shape[0])
+    lw = GatedLayerWeights()
+    lw.Wcat = dev(torch.cat([conv.A_1.weight, conv.A_2.weight, conv.B_1.weight, conv.B_2.weight], 0))
+    # B_3's bias rides on the B2h rows: B1h[src] + (B2h[dst] + b3) + e*W3^T (as in engine.prepare_layer)
+    lw.bcat = dev(torch.cat([conv.A_1.bias, conv.A_2.bias, conv.B_1.bias, conv.B_2.bias + conv.B_3.bias], 0))
+    lw.W3, lw.b3 = dev(conv.B_3.weight), dev(conv.B_3.bias)
+    lw.norm, lw.scale_e, lw.shift_e = engine._norm_affine(conv.bn_e, device)
+    kind_h, lw.scale_h, lw.shift_h = engine._norm_affine(conv.bn_h, device)
+    assert kind_h == lw.norm
+    lw.ref = False
+    lw.planes = hip_ops.weight_planes(lw.Wcat) if hip_ops.planes_supported(hidden, 4 * hidden) and lw.Wcat.is_cuda else None
+    return lw
+
+
+class Prepared:
+    """Device-resident, kernel-ready copies of a GatedGCNModel's parameters (eval semantics)."""
+
+    def __init__(self, model, device):
+        def dev(t):
+            return t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+        check_arithmetic(model)
+        self.device = device
+        self.hidden = built_width(model.node_encoder.linear2.out_features)
+        self.enc_node = tuple(dev(t) for t in (model.node_encoder.linear1.weight, model.node_encoder.linear1.bias,
+                                               model.node_encoder.linear2.weight, model.node_encoder.linear2.bias))
+        self.enc_edge = tuple(dev(t) for t in (model.edge_encoder.linear1.weight, model.edge_encoder.linear1.bias,
+                                               model.edge_encoder.linear2.weight, model.edge_encoder.linear2.bias))
+        self.layers = [prepare_layer(conv, device) for conv in model.gnn.convs]
+        self.predictor = engine.prepare_predictor(model.predictor, device)
+        weights = [t for lw in self.layers for t in (lw.Wcat, lw.W3)] + [self.predictor["_W1"], self.predictor["W2"]]
+        amax = max((float(t.abs().max()) if t.numel() else 0.0) for t in weights) if weights else 0.0
+        self.force_bf16x6 = not (amax < engine.hip_ops_fp16_max())   # fp16x3's operand range, checked once for the weights
+        self.range_verified = self.range_failed = None
+
+
+# ---------------------------------------------------------------------------------------------------
+# graphs: true views of a reversed graph, and the doubled edge list of directed=False
+# ---------------------------------------------------------------------------------------------------
+
+def edge_list_of(views):
+    """(src, dst) int32 in edge-id order, in the views' own node numbering."""
+    src = torch.empty(views.num_edges, dtype=torch.int32, device=views.device)
+    dst = torch.empty_like(src)
+    eid = views.srt_eid.long()
+    src[eid], dst[eid] = views.srt_src, views.srt_dst
+    return (dst, src) if views.transposed else (src, dst)
+
+
+def _carry_numbering(new, views):
+    new.node_perm, new.node_gather = views.node_perm, views.node_gather   # (built from internal ids: the same renumbering applies)
+    return new
+
+
+def in_edge_views(views):
+    """Views whose CONTIGUOUS runs are the in-edges of the graph `views` stands for.  The aggregation of this model reads
+    in_ptr / srt_src only, so views of dgl.reverse(g) (GraphViews.reversed: the same arrays, roles exchanged by the caller)
+    are rebuilt once over the swapped edge list - same edge ids - and kept with the views they came from (GraphViews._derived,
+    which graph.views_for's cache keeps alive with the graph object)."""
+    if not views.transposed:
+        return views
+    hit = views._derived.get("reversed")
+    if hit is None:
+        src, dst = edge_list_of(views)
+        hit = views._derived["reversed"] = _carry_numbering(GraphViews(src, dst, views.num_nodes, validate=False), views)
+    return hit
+
+
+def doubled_edge_list(src, dst):
+    """dgl.add_reverse_edges (full_graph.py:48): src|dst -> dst|src - edge k keeps its id, its reverse copy gets id E + k."""
+    return torch.cat([src, dst]), torch.cat([dst, src])
+
+
+def doubled_row_maps(srt_eid_doubled, srt_eid, num_edges):
+    """The two row maps of directed=False, from the sorted edge ids of the doubled views and of the original ones (E = num_edges):
+    enc_gather[p]   = the ORIGINAL edge whose encoded features row p of the doubled sorted order carries (e fed twice: id >= E -> id - E),
+    score_gather[q] = the doubled sorted position of the edge at sorted position q of the original views - the rows of the first E ids,
+                      e[:E], in the order the scorer reads them.  Both int32, on the inputs' device."""
+    eid2, E = srt_eid_doubled, int(num_edges)
+    enc_gather = torch.where(eid2 >= E, eid2 - E, eid2).to(torch.int32).contiguous()
+    pos_of = torch.empty(2 * E, dtype=torch.int32, device=eid2.device)
+    pos_of[eid2.long()] = torch.arange(2 * E, dtype=torch.int32, device=eid2.device)
+    return enc_gather, pos_of[srt_eid.long()].contiguous()
+
+
+class Doubled:
+    """The doubled graph of directed=False: views over doubled_edge_list and the two maps of doubled_row_maps."""
+
+    def __init__(self, views):
+        src, dst = doubled_edge_list(*edge_list_of(views))
+        self.views = _carry_numbering(GraphViews(src, dst, views.num_nodes, validate=False), views)
+        self.enc_gather, self.score_gather = doubled_row_maps(self.views.srt_eid, views.srt_eid, views.num_edges)
+
+
+def doubled_for(views):
+    """(views: not transposed - run_stack hands in in_edge_views' result)"""
+    hit = views._derived.get("doubled")
+    if hit is None:
+        hit = views._derived["doubled"] = Doubled(views)
+    return hit
+
+
+# ---------------------------------------------------------------------------------------------------
+# kernel sequences (ops = gnnome_amd.ops)
+# ---------------------------------------------------------------------------------------------------
+
+def layer_step(ops, lw, views, h, e, raw_edges=None, scratch=None, n_out=None):
+    """One GatedGCN layer on sorted-order e; returns (new h, e).  e = None with raw_edges = (e_raw, encoder weights): the edge
+    encoder is folded into the gate (layer 0), as in the symmetric model."""
+    H = h.shape[1]
+    P = ops.linear(h, lw.Wcat, lw.bcat, planes=lw.planes)   # [N,4H] = A1h|A2h|B1h|B2h (gated_gcn_full.py:194-199)
+    A1, A2, B1, B2 = (P[:, i * H:(i + 1) * H] for i in range(4))
+    e = engine.gate(ops, lw, views, e, B1, B2, raw_edges, scratch)
+    return ops.node_aggregate_in(e, A1, A2, views, h, lw.norm, lw.scale_h, lw.shift_h, num_nodes_out=n_out), e
+
+
+def run_stack(ops, prep, views, x, e_raw, directed=True):
+    """Encoders -> L layers -> scorer; logits[E] at the original edge ids."""
+    score_views = views = in_edge_views(views)
+    h = engine.encode_nodes(ops, views, x, prep.enc_node)
+    if directed:
+        e = engine.encode_edges(ops, prep, views, e_raw)   # None: layer 0's gate produces it on the fly
+    else:
+        dbl = doubled_for(views)
+        views = dbl.views
+        e = ops.encode(e_raw, *prep.enc_edge, gather=dbl.enc_gather, rows=views.num_edges)
+    scratch = {}
+    for lw in prep.layers:
+        h, e = layer_step(ops, lw, views, h, e, raw_edges=(e_raw, prep.enc_edge), scratch=scratch)
+    if e is None:   # a model without layers: the scorer reads the encoder's output
+        e = ops.encode(e_raw, *prep.enc_edge, gather=views.srt_eid, rows=views.num_edges)
+    if not directed:
+        e = ops.gather_rows(e, dbl.score_gather)
+    logits = torch.empty(score_views.num_edges, dtype=torch.float32, device=h.device)
+    engine.score_step(ops, prep.predictor, score_views, h, e, logits)
+    return logits
+
+
+def forward_in_range(ops, prep, views, x, e, xd, ed, directed, check=True):
+    """engine.forward_in_range for this stack: a forward whose logits are not all finite left fp16x3's operand range and is run
+    again as bf16x6; checked once per set of inputs."""
+    if ops._TUNING.get(10, 0) == 1:
+        return run_stack(ops, prep, views, xd, ed, directed)
+    if prep.force_bf16x6 or engine._same_inputs(prep.range_failed, views, x, e):
+        with ops.bf16x6_arithmetic():
+            return run_stack(ops, prep, views, xd, ed, directed)
+    logits = run_stack(ops, prep, views, xd, ed, directed)
+    if not check or engine._same_inputs(prep.range_verified, views, x, e):
+        return logits
+    if bool(torch.isfinite(logits).all()):
+        prep.range_verified = engine._inputs_key(views, x, e)
+        return logits
+    prep.range_failed = engine._inputs_key(views, x, e)
+    with ops.bf16x6_arithmetic():
+        return run_stack(ops, prep, views, xd, ed, directed)
+
+
+# ---------------------------------------------------------------------------------------------------
+# module entry points
+# ---------------------------------------------------------------------------------------------------
+
+def model_forward(model, graph, x, e):
+    """models/full_graph.py:42-53 on the MI355X."""
+    if model.training:
+        return train_forward(model, graph, x, e).to(x.device)
+    out_device = x.device
+    device = engine.compute_device(x, e)
+    prep = engine.prepared_for(model, device, Prepared)
+    views = views_for(graph, device, node_order="input")
+    if x.shape[0] != views.num_nodes or e.shape[0] != views.num_edges:
+        raise ValueError(f"x has {x.shape[0]} rows for {views.num_nodes} nodes, e has {e.shape[0]} rows for {views.num_edges} edges")
+    with torch.no_grad():
+        xd = x.detach().to(device=device, dtype=torch.float32).contiguous()
+        ed = e.detach().to(device=device, dtype=torch.float32).contiguous()
+        logits = forward_in_range(hip_ops, prep, views, x, e, xd, ed, bool(model.directed), check=getattr(model, "range_check", True))
+    views.check_range()   # a fresh graph's deferred endpoint check, after the whole forward has been enqueued
+    return logits.unsqueeze(1).to(out_device)
+
+
+def layer_forward_edge_id_order(conv, g, h, e):
+    """gated_gcn_full.py:182-230 with e given and returned in edge-id order."""
+    engine._refuse_training(conv)
+    out_device = h.device
+    device = engine.compute_device(h, e)
+    lw = engine.prepared_for(conv, device, prepare_layer)
+    views = in_edge_views(views_for(g, device))
+    with torch.no_grad():
+        hd = h.detach().to(device=device, dtype=torch.float32).contiguous()
+        ed = e.detach().to(device=device, dtype=torch.float32).contiguous()
+        es = hip_ops.gather_rows(ed, views.srt_eid)
+        if views.node_gather is not None:   # views over renumbered nodes: rows in, rows out in the caller's numbering
+            hd = hip_ops.gather_rows(hd, views.node_gather)
+        h_new, es = layer_step(hip_ops, lw, views, hd, es)
+        if views.node_perm is not None:
+            h_new = h_new.index_select(0, views.node_perm)
+        e_new = torch.empty_like(es)
+        e_new[views.srt_eid.long()] = es
+        h_new = F.dropout(h_new, conv.dropout, training=conv.training)
+    views.check_range()
+    return h_new.to(out_device), e_new.to(out_device)
+
+
+# ---------------------------------------------------------------------------------------------------
+# train mode: the symmetric training step on an adapter with a zero A_3
+# ---------------------------------------------------------------------------------------------------
+
+class _ZeroLinear:
+    """A_3 as the symmetric step sees it for this model: zero weight and bias - tensors, not Parameters."""
+
+    def __init__(self, like):
+        self.weight = torch.zeros_like(like.weight, requires_grad=False)
+        self.bias = torch.zeros_like(like.bias, requires_grad=False)
+
+
+class _SymLayer:
+    bn_e_updates = 1   # gated_gcn_full.py:207 applies bn_e once per layer (the symmetric layer twice): one momentum update per step
+
+    def __init__(self, conv):
+        self.conv = conv
+        self.A_1, self.A_2, self.B_1, self.B_2, self.B_3 = conv.A_1, conv.A_2, conv.B_1, conv.B_2, conv.B_3
+        self.bn_h, self.bn_e = conv.bn_h, conv.bn_e
+        self.A_3 = _ZeroLinear(conv.A_2)
+
+    @property
+    def dropout(self):
+        return self.conv.dropout
+
+
+class _Convs:
+    def __init__(self, convs):
+        self.convs = convs
+
+
+class SymAdapter:
+    """GatedGCNModel under the attribute names train._TrainStep reads of a SymGatedGCNModel; every Parameter is the model's own."""
+
+    def __init__(self, model):
+        self.linear1_node, self.linear2_node = model.node_encoder.linear1, model.node_encoder.linear2
+        self.linear1_edge, self.linear2_edge = model.edge_encoder.linear1, model.edge_encoder.linear2
+        self.gnn = _Convs([_SymLayer(conv) for conv in model.gnn.convs])
+        self.predictor = model.predictor
+        self.device = next(model.parameters()).device
+        self.layers = len(model.gnn.convs)
+        # the step returns its gradients under the symmetric model's names, in the order of the model's own named_parameters()
+        own = [n for n, _ in model.named_parameters()]
+        self.names = [_sym_name(n) for n in own]
+        self.activation_storage = getattr(model, "activation_storage", "fp32")
+        self.recompute_gate = getattr(model, "recompute_gate", False)
+
+
+def _sym_name(name):
+    for enc, kind in (("node_encoder.", "_node"), ("edge_encoder.", "_edge")):
+        if name.startswith(enc):
+            layer, leaf = name[len(enc):].split(".")      # linear1.weight -> linear1_node.weight
+            return f"{layer}{kind}.{leaf}"
+    return name
+
+
+def train_forward(model, graph, x, e):
+    """`model(graph, x, e)` in train mode with autograd support, through train._TrainStep (see the module docstring)."""
+    from .train import TRAIN_SCORE_HIDDEN, WholeGraph, _TrainStep
+    check_arithmetic(model)
+    if not model.directed:
+        raise NotImplementedError("train mode of GatedGCNModel is built for directed=True; directed=False is served in eval mode")
+    device = engine.compute_device(x, e)
+    params = [p for _, p in model.named_parameters()]
+    if any(p.device != device for p in params):
+        raise RuntimeError("training needs the model on the compute device: call model.to(device) first")
+    built_width(model.node_encoder.linear2.out_features)
+    built_width(model.predictor.W1.out_features, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")
+    adapter = model.__dict__.get("_gnnome_sym_adapter")
+    if adapter is None or adapter.device != device or adapter.layers != len(model.gnn.convs):
+        adapter = model.__dict__["_gnnome_sym_adapter"] = SymAdapter(model)
+    adapter.activation_storage = getattr(model, "activation_storage", "fp32")
+    adapter.recompute_gate = getattr(model, "recompute_gate", False)
+    views = views_for(graph, device, node_order="input")
+    xd = x.detach().to(device=device, dtype=torch.float32).contiguous()
+    ed = e.detach().to(device=device, dtype=torch.float32).contiguous()
+    out = _TrainStep.apply(adapter, WholeGraph(views), xd, ed, adapter.names, *params)
+    views.check_range()
+    return out

@@ -83,4 +83,87 @@ class ScorePredictor(nn.Module):
         return engine.score_forward_edge_id_order(self, graph, x, e)
 
 
-__all__ = ["SymGatedGCN", "SymGatedGCN_processor", "ScorePredictor", "views_for"]
+class NodeEncoder(nn.Module):
+    """layers/node_encoder.py:5-34: linear1 -> relu -> linear2.  Owns the parameters; the arithmetic is gnnome_encode_f32."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, bias=True):
+        super().__init__()
+        if not bias:
+            raise ValueError("the encoder kernels add both biases (the reference builds its encoders with bias=True)")
+        if not (1 <= in_channels <= 8 and 1 <= hidden_channels <= 64):
+            raise ValueError("the encoder kernels take in_channels <= 8 and hidden_channels <= 64 (reference: 2, 16)")
+        self.linear1 = nn.Linear(in_channels, hidden_channels, bias=bias)
+        self.linear2 = nn.Linear(hidden_channels, out_channels, bias=bias)
+        self.relu = nn.ReLU()
+
+    def forward(self, x):
+        """rows[., in_channels] -> rows[., out_channels] on the MI355X (eval semantics, no autograd history)."""
+        from . import ops as hip_ops
+        engine._refuse_training(self)
+        out_device = x.device
+        device = engine.compute_device(x)
+        with torch.no_grad():
+            w = [t.detach().to(device=device, dtype=torch.float32).contiguous()
+                 for t in (self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias)]
+            return hip_ops.encode(x.detach().to(device=device, dtype=torch.float32).contiguous(), *w).to(out_device)
+
+
+class EdgeEncoder(NodeEncoder):
+    """layers/edge_encoder.py:4-34: the same two-layer encoder for the edge features."""
+
+
+class GatedGCN(nn.Module):
+    """layers/gated_gcn_full.py:145-230: the one-direction gated layer - SymGatedGCN without A_3 and without the pass over
+    dgl.reverse(g).  Same refusals as SymGatedGCN; runs at the built widths only (no zero-padding for this layer).
+    Train mode goes through GatedGCNModel (engine_gated.py: the symmetric training step with a zero A_3, at its cost)."""
+    arithmetic = "auto"   # "auto" | "fast": the matrix-core kernels; "reference" is not served for this layer
+
+    def __init__(self, in_channels, out_channels, normalization, dropout=None, residual=True):
+        super().__init__()
+        from . import engine_gated
+        if in_channels != out_channels:
+            raise ValueError("the GatedGCN path is only ever built with in_channels == out_channels "
+                             "(layers/processor.py:25-27); unequal widths are not supported")
+        if not residual:
+            raise ValueError("residual=False is never used by the reference drivers and is not supported")
+        engine_gated.built_width(in_channels)
+        self.dropout = dropout if dropout else 0.0
+        self.normalization = normalization
+        self.residual = residual
+        dtype = torch.float32
+        self.A_1 = nn.Linear(in_channels, out_channels, dtype=dtype)
+        self.A_2 = nn.Linear(in_channels, out_channels, dtype=dtype)
+        self.B_1 = nn.Linear(in_channels, out_channels, dtype=dtype)
+        self.B_2 = nn.Linear(in_channels, out_channels, dtype=dtype)
+        self.B_3 = nn.Linear(in_channels, out_channels, dtype=dtype)
+        if normalization == "batch":
+            self.bn_h = nn.BatchNorm1d(out_channels, track_running_stats=True)
+            self.bn_e = nn.BatchNorm1d(out_channels, track_running_stats=True)
+        elif normalization == "layer":
+            self.bn_h = nn.LayerNorm(out_channels)
+            self.bn_e = nn.LayerNorm(out_channels)
+        else:
+            # the reference calls self.bn_e unconditionally (gated_gcn_full.py:207), so 'none' raises AttributeError there
+            raise ValueError("normalization must be 'batch' or 'layer'")
+
+    def forward(self, g, h, e):
+        """(h[N,H], e[E,H] in edge-id order) -> (h', e') like gated_gcn_full.py:182-230."""
+        from . import engine_gated
+        return engine_gated.layer_forward_edge_id_order(self, g, h, e)
+
+
+class GatedGCN_processor(nn.Module):
+    def __init__(self, num_layers, hidden_features, normalization, dropout=None):
+        super().__init__()
+        self.convs = nn.ModuleList([
+            GatedGCN(hidden_features, hidden_features, normalization, dropout) for _ in range(num_layers)
+        ])
+
+    def forward(self, graph, h, e):
+        for conv in self.convs:
+            h, e = conv(graph, h, e)
+        return h, e
+
+
+__all__ = ["SymGatedGCN", "SymGatedGCN_processor", "ScorePredictor", "NodeEncoder", "EdgeEncoder", "GatedGCN", "GatedGCN_processor",
+           "views_for"]

@@ -25,7 +25,7 @@ weights/weights.pt, same call.  Differences, all deliberate:
 import torch.nn as nn
 
 from . import engine
-from .layers import ScorePredictor, SymGatedGCN_processor
+from .layers import EdgeEncoder, GatedGCN_processor, NodeEncoder, ScorePredictor, SymGatedGCN_processor
 
 
 class SymGatedGCNModel(nn.Module):
@@ -52,4 +52,39 @@ class SymGatedGCNModel(nn.Module):
         return engine.model_forward(self, graph, x, e)
 
 
-__all__ = ["SymGatedGCNModel"]
+class GatedGCNModel(nn.Module):
+    """Drop-in for the reference's models/full_graph.py:33-53 - the one-direction baseline the symmetric model is compared against:
+    NodeEncoder and EdgeEncoder, GatedGCN_processor (layers/gated_gcn_full.py:145-230: no A_3, no pass over dgl.reverse(g)),
+    ScorePredictor.  Same constructor and state_dict keys (`node_encoder.linear{1,2}.*`, `edge_encoder.linear{1,2}.*`,
+    `gnn.convs.N.*`, `predictor.W{1,2,3}.*`), same call; `graph` and the inputs as for SymGatedGCNModel.
+
+    Eval mode runs its own kernel sequence (gnnome_amd/engine_gated.py): a [N,4H] projection, the symmetric model's gate, the in-edge
+    aggregation kernel gnnome_node_aggregate_in_f32, the symmetric model's scorer.  directed=False runs the stack on the doubled edge
+    list and scores the original graph (full_graph.py:47-51).  Built widths only: hidden_features in {64, 128, 256},
+    hidden_edge_scores in {32, 64, 128}; `arithmetic` "auto" / "fast" (the matrix-core kernels) - "reference" raises.
+
+    Train mode (directed=True) goes through the SYMMETRIC model's training step with a zero A_3 per layer - zero tensors, not
+    Parameters, never updated: exact for every parameter this model has, and it costs what the symmetric step costs (the out-edge
+    pass and the fifth projection block run on zeros); a one-direction backward is not built."""
+    arithmetic = "auto"
+    activation_storage = "fp32"
+    range_check = True
+
+    def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, num_layers, hidden_edge_scores,
+                 normalization, dropout=None, directed=True):
+        super().__init__()
+        from . import engine_gated
+        engine_gated.built_width(hidden_features)
+        engine_gated.built_width(hidden_edge_scores, engine.BUILT_SCORE_HIDDEN, "hidden_edge_scores")
+        self.directed = directed
+        self.node_encoder = NodeEncoder(node_features, hidden_ne_features, hidden_features)
+        self.edge_encoder = EdgeEncoder(edge_features, hidden_ne_features, hidden_features)
+        self.gnn = GatedGCN_processor(num_layers, hidden_features, normalization, dropout=dropout)
+        self.predictor = ScorePredictor(hidden_features, hidden_edge_scores)
+
+    def forward(self, graph, x, e):
+        from . import engine_gated
+        return engine_gated.model_forward(self, graph, x, e)
+
+
+__all__ = ["SymGatedGCNModel", "GatedGCNModel"]

@@ -81,7 +81,7 @@ class GraphViews:
     """In-edge / out-edge orderings of one edge list (see include/gnnome_hip.h, "graph views")."""
 
     __slots__ = ("num_nodes", "num_edges", "in_ptr", "srt_src", "srt_dst", "srt_eid", "out_ptr", "out_pos", "out_dst", "device",
-                 "transposed", "_range", "_bad", "node_perm", "node_gather", "_stream", "_c_block", "_records", "__weakref__")
+                 "transposed", "_range", "_bad", "node_perm", "node_gather", "_stream", "_c_block", "_records", "_derived", "__weakref__")
 
     def __init__(self, src, dst, num_nodes, validate="now", node_perm=None):
         """node_perm (int64[N], optional): the views are built over RENUMBERED nodes, node_perm[caller's id] = internal id
@@ -109,6 +109,7 @@ class GraphViews:
         self.num_nodes, self.num_edges, self.device, self.transposed = n, e, dev, False
         self.node_perm = self.node_gather = None
         self._stream = self._c_block = self._records = None
+        self._derived = {}   # views built FROM these and kept with them (engine_gated: the reversed and the doubled graph); shared with reversed()
         if node_perm is not None:
             node_perm = node_perm.to(device=dev, dtype=torch.int64)
             if node_perm.numel() != n:
@@ -679,6 +680,32 @@ def node_aggregate(e, A1h, A2h, A3h, views, h_in, norm_kind, scale, shift, num_n
                                                            _ptr(views.out_ptr), _ptr(views.out_pos), _ptr(views.out_dst), _ptr(h_in),
                                                            ldh, _ptr(h_out), norm_kind, _ptr(scale), _ptr(shift),
                                                            _stream(h_in.device)), "node_aggregate_range_f32")
+    return h_out
+
+
+def node_aggregate_in(e, A1h, A2h, views, h_in, norm_kind, scale, shift, num_nodes_out=None, node_range=None, out=None):
+    """The GatedGCN layer's node update (gnnome_node_aggregate_in_f32): h' = relu(norm_h(A1h + fwd)) + h over the in-edges alone.
+    node_range = (begin, end): only those rows of `out` (required then) are computed - gnnome_node_aggregate_in_range_f32."""
+    lib = _lib.load()
+    A1h, ldn = _rows(A1h, "node_aggregate_in.A1h")
+    A2h, l2 = _rows(A2h, "node_aggregate_in.A2h")
+    h_in, ldh = _rows(h_in, "node_aggregate_in.h_in")
+    assert ldn == l2
+    hidden = h_in.shape[1]
+    n_out = int(h_in.shape[0] if num_nodes_out is None else num_nodes_out)
+    h_out = torch.empty((h_in.shape[0], hidden), dtype=torch.float32, device=h_in.device) if out is None else out
+    assert h_out.is_contiguous() and h_out.shape == (h_in.shape[0], hidden) and h_out.dtype == torch.float32
+    with _on(h_in.device):
+        if node_range is None:
+            _lib.check(lib.gnnome_node_aggregate_in_f32(_ptr(e), hidden, n_out, _ptr(A1h), _ptr(A2h), ldn, _ptr(views.in_ptr),
+                                                        _ptr(views.srt_src), _ptr(h_in), ldh, _ptr(h_out), norm_kind, _ptr(scale),
+                                                        _ptr(shift), _stream(h_in.device)), "node_aggregate_in_f32")
+        else:
+            assert out is not None, "node_aggregate_in(node_range=...) writes rows of a caller-owned `out`"
+            _lib.check(lib.gnnome_node_aggregate_in_range_f32(_ptr(e), hidden, n_out, int(node_range[0]), int(node_range[1]), _ptr(A1h),
+                                                              _ptr(A2h), ldn, _ptr(views.in_ptr), _ptr(views.srt_src), _ptr(h_in), ldh,
+                                                              _ptr(h_out), norm_kind, _ptr(scale), _ptr(shift), _stream(h_in.device)),
+                       "node_aggregate_in_range_f32")
     return h_out
 
 

@@ -148,6 +148,12 @@ def _bn_bwd(sh, dy, x, scale, shift, mean, rstd, rows, n_once, out, stats=None, 
     return s2h, s1
 
 
+def _bn_e_updates(conv):
+    """Momentum updates bn_e's running statistics receive per step: 2 in SymGatedGCN (applied at gated_gcn_full.py:106 and :119), 1 where
+    the layer says so (`bn_e_updates`: the one-direction GatedGCN applies it once, :207 - gnnome_amd/engine_gated.py)."""
+    return getattr(conv, "bn_e_updates", 2)
+
+
 ACTIVATION_STORAGE = ("fp32", "bf16")
 def _switch(name):   # GNNOME_<NAME>=0 in the environment turns a switch off for a whole process (bench.py A/B runs of one build)
     import os
@@ -265,7 +271,7 @@ class _TrainStep(torch.autograd.Function):
                 W3 = d(conv.B_3.weight)
                 path = "moments"
                 mean_e, rstd_e, sc_e, sh_e = _bn_train_fused(sh, conv.bn_e, ops.edge_gate_moments_only(e, blk(P, "B1"), blk(P, "B2"), views, W3, storage=storage),
-                                                             updates=2)
+                                                             updates=_bn_e_updates(conv))
                 e_new, xe = ops.edge_gate_bn(e, blk(P, "B1"), blk(P, "B2"), views, W3, sc_e, sh_e, storage=storage)
             else:
                 path, xe, stats = _raw_gate(sh, conv, e, blk(P, "B1"), blk(P, "B2"), layer_norm, storage)
@@ -275,9 +281,9 @@ class _TrainStep(torch.autograd.Function):
                 e_new = ops.ln_relu_res(xe, d(conv.bn_e.weight), d(conv.bn_e.bias), e, width=ln_width)
             else:
                 if path == "moments":
-                    mean_e, rstd_e, sc_e, sh_e = _bn_train_fused(sh, conv.bn_e, stats, updates=2)
+                    mean_e, rstd_e, sc_e, sh_e = _bn_train_fused(sh, conv.bn_e, stats, updates=_bn_e_updates(conv))
                 else:
-                    mean_e, rstd_e, sc_e, sh_e = _bn_train(sh, conv.bn_e, stats[0], stats[1], e_own, sh.e_global, updates=2)
+                    mean_e, rstd_e, sc_e, sh_e = _bn_train(sh, conv.bn_e, stats[0], stats[1], e_own, sh.e_global, updates=_bn_e_updates(conv))
                 e_new = ops.bn_relu_res(xe, sc_e, sh_e, e)
             if recompute:
                 xe = None   # the backward runs the same gate launch again (same kernel, same operands: the same bits)

@@ -327,11 +327,12 @@ def _set_rng_state(st):
 
 
 def train(train_set, valid_set, out=None, hyperparameters=None, overfit=False, dropout=None, seed=None, resume=False, device=None,
-          models_dir="models", checkpoints_dir="checkpoints", trace=None):
+          models_dir="models", checkpoints_dir="checkpoints", trace=None, model_class=SymGatedGCNModel):
     """train.py:188-450 (see the module docstring) -> the list of epoch records.  `hyperparameters`: overrides of
     configs/hyperparameters.py by the reference's key names.  `trace` (for tests): a list that receives the initial state dict and
     one dict per step (graph, mask fraction, the step's full-graph node and edge ids, its edges, loss and counts; the first training
-    step's gradients) - it copies to the host per step."""
+    step's gradients) - it copies to the host per step.  `model_class`: the model to train, SymGatedGCNModel or GatedGCNModel (same
+    constructor arguments)."""
     hp = hyperparameters_with(hyperparameters)
     seed = hp["seed"] if seed is None else seed
     dropout = hp["dropout"] if dropout is None else dropout
@@ -346,7 +347,7 @@ def train(train_set, valid_set, out=None, hyperparameters=None, overfit=False, d
     ds_valid = ds_train if overfit else [_Graph(n, g, device) for n, g in load_dataset(valid_set)]
     pos_weight = torch.tensor([pos_weight_of([(g.name, g.y) for g in ds_train])], device=device)
 
-    model = SymGatedGCNModel(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_ne_features"], hp["num_gnn_layers"],
+    model = model_class(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_ne_features"], hp["num_gnn_layers"],
                              hp["hidden_edge_scores"], hp["normalization"], dropout=dropout).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=hp["lr"])
     scheduler = ReduceLROnPlateau(optimizer, mode="min", factor=hp["decay"], patience=hp["patience"])

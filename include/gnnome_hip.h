@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 24
+#define GNNOME_ABI_VERSION 25
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -238,6 +238,31 @@ int gnnome_node_aggregate_range_f32(const float* e, int hidden, int64_t num_node
                                     const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_pos,
                                     const int32_t* out_dst, const float* h_in, int ld_h, float* h_out, int norm_kind,
                                     const float* norm_scale, const float* norm_shift, void* stream);
+
+/* ---- in-edge gated aggregation + node update: the GatedGCN layer (one direction) ---------------------
+ * For every node i < num_nodes_out, with s_p = sigmoid(e[p,:]):
+ *   fwd = sum_{p in in(i)} s_p * A2h[srt_src[p],:] / (sum_{p in in(i)} s_p + 1e-6)
+ *   h_out[i,:] = relu(norm_h(A1h[i,:] + fwd)) + h_in[i,:]
+ * Replaces sigmoid + the one update_all pair + the node epilogue of the reference's GatedGCN layer, gated_gcn_full.py:212-225
+ * (the symmetric layer without A_3 and without the pass over dgl.reverse(g)).  A pure stream over the destination-sorted e rows
+ * plus one gathered table: no out_ptr / out_pos / out_dst.  hidden in {64,128,256}; norm_kind GNNOME_NORM_AFFINE or
+ * GNNOME_NORM_LAYER; ld_node is free (a [N,4H] projection here, any row stride >= hidden that is a multiple of 4); the table rows
+ * A2h[srt_src[p]] may lie beyond num_nodes_out (halo rows of a partition).  All row pointers, norm_scale and norm_shift 16-byte aligned.
+ * The summation order depends on the graph only: bit-reproducible, and for every node whose in + out list gnnome_node_aggregate_f32
+ * reduces with one wave (<= 4096 items) EQUAL BIT FOR BIT to that entry's result with an all-zero A3h table.  A node with more than
+ * 4096 in-edges is still reduced by its one wave (about a millisecond per 10^5 edges - an estimate), in two levels of fixed
+ * 128-item blocks.  h_out is dense [num_nodes_out, H]; it must not alias h_in. */
+int gnnome_node_aggregate_in_f32(const float* e, int hidden, int64_t num_nodes_out, const float* A1h, const float* A2h, int ld_node,
+                                 const int32_t* in_ptr, const int32_t* srt_src, const float* h_in, int ld_h, float* h_out,
+                                 int norm_kind, const float* norm_scale, const float* norm_shift, void* stream);
+
+/* The same update for the nodes [node_begin, node_end) only - all pointers and num_nodes_out describe the WHOLE graph exactly as for
+ * gnnome_node_aggregate_in_f32, rows outside the range are not touched (the contract of gnnome_node_aggregate_range_f32).  Results are
+ * bit-identical to the single launch; there is no hub pass here, so the ranges of one aggregation may be issued in any order. */
+int gnnome_node_aggregate_in_range_f32(const float* e, int hidden, int64_t num_nodes_out, int64_t node_begin, int64_t node_end,
+                                       const float* A1h, const float* A2h, int ld_node, const int32_t* in_ptr, const int32_t* srt_src,
+                                       const float* h_in, int ld_h, float* h_out, int norm_kind, const float* norm_scale,
+                                       const float* norm_shift, void* stream);
 
 /* ---- streaming aggregation (round 5) -----------------------------------------------------------------
  * The same node update as gnnome_node_aggregate_f32 with norm_kind = GNNOME_NORM_AFFINE (gated_gcn_full.py:111-114, :124-127,
