@@ -1,0 +1,202 @@
+// gnnome_node_neighbour_sum_f32: the unweighted, degree-normalised neighbour sum of the two sum / mean baselines, one wave per
+// destination node, no atomics.
+//
+//   out_i = dscale_i * ( sscale_i * h_i + sum_{p in in(i)} sscale[src_p] * h[src_p,:] + [both] sum_{q in out(i)} sscale[dst_q] * h[dst_q,:] )
+//
+// Reference lines replaced: models/full_graph.py:65-75 and :109-119 build g' = add_self_loop(g) (directed=True) or
+// add_self_loop(add_reverse_edges(g)) (directed=False) and run DGL's GraphConv(norm='both') (layers/processor.py:35-46) or
+// SAGEConv('mean') (:73-84) on it; the message passing of both is this sum - GraphConv with sscale = dout'^-1/2 and
+// dscale = din'^-1/2, SAGEConv with sscale absent and dscale = 1/din'.  g' is never built: the in-edges of a node are a contiguous
+// run of srt_src (CSR by dst), its out-edges a contiguous run of out_dst (CSR by src), the loop edge is the node's own row.
+// There is no e[E,H] stream here - the kernel is a pure gather of h rows.  Bound: the gather's traffic, (E' + N) H 4 bytes read
+// (E' = E, or 2 E with both lists) and N H 4 written; where the rows come from (L2, Infinity Cache, HBM) depends on the numbering.
+//
+// Lane mapping: node_aggregate_in.hip's.  A row of H floats is covered by H/4 lanes holding a float4 each, a wave64 walks
+// G = 64/(H/4) rows at once (U = 4 requests per lane group in flight), lane l of a 64-item batch loads the batch's l-th neighbour
+// id (and its sscale), which the lane groups then fetch with ds_bpermute (one group, H = 256: v_readlane).
+//
+// ASSOCIATION - fixed, a function of the graph alone, so two runs leave equal bits:
+//   * the accumulator of lane group 0 starts at the self term sscale_i * h_i, the other groups' at zero;
+//   * then the in-list, then (both) the out-list.  Item k of a list (ascending sorted position) goes to lane group k mod G of its
+//     64-item batch and is added there in ascending order, as fma(sscale, row, sum) (one rounding per item);
+//   * a list of more than kNbrHubThreshold = 4096 items is summed in TWO LEVELS, as node_aggregate_in.hip does: every
+//     kNbrHubBlock = 128 items (two batches) the per-group sums of the block are added, in block order, to the node's accumulators,
+//     which keeps the rounding error of a 10^5-term sum at that of a ~10^3-term one.  A shorter list is one block;
+//   * the G group accumulators are combined with the __shfl_xor tree of in_group_sum, and the result is multiplied by dscale_i.
+// HUBS: a node's single wave walks its whole lists - no second launch, no scratch, no hub list.  The wave is alone with them:
+// about a millisecond per 10^5 neighbours (an ESTIMATE from node_aggregate_in's per-wave row rate, not a measurement), during which
+// the rest of the chip works on the other nodes.
+//
+// gnnome_relu_rows_f32: the ReLU between two layers of those models (processor.py:44, :82), in place on row-strided rows, NaN kept.
+#include "common.h"
+
+namespace gnnome {
+
+constexpr int kNbrThreads = 256;
+constexpr int kNbrHubThreshold = 4096;   // items above which a list is summed in two levels
+constexpr int kNbrHubBlock = 128;        // items per first-level block of such a list (a multiple of the 64-item batch)
+constexpr int kNbrInFlight = 4;          // row requests per lane group in flight
+
+template <int H>
+__device__ __forceinline__ float nbr_group_sum(float v) {
+    // all-reduce over the lane groups (lanes with equal lane % (H/4)): node_aggregate_in.hip's in_group_sum
+    constexpr int LPR = H / 4;
+#pragma unroll
+    for (int m = LPR; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// acc += sum over items [lo, hi) of one list (idx: the list's first neighbour id; NULL only for an empty list) of sscale[j] * h[j,:],
+// lane group g taking every G-th item of every 64-item batch.  The bounds are wave-uniform (scalar loops).
+template <int H, bool SS>
+__device__ __forceinline__ void accumulate_rows(const float* __restrict__ h, int ldh, const float* __restrict__ sscale,
+                                                const int32_t* __restrict__ idx, int lo, int hi, int lane, int group, int c, f32x4& acc) {
+    constexpr int LPR = H / 4, G = 64 / LPR, U = kNbrInFlight;
+    // the value lane `it` holds: `it` is uniform inside a lane group, so with one group (H = 256) it is a scalar read
+    auto pick = [&](int v, int it) -> int {
+        if (G == 1) return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(it));
+        return __builtin_amdgcn_ds_bpermute(it << 2, v);
+    };
+    for (int base = lo; base < hi; base += 64) {
+        const int j = base + lane;   // lane l owns item base + l
+        int my_n = 0;
+        float my_s = 1.0f;
+        if (j < hi) {
+            my_n = idx[j];
+            if (SS) my_s = sscale[my_n];
+        }
+        const int m = min(64, hi - base);
+        for (int j0 = 0; j0 < m; j0 += G * U) {
+            f32x4 a[U];
+            float s[U];
+            bool live[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int it = j0 + u * G + group;
+                live[u] = it < m;
+                const int sel = live[u] ? it : j0;   // (a dead slot reads item j0, which exists)
+                a[u] = *reinterpret_cast<const f32x4*>(h + (int64_t)pick(my_n, sel) * ldh + c);
+                s[u] = SS ? __int_as_float(pick(__float_as_int(my_s), sel)) : 1.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (live[u]) {
+                    if (SS) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) acc[k] = fmaf(s[u], a[u][k], acc[k]);
+                    } else {
+                        acc += a[u];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// one list of `len` items into the node's accumulators: one block, or fixed 128-item blocks above the hub threshold
+template <int H, bool SS>
+__device__ __forceinline__ void accumulate_list(const float* __restrict__ h, int ldh, const float* __restrict__ sscale,
+                                                const int32_t* __restrict__ idx, int len, int lane, int group, int c, f32x4& acc) {
+    const int blk = len > kNbrHubThreshold ? kNbrHubBlock : len;   // (wave-uniform)
+    for (int blo = 0; blo < len; blo += blk) {
+        f32x4 part = {0.f, 0.f, 0.f, 0.f};
+        accumulate_rows<H, SS>(h, ldh, sscale, idx, blo, min(len, blo + blk), lane, group, c, part);
+        acc += part;
+    }
+}
+
+template <int H, bool SS>
+__global__ __launch_bounds__(kNbrThreads) void k_node_neighbour_sum(const float* __restrict__ h, int ldh, int64_t num_nodes,
+                                                                    const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ srt_src,
+                                                                    const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_dst,
+                                                                    const float* __restrict__ sscale, const float* __restrict__ dscale,
+                                                                    float* __restrict__ out, int ldo, int total_blocks) {
+    constexpr int LPR = H / 4;
+    // the wave index read as a scalar: the node and everything loaded through it (the list bounds, its scales) live in scalar registers
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t node = (int64_t)xcd_remap(blockIdx.x, total_blocks) * (kNbrThreads / 64) + wave;
+    if (node >= num_nodes) return;
+    const int group = lane / LPR, c = (lane % LPR) * 4;
+
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (group == 0) {   // the loop edge of g': the node's own row
+        acc = *reinterpret_cast<const f32x4*>(h + node * ldh + c);
+        if (SS) acc *= sscale[node];
+    }
+    const int ib = in_ptr[node], din = in_ptr[node + 1] - ib;
+    accumulate_list<H, SS>(h, ldh, sscale, srt_src + ib, din, lane, group, c, acc);
+    if (out_ptr != nullptr) {   // directed=False: the reverse copies of the node's out-edges
+        const int ob = out_ptr[node], dout = out_ptr[node + 1] - ob;
+        accumulate_list<H, SS>(h, ldh, sscale, out_dst + ob, dout, lane, group, c, acc);
+    }
+
+    f32x4 v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = nbr_group_sum<H>(acc[k]);
+    if (dscale != nullptr) v *= dscale[node];
+    if (group == 0) *reinterpret_cast<f32x4*>(out + node * ldo + c) = v;
+}
+
+template <int H>
+static int launch_neighbour_sum(const float* h, int ldh, int64_t n, const int32_t* in_ptr, const int32_t* srt_src, const int32_t* out_ptr,
+                                const int32_t* out_dst, const float* sscale, const float* dscale, float* out, int ldo, hipStream_t s) {
+    const int64_t blocks = (n + (kNbrThreads / 64) - 1) / (kNbrThreads / 64);
+    GN_REQUIRE(blocks < (1ll << 31), "node_neighbour_sum: too many nodes");
+    if (sscale != nullptr)
+        hipLaunchKernelGGL((k_node_neighbour_sum<H, true>), dim3((unsigned)blocks), dim3(kNbrThreads), 0, s, h, ldh, n, in_ptr, srt_src, out_ptr,
+                           out_dst, sscale, dscale, out, ldo, (int)blocks);
+    else
+        hipLaunchKernelGGL((k_node_neighbour_sum<H, false>), dim3((unsigned)blocks), dim3(kNbrThreads), 0, s, h, ldh, n, in_ptr, srt_src, out_ptr,
+                           out_dst, sscale, dscale, out, ldo, (int)blocks);
+    GN_LAUNCH_CHECK();
+    return GNNOME_OK;
+}
+
+constexpr int kReluThreads = 256;
+
+// x <- relu(x) on rows of `hidden` floats with row stride ld; NaN stays NaN (relu_keep_nan, see common.h)
+__global__ __launch_bounds__(kReluThreads) void k_relu_rows(float* __restrict__ x, int ld, int64_t rows, int hidden) {
+    const int q = hidden / 4;
+    const int64_t total = rows * q;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4* p = reinterpret_cast<f32x4*>(x + (i / q) * ld + (i % q) * 4);
+        f32x4 v = *p;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = relu_keep_nan(v[k]);
+        *p = v;
+    }
+}
+
+}  // namespace gnnome
+
+extern "C" int gnnome_node_neighbour_sum_f32(const float* h, int ld_h, int hidden, int64_t num_nodes, const int32_t* in_ptr,
+                                             const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_dst, const float* sscale,
+                                             const float* dscale, float* out, int ld_out, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_nodes >= 0, "node_neighbour_sum: negative node count");
+    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "node_neighbour_sum: hidden=%d not in {64,128,256}", hidden);
+    if (num_nodes == 0) return GNNOME_OK;
+    // srt_src / out_dst may be NULL for a graph without edges (never dereferenced then); out_ptr == NULL selects the directed form
+    GN_REQUIRE(h && in_ptr && out, "node_neighbour_sum: null pointer");
+    GN_REQUIRE(ld_h >= hidden && ld_h % 4 == 0 && ld_out >= hidden && ld_out % 4 == 0, "node_neighbour_sum: bad strides");
+    GN_REQUIRE(((uintptr_t)h % 16 == 0) && ((uintptr_t)out % 16 == 0), "node_neighbour_sum: h and out must be 16-byte aligned");
+    GN_REQUIRE(out != h, "node_neighbour_sum: out must not alias h");
+    hipStream_t s = (hipStream_t)stream;
+    switch (hidden) {
+        case 64: return launch_neighbour_sum<64>(h, ld_h, num_nodes, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, s);
+        case 128: return launch_neighbour_sum<128>(h, ld_h, num_nodes, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, s);
+        default: return launch_neighbour_sum<256>(h, ld_h, num_nodes, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, s);
+    }
+}
+
+extern "C" int gnnome_relu_rows_f32(float* x, int ld, int64_t rows, int hidden, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(rows >= 0 && hidden > 0 && hidden % 4 == 0, "relu_rows: bad shape rows=%lld hidden=%d", (long long)rows, hidden);
+    if (rows == 0) return GNNOME_OK;
+    GN_REQUIRE(x && ld >= hidden && ld % 4 == 0 && (uintptr_t)x % 16 == 0, "relu_rows: x must be a 16-byte aligned table, row stride a multiple of 4");
+    const int64_t total = rows * (hidden / 4);
+    const unsigned grid = (unsigned)((total + kReluThreads - 1) / kReluThreads < 65536 ? (total + kReluThreads - 1) / kReluThreads : 65536);
+    hipLaunchKernelGGL(k_relu_rows, dim3(grid), dim3(kReluThreads), 0, (hipStream_t)stream, x, ld, rows, hidden);
+    GN_LAUNCH_CHECK();
+    return GNNOME_OK;
+}

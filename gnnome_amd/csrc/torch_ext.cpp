@@ -9,6 +9,7 @@
 //     e_new  = torch.ops.gnnome_hip.edge_gate(e, B1h, B2h, srt_src, srt_dst, W3, scale, shift, norm_kind)   # :97, 104-110
 //     h_new  = torch.ops.gnnome_hip.node_aggregate(e_new, A1h, A2h, A3h, in_ptr, srt_src, out_ptr, out_pos, out_dst, h, scale, shift, norm_kind)
 //     h_new  = torch.ops.gnnome_hip.node_aggregate_in(e_new, A1h, A2h, in_ptr, srt_src, h, scale, shift, norm_kind)   # GatedGCN, :212-225
+//     agg    = torch.ops.gnnome_hip.node_neighbour_sum(h, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale)   # GCNModel / SAGEModel, full_graph.py:65-75, :109-119
 //     logits = torch.ops.gnnome_hip.edge_score(e, Ps, Qd, srt_src, srt_dst, srt_eid, W1e, W2, b2, W3, b3)   # score_predictor.py:12-24
 //
 // Built by gnnome_amd/csrc/Makefile (target torch_ext: g++ against this interpreter's torch headers, linked to libgnnome_hip.so beside it);
@@ -203,6 +204,30 @@ Tensor node_aggregate_in(const Tensor& e, const Tensor& A1h, const Tensor& A2h, 
     return out;
 }
 
+// ---- the degree-normalised neighbour sum of GCNModel / SAGEModel (gnnome_node_neighbour_sum_f32; full_graph.py:65-75, :109-119) ---------------
+// out_ptr and out_dst given: the doubled graph of directed=False; sscale / dscale absent: 1
+Tensor node_neighbour_sum(const Tensor& h, const Tensor& in_ptr, const Tensor& srt_src, const OptTensor& out_ptr, const OptTensor& out_dst,
+                          const OptTensor& sscale, const OptTensor& dscale) {
+    const int ldh = rows_ld(h, "node_neighbour_sum.h");
+    const int64_t N = h.size(0), H = h.size(1);
+    const bool both = out_ptr.has_value() && out_ptr->defined();
+    TORCH_CHECK(both == (out_dst.has_value() && out_dst->defined()), "node_neighbour_sum: out_ptr and out_dst come together");
+    TORCH_CHECK(in_ptr.numel() == N + 1 && (!both || (out_ptr->numel() == N + 1 && out_dst->numel() == srt_src.numel())) &&
+                    (!sscale.has_value() || !sscale->defined() || sscale->numel() == N) &&
+                    (!dscale.has_value() || !dscale->defined() || dscale->numel() == N),
+                "node_neighbour_sum: shapes h[N,H] in_ptr[N+1] srt_src[E] out_ptr[N+1] out_dst[E] sscale,dscale[N]");
+    Guard guard(h.device());
+    Tensor out = at::empty({N, H}, h.options());
+    ok(gnnome_node_neighbour_sum_f32(f32(h, "node_neighbour_sum.h"), ldh, (int)H, N, i32(in_ptr, "node_neighbour_sum.in_ptr"),
+                                     srt_src.numel() ? i32(srt_src, "node_neighbour_sum.srt_src") : nullptr,
+                                     both ? i32(*out_ptr, "node_neighbour_sum.out_ptr") : nullptr,
+                                     both && out_dst->numel() ? i32(*out_dst, "node_neighbour_sum.out_dst") : nullptr,
+                                     f32_opt(sscale, "node_neighbour_sum.sscale"), f32_opt(dscale, "node_neighbour_sum.dscale"),
+                                     N ? out.data_ptr<float>() : nullptr, (int)std::max<int64_t>(H, 1), stream_of(h)),
+       "gnnome_node_neighbour_sum_f32");
+    return out;
+}
+
 // ---- the edge scorer (gnnome_edge_score_f32; score_predictor.py:12-24), logits in edge-id order -------------------------------------------------
 Tensor edge_score(const Tensor& e, const Tensor& Ps, const Tensor& Qd, const Tensor& srt_src, const Tensor& srt_dst, const Tensor& srt_eid,
                   const Tensor& W1e, const Tensor& W2, const Tensor& b2, const Tensor& W3, const Tensor& b3) {
@@ -245,6 +270,9 @@ Tensor node_aggregate_in_meta(const Tensor&, const Tensor&, const Tensor&, const
                               const Tensor&, int64_t) {
     return at::empty_like(h_in);
 }
+Tensor node_neighbour_sum_meta(const Tensor& h, const Tensor&, const Tensor&, const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&) {
+    return at::empty({h.size(0), h.size(1)}, h.options());
+}
 Tensor edge_score_meta(const Tensor& e, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
                        const Tensor&, const Tensor&, const Tensor&) {
     return at::empty({e.size(0)}, e.options());
@@ -262,6 +290,8 @@ TORCH_LIBRARY(gnnome_hip, m) {
           "Tensor h_in, Tensor scale, Tensor shift, int norm_kind=0) -> Tensor");
     m.def("node_aggregate_in(Tensor e, Tensor A1h, Tensor A2h, Tensor in_ptr, Tensor srt_src, Tensor h_in, Tensor scale, Tensor shift, "
           "int norm_kind=0) -> Tensor");
+    m.def("node_neighbour_sum(Tensor h, Tensor in_ptr, Tensor srt_src, Tensor? out_ptr=None, Tensor? out_dst=None, Tensor? sscale=None, "
+          "Tensor? dscale=None) -> Tensor");
     m.def("edge_score(Tensor e, Tensor Ps, Tensor Qd, Tensor srt_src, Tensor srt_dst, Tensor srt_eid, Tensor W1e, Tensor W2, Tensor b2, Tensor W3, "
           "Tensor b3) -> Tensor");
     m.def("abi_version() -> int", []() -> int64_t { return gnnome_abi_version(); });   // the libgnnome_hip.so this extension is bound to
@@ -275,6 +305,7 @@ TORCH_LIBRARY_IMPL(gnnome_hip, CUDA, m) {   // the CUDA dispatch key is the HIP 
     m.impl("edge_gate", &edge_gate);
     m.impl("node_aggregate", &node_aggregate);
     m.impl("node_aggregate_in", &node_aggregate_in);
+    m.impl("node_neighbour_sum", &node_neighbour_sum);
     m.impl("edge_score", &edge_score);
 }
 
@@ -286,5 +317,6 @@ TORCH_LIBRARY_IMPL(gnnome_hip, Meta, m) {
     m.impl("edge_gate", &edge_gate_meta);
     m.impl("node_aggregate", &node_aggregate_meta);
     m.impl("node_aggregate_in", &node_aggregate_in_meta);
+    m.impl("node_neighbour_sum", &node_neighbour_sum_meta);
     m.impl("edge_score", &edge_score_meta);
 }

@@ -165,5 +165,77 @@ class GatedGCN_processor(nn.Module):
         return h, e
 
 
+def _model_level_only(module):
+    raise NotImplementedError(f"{type(module).__name__} owns parameters only: the reference runs it on g' = add_self_loop(g), which is never "
+                              "built here - call GCNModel / SAGEModel, whose forward runs the whole stack (gnnome_amd/engine_baselines.py)")
+
+
+class GraphConv(nn.Module):
+    """The parameters of DGL 0.8.1's GraphConv(in, out, norm='both', weight=True, bias=True) as layers/processor.py:39 builds it:
+    `weight` [in, out] (NOT nn.Linear's layout; Xavier uniform) and `bias` [out] (zeros).  In eval mode GCNModel computes
+    h' = (din'^-1/2 * sum_{j in N'(i)} dout'[j]^-1/2 h[j]) weight + bias with it."""
+
+    def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True):
+        super().__init__()
+        from . import engine_baselines
+        if in_feats != out_feats or norm != "both" or not weight or not bias:
+            raise ValueError("GraphConv is built as layers/processor.py:39 builds it: in == out, norm='both', weight=True, bias=True")
+        engine_baselines.built_width(in_feats)
+        self.weight = nn.Parameter(torch.empty(in_feats, out_feats))
+        self.bias = nn.Parameter(torch.zeros(out_feats))
+        nn.init.xavier_uniform_(self.weight)
+
+    def forward(self, graph, feat):
+        _model_level_only(self)
+
+
+class SAGEConv(nn.Module):
+    """The parameters of DGL 0.8.1's SAGEConv(in, out, 'mean', feat_drop) as layers/processor.py:77 builds it: `bias` [out] (zeros),
+    `fc_self` and `fc_neigh` (nn.Linear without bias; Xavier uniform with the ReLU gain, as DGL initialises them).  In eval mode
+    SAGEModel computes h' = h fc_self.weight^T + (1/din' * sum_{j in N'(i)} h[j]) fc_neigh.weight^T + bias with it; feat_drop is
+    the identity there."""
+
+    def __init__(self, in_feats, out_feats, aggregator_type="mean", feat_drop=0.0, bias=True):
+        super().__init__()
+        from . import engine_baselines
+        if in_feats != out_feats or aggregator_type != "mean" or not bias:
+            raise ValueError("SAGEConv is built as layers/processor.py:77 builds it: in == out, the 'mean' aggregator, bias=True")
+        engine_baselines.built_width(in_feats)
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.bias = nn.Parameter(torch.zeros(out_feats))
+        self.fc_self = nn.Linear(in_feats, out_feats, bias=False)
+        self.fc_neigh = nn.Linear(in_feats, out_feats, bias=False)
+        gain = nn.init.calculate_gain("relu")
+        nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
+        nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
+
+    def forward(self, graph, feat):
+        _model_level_only(self)
+
+
+class GCN_processor(nn.Module):
+    """layers/processor.py:35-46: num_layers GraphConv, a ReLU after every one but the last.  State-dict keys `convs.N.weight`, `convs.N.bias`."""
+
+    def __init__(self, num_layers, hidden_features):
+        super().__init__()
+        self.convs = nn.ModuleList([GraphConv(hidden_features, hidden_features, weight=True, bias=True) for _ in range(num_layers)])
+
+    def forward(self, graph, h, e):
+        _model_level_only(self)
+
+
+class SAGE_processor(nn.Module):
+    """layers/processor.py:73-84: num_layers SAGEConv('mean'), a ReLU after every one but the last.  State-dict keys `convs.N.bias`,
+    `convs.N.fc_self.weight`, `convs.N.fc_neigh.weight`.  dropout=None means 0.0 here (the reference hands None to nn.Dropout, which fails)."""
+
+    def __init__(self, num_layers, hidden_features, dropout=None):
+        super().__init__()
+        drop = dropout if dropout else 0.0
+        self.convs = nn.ModuleList([SAGEConv(hidden_features, hidden_features, "mean", feat_drop=drop) for _ in range(num_layers)])
+
+    def forward(self, graph, h, e):
+        _model_level_only(self)
+
+
 __all__ = ["SymGatedGCN", "SymGatedGCN_processor", "ScorePredictor", "NodeEncoder", "EdgeEncoder", "GatedGCN", "GatedGCN_processor",
-           "views_for"]
+           "GraphConv", "SAGEConv", "GCN_processor", "SAGE_processor", "views_for"]

@@ -25,7 +25,8 @@ weights/weights.pt, same call.  Differences, all deliberate:
 import torch.nn as nn
 
 from . import engine
-from .layers import EdgeEncoder, GatedGCN_processor, NodeEncoder, ScorePredictor, SymGatedGCN_processor
+from .layers import (EdgeEncoder, GatedGCN_processor, GCN_processor, NodeEncoder, SAGE_processor, ScorePredictor,
+                     SymGatedGCN_processor)
 
 
 class SymGatedGCNModel(nn.Module):
@@ -87,4 +88,61 @@ class GatedGCNModel(nn.Module):
         return engine_gated.model_forward(self, graph, x, e)
 
 
-__all__ = ["SymGatedGCNModel", "GatedGCNModel"]
+class _BaselineModel(nn.Module):
+    """What GCNModel and SAGEModel share: encoders, the scorer, the refusals and the call (gnnome_amd/engine_baselines.py)."""
+    kind = None
+    range_check = True
+
+    def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, hidden_edge_scores, directed):
+        super().__init__()
+        from . import engine_baselines
+        engine_baselines.built_width(hidden_features)
+        engine_baselines.built_width(hidden_edge_scores, engine.BUILT_SCORE_HIDDEN, "hidden_edge_scores")
+        self.directed = directed
+        self.node_encoder = NodeEncoder(node_features, hidden_ne_features, hidden_features)
+        self.edge_encoder = EdgeEncoder(edge_features, hidden_ne_features, hidden_features)
+
+    def forward(self, graph, x, e):
+        from . import engine_baselines
+        return engine_baselines.model_forward(self, graph, x, e)
+
+
+class GCNModel(_BaselineModel):
+    """Drop-in for the reference's models/full_graph.py:56-75 - the GCN ablation baseline: NodeEncoder and EdgeEncoder, GCN_processor
+    (layers/processor.py:35-46: DGL's GraphConv with norm='both', a ReLU between layers), ScorePredictor.  Same constructor and
+    state_dict keys (`node_encoder.linear{1,2}.*`, `edge_encoder.linear{1,2}.*`, `gnn.convs.N.{weight,bias}`, `predictor.W{1,2,3}.*`),
+    same call; `graph` and the inputs as for SymGatedGCNModel; logits [E,1] in edge-id order on the inputs' device.
+
+    The convolutions run on g' = add_self_loop(g), or add_self_loop(add_reverse_edges(g)) with directed=False, which is never built:
+    the degree-normalised neighbour sum is the kernel gnnome_node_neighbour_sum_f32 over the graph's own in- and out-lists.  The encoded
+    e goes unchanged to the scorer, which scores the original graph.  `normalization` is accepted and unused, as in the reference.
+    Built widths only: hidden_features in {64, 128, 256}, hidden_edge_scores in {32, 64, 128}.  Eval mode only: a call in train mode
+    raises NotImplementedError."""
+    kind = "gcn"
+
+    def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, num_layers, hidden_edge_scores,
+                 normalization, dropout=None, directed=True):
+        super().__init__(node_features, edge_features, hidden_features, hidden_ne_features, hidden_edge_scores, directed)
+        self.gnn = GCN_processor(num_layers, hidden_features)
+        self.predictor = ScorePredictor(hidden_features, hidden_edge_scores)
+
+
+class SAGEModel(_BaselineModel):
+    """Drop-in for the reference's models/full_graph.py:100-119 - the GraphSAGE ablation baseline: NodeEncoder and EdgeEncoder,
+    SAGE_processor (layers/processor.py:73-84: DGL's SAGEConv with the 'mean' aggregator, a ReLU between layers), ScorePredictor.
+    Same constructor and state_dict keys (`gnn.convs.N.bias`, `gnn.convs.N.fc_self.weight`, `gnn.convs.N.fc_neigh.weight`, the
+    encoders' and the predictor's as for GCNModel), same call; g', the scorer, `normalization`, the built widths and eval mode as for
+    GCNModel.
+
+    One divergence: the reference's default dropout=None reaches nn.Dropout(None) and fails at construction; here None means 0.0.
+    (feat_drop is the identity in eval mode, which is all that is served.)"""
+    kind = "sage"
+
+    def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, num_layers, hidden_edge_scores,
+                 normalization, dropout=None, directed=True):
+        super().__init__(node_features, edge_features, hidden_features, hidden_ne_features, hidden_edge_scores, directed)
+        self.gnn = SAGE_processor(num_layers, hidden_features, dropout=dropout)
+        self.predictor = ScorePredictor(hidden_features, hidden_edge_scores)
+
+
+__all__ = ["SymGatedGCNModel", "GatedGCNModel", "GCNModel", "SAGEModel"]

@@ -709,6 +709,42 @@ def node_aggregate_in(e, A1h, A2h, views, h_in, norm_kind, scale, shift, num_nod
     return h_out
 
 
+def node_neighbour_sum(h, views, sscale=None, dscale=None, both=False, out=None):
+    """The message passing of GCNModel / SAGEModel on the self-looped graph (gnnome_node_neighbour_sum_f32):
+    out[i] = dscale[i] * (sscale[i] h[i] + sum over the in-edges of i of sscale[src] h[src] + [both] sum over its out-edges of sscale[dst] h[dst]).
+    sscale, dscale: float32[N] or None (= 1).  h and out may be column blocks of a wider table.  Views of a reversed graph
+    (GraphViews.reversed) exchange the roles of the two lists."""
+    lib = _lib.load()
+    h, ldh = _rows(h, "node_neighbour_sum.h")
+    n, hidden = h.shape
+    if n != views.num_nodes:
+        raise ValueError(f"node_neighbour_sum: h has {n} rows for {views.num_nodes} nodes")
+    if out is None:
+        out = torch.empty((n, hidden), dtype=torch.float32, device=h.device)
+    out, ldo = _rows(out, "node_neighbour_sum.out")
+    if out.shape != h.shape or out.device != h.device:
+        raise ValueError(f"node_neighbour_sum: out is {tuple(out.shape)} on {out.device}, h is {tuple(h.shape)} on {h.device}")
+    for name, t in (("sscale", sscale), ("dscale", dscale)):
+        if t is not None and (_f32(t, "node_neighbour_sum." + name).shape != (n,) or not t.is_contiguous()):
+            raise ValueError(f"node_neighbour_sum: {name} is one contiguous float per node")
+    lists = [(views.in_ptr, views.srt_src), (views.out_ptr, views.out_dst)]
+    if views.transposed:
+        lists.reverse()
+    (ptr_a, idx_a), (ptr_b, idx_b) = lists
+    with _on(h.device):
+        _lib.check(lib.gnnome_node_neighbour_sum_f32(_ptr(h), ldh, hidden, n, _ptr(ptr_a), _ptr(idx_a), _ptr(ptr_b) if both else None,
+                                                     _ptr(idx_b) if both else None, _ptr(sscale), _ptr(dscale), _ptr(out), ldo,
+                                                     _stream(h.device)), "node_neighbour_sum_f32")
+    return out
+
+
+def relu_rows(x):
+    """x <- relu(x) in place (gnnome_relu_rows_f32; NaN stays NaN); x may be a column block of a wider table."""
+    x, ld = _rows(x, "relu_rows.x")
+    _call("gnnome_relu_rows_f32", x.device, _ptr(x), ld, x.shape[0], x.shape[1])
+    return x
+
+
 def edge_score(e, Ps, Qd, views, W1e, W2, b2, W3, b3, logits, num_edges=None, scatter_to_edge_id=True, z1_out=None):
     lib = _lib.load()
     e, _ = _rows(e, "edge_score.e")

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 25
+#define GNNOME_ABI_VERSION 26
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -263,6 +263,29 @@ int gnnome_node_aggregate_in_range_f32(const float* e, int hidden, int64_t num_n
                                        const float* A1h, const float* A2h, int ld_node, const int32_t* in_ptr, const int32_t* srt_src,
                                        const float* h_in, int ld_h, float* h_out, int norm_kind, const float* norm_scale,
                                        const float* norm_shift, void* stream);
+
+/* ---- unweighted, degree-normalised neighbour sum: the message passing of GCNModel and SAGEModel -------
+ * For every node i < num_nodes:
+ *   out[i,:] = dscale[i] * ( sscale[i] * h[i,:] + sum_{p in in(i)} sscale[srt_src[p]] * h[srt_src[p],:]
+ *                                               + sum_{q in out(i)} sscale[out_dst[q]] * h[out_dst[q],:] )     (last sum: out_ptr != NULL only)
+ * Replaces the convolutions' message passing on g' = dgl.add_self_loop(g) (directed=True) or add_self_loop(add_reverse_edges(g))
+ * (directed=False), models/full_graph.py:65-75 (GCNModel) and :109-119 (SAGEModel): DGL's GraphConv(norm='both') of
+ * layers/processor.py:35-46 with sscale = dout'^-1/2, dscale = din'^-1/2, and SAGEConv('mean') of :73-84 with sscale = NULL,
+ * dscale = 1/din'.  g' is never built: in(i) = [in_ptr[i], in_ptr[i+1]) of srt_src, out(i) = [out_ptr[i], out_ptr[i+1]) of out_dst
+ * (the arrays of gnnome_build_graph_views), the loop edge is the node's own row and counts once more where the graph already has one.
+ * sscale, dscale: per-node floats, each may be NULL (= 1).  out_ptr == NULL selects the directed form (in-list only); srt_src and
+ * out_dst may be NULL for a graph without edges.  h and out are row-strided (ld_h, ld_out >= hidden, multiples of 4; 16-byte aligned):
+ * column blocks of a wider table - of the same one, too, as long as they do not overlap.  hidden in {64,128,256}.
+ * One wave per node, no atomics; the association is fixed and a function of the graph alone (self term, in-list ascending, out-list
+ * ascending; lists above 4096 items in fixed 128-item blocks - csrc/node_neighbour.hip), so two runs leave equal bits.  A hub is walked
+ * by its own wave: about a millisecond per 10^5 neighbours (an estimate). */
+int gnnome_node_neighbour_sum_f32(const float* h, int ld_h, int hidden, int64_t num_nodes, const int32_t* in_ptr, const int32_t* srt_src,
+                                  const int32_t* out_ptr, const int32_t* out_dst, const float* sscale, const float* dscale, float* out,
+                                  int ld_out, void* stream);
+
+/* x[r, 0..hidden) <- relu(x[r, 0..hidden)) in place for r < rows, row stride ld (a multiple of 4; x 16-byte aligned, hidden % 4 == 0):
+ * the ReLU between two layers of GCN_processor / SAGE_processor (processor.py:44, :82).  NaN stays NaN. */
+int gnnome_relu_rows_f32(float* x, int ld, int64_t rows, int hidden, void* stream);
 
 /* ---- streaming aggregation (round 5) -----------------------------------------------------------------
  * The same node update as gnnome_node_aggregate_f32 with norm_kind = GNNOME_NORM_AFFINE (gated_gcn_full.py:111-114, :124-127,
