@@ -6,6 +6,6 @@ Compute runs in libgnnome_hip.so (hand-written HIP for gfx950, C ABI in include/
 there is no CPU or PyTorch fallback.
 """
 from . import layers, models  # noqa: F401
-from .models import GatedGCNModel, GCNModel, SAGEModel, SymGatedGCNModel  # noqa: F401
+from .models import GATModel, GatedGCNModel, GCNModel, SAGEModel, SymGatedGCNModel  # noqa: F401
 
-__all__ = ["models", "layers", "SymGatedGCNModel", "GatedGCNModel", "GCNModel", "SAGEModel"]
+__all__ = ["models", "layers", "SymGatedGCNModel", "GatedGCNModel", "GCNModel", "SAGEModel", "GATModel"]

@@ -10,6 +10,7 @@
 //     h_new  = torch.ops.gnnome_hip.node_aggregate(e_new, A1h, A2h, A3h, in_ptr, srt_src, out_ptr, out_pos, out_dst, h, scale, shift, norm_kind)
 //     h_new  = torch.ops.gnnome_hip.node_aggregate_in(e_new, A1h, A2h, in_ptr, srt_src, h, scale, shift, norm_kind)   # GatedGCN, :212-225
 //     agg    = torch.ops.gnnome_hip.node_neighbour_sum(h, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale)   # GCNModel / SAGEModel, full_graph.py:65-75, :109-119
+//     agg    = torch.ops.gnnome_hip.node_attention_sum(feat, el, er, in_ptr, srt_src, out_ptr, out_dst, bias, negative_slope)   # GATModel, full_graph.py:78-97
 //     logits = torch.ops.gnnome_hip.edge_score(e, Ps, Qd, srt_src, srt_dst, srt_eid, W1e, W2, b2, W3, b3)   # score_predictor.py:12-24
 //
 // Built by gnnome_amd/csrc/Makefile (target torch_ext: g++ against this interpreter's torch headers, linked to libgnnome_hip.so beside it);
@@ -228,6 +229,32 @@ Tensor node_neighbour_sum(const Tensor& h, const Tensor& in_ptr, const Tensor& s
     return out;
 }
 
+// ---- the edge-softmax attention sum of GATModel (gnnome_node_attention_sum_f32; full_graph.py:78-97, processor.py:49-70) -----------------------
+// feat [N,3H], el / er [N,4] (three heads and a pad), all row-strided; out_ptr and out_dst given: the doubled graph of directed=False
+Tensor node_attention_sum(const Tensor& feat, const Tensor& el, const Tensor& er, const Tensor& in_ptr, const Tensor& srt_src,
+                          const OptTensor& out_ptr, const OptTensor& out_dst, const OptTensor& bias, double negative_slope) {
+    const int ldf = rows_ld(feat, "node_attention_sum.feat"), ld_el = rows_ld(el, "node_attention_sum.el"), ld_er = rows_ld(er, "node_attention_sum.er");
+    const int64_t N = feat.size(0), W = feat.size(1), heads = 3;
+    const bool both = out_ptr.has_value() && out_ptr->defined();
+    TORCH_CHECK(both == (out_dst.has_value() && out_dst->defined()), "node_attention_sum: out_ptr and out_dst come together");
+    TORCH_CHECK(W % heads == 0 && el.size(0) == N && el.size(1) == 4 && er.size(0) == N && er.size(1) == 4 && in_ptr.numel() == N + 1 &&
+                    (!both || (out_ptr->numel() == N + 1 && out_dst->numel() == srt_src.numel())) &&
+                    (!bias.has_value() || !bias->defined() || bias->numel() == W),
+                "node_attention_sum: shapes feat[N,3H] el,er[N,4] in_ptr[N+1] srt_src[E] out_ptr[N+1] out_dst[E] bias[3H]");
+    Guard guard(feat.device());
+    Tensor out = at::empty({N, W}, feat.options());
+    ok(gnnome_node_attention_sum_f32(f32(feat, "node_attention_sum.feat"), ldf, f32(el, "node_attention_sum.el"), ld_el,
+                                     f32(er, "node_attention_sum.er"), ld_er, (int)(W / heads), (int)heads, N,
+                                     i32(in_ptr, "node_attention_sum.in_ptr"),
+                                     srt_src.numel() ? i32(srt_src, "node_attention_sum.srt_src") : nullptr,
+                                     both ? i32(*out_ptr, "node_attention_sum.out_ptr") : nullptr,
+                                     both && out_dst->numel() ? i32(*out_dst, "node_attention_sum.out_dst") : nullptr, (float)negative_slope,
+                                     f32_opt(bias, "node_attention_sum.bias"), N ? out.data_ptr<float>() : nullptr,
+                                     (int)std::max<int64_t>(W, 1), stream_of(feat)),
+       "gnnome_node_attention_sum_f32");
+    return out;
+}
+
 // ---- the edge scorer (gnnome_edge_score_f32; score_predictor.py:12-24), logits in edge-id order -------------------------------------------------
 Tensor edge_score(const Tensor& e, const Tensor& Ps, const Tensor& Qd, const Tensor& srt_src, const Tensor& srt_dst, const Tensor& srt_eid,
                   const Tensor& W1e, const Tensor& W2, const Tensor& b2, const Tensor& W3, const Tensor& b3) {
@@ -273,6 +300,10 @@ Tensor node_aggregate_in_meta(const Tensor&, const Tensor&, const Tensor&, const
 Tensor node_neighbour_sum_meta(const Tensor& h, const Tensor&, const Tensor&, const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&) {
     return at::empty({h.size(0), h.size(1)}, h.options());
 }
+Tensor node_attention_sum_meta(const Tensor& feat, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const OptTensor&, const OptTensor&,
+                               const OptTensor&, double) {
+    return at::empty({feat.size(0), feat.size(1)}, feat.options());
+}
 Tensor edge_score_meta(const Tensor& e, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
                        const Tensor&, const Tensor&, const Tensor&) {
     return at::empty({e.size(0)}, e.options());
@@ -292,6 +323,8 @@ TORCH_LIBRARY(gnnome_hip, m) {
           "int norm_kind=0) -> Tensor");
     m.def("node_neighbour_sum(Tensor h, Tensor in_ptr, Tensor srt_src, Tensor? out_ptr=None, Tensor? out_dst=None, Tensor? sscale=None, "
           "Tensor? dscale=None) -> Tensor");
+    m.def("node_attention_sum(Tensor feat, Tensor el, Tensor er, Tensor in_ptr, Tensor srt_src, Tensor? out_ptr=None, Tensor? out_dst=None, "
+          "Tensor? bias=None, float negative_slope=0.2) -> Tensor");
     m.def("edge_score(Tensor e, Tensor Ps, Tensor Qd, Tensor srt_src, Tensor srt_dst, Tensor srt_eid, Tensor W1e, Tensor W2, Tensor b2, Tensor W3, "
           "Tensor b3) -> Tensor");
     m.def("abi_version() -> int", []() -> int64_t { return gnnome_abi_version(); });   // the libgnnome_hip.so this extension is bound to
@@ -306,6 +339,7 @@ TORCH_LIBRARY_IMPL(gnnome_hip, CUDA, m) {   // the CUDA dispatch key is the HIP 
     m.impl("node_aggregate", &node_aggregate);
     m.impl("node_aggregate_in", &node_aggregate_in);
     m.impl("node_neighbour_sum", &node_neighbour_sum);
+    m.impl("node_attention_sum", &node_attention_sum);
     m.impl("edge_score", &edge_score);
 }
 
@@ -318,5 +352,6 @@ TORCH_LIBRARY_IMPL(gnnome_hip, Meta, m) {
     m.impl("node_aggregate", &node_aggregate_meta);
     m.impl("node_aggregate_in", &node_aggregate_in_meta);
     m.impl("node_neighbour_sum", &node_neighbour_sum_meta);
+    m.impl("node_attention_sum", &node_attention_sum_meta);
     m.impl("edge_score", &edge_score_meta);
 }

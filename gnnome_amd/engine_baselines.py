@@ -26,7 +26,7 @@ KINDS = ("gcn", "sage")
 def built_width(width, built=engine.BUILT_HIDDEN, what="hidden_features"):
     """The baselines run at the built widths only (zero-padding is not served for them)."""
     if width not in built:
-        raise ValueError(f"{what}={width}: GCNModel / SAGEModel are built for {what} in {tuple(built)}")
+        raise ValueError(f"{what}={width}: GCNModel / SAGEModel / GATModel are built for {what} in {tuple(built)}")
     return width
 
 
@@ -140,9 +140,9 @@ def run_stack(ops, prep, views, x, e_raw, directed=True):
     return logits
 
 
-def forward_in_range(ops, prep, views, x, e, xd, ed, directed, check=True):
-    """engine_gated.forward_in_range for these stacks: a forward whose logits are not all finite left fp16x3's operand range and is
-    run again as bf16x6; checked once per set of inputs."""
+def forward_in_range(ops, prep, views, x, e, xd, ed, directed, check=True, run_stack=run_stack):
+    """engine_gated.forward_in_range for these stacks (run_stack: this module's, or engine_gat's): a forward whose logits are not all
+    finite left fp16x3's operand range and is run again as bf16x6; checked once per set of inputs."""
     if ops._TUNING.get(10, 0) == 1:
         return run_stack(ops, prep, views, xd, ed, directed)
     if prep.force_bf16x6 or engine._same_inputs(prep.range_failed, views, x, e):
@@ -159,20 +159,21 @@ def forward_in_range(ops, prep, views, x, e, xd, ed, directed, check=True):
         return run_stack(ops, prep, views, xd, ed, directed)
 
 
-def model_forward(model, graph, x, e):
-    """models/full_graph.py:65-75 / :109-119 on the MI355X."""
+def model_forward(model, graph, x, e, prepared=Prepared, stack=run_stack):
+    """models/full_graph.py:65-75 / :109-119 on the MI355X (and, with engine_gat's `prepared` and `stack`, :87-97)."""
     if model.training:
-        raise NotImplementedError(f"{type(model).__name__} is built for eval mode only: call .eval() (train mode of the GCN / SAGE "
+        raise NotImplementedError(f"{type(model).__name__} is built for eval mode only: call .eval() (train mode of the GCN / SAGE / GAT "
                                   "baselines is not served)")
     out_device = x.device
     device = engine.compute_device(x, e)
-    prep = engine.prepared_for(model, device, Prepared)
+    prep = engine.prepared_for(model, device, prepared)
     views = views_for(graph, device, node_order="input")
     if x.shape[0] != views.num_nodes or e.shape[0] != views.num_edges:
         raise ValueError(f"x has {x.shape[0]} rows for {views.num_nodes} nodes, e has {e.shape[0]} rows for {views.num_edges} edges")
     with torch.no_grad():
         xd = x.detach().to(device=device, dtype=torch.float32).contiguous()
         ed = e.detach().to(device=device, dtype=torch.float32).contiguous()
-        logits = forward_in_range(hip_ops, prep, views, x, e, xd, ed, bool(model.directed), check=getattr(model, "range_check", True))
+        logits = forward_in_range(hip_ops, prep, views, x, e, xd, ed, bool(model.directed), check=getattr(model, "range_check", True),
+                                  run_stack=stack)
     views.check_range()   # a fresh graph's deferred endpoint check, after the whole forward has been enqueued
     return logits.unsqueeze(1).to(out_device)

@@ -167,7 +167,8 @@ class GatedGCN_processor(nn.Module):
 
 def _model_level_only(module):
     raise NotImplementedError(f"{type(module).__name__} owns parameters only: the reference runs it on g' = add_self_loop(g), which is never "
-                              "built here - call GCNModel / SAGEModel, whose forward runs the whole stack (gnnome_amd/engine_baselines.py)")
+                              "built here - call GCNModel / SAGEModel / GATModel, whose forward runs the whole stack "
+                              "(gnnome_amd/engine_baselines.py, engine_gat.py)")
 
 
 class GraphConv(nn.Module):
@@ -237,5 +238,56 @@ class SAGE_processor(nn.Module):
         _model_level_only(self)
 
 
+class GATConv(nn.Module):
+    """The parameters of DGL 0.8.1's GATConv(in, out, num_heads, feat_drop, attn_drop=0) as layers/processor.py:55 builds it
+    (negative_slope=0.2, residual=False, activation=None, bias=True): `fc` (nn.Linear [heads*out, in] without bias), `attn_l` and `attn_r`
+    [1, heads, out] (all three Xavier normal with the ReLU gain, as DGL initialises them) and `bias` [heads*out] (zeros).  In eval mode
+    GATModel computes, per head k, feat = fc(h)[:, k], el = (feat * attn_l[k]).sum(-1), er = (feat * attn_r[k]).sum(-1) and
+    rst[i, k] = sum_{p in N'(i)} softmax_p(leaky_relu(el[nbr_p] + er[i], 0.2)) feat[nbr_p] + bias[k] with it; feat_drop is the identity there."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2, residual=False, activation=None,
+                 bias=True):
+        super().__init__()
+        from . import engine_baselines
+        if in_feats != out_feats or attn_drop or residual or activation is not None or not bias:
+            raise ValueError("GATConv is built as layers/processor.py:55 builds it: in == out, attn_drop=0, residual=False, activation=None, "
+                             "bias=True")
+        if num_heads != 3:
+            raise ValueError(f"num_heads={num_heads}: the attention kernel is built for 3 heads (layers/processor.py:50)")
+        engine_baselines.built_width(in_feats, what="hidden_features (GATConv)")
+        self.num_heads, self.negative_slope = num_heads, float(negative_slope)
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.fc = nn.Linear(in_feats, num_heads * out_feats, bias=False)
+        self.attn_l = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.attn_r = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.bias = nn.Parameter(torch.zeros(num_heads * out_feats))
+        gain = nn.init.calculate_gain("relu")
+        nn.init.xavier_normal_(self.fc.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn_l, gain=gain)
+        nn.init.xavier_normal_(self.attn_r, gain=gain)
+
+    def forward(self, graph, feat):
+        _model_level_only(self)
+
+
+class GAT_processor(nn.Module):
+    """layers/processor.py:49-70: num_layers GATConv of 3 heads, each followed by nn.Linear(3H, H) on the concatenated heads, a ReLU after
+    every layer but the last.  State-dict keys `convs.N.{attn_l, attn_r, bias, fc.weight}`, `linears.N.{weight, bias}`.  dropout=None means
+    0.0 here (the reference hands None to nn.Dropout, which fails); the reference's print at construction is not reproduced."""
+
+    def __init__(self, num_layers, hidden_features, dropout=0.0, num_heads=3):
+        super().__init__()
+        if num_heads != 3:
+            raise ValueError(f"num_heads={num_heads}: the attention kernel is built for 3 heads (layers/processor.py:50)")
+        self.num_heads = num_heads
+        drop = dropout if dropout else 0.0
+        self.convs = nn.ModuleList([GATConv(hidden_features, hidden_features, num_heads=num_heads, feat_drop=drop, attn_drop=0)
+                                    for _ in range(num_layers)])
+        self.linears = nn.ModuleList([nn.Linear(num_heads * hidden_features, hidden_features) for _ in range(num_layers)])
+
+    def forward(self, graph, h, e):
+        _model_level_only(self)
+
+
 __all__ = ["SymGatedGCN", "SymGatedGCN_processor", "ScorePredictor", "NodeEncoder", "EdgeEncoder", "GatedGCN", "GatedGCN_processor",
-           "GraphConv", "SAGEConv", "GCN_processor", "SAGE_processor", "views_for"]
+           "GraphConv", "SAGEConv", "GCN_processor", "SAGE_processor", "GATConv", "GAT_processor", "views_for"]

@@ -25,7 +25,7 @@ weights/weights.pt, same call.  Differences, all deliberate:
 import torch.nn as nn
 
 from . import engine
-from .layers import (EdgeEncoder, GatedGCN_processor, GCN_processor, NodeEncoder, SAGE_processor, ScorePredictor,
+from .layers import (EdgeEncoder, GAT_processor, GatedGCN_processor, GCN_processor, NodeEncoder, SAGE_processor, ScorePredictor,
                      SymGatedGCN_processor)
 
 
@@ -89,7 +89,7 @@ class GatedGCNModel(nn.Module):
 
 
 class _BaselineModel(nn.Module):
-    """What GCNModel and SAGEModel share: encoders, the scorer, the refusals and the call (gnnome_amd/engine_baselines.py)."""
+    """What GCNModel, SAGEModel and GATModel share: encoders, the scorer, the refusals and the call (gnnome_amd/engine_baselines.py)."""
     kind = None
     range_check = True
 
@@ -145,4 +145,28 @@ class SAGEModel(_BaselineModel):
         self.predictor = ScorePredictor(hidden_features, hidden_edge_scores)
 
 
-__all__ = ["SymGatedGCNModel", "GatedGCNModel", "GCNModel", "SAGEModel"]
+class GATModel(_BaselineModel):
+    """Drop-in for the reference's models/full_graph.py:78-97 - the attention ablation baseline: NodeEncoder and EdgeEncoder,
+    GAT_processor (layers/processor.py:49-70: DGL's GATConv with 3 heads, nn.Linear(3H, H) on the concatenated heads, a ReLU between
+    layers), ScorePredictor.  Same constructor and state_dict keys (`gnn.convs.N.{attn_l, attn_r, bias, fc.weight}`,
+    `gnn.linears.N.{weight, bias}`, the encoders' and the predictor's as for GCNModel), same call; g', the scorer, `normalization`, the
+    built widths and eval mode as for GCNModel.
+
+    Per layer (gnnome_amd/engine_gat.py): ONE projection on [fc.weight ; attn_l fc ; attn_r fc] gives feat, el and er as column blocks of
+    a [N, 3H + 64] table, the edge softmax and the weighted sum are the kernel gnnome_node_attention_sum_f32 over the graph's own in- and
+    out-lists, then the head mix.  As for SAGEModel, dropout=None means 0.0 (the reference fails on it), and the reference's print at
+    construction is not reproduced."""
+    kind = "gat"
+
+    def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, num_layers, hidden_edge_scores,
+                 normalization, dropout=None, directed=True):
+        super().__init__(node_features, edge_features, hidden_features, hidden_ne_features, hidden_edge_scores, directed)
+        self.gnn = GAT_processor(num_layers, hidden_features, dropout=dropout, num_heads=3)
+        self.predictor = ScorePredictor(hidden_features, hidden_edge_scores)
+
+    def forward(self, graph, x, e):
+        from . import engine_gat
+        return engine_gat.model_forward(self, graph, x, e)
+
+
+__all__ = ["SymGatedGCNModel", "GatedGCNModel", "GCNModel", "SAGEModel", "GATModel"]

@@ -738,6 +738,42 @@ def node_neighbour_sum(h, views, sscale=None, dscale=None, both=False, out=None)
     return out
 
 
+def node_attention_sum(feat, views, el, er, bias=None, negative_slope=0.2, both=False, out=None):
+    """The message passing of GATModel on the self-looped graph (gnnome_node_attention_sum_f32), heads = 3:
+    out[i, k] = sum over N'(i) of softmax_p(leaky_relu(el[nbr_p, k] + er[i, k], negative_slope)) * feat[nbr_p, k] + bias[k], N'(i) = i itself,
+    its in-edges' sources and, `both`, its out-edges' targets.  feat, out: [N, 3H] (head k in columns kH..(k+1)H); el, er: [N, 4] (three heads
+    and a pad); bias: float32[3H] or None.  feat, el, er and out may be column blocks of wider tables.  Views of a reversed graph
+    (GraphViews.reversed) exchange the roles of the two lists."""
+    lib = _lib.load()
+    feat, ldf = _rows(feat, "node_attention_sum.feat")
+    el, ld_el = _rows(el, "node_attention_sum.el")
+    er, ld_er = _rows(er, "node_attention_sum.er")
+    n, width = feat.shape
+    heads = 3
+    if n != views.num_nodes:
+        raise ValueError(f"node_attention_sum: feat has {n} rows for {views.num_nodes} nodes")
+    if width % heads or el.shape != (n, 4) or er.shape != (n, 4) or el.device != feat.device or er.device != feat.device:
+        raise ValueError(f"node_attention_sum: feat is [N, 3H], el and er are [N, 4] (three heads and a pad) on feat's device; got "
+                         f"{tuple(feat.shape)}, {tuple(el.shape)}, {tuple(er.shape)}")
+    if out is None:
+        out = torch.empty((n, width), dtype=torch.float32, device=feat.device)
+    out, ldo = _rows(out, "node_attention_sum.out")
+    if out.shape != feat.shape or out.device != feat.device:
+        raise ValueError(f"node_attention_sum: out is {tuple(out.shape)} on {out.device}, feat is {tuple(feat.shape)} on {feat.device}")
+    if bias is not None and (_f32(bias, "node_attention_sum.bias").shape != (width,) or not bias.is_contiguous()):
+        raise ValueError("node_attention_sum: bias is one contiguous float per output column")
+    lists = [(views.in_ptr, views.srt_src), (views.out_ptr, views.out_dst)]
+    if views.transposed:
+        lists.reverse()
+    (ptr_a, idx_a), (ptr_b, idx_b) = lists
+    with _on(feat.device):
+        _lib.check(lib.gnnome_node_attention_sum_f32(_ptr(feat), ldf, _ptr(el), ld_el, _ptr(er), ld_er, width // heads, heads, n, _ptr(ptr_a),
+                                                     _ptr(idx_a), _ptr(ptr_b) if both else None, _ptr(idx_b) if both else None,
+                                                     float(negative_slope), _ptr(bias), _ptr(out), ldo, _stream(feat.device)),
+                   "node_attention_sum_f32")
+    return out
+
+
 def relu_rows(x):
     """x <- relu(x) in place (gnnome_relu_rows_f32; NaN stays NaN); x may be a column block of a wider table."""
     x, ld = _rows(x, "relu_rows.x")

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 26
+#define GNNOME_ABI_VERSION 27
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -286,6 +286,30 @@ int gnnome_node_neighbour_sum_f32(const float* h, int ld_h, int hidden, int64_t 
 /* x[r, 0..hidden) <- relu(x[r, 0..hidden)) in place for r < rows, row stride ld (a multiple of 4; x 16-byte aligned, hidden % 4 == 0):
  * the ReLU between two layers of GCN_processor / SAGE_processor (processor.py:44, :82).  NaN stays NaN. */
 int gnnome_relu_rows_f32(float* x, int ld, int64_t rows, int hidden, void* stream);
+
+/* ---- edge-softmax attention sum: the message passing of GATModel ---------------------------------------
+ * For every node i < num_nodes and head k < heads, over N'(i) = {i} + in(i) (+ out(i) when out_ptr != NULL), parallel edges and loops
+ * as separate items:
+ *   a_{p,k}     = softmax over p in N'(i) of leaky_relu(el[nbr_p,k] + er[i,k], negative_slope)
+ *   out[i,k,:]  = sum_{p in N'(i)} a_{p,k} * feat[nbr_p,k,:] + bias[k,:]
+ * Replaces everything after el / er in DGL's GATConv(hidden, hidden, num_heads=3) of layers/processor.py:49-70 on
+ * g' = dgl.add_self_loop(g) (directed=True) or add_self_loop(add_reverse_edges(g)) (directed=False), models/full_graph.py:78-97.
+ * g' is never built: in(i) = [in_ptr[i], in_ptr[i+1]) of srt_src, out(i) = [out_ptr[i], out_ptr[i+1]) of out_dst (the arrays of
+ * gnnome_build_graph_views), the loop edge is the node's own row and counts once more where the graph already has one.
+ * feat and out are [N, heads*hidden] (head k in columns [k*hidden, (k+1)*hidden)), row-strided (ld_feat, ld_out multiples of 4, 16-byte
+ * aligned), out must not alias feat; el and er are per-node rows of 4 floats - the three heads and a pad - with row strides ld_el,
+ * ld_er (multiples of 4, 16-byte aligned): all of them may be column blocks of one projection table.  bias[heads*hidden] may be NULL.
+ * out_ptr == NULL selects the directed form; srt_src and out_dst may be NULL for a graph without edges.  hidden in {64,128,256},
+ * heads == 3; anything else is GNNOME_EINVAL.
+ * One wave per node, two passes (the per-head maximum over the 16-byte score rows, then exp(s - max), an fp32 numerator and
+ * denominator, one division per (node, head)), no atomics.  The association is fixed and a function of the graph alone (self term,
+ * in-list ascending, out-list ascending; lists above 4096 items in fixed 128-item blocks, numerator and denominator alike -
+ * csrc/node_attention.hip), so two runs leave equal bits.  A NaN in el, er or feat of any member of N'(i) leaves a non-finite out[i,k,:].
+ * A node that sees its loop alone gets out = feat + bias bit for bit.  A hub is walked by its own wave: about three milliseconds per 10^5
+ * neighbours (an estimate). */
+int gnnome_node_attention_sum_f32(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er, int hidden,
+                                  int heads, int64_t num_nodes, const int32_t* in_ptr, const int32_t* srt_src, const int32_t* out_ptr,
+                                  const int32_t* out_dst, float negative_slope, const float* bias, float* out, int ld_out, void* stream);
 
 /* ---- streaming aggregation (round 5) -----------------------------------------------------------------
  * The same node update as gnnome_node_aggregate_f32 with norm_kind = GNNOME_NORM_AFFINE (gated_gcn_full.py:111-114, :124-127,
