@@ -8,46 +8,9 @@ it, and operands far below 1 keep their precision because the second plane is st
 import numpy as np
 import torch
 
+from product_probes import bf16x6, f16x3, split_f16      # the emulators live with the probes that are built on them
+
 K, M, N = 256, 1024, 256
-
-
-def split_f16(a):
-    a1 = a.astype(np.float16)
-    r = ((a - a1.astype(np.float32)) * np.float32(2048)).astype(np.float32)      # exact: a - a1 fits fp32, so does its 2^11-fold
-    return a1.astype(np.float32), r.astype(np.float16).astype(np.float32)
-
-
-def trunc_bf16(a):
-    return (a.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
-
-
-def split_bf16(a):
-    h = trunc_bf16(a)
-    r = (a - h).astype(np.float32)
-    m = trunc_bf16(r)
-    return h, m, (r - m).astype(np.float32)
-
-
-def chain(terms, k=K):
-    """fp32 accumulator over 16-wide k steps; within a step the products are exact and summed before one rounding (a model of one MFMA)."""
-    out = np.zeros((terms[0][0].shape[0], terms[0][1].shape[0]), np.float32)
-    for k0 in range(0, k, 16):
-        for a, b in terms:
-            out = (out.astype(np.float64) + a[:, k0:k0 + 16].astype(np.float64) @ b[:, k0:k0 + 16].astype(np.float64).T).astype(np.float32)
-    return out
-
-
-def f16x3(x, w):
-    x1, x2 = split_f16(x)
-    w1, w2 = split_f16(w)
-    main, corr = chain([(x1, w1)]), chain([(x1, w2), (x2, w1)])
-    return (main + corr * np.float32(1 / 2048)).astype(np.float32)
-
-
-def bf16x6(x, w):
-    xh, xm, xl = split_bf16(x)
-    wh, wm, wl = split_bf16(w)
-    return chain([(xl, wh), (xh, wl), (xm, wm), (xm, wh), (xh, wm), (xh, wh)])
 
 
 def _operands(seed, xs=3.0):
@@ -125,11 +88,6 @@ def test_whole_model_probabilities_with_emulated_products():
     def k128(fn):
         return lambda a, w: fn(np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(w, dtype=np.float32))
 
-    global K
-    old_k, K = K, hidden
-    try:
-        d32, d6, d16 = run(None), run(k128(bf16x6)), run(k128(f16x3))
-    finally:
-        K = old_k
+    d32, d6, d16 = run(None), run(k128(bf16x6)), run(k128(f16x3))      # (the emulators take K from their operands)
     print(f"max |dp| against fp64: fp32 model {d32:.2e}, bf16x6 {d6:.2e}, fp16x3 {d16:.2e}")
     assert d16 <= 2 * max(d32, d6) + 1e-7 and d16 < 1e-5
