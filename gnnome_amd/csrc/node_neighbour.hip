@@ -28,82 +28,9 @@
 // the rest of the chip works on the other nodes.
 //
 // gnnome_relu_rows_f32: the ReLU between two layers of those models (processor.py:44, :82), in place on row-strided rows, NaN kept.
-#include "common.h"
+#include "node_neighbour.h"   // the lane mapping and the association above, shared with node_neighbour_bwd.hip
 
 namespace gnnome {
-
-constexpr int kNbrThreads = 256;
-constexpr int kNbrHubThreshold = 4096;   // items above which a list is summed in two levels
-constexpr int kNbrHubBlock = 128;        // items per first-level block of such a list (a multiple of the 64-item batch)
-constexpr int kNbrInFlight = 4;          // row requests per lane group in flight
-
-template <int H>
-__device__ __forceinline__ float nbr_group_sum(float v) {
-    // all-reduce over the lane groups (lanes with equal lane % (H/4)): node_aggregate_in.hip's in_group_sum
-    constexpr int LPR = H / 4;
-#pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-// acc += sum over items [lo, hi) of one list (idx: the list's first neighbour id; NULL only for an empty list) of sscale[j] * h[j,:],
-// lane group g taking every G-th item of every 64-item batch.  The bounds are wave-uniform (scalar loops).
-template <int H, bool SS>
-__device__ __forceinline__ void accumulate_rows(const float* __restrict__ h, int ldh, const float* __restrict__ sscale,
-                                                const int32_t* __restrict__ idx, int lo, int hi, int lane, int group, int c, f32x4& acc) {
-    constexpr int LPR = H / 4, G = 64 / LPR, U = kNbrInFlight;
-    // the value lane `it` holds: `it` is uniform inside a lane group, so with one group (H = 256) it is a scalar read
-    auto pick = [&](int v, int it) -> int {
-        if (G == 1) return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(it));
-        return __builtin_amdgcn_ds_bpermute(it << 2, v);
-    };
-    for (int base = lo; base < hi; base += 64) {
-        const int j = base + lane;   // lane l owns item base + l
-        int my_n = 0;
-        float my_s = 1.0f;
-        if (j < hi) {
-            my_n = idx[j];
-            if (SS) my_s = sscale[my_n];
-        }
-        const int m = min(64, hi - base);
-        for (int j0 = 0; j0 < m; j0 += G * U) {
-            f32x4 a[U];
-            float s[U];
-            bool live[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int it = j0 + u * G + group;
-                live[u] = it < m;
-                const int sel = live[u] ? it : j0;   // (a dead slot reads item j0, which exists)
-                a[u] = *reinterpret_cast<const f32x4*>(h + (int64_t)pick(my_n, sel) * ldh + c);
-                s[u] = SS ? __int_as_float(pick(__float_as_int(my_s), sel)) : 1.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (live[u]) {
-                    if (SS) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) acc[k] = fmaf(s[u], a[u][k], acc[k]);
-                    } else {
-                        acc += a[u];
-                    }
-                }
-            }
-        }
-    }
-}
-
-// one list of `len` items into the node's accumulators: one block, or fixed 128-item blocks above the hub threshold
-template <int H, bool SS>
-__device__ __forceinline__ void accumulate_list(const float* __restrict__ h, int ldh, const float* __restrict__ sscale,
-                                                const int32_t* __restrict__ idx, int len, int lane, int group, int c, f32x4& acc) {
-    const int blk = len > kNbrHubThreshold ? kNbrHubBlock : len;   // (wave-uniform)
-    for (int blo = 0; blo < len; blo += blk) {
-        f32x4 part = {0.f, 0.f, 0.f, 0.f};
-        accumulate_rows<H, SS>(h, ldh, sscale, idx, blo, min(len, blo + blk), lane, group, c, part);
-        acc += part;
-    }
-}
 
 template <int H, bool SS>
 __global__ __launch_bounds__(kNbrThreads) void k_node_neighbour_sum(const float* __restrict__ h, int ldh, int64_t num_nodes,
@@ -118,21 +45,7 @@ __global__ __launch_bounds__(kNbrThreads) void k_node_neighbour_sum(const float*
     if (node >= num_nodes) return;
     const int group = lane / LPR, c = (lane % LPR) * 4;
 
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (group == 0) {   // the loop edge of g': the node's own row
-        acc = *reinterpret_cast<const f32x4*>(h + node * ldh + c);
-        if (SS) acc *= sscale[node];
-    }
-    const int ib = in_ptr[node], din = in_ptr[node + 1] - ib;
-    accumulate_list<H, SS>(h, ldh, sscale, srt_src + ib, din, lane, group, c, acc);
-    if (out_ptr != nullptr) {   // directed=False: the reverse copies of the node's out-edges
-        const int ob = out_ptr[node], dout = out_ptr[node + 1] - ob;
-        accumulate_list<H, SS>(h, ldh, sscale, out_dst + ob, dout, lane, group, c, acc);
-    }
-
-    f32x4 v;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = nbr_group_sum<H>(acc[k]);
+    f32x4 v = nbr_node_sum<H, SS>(h, ldh, sscale, node, in_ptr, srt_src, out_ptr, out_dst, lane, group, c);
     if (dscale != nullptr) v *= dscale[node];
     if (group == 0) *reinterpret_cast<f32x4*>(out + node * ldo + c) = v;
 }

@@ -10,6 +10,7 @@
 //     h_new  = torch.ops.gnnome_hip.node_aggregate(e_new, A1h, A2h, A3h, in_ptr, srt_src, out_ptr, out_pos, out_dst, h, scale, shift, norm_kind)
 //     h_new  = torch.ops.gnnome_hip.node_aggregate_in(e_new, A1h, A2h, in_ptr, srt_src, h, scale, shift, norm_kind)   # GatedGCN, :212-225
 //     agg    = torch.ops.gnnome_hip.node_neighbour_sum(h, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale)   # GCNModel / SAGEModel, full_graph.py:65-75, :109-119
+//     dh     = torch.ops.gnnome_hip.node_neighbour_sum_bwd(g, out_ptr, out_dst, in_ptr, srt_src, rscale, oscale, add, mult, y)   # its gradient w.r.t. h + the step's epilogue
 //     agg    = torch.ops.gnnome_hip.node_attention_sum(feat, el, er, in_ptr, srt_src, out_ptr, out_dst, bias, negative_slope)   # GATModel, full_graph.py:78-97
 //     logits = torch.ops.gnnome_hip.edge_score(e, Ps, Qd, srt_src, srt_dst, srt_eid, W1e, W2, b2, W3, b3)   # score_predictor.py:12-24
 //
@@ -229,6 +230,42 @@ Tensor node_neighbour_sum(const Tensor& h, const Tensor& in_ptr, const Tensor& s
     return out;
 }
 
+// ---- the neighbour sum's gradient with the training step's epilogue (gnnome_node_neighbour_sum_bwd_f32; the backward of processor.py:35-46, :73-84)
+// in_ptr and srt_src given: the doubled graph of directed=False; rscale / oscale absent: 1; add, mult, y absent: that epilogue step is skipped
+Tensor node_neighbour_sum_bwd(const Tensor& g, const Tensor& out_ptr, const Tensor& out_dst, const OptTensor& in_ptr, const OptTensor& srt_src,
+                              const OptTensor& rscale, const OptTensor& oscale, const OptTensor& add, const OptTensor& mult, const OptTensor& y) {
+    const int ldg = rows_ld(g, "node_neighbour_sum_bwd.g");
+    const int64_t N = g.size(0), H = g.size(1);
+    const bool both = in_ptr.has_value() && in_ptr->defined();
+    TORCH_CHECK(both == (srt_src.has_value() && srt_src->defined()), "node_neighbour_sum_bwd: in_ptr and srt_src come together");
+    auto given = [](const OptTensor& t) { return t.has_value() && t->defined(); };
+    TORCH_CHECK(out_ptr.numel() == N + 1 && (!both || (in_ptr->numel() == N + 1 && srt_src->numel() == out_dst.numel())) &&
+                    (!given(rscale) || rscale->numel() == N) && (!given(oscale) || oscale->numel() == N),
+                "node_neighbour_sum_bwd: shapes g[N,H] out_ptr[N+1] out_dst[E] in_ptr[N+1] srt_src[E] rscale,oscale[N]");
+    int ld[3] = {0, 0, 0};
+    const float* ptr[3] = {nullptr, nullptr, nullptr};
+    const OptTensor* tables[3] = {&add, &mult, &y};
+    const char* names[3] = {"node_neighbour_sum_bwd.add", "node_neighbour_sum_bwd.mult", "node_neighbour_sum_bwd.y"};
+    for (int k = 0; k < 3; ++k) {
+        if (!given(*tables[k])) continue;
+        const Tensor& t = **tables[k];
+        ld[k] = rows_ld(t, names[k]);
+        TORCH_CHECK(t.size(0) == N && t.size(1) == H, names[k], ": expected g's shape");
+        ptr[k] = N ? f32(t, names[k]) : nullptr;
+    }
+    Guard guard(g.device());
+    Tensor out = at::empty({N, H}, g.options());
+    ok(gnnome_node_neighbour_sum_bwd_f32(f32(g, "node_neighbour_sum_bwd.g"), ldg, (int)H, N, i32(out_ptr, "node_neighbour_sum_bwd.out_ptr"),
+                                         out_dst.numel() ? i32(out_dst, "node_neighbour_sum_bwd.out_dst") : nullptr,
+                                         both ? i32(*in_ptr, "node_neighbour_sum_bwd.in_ptr") : nullptr,
+                                         both && srt_src->numel() ? i32(*srt_src, "node_neighbour_sum_bwd.srt_src") : nullptr, both ? 1 : 0,
+                                         f32_opt(rscale, "node_neighbour_sum_bwd.rscale"), f32_opt(oscale, "node_neighbour_sum_bwd.oscale"),
+                                         ptr[0], ld[0], ptr[1], ld[1], ptr[2], ld[2], N ? out.data_ptr<float>() : nullptr,
+                                         (int)std::max<int64_t>(H, 1), stream_of(g)),
+       "gnnome_node_neighbour_sum_bwd_f32");
+    return out;
+}
+
 // ---- the edge-softmax attention sum of GATModel (gnnome_node_attention_sum_f32; full_graph.py:78-97, processor.py:49-70) -----------------------
 // feat [N,3H], el / er [N,4] (three heads and a pad), all row-strided; out_ptr and out_dst given: the doubled graph of directed=False
 Tensor node_attention_sum(const Tensor& feat, const Tensor& el, const Tensor& er, const Tensor& in_ptr, const Tensor& srt_src,
@@ -300,6 +337,10 @@ Tensor node_aggregate_in_meta(const Tensor&, const Tensor&, const Tensor&, const
 Tensor node_neighbour_sum_meta(const Tensor& h, const Tensor&, const Tensor&, const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&) {
     return at::empty({h.size(0), h.size(1)}, h.options());
 }
+Tensor node_neighbour_sum_bwd_meta(const Tensor& g, const Tensor&, const Tensor&, const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&,
+                                   const OptTensor&, const OptTensor&, const OptTensor&) {
+    return at::empty({g.size(0), g.size(1)}, g.options());
+}
 Tensor node_attention_sum_meta(const Tensor& feat, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const OptTensor&, const OptTensor&,
                                const OptTensor&, double) {
     return at::empty({feat.size(0), feat.size(1)}, feat.options());
@@ -323,6 +364,8 @@ TORCH_LIBRARY(gnnome_hip, m) {
           "int norm_kind=0) -> Tensor");
     m.def("node_neighbour_sum(Tensor h, Tensor in_ptr, Tensor srt_src, Tensor? out_ptr=None, Tensor? out_dst=None, Tensor? sscale=None, "
           "Tensor? dscale=None) -> Tensor");
+    m.def("node_neighbour_sum_bwd(Tensor g, Tensor out_ptr, Tensor out_dst, Tensor? in_ptr=None, Tensor? srt_src=None, Tensor? rscale=None, "
+          "Tensor? oscale=None, Tensor? add=None, Tensor? mult=None, Tensor? y=None) -> Tensor");
     m.def("node_attention_sum(Tensor feat, Tensor el, Tensor er, Tensor in_ptr, Tensor srt_src, Tensor? out_ptr=None, Tensor? out_dst=None, "
           "Tensor? bias=None, float negative_slope=0.2) -> Tensor");
     m.def("edge_score(Tensor e, Tensor Ps, Tensor Qd, Tensor srt_src, Tensor srt_dst, Tensor srt_eid, Tensor W1e, Tensor W2, Tensor b2, Tensor W3, "
@@ -339,6 +382,7 @@ TORCH_LIBRARY_IMPL(gnnome_hip, CUDA, m) {   // the CUDA dispatch key is the HIP 
     m.impl("node_aggregate", &node_aggregate);
     m.impl("node_aggregate_in", &node_aggregate_in);
     m.impl("node_neighbour_sum", &node_neighbour_sum);
+    m.impl("node_neighbour_sum_bwd", &node_neighbour_sum_bwd);
     m.impl("node_attention_sum", &node_attention_sum);
     m.impl("edge_score", &edge_score);
 }
@@ -352,6 +396,7 @@ TORCH_LIBRARY_IMPL(gnnome_hip, Meta, m) {
     m.impl("node_aggregate", &node_aggregate_meta);
     m.impl("node_aggregate_in", &node_aggregate_in_meta);
     m.impl("node_neighbour_sum", &node_neighbour_sum_meta);
+    m.impl("node_neighbour_sum_bwd", &node_neighbour_sum_bwd_meta);
     m.impl("node_attention_sum", &node_attention_sum_meta);
     m.impl("edge_score", &edge_score_meta);
 }

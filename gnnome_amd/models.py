@@ -116,8 +116,10 @@ class GCNModel(_BaselineModel):
     The convolutions run on g' = add_self_loop(g), or add_self_loop(add_reverse_edges(g)) with directed=False, which is never built:
     the degree-normalised neighbour sum is the kernel gnnome_node_neighbour_sum_f32 over the graph's own in- and out-lists.  The encoded
     e goes unchanged to the scorer, which scores the original graph.  `normalization` is accepted and unused, as in the reference.
-    Built widths only: hidden_features in {64, 128, 256}, hidden_edge_scores in {32, 64, 128}.  Eval mode only: a call in train mode
-    raises NotImplementedError."""
+    Built widths only: hidden_features in {64, 128, 256}, hidden_edge_scores in {32, 64, 128}.  The call serves eval mode only: in train
+    mode it raises NotImplementedError.  The training step is the explicit entry engine_baselines.train_forward(model, graph, x, e)
+    (logits with autograd history to the parameters; its backward runs on gnnome_node_neighbour_sum_bwd_f32), which
+    trainer.train(model_class=GCNModel) calls."""
     kind = "gcn"
 
     def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, num_layers, hidden_edge_scores,
@@ -135,7 +137,9 @@ class SAGEModel(_BaselineModel):
     GCNModel.
 
     One divergence: the reference's default dropout=None reaches nn.Dropout(None) and fails at construction; here None means 0.0.
-    (feat_drop is the identity in eval mode, which is all that is served.)"""
+    feat_drop is the identity in eval mode; the training step (engine_baselines.train_forward, as for GCNModel - the call itself refuses
+    train mode) draws one scaled keep-mask per layer through train.dropout_mask and applies it to the layer's input before both the self
+    and the neighbour path, as DGL's SAGEConv does."""
     kind = "sage"
 
     def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, num_layers, hidden_edge_scores,
@@ -150,7 +154,8 @@ class GATModel(_BaselineModel):
     GAT_processor (layers/processor.py:49-70: DGL's GATConv with 3 heads, nn.Linear(3H, H) on the concatenated heads, a ReLU between
     layers), ScorePredictor.  Same constructor and state_dict keys (`gnn.convs.N.{attn_l, attn_r, bias, fc.weight}`,
     `gnn.linears.N.{weight, bias}`, the encoders' and the predictor's as for GCNModel), same call; g', the scorer, `normalization`, the
-    built widths and eval mode as for GCNModel.
+    built widths and eval mode as for GCNModel.  Train mode is not built for this model: the call raises, and
+    engine_baselines.train_forward refuses it (the edge softmax's backward is another kernel).
 
     Per layer (gnnome_amd/engine_gat.py): ONE projection on [fc.weight ; attn_l fc ; attn_r fc] gives feat, el and er as column blocks of
     a [N, 3H + 64] table, the edge softmax and the weighted sum are the kernel gnnome_node_attention_sum_f32 over the graph's own in- and

@@ -781,6 +781,58 @@ def relu_rows(x):
     return x
 
 
+def node_neighbour_sum_bwd(g, views, rscale=None, oscale=None, both=False, add=None, y=None, mult=None, out=None):
+    """The gradient of node_neighbour_sum with respect to h, with the training step's element-wise work folded into the store
+    (gnnome_node_neighbour_sum_bwd_f32):
+    s[j] = rscale[j] g[j] + sum over the out-edges of j of rscale[dst] g[dst] + [both] sum over its in-edges of rscale[src] g[src], then
+    v = oscale[j] * s;  v = add[j] + v;  v = v * mult[j];  out[j] = v where y[j] > 0, else 0 - each step skipped where its operand is None,
+    each one fp32 rounding of its own.  rscale is the forward's dscale, oscale its sscale: float32[N] or None (= 1).  g, add, y, mult and
+    out are [N,H] and may be column blocks of wider tables.  Views of a reversed graph exchange the roles of the two lists.  With oscale
+    alone the bits are node_neighbour_sum(g, views.reversed(), sscale=rscale, dscale=oscale, both=both)'s."""
+    lib = _lib.load()
+    g, ldg = _rows(g, "node_neighbour_sum_bwd.g")
+    n, hidden = g.shape
+    if n != views.num_nodes:
+        raise ValueError(f"node_neighbour_sum_bwd: g has {n} rows for {views.num_nodes} nodes")
+    if out is None:
+        out = torch.empty((n, hidden), dtype=torch.float32, device=g.device)
+    tables = {"out": out, "add": add, "mult": mult, "y": y}
+    lds = {}
+    for name, t in tables.items():
+        if t is None:
+            lds[name] = 0
+            continue
+        t, lds[name] = _rows(t, "node_neighbour_sum_bwd." + name)
+        if t.shape != g.shape or t.device != g.device:
+            raise ValueError(f"node_neighbour_sum_bwd: {name} is {tuple(t.shape)} on {t.device}, g is {tuple(g.shape)} on {g.device}")
+    for name, t in (("rscale", rscale), ("oscale", oscale)):
+        if t is not None and (_f32(t, "node_neighbour_sum_bwd." + name).shape != (n,) or not t.is_contiguous()):
+            raise ValueError(f"node_neighbour_sum_bwd: {name} is one contiguous float per node")
+    lists = [(views.out_ptr, views.out_dst), (views.in_ptr, views.srt_src)]
+    if views.transposed:
+        lists.reverse()
+    (ptr_a, idx_a), (ptr_b, idx_b) = lists
+    with _on(g.device):
+        _lib.check(lib.gnnome_node_neighbour_sum_bwd_f32(_ptr(g), ldg, hidden, n, _ptr(ptr_a), _ptr(idx_a), _ptr(ptr_b) if both else None,
+                                                         _ptr(idx_b) if both else None, 1 if both else 0, _ptr(rscale), _ptr(oscale),
+                                                         _ptr(add), lds["add"], _ptr(mult), lds["mult"], _ptr(y), lds["y"], _ptr(out),
+                                                         lds["out"], _stream(g.device)), "node_neighbour_sum_bwd_f32")
+    return out
+
+
+def relu_mul_rows(x, mult, relu=True):
+    """x <- relu(x) * mult in place (gnnome_relu_mul_rows_f32; NaN stays NaN), relu=False: x <- x * mult.  x and mult may be column blocks of
+    wider tables.  mult=None is refused: relu_rows is the ReLU alone."""
+    x, ld = _rows(x, "relu_mul_rows.x")
+    if mult is None:
+        raise ValueError("relu_mul_rows: mult is None - relu_rows is the ReLU alone")
+    mult, ldm = _rows(mult, "relu_mul_rows.mult")
+    if mult.shape != x.shape or mult.device != x.device:
+        raise ValueError(f"relu_mul_rows: mult is {tuple(mult.shape)} on {mult.device}, x is {tuple(x.shape)} on {x.device}")
+    _call("gnnome_relu_mul_rows_f32", x.device, _ptr(x), ld, _ptr(mult), ldm, x.shape[0], x.shape[1], 1 if relu else 0)
+    return x
+
+
 def edge_score(e, Ps, Qd, views, W1e, W2, b2, W3, b3, logits, num_edges=None, scatter_to_edge_id=True, z1_out=None):
     lib = _lib.load()
     e, _ = _rows(e, "edge_score.e")

@@ -226,6 +226,24 @@ def _no_bf16_storage():
                       "normalization='layer' and the recomputed gate take \"fp32\"")
 
 
+def encoder_bwd(ops, g, dout, inp, gather, rows, l1, l2, pfx1, pfx2):
+    """The gradients of one two-layer encoder (models/full_graph.py:26-27; l1, l2: its nn.Linear modules) into g[pfx1 / pfx2 + ".weight" /
+    ".bias"], from dout = the gradient of its output rows; the hidden rows are recomputed (ops.encode_hidden), not kept.  Shared with the
+    training step of GCNModel / SAGEModel (engine_baselines.py)."""
+    d = lambda t: t.detach().contiguous()  # noqa: E731
+    W1e_, b1e_, W2e_ = d(l1.weight), d(l1.bias), d(l2.weight)
+    t = ops.encode_hidden(inp, W1e_, b1e_, gather=gather, rows=rows)
+    g[pfx2 + ".weight"] = ops.wgrad(dout, t)
+    g[pfx2 + ".bias"] = ops.colsum2(dout)[0]
+    dt = ops.relu_bwd(ops.linear(dout, W2e_.t().contiguous(), None), t)
+    F_ = inp.shape[1]
+    src = inp if gather is None else inp[gather.long()]
+    x4 = torch.zeros((rows, 4 * ((F_ + 3) // 4)), dtype=torch.float32, device=inp.device)
+    x4[:, :F_] = src
+    g[pfx1 + ".weight"] = ops.wgrad(dt, x4)[:, :F_].contiguous()
+    g[pfx1 + ".bias"] = ops.colsum2(dt)[0] if dt.shape[1] in (16, 32, 64) else dt.sum(0)
+
+
 class _TrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, sh, x, e_raw, names, *params):
@@ -501,21 +519,8 @@ class _TrainStep(torch.autograd.Function):
             saved[li] = s = None    # this layer's activations are done with: their memory serves the next layer's temporaries
 
         # ---- encoders (models/full_graph.py:26-27)
-        def encoder_bwd(dout, inp, gather, rows, l1, l2, pfx1, pfx2):
-            W1e_, b1e_, W2e_ = d(l1.weight), d(l1.bias), d(l2.weight)
-            t = ops.encode_hidden(inp, W1e_, b1e_, gather=gather, rows=rows)
-            g[pfx2 + ".weight"] = ops.wgrad(dout, t)
-            g[pfx2 + ".bias"] = ops.colsum2(dout)[0]
-            dt = ops.relu_bwd(ops.linear(dout, W2e_.t().contiguous(), None), t)
-            F_ = inp.shape[1]
-            src = inp if gather is None else inp[gather.long()]
-            x4 = torch.zeros((rows, 4 * ((F_ + 3) // 4)), dtype=torch.float32, device=inp.device)
-            x4[:, :F_] = src
-            g[pfx1 + ".weight"] = ops.wgrad(dt, x4)[:, :F_].contiguous()
-            g[pfx1 + ".bias"] = ops.colsum2(dt)[0] if dt.shape[1] in (16, 32, 64) else dt.sum(0)
-
-        encoder_bwd(dh, tail["x"], getattr(views, "node_gather", None), n_local, model.linear1_node, model.linear2_node, "linear1_node", "linear2_node")
-        encoder_bwd(de, tail["e_raw"], views.srt_eid, e_local, model.linear1_edge, model.linear2_edge, "linear1_edge", "linear2_edge")
+        encoder_bwd(ops, g, dh, tail["x"], getattr(views, "node_gather", None), n_local, model.linear1_node, model.linear2_node, "linear1_node", "linear2_node")
+        encoder_bwd(ops, g, de, tail["e_raw"], views.srt_eid, e_local, model.linear1_edge, model.linear2_edge, "linear1_edge", "linear2_edge")
 
         ctx.saved = ctx.tail = None
         grads = sh.sum_ranks([g[n].contiguous() for n in ctx.names])

@@ -280,6 +280,15 @@ def _edge_src_dst(views):
     return src, dst
 
 
+def _model_step(model, views, x, e):
+    """`model(views, x, e)` - except for GCNModel / SAGEModel in train mode, whose call refuses train mode and whose training step is the
+    explicit entry engine_baselines.train_forward."""
+    if model.training and getattr(model, "kind", None) in ("gcn", "sage"):
+        from . import engine_baselines
+        return engine_baselines.train_forward(model, views, x, e)
+    return model(views, x, e)
+
+
 def _run_epoch_phase(model, optimizer, graphs, hp, pos_weight, device, training, trace, epoch):
     phase = "train" if training else "valid"
     logs, skipped, first_grads = [], 0, trace is not None and training and not any(t.get("grads") is not None for t in trace)
@@ -292,8 +301,8 @@ def _run_epoch_phase(model, optimizer, graphs, hp, pos_weight, device, training,
         skipped += skip
         log = torch.zeros((len(steps), 5), dtype=torch.float64, device=device)
         for i, (views, ci) in enumerate(steps):
-            org = model(views, ci.x, ci.e).squeeze(-1)
-            rev = model(views.reversed(), ci.x_rev, ci.e).squeeze(-1) if hp["use_symmetry_loss"] else None
+            org = _model_step(model, views, ci.x, ci.e).squeeze(-1)
+            rev = _model_step(model, views.reversed(), ci.x_rev, ci.e).squeeze(-1) if hp["use_symmetry_loss"] else None
             loss = _LossAndCounts.apply(org, rev, ci.y, pos_weight, alpha, log[i])
             if training:
                 optimizer.zero_grad()
@@ -331,8 +340,8 @@ def train(train_set, valid_set, out=None, hyperparameters=None, overfit=False, d
     """train.py:188-450 (see the module docstring) -> the list of epoch records.  `hyperparameters`: overrides of
     configs/hyperparameters.py by the reference's key names.  `trace` (for tests): a list that receives the initial state dict and
     one dict per step (graph, mask fraction, the step's full-graph node and edge ids, its edges, loss and counts; the first training
-    step's gradients) - it copies to the host per step.  `model_class`: the model to train, SymGatedGCNModel or GatedGCNModel (same
-    constructor arguments)."""
+    step's gradients) - it copies to the host per step.  `model_class`: the model to train, SymGatedGCNModel, GatedGCNModel, GCNModel or
+    SAGEModel (same constructor arguments)."""
     hp = hyperparameters_with(hyperparameters)
     seed = hp["seed"] if seed is None else seed
     dropout = hp["dropout"] if dropout is None else dropout

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 27
+#define GNNOME_ABI_VERSION 28
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -286,6 +286,35 @@ int gnnome_node_neighbour_sum_f32(const float* h, int ld_h, int hidden, int64_t 
 /* x[r, 0..hidden) <- relu(x[r, 0..hidden)) in place for r < rows, row stride ld (a multiple of 4; x 16-byte aligned, hidden % 4 == 0):
  * the ReLU between two layers of GCN_processor / SAGE_processor (processor.py:44, :82).  NaN stays NaN. */
 int gnnome_relu_rows_f32(float* x, int ld, int64_t rows, int hidden, void* stream);
+
+/* ---- the neighbour sum's gradient with respect to h, with the training step's element-wise epilogue ------
+ * For every node j < num_nodes:
+ *   s     = rscale[j] * g[j,:] + sum_{q in out(j)} rscale[out_dst[q]] * g[out_dst[q],:]
+ *                              + sum_{p in in(j)} rscale[srt_src[p]] * g[srt_src[p],:]                       (last sum: both != 0 only)
+ *   v     = oscale[j] * s ;  v = add[j,:] + v ;  v = v * mult[j,:] ;  out[j,:] = y[j,:] > 0 ? v : 0
+ * each of the four steps skipped where its operand is NULL, each one fp32 rounding of its own (never contracted into an fma), so the
+ * result equals the four element-wise passes bit for bit.  Replaces what torch autograd runs in the reference's training loop
+ * (train.py:328-330) for DGL's GraphConv(norm='both') and SAGEConv('mean') on g' under layers/processor.py:35-46 and :73-84 - the
+ * transposed message passing, then the backward of SAGEConv's feat_drop and of the ReLU of :44 / :82:
+ *   GCN   g = dA, rscale = din'^-1/2, oscale = dout'^-1/2, y = the layer's post-ReLU input (NULL at layer 0)
+ *   SAGE  g = dT[:, H:], rscale = 1/din', add = dT[:, :H], mult = the layer's scaled keep-mask, y = its stored input h_d (NULL at layer 0)
+ * rscale is gnnome_node_neighbour_sum_f32's dscale, oscale its sscale; out(j) = [out_ptr[j], out_ptr[j+1]) of out_dst, in(j) =
+ * [in_ptr[j], in_ptr[j+1]) of srt_src; in_ptr is read with `both` only, out_dst and srt_src may be NULL for a graph without edges.
+ * g, add, mult, y and out are row-strided [N,hidden] tables, each with its own row stride (>= hidden, a multiple of 4) and 16-byte
+ * aligned - column blocks of wider tables; out must not alias g or add.  hidden in {64,128,256}; num_nodes == 0 returns at once.
+ * One wave per node, no atomics, the forward kernel's lane mapping and association (self term, out-list ascending, in-list ascending;
+ * lists above 4096 items in fixed 128-item blocks - csrc/node_neighbour.h): with oscale alone the bits are those of
+ * gnnome_node_neighbour_sum_f32 on the reversed graph with sscale = rscale, dscale = oscale, and two runs leave equal bits. */
+int gnnome_node_neighbour_sum_bwd_f32(const float* g, int ld_g, int hidden, int64_t num_nodes, const int32_t* out_ptr, const int32_t* out_dst,
+                                      const int32_t* in_ptr, const int32_t* srt_src, int both, const float* rscale, const float* oscale,
+                                      const float* add, int ld_add, const float* mult, int ld_mult, const float* y, int ld_y, float* out,
+                                      int ld_out, void* stream);
+
+/* x[r, 0..hidden) <- relu(x[r, 0..hidden)) * mult[r, 0..hidden) in place for r < rows (relu == 0: x <- x * mult, the encoder's output
+ * has no ReLU): SAGEConv's feat_drop (processor.py:77) on a layer's input, applied where the ReLU of :82 touches the row.  mult is the
+ * scaled keep-mask, 0 or 1/(1-p); NULL is GNNOME_EINVAL (gnnome_relu_rows_f32 is the ReLU alone).  Row strides ld, ld_mult multiples of
+ * 4, both tables 16-byte aligned and distinct, hidden % 4 == 0.  NaN stays NaN. */
+int gnnome_relu_mul_rows_f32(float* x, int ld, const float* mult, int ld_mult, int64_t rows, int hidden, int relu, void* stream);
 
 /* ---- edge-softmax attention sum: the message passing of GATModel ---------------------------------------
  * For every node i < num_nodes and head k < heads, over N'(i) = {i} + in(i) (+ out(i) when out_ptr != NULL), parallel edges and loops
