@@ -44,6 +44,9 @@ SIGNATURES = {
     "gnnome_node_neighbour_sum_bwd_f32": [_p, _i, _i, _l, _p, _p, _p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p],
     "gnnome_relu_mul_rows_f32": [_p, _i, _p, _i, _l, _i, _i, _p],
     "gnnome_node_attention_sum_f32": [_p, _i, _p, _i, _p, _i, _i, _i, _l, _p, _p, _p, _p, ctypes.c_float, _p, _p, _i, _p],
+    "gnnome_node_attention_sum_stats_f32": [_p, _i, _p, _i, _p, _i, _i, _i, _l, _p, _p, _p, _p, ctypes.c_float, _p, _p, _i, _p, _i, _p],
+    "gnnome_node_attention_sum_bwd_f32": [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _i, _i, _i, _l, _p, _p, _p, _p, _i, ctypes.c_float,
+                                          _p, _i, _p, _i, _p, _i, _p, _p],
     "gnnome_stream_schedule_sizes": [_l, _l, _i, ctypes.POINTER(_l), ctypes.POINTER(_sz)],
     "gnnome_build_stream_schedule": [_l, _l, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p],
     "gnnome_node_aggregate_stream_f32": [_p, _i, _l, _l, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p,
@@ -147,7 +150,7 @@ SIGNATURES = {
     "gnnome_pr_curve_ap": [_p, _p, _l, _p, _p, _sz, _p],
 }
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 # the parameter blocks of gnnome_model_forward_f32 (include/gnnome_hip.h), field for field

@@ -38,31 +38,13 @@
 // HUBS: a node's single wave walks its whole lists twice - no second launch, no scratch, no hub list.  About three milliseconds per 10^5
 // neighbours (an ESTIMATE: three times node_neighbour.hip's per-wave row estimate for the three-heads-wide rows, not a measurement),
 // during which the rest of the chip works on the other nodes.
-#include "common.h"
+//
+// gnnome_node_attention_sum_stats_f32 is the TRAINING FORM: the same kernel template with two more arguments (k_node_attention_sum<H,
+// float*, int>) also leaves, per node, the row m0 m1 m2 0 | 1/den0 1/den1 1/den2 0 that the backward (node_attention_bwd.hip)
+// recomputes every weight from.  The plain entry's kernels k_node_attention_sum<H> keep their arguments and their code.
+#include "node_attention.h"   // the constants and the score, shared with node_attention_bwd.hip
 
 namespace gnnome {
-
-constexpr int kAttThreads = 256;
-constexpr int kAttHeads = 3;
-constexpr int kAttHubThreshold = 4096;   // items above which a list is summed in two levels
-constexpr int kAttHubBlock = 128;        // items per first-level block of such a list (a multiple of the 64-item batch)
-constexpr int kAttInFlight = 4;          // rows (three 16-byte requests each) per lane group in flight
-constexpr float kLog2e = 1.4426950408889634f;
-
-struct AttScores {   // per head
-    float v[kAttHeads];
-};
-
-// leaky_relu(el + er) per head; a NaN stays a NaN (NaN > 0 is false, slope * NaN is NaN)
-__device__ __forceinline__ AttScores att_scores(const f32x4 el, const AttScores& er, float slope) {
-    AttScores s;
-#pragma unroll
-    for (int k = 0; k < kAttHeads; ++k) {
-        const float x = el[k] + er.v[k];
-        s.v[k] = x > 0.f ? x : slope * x;
-    }
-    return s;
-}
 
 // pass one: m <- max(m, scores of the list's items), lane l taking item l of every 64-item batch
 __device__ __forceinline__ void att_list_max(const float* __restrict__ el, int ld_el, const int32_t* __restrict__ idx, int len, int lane,
@@ -152,13 +134,24 @@ __device__ __forceinline__ void att_accumulate_list(const float* __restrict__ fe
     }
 }
 
-template <int H>
+// the statistics row of a node, m0 m1 m2 0 | 1/den0 1/den1 1/den2 0: stored by the training form, which hands in (stats, ld_stats) ...
+__device__ __forceinline__ void att_store_stats(int64_t node, const AttScores& m, const AttScores& inv, float* __restrict__ stats, int ld_stats) {
+    *reinterpret_cast<f32x4*>(stats + node * ld_stats) = f32x4{m.v[0], m.v[1], m.v[2], 0.f};
+    *reinterpret_cast<f32x4*>(stats + node * ld_stats + 4) = f32x4{inv.v[0], inv.v[1], inv.v[2], 0.f};
+}
+__device__ __forceinline__ void att_store_stats(int64_t, const AttScores&, const AttScores&) {}   // ... and not by the plain form, which has none
+
+// One kernel template for both entries.  Stats... is EMPTY for gnnome_node_attention_sum_f32 - the kernel then has the arguments and the
+// code it always had - and (float* stats, int ld_stats) for the training form gnnome_node_attention_sum_stats_f32, whose lane 0 also
+// leaves the very maximum and reciprocal that made `out`: out has the bits of the plain form.
+template <int H, typename... Stats>
 __global__ __launch_bounds__(kAttThreads) void k_node_attention_sum(const float* __restrict__ feat, int ldf, const float* __restrict__ el,
                                                                     int ld_el, const float* __restrict__ er_rows, int ld_er, int64_t num_nodes,
                                                                     const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ srt_src,
                                                                     const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_dst,
                                                                     float slope, const float* __restrict__ bias, float* __restrict__ out, int ldo,
-                                                                    int total_blocks) {
+                                                                    int total_blocks, Stats... stats) {
+    constexpr bool STATS = sizeof...(Stats) != 0;
     constexpr int LPR = H / 4;
     // the wave index read as a scalar: the node and everything loaded through it (the list bounds, its own score rows) live in scalar registers
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -210,6 +203,7 @@ __global__ __launch_bounds__(kAttThreads) void k_node_attention_sum(const float*
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
         const float inv = 1.0f / d;   // the one division per (node, head)
+        if (STATS) den.v[k] = inv;
         f32x4 v;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -225,26 +219,31 @@ __global__ __launch_bounds__(kAttThreads) void k_node_attention_sum(const float*
         }
         if (group == 0) *reinterpret_cast<f32x4*>(out + node * ldo + k * H + c) = v;
     }
+    if (STATS && lane == 0) att_store_stats(node, m, den, stats...);   // (den holds the reciprocals by now)
 }
 
 template <int H>
 static int launch_attention_sum(const float* feat, int ldf, const float* el, int ld_el, const float* er, int ld_er, int64_t n,
                                 const int32_t* in_ptr, const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_dst, float slope,
-                                const float* bias, float* out, int ldo, hipStream_t s) {
+                                const float* bias, float* out, int ldo, float* stats, int ld_stats, hipStream_t s) {
     const int64_t blocks = (n + (kAttThreads / 64) - 1) / (kAttThreads / 64);
     GN_REQUIRE(blocks < (1ll << 31), "node_attention_sum: too many nodes");
-    hipLaunchKernelGGL((k_node_attention_sum<H>), dim3((unsigned)blocks), dim3(kAttThreads), 0, s, feat, ldf, el, ld_el, er, ld_er, n, in_ptr,
-                       srt_src, out_ptr, out_dst, slope, bias, out, ldo, (int)blocks);
+    if (stats == nullptr)
+        hipLaunchKernelGGL((k_node_attention_sum<H>), dim3((unsigned)blocks), dim3(kAttThreads), 0, s, feat, ldf, el, ld_el, er, ld_er, n, in_ptr,
+                           srt_src, out_ptr, out_dst, slope, bias, out, ldo, (int)blocks);
+    else
+        hipLaunchKernelGGL((k_node_attention_sum<H, float*, int>), dim3((unsigned)blocks), dim3(kAttThreads), 0, s, feat, ldf, el, ld_el, er, ld_er, n,
+                           in_ptr, srt_src, out_ptr, out_dst, slope, bias, out, ldo, (int)blocks, stats, ld_stats);
     GN_LAUNCH_CHECK();
     return GNNOME_OK;
 }
 
 }  // namespace gnnome
 
-extern "C" int gnnome_node_attention_sum_f32(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er, int hidden,
-                                             int heads, int64_t num_nodes, const int32_t* in_ptr, const int32_t* srt_src,
-                                             const int32_t* out_ptr, const int32_t* out_dst, float negative_slope, const float* bias, float* out,
-                                             int ld_out, void* stream) {
+static int attention_sum_checked(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er, int hidden, int heads,
+                                 int64_t num_nodes, const int32_t* in_ptr, const int32_t* srt_src, const int32_t* out_ptr,
+                                 const int32_t* out_dst, float negative_slope, const float* bias, float* out, int ld_out, bool want_stats,
+                                 float* stats, int ld_stats, void* stream) {
     using namespace gnnome;
     GN_REQUIRE(num_nodes >= 0, "node_attention_sum: negative node count");
     GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "node_attention_sum: hidden=%d not in {64,128,256}", hidden);
@@ -259,16 +258,38 @@ extern "C" int gnnome_node_attention_sum_f32(const float* feat, int ld_feat, con
                    ((uintptr_t)bias % 16 == 0),
                "node_attention_sum: feat, el, er, bias and out must be 16-byte aligned");
     GN_REQUIRE(out != feat, "node_attention_sum: out must not alias feat");
+    if (want_stats) {
+        GN_REQUIRE(stats != nullptr && ld_stats >= kAttStatsRow && ld_stats % 4 == 0 && (uintptr_t)stats % 16 == 0,
+                   "node_attention_sum_stats: stats holds rows of 8 floats, 16-byte aligned, row stride a multiple of 4");
+        GN_REQUIRE(stats != out && (const float*)stats != feat && (const float*)stats != el && (const float*)stats != er,
+                   "node_attention_sum_stats: stats must not alias feat, el, er or out");
+    }
     hipStream_t s = (hipStream_t)stream;
     switch (hidden) {
         case 64:
             return launch_attention_sum<64>(feat, ld_feat, el, ld_el, er, ld_er, num_nodes, in_ptr, srt_src, out_ptr, out_dst, negative_slope,
-                                            bias, out, ld_out, s);
+                                            bias, out, ld_out, stats, ld_stats, s);
         case 128:
             return launch_attention_sum<128>(feat, ld_feat, el, ld_el, er, ld_er, num_nodes, in_ptr, srt_src, out_ptr, out_dst, negative_slope,
-                                             bias, out, ld_out, s);
+                                             bias, out, ld_out, stats, ld_stats, s);
         default:
             return launch_attention_sum<256>(feat, ld_feat, el, ld_el, er, ld_er, num_nodes, in_ptr, srt_src, out_ptr, out_dst, negative_slope,
-                                             bias, out, ld_out, s);
+                                             bias, out, ld_out, stats, ld_stats, s);
     }
+}
+
+extern "C" int gnnome_node_attention_sum_f32(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er, int hidden,
+                                             int heads, int64_t num_nodes, const int32_t* in_ptr, const int32_t* srt_src,
+                                             const int32_t* out_ptr, const int32_t* out_dst, float negative_slope, const float* bias, float* out,
+                                             int ld_out, void* stream) {
+    return attention_sum_checked(feat, ld_feat, el, ld_el, er, ld_er, hidden, heads, num_nodes, in_ptr, srt_src, out_ptr, out_dst,
+                                 negative_slope, bias, out, ld_out, false, nullptr, 0, stream);
+}
+
+extern "C" int gnnome_node_attention_sum_stats_f32(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er,
+                                                   int hidden, int heads, int64_t num_nodes, const int32_t* in_ptr, const int32_t* srt_src,
+                                                   const int32_t* out_ptr, const int32_t* out_dst, float negative_slope, const float* bias,
+                                                   float* out, int ld_out, float* stats, int ld_stats, void* stream) {
+    return attention_sum_checked(feat, ld_feat, el, ld_el, er, ld_er, hidden, heads, num_nodes, in_ptr, srt_src, out_ptr, out_dst,
+                                 negative_slope, bias, out, ld_out, true, stats, ld_stats, stream);
 }

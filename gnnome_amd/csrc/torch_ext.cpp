@@ -12,6 +12,7 @@
 //     agg    = torch.ops.gnnome_hip.node_neighbour_sum(h, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale)   # GCNModel / SAGEModel, full_graph.py:65-75, :109-119
 //     dh     = torch.ops.gnnome_hip.node_neighbour_sum_bwd(g, out_ptr, out_dst, in_ptr, srt_src, rscale, oscale, add, mult, y)   # its gradient w.r.t. h + the step's epilogue
 //     agg    = torch.ops.gnnome_hip.node_attention_sum(feat, el, er, in_ptr, srt_src, out_ptr, out_dst, bias, negative_slope)   # GATModel, full_graph.py:78-97
+//     dfeat, del, der = torch.ops.gnnome_hip.node_attention_sum_bwd(g, feat, el, er, out, stats, in_ptr, srt_src, out_ptr, out_dst, both, bias, negative_slope)   # its gradient
 //     logits = torch.ops.gnnome_hip.edge_score(e, Ps, Qd, srt_src, srt_dst, srt_eid, W1e, W2, b2, W3, b3)   # score_predictor.py:12-24
 //
 // Built by gnnome_amd/csrc/Makefile (target torch_ext: g++ against this interpreter's torch headers, linked to libgnnome_hip.so beside it);
@@ -292,6 +293,37 @@ Tensor node_attention_sum(const Tensor& feat, const Tensor& el, const Tensor& er
     return out;
 }
 
+// ---- the attention sum's gradient (gnnome_node_attention_sum_bwd_f32; the backward of GATConv's message passing, processor.py:49-70) -----------
+// g, feat, out [N,3H], el / er [N,4], stats [N,8] (gnnome_node_attention_sum_stats_f32's), all row-strided; both: the doubled graph of directed=False
+std::tuple<Tensor, Tensor, Tensor> node_attention_sum_bwd(const Tensor& g, const Tensor& feat, const Tensor& el, const Tensor& er, const Tensor& out,
+                                                          const Tensor& stats, const Tensor& in_ptr, const Tensor& srt_src, const Tensor& out_ptr,
+                                                          const Tensor& out_dst, bool both, const OptTensor& bias, double negative_slope) {
+    const int ldg = rows_ld(g, "node_attention_sum_bwd.g"), ldf = rows_ld(feat, "node_attention_sum_bwd.feat"),
+              ld_el = rows_ld(el, "node_attention_sum_bwd.el"), ld_er = rows_ld(er, "node_attention_sum_bwd.er"),
+              ldo = rows_ld(out, "node_attention_sum_bwd.out"), lds = rows_ld(stats, "node_attention_sum_bwd.stats");
+    const int64_t N = g.size(0), W = g.size(1), heads = 3;
+    TORCH_CHECK(W % heads == 0 && feat.size(0) == N && feat.size(1) == W && out.size(0) == N && out.size(1) == W && el.size(0) == N &&
+                    el.size(1) == 4 && er.size(0) == N && er.size(1) == 4 && stats.size(0) == N && stats.size(1) == 8 && in_ptr.numel() == N + 1 &&
+                    out_ptr.numel() == N + 1 && out_dst.numel() == srt_src.numel() && (!bias.has_value() || !bias->defined() || bias->numel() == W),
+                "node_attention_sum_bwd: shapes g,feat,out[N,3H] el,er[N,4] stats[N,8] in_ptr,out_ptr[N+1] srt_src,out_dst[E] bias[3H]");
+    Guard guard(g.device());
+    Tensor dfeat = at::empty({N, W}, g.options()), del = at::empty({N, 4}, g.options()), der = at::empty({N, 4}, g.options()),
+           work = at::empty({N, 16}, g.options());
+    ok(gnnome_node_attention_sum_bwd_f32(f32(g, "node_attention_sum_bwd.g"), ldg, f32(feat, "node_attention_sum_bwd.feat"), ldf,
+                                         f32(el, "node_attention_sum_bwd.el"), ld_el, f32(er, "node_attention_sum_bwd.er"), ld_er,
+                                         f32(out, "node_attention_sum_bwd.out"), ldo, f32_opt(bias, "node_attention_sum_bwd.bias"),
+                                         f32(stats, "node_attention_sum_bwd.stats"), lds, (int)(W / heads), (int)heads, N,
+                                         i32(in_ptr, "node_attention_sum_bwd.in_ptr"),
+                                         srt_src.numel() ? i32(srt_src, "node_attention_sum_bwd.srt_src") : nullptr,
+                                         i32(out_ptr, "node_attention_sum_bwd.out_ptr"),
+                                         out_dst.numel() ? i32(out_dst, "node_attention_sum_bwd.out_dst") : nullptr, both ? 1 : 0,
+                                         (float)negative_slope, N ? dfeat.data_ptr<float>() : nullptr, (int)std::max<int64_t>(W, 1),
+                                         N ? del.data_ptr<float>() : nullptr, 4, N ? der.data_ptr<float>() : nullptr, 4,
+                                         N ? work.data_ptr<float>() : nullptr, stream_of(g)),
+       "gnnome_node_attention_sum_bwd_f32");
+    return {dfeat, del, der};
+}
+
 // ---- the edge scorer (gnnome_edge_score_f32; score_predictor.py:12-24), logits in edge-id order -------------------------------------------------
 Tensor edge_score(const Tensor& e, const Tensor& Ps, const Tensor& Qd, const Tensor& srt_src, const Tensor& srt_dst, const Tensor& srt_eid,
                   const Tensor& W1e, const Tensor& W2, const Tensor& b2, const Tensor& W3, const Tensor& b3) {
@@ -345,6 +377,11 @@ Tensor node_attention_sum_meta(const Tensor& feat, const Tensor&, const Tensor&,
                                const OptTensor&, double) {
     return at::empty({feat.size(0), feat.size(1)}, feat.options());
 }
+std::tuple<Tensor, Tensor, Tensor> node_attention_sum_bwd_meta(const Tensor& g, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                                                               const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, bool,
+                                                               const OptTensor&, double) {
+    return {at::empty({g.size(0), g.size(1)}, g.options()), at::empty({g.size(0), 4}, g.options()), at::empty({g.size(0), 4}, g.options())};
+}
 Tensor edge_score_meta(const Tensor& e, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
                        const Tensor&, const Tensor&, const Tensor&) {
     return at::empty({e.size(0)}, e.options());
@@ -368,6 +405,8 @@ TORCH_LIBRARY(gnnome_hip, m) {
           "Tensor? oscale=None, Tensor? add=None, Tensor? mult=None, Tensor? y=None) -> Tensor");
     m.def("node_attention_sum(Tensor feat, Tensor el, Tensor er, Tensor in_ptr, Tensor srt_src, Tensor? out_ptr=None, Tensor? out_dst=None, "
           "Tensor? bias=None, float negative_slope=0.2) -> Tensor");
+    m.def("node_attention_sum_bwd(Tensor g, Tensor feat, Tensor el, Tensor er, Tensor out, Tensor stats, Tensor in_ptr, Tensor srt_src, "
+          "Tensor out_ptr, Tensor out_dst, bool both=False, Tensor? bias=None, float negative_slope=0.2) -> (Tensor, Tensor, Tensor)");
     m.def("edge_score(Tensor e, Tensor Ps, Tensor Qd, Tensor srt_src, Tensor srt_dst, Tensor srt_eid, Tensor W1e, Tensor W2, Tensor b2, Tensor W3, "
           "Tensor b3) -> Tensor");
     m.def("abi_version() -> int", []() -> int64_t { return gnnome_abi_version(); });   // the libgnnome_hip.so this extension is bound to
@@ -384,6 +423,7 @@ TORCH_LIBRARY_IMPL(gnnome_hip, CUDA, m) {   // the CUDA dispatch key is the HIP 
     m.impl("node_neighbour_sum", &node_neighbour_sum);
     m.impl("node_neighbour_sum_bwd", &node_neighbour_sum_bwd);
     m.impl("node_attention_sum", &node_attention_sum);
+    m.impl("node_attention_sum_bwd", &node_attention_sum_bwd);
     m.impl("edge_score", &edge_score);
 }
 
@@ -398,5 +438,6 @@ TORCH_LIBRARY_IMPL(gnnome_hip, Meta, m) {
     m.impl("node_neighbour_sum", &node_neighbour_sum_meta);
     m.impl("node_neighbour_sum_bwd", &node_neighbour_sum_bwd_meta);
     m.impl("node_attention_sum", &node_attention_sum_meta);
+    m.impl("node_attention_sum_bwd", &node_attention_sum_bwd_meta);
     m.impl("edge_score", &edge_score_meta);
 }

@@ -184,14 +184,83 @@ def _conv_weight(conv, kind):
     return torch.cat([conv.fc_self.weight.detach(), conv.fc_neigh.weight.detach()], 1)
 
 
-def _step_forward(ops, model, views, sc, x, e_raw, masks):
-    """The train-mode forward on sorted-order e -> (logits[E], what the backward reads)."""
+def encoders_forward(ops, model, views, x, e_raw):
+    """The two encoders on the live parameters -> (h [N,H], e [E,H] in sorted order: what the scorer reads).  Shared with engine_gat's step."""
     d = lambda t: t.detach().contiguous()  # noqa: E731
-    kind, both, convs = model.kind, not model.directed, model.gnn.convs
     ne, ee = model.node_encoder, model.edge_encoder
     h = engine.encode_nodes(ops, views, x, (d(ne.linear1.weight), d(ne.linear1.bias), d(ne.linear2.weight), d(ne.linear2.bias)))
     e = ops.encode(e_raw, d(ee.linear1.weight), d(ee.linear1.bias), d(ee.linear2.weight), d(ee.linear2.bias), gather=views.srt_eid,
                    rows=views.num_edges)
+    return h, e
+
+
+def score_forward(ops, model, views, h, e):
+    """The scorer on the live parameters, keeping z1 -> (logits[E], what score_backward reads).  Shared with engine_gat's step."""
+    d = lambda t: t.detach().contiguous()  # noqa: E731
+    H = h.shape[1]
+    pred = model.predictor
+    hs = pred.W1.out_features
+    W1 = d(pred.W1.weight)
+    W_nodes = torch.cat([W1[:, :H], W1[:, H:2 * H]], 0).contiguous()
+    b_nodes = torch.cat([torch.zeros_like(pred.W1.bias), pred.W1.bias]).detach().contiguous()
+    PQ = ops.linear(h, W_nodes, b_nodes)
+    z1 = torch.empty((views.num_edges, hs), dtype=torch.float32, device=h.device)
+    logits = torch.empty(views.num_edges, dtype=torch.float32, device=h.device)
+    ops.edge_score(e, PQ[:, :hs], PQ[:, hs:], views, W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)),
+                   d(pred.W3.bias.reshape(-1)), logits, z1_out=z1)
+    return logits, dict(h=h, e=e, z1=z1, W1=W1, W_nodes=W_nodes)
+
+
+def score_backward(ops, model, views, kept, dlogits, g):
+    """The scorer's backward (score_predictor.py:12-17), as train._TrainStep.backward runs it on one rank: the predictor's gradients into
+    g -> (dY = the gradient of the last layer's output [N,H], de = the gradient of the encoded e, which no layer touches)."""
+    d = lambda t: t.detach().contiguous()  # noqa: E731
+    pred = model.predictor
+    N, H = kept["h"].shape
+    hs = pred.W1.out_features
+    dl = dlogits.reshape(-1).contiguous().float()
+    dz1, dz2, u = ops.score_tail_bwd(kept["z1"], dl, views, d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)))
+    g["predictor.W2.weight"] = ops.wgrad(dz2, kept["z1"])
+    g["predictor.W2.bias"] = ops.colsum2(dz2)[0]
+    g["predictor.W3.weight"] = ops.colsum2(u)[0].reshape(1, 32)
+    g["predictor.W3.bias"] = dl.sum().reshape(1)
+    W1 = kept["W1"]
+    de = ops.linear(dz1, W1[:, 2 * H:].t().contiguous(), None)   # the layers never touch e: this is the edge encoder's gradient
+    gW1e = ops.wgrad(dz1, kept["e"])
+    dPQ = torch.empty((N, 2 * hs), dtype=torch.float32, device=dl.device)
+    ops.segment_sum2(dz1, views, N, out_in=dPQ[:, hs:], out_out=dPQ[:, :hs])   # gathered by srt_dst / srt_src in the forward
+    g["predictor.W1.bias"] = ops.colsum2(dPQ[:, hs:].contiguous())[0]
+    gWn = ops.wgrad(dPQ, kept["h"])
+    g["predictor.W1.weight"] = torch.cat([gWn[:hs], gWn[hs:], gW1e], 1)
+    return ops.linear(dPQ, kept["W_nodes"].t().contiguous(), None), de
+
+
+def encoders_backward(ops, model, views, g, dY, de, x, e_raw):
+    """The two encoders' gradients into g (models/full_graph.py:63-64) from dY = d h [N,H] and de = d e [E,H]."""
+    from .train import encoder_bwd
+    ne, ee = model.node_encoder, model.edge_encoder
+    encoder_bwd(ops, g, dY, x, getattr(views, "node_gather", None), views.num_nodes, ne.linear1, ne.linear2, "node_encoder.linear1",
+                "node_encoder.linear2")
+    encoder_bwd(ops, g, de, e_raw, views.srt_eid, views.num_edges, ee.linear1, ee.linear2, "edge_encoder.linear1", "edge_encoder.linear2")
+
+
+def _draw_masks(model, views, x):
+    """One scaled keep-mask per layer, drawn once per step: a forward that is run again as bf16x6 drops the same elements."""
+    from . import train
+    masks = [None] * len(model.gnn.convs)
+    if model.kind == "sage":
+        H = model.node_encoder.linear2.out_features   # (train.dropout_mask is looked up here, at call time: tests substitute known masks)
+        masks = [train.dropout_mask(views.num_nodes, H, conv.feat_drop.p, x.device) if conv.feat_drop.p > 0 else None
+                 for conv in model.gnn.convs]
+    return masks
+
+
+def _step_forward(ops, model, views, x, e_raw, masks):
+    """The train-mode forward on sorted-order e -> (logits[E], what the backward reads)."""
+    d = lambda t: t.detach().contiguous()  # noqa: E731
+    kind, both, convs = model.kind, not model.directed, model.gnn.convs
+    sc = scales_for(views, model.directed)
+    h, e = encoders_forward(ops, model, views, x, e_raw)
     N, H = h.shape
     layers = []
     if kind == "gcn":
@@ -219,43 +288,19 @@ def _step_forward(ops, model, views, sc, x, e_raw, masks):
             else:
                 ops.relu_rows(nxt[:, :H])
             T = nxt
-    pred = model.predictor
-    hs = pred.W1.out_features
-    W1 = d(pred.W1.weight)
-    W_nodes = torch.cat([W1[:, :H], W1[:, H:2 * H]], 0).contiguous()
-    b_nodes = torch.cat([torch.zeros_like(pred.W1.bias), pred.W1.bias]).detach().contiguous()
-    PQ = ops.linear(h, W_nodes, b_nodes)
-    z1 = torch.empty((views.num_edges, hs), dtype=torch.float32, device=h.device)
-    logits = torch.empty(views.num_edges, dtype=torch.float32, device=h.device)
-    ops.edge_score(e, PQ[:, :hs], PQ[:, hs:], views, W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)),
-                   d(pred.W3.bias.reshape(-1)), logits, z1_out=z1)
-    return logits, dict(layers=layers, h=h, e=e, z1=z1, W1=W1, W_nodes=W_nodes)
+    logits, kept = score_forward(ops, model, views, h, e)
+    kept["layers"] = layers
+    return logits, kept
 
 
-def _step_backward(ops, model, views, sc, x, e_raw, kept, dlogits):
+def _step_backward(ops, model, views, x, e_raw, kept, dlogits):
     """-> {parameter name: gradient}."""
-    from .train import encoder_bwd
     d = lambda t: t.detach().contiguous()  # noqa: E731
-    kind, both, convs, pred = model.kind, not model.directed, model.gnn.convs, model.predictor
+    kind, both, convs = model.kind, not model.directed, model.gnn.convs
+    sc = scales_for(views, model.directed)
     N, H = kept["h"].shape
-    hs = pred.W1.out_features
     g = {}
-    # ---- scorer (score_predictor.py:12-17), as train._TrainStep.backward runs it on one rank
-    dl = dlogits.reshape(-1).contiguous().float()
-    dz1, dz2, u = ops.score_tail_bwd(kept["z1"], dl, views, d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)))
-    g["predictor.W2.weight"] = ops.wgrad(dz2, kept["z1"])
-    g["predictor.W2.bias"] = ops.colsum2(dz2)[0]
-    g["predictor.W3.weight"] = ops.colsum2(u)[0].reshape(1, 32)
-    g["predictor.W3.bias"] = dl.sum().reshape(1)
-    W1 = kept["W1"]
-    de = ops.linear(dz1, W1[:, 2 * H:].t().contiguous(), None)   # the layers never touch e: this is the edge encoder's gradient
-    gW1e = ops.wgrad(dz1, kept["e"])
-    dPQ = torch.empty((N, 2 * hs), dtype=torch.float32, device=dl.device)
-    ops.segment_sum2(dz1, views, N, out_in=dPQ[:, hs:], out_out=dPQ[:, :hs])   # gathered by srt_dst / srt_src in the forward
-    g["predictor.W1.bias"] = ops.colsum2(dPQ[:, hs:].contiguous())[0]
-    gWn = ops.wgrad(dPQ, kept["h"])
-    g["predictor.W1.weight"] = torch.cat([gWn[:hs], gWn[hs:], gW1e], 1)
-    dY = ops.linear(dPQ, kept["W_nodes"].t().contiguous(), None)
+    dY, de = score_backward(ops, model, views, kept, dlogits, g)
     # ---- layers, last to first (layers/processor.py:42-46, :80-84)
     for i in range(len(convs) - 1, -1, -1):
         conv, s, pfx = convs[i], kept["layers"][i], f"gnn.convs.{i}."
@@ -271,31 +316,27 @@ def _step_backward(ops, model, views, sc, x, e_raw, kept, dlogits):
             dY = ops.node_neighbour_sum_bwd(dT[:, H:], views, rscale=sc.din_inv, both=both, add=dT[:, :H], mult=s["mask"],
                                             y=s["T"][:, :H] if i > 0 else None)
         kept["layers"][i] = s = None
-    # ---- encoders (models/full_graph.py:63-64)
-    ne, ee = model.node_encoder, model.edge_encoder
-    encoder_bwd(ops, g, dY, x, getattr(views, "node_gather", None), N, ne.linear1, ne.linear2, "node_encoder.linear1", "node_encoder.linear2")
-    encoder_bwd(ops, g, de, e_raw, views.srt_eid, views.num_edges, ee.linear1, ee.linear2, "edge_encoder.linear1", "edge_encoder.linear2")
+    encoders_backward(ops, model, views, g, dY, de, x, e_raw)
     return g
 
 
 class _BaselineStep(torch.autograd.Function):
+    """One training step as ONE autograd node whose inputs are the model's parameters.  `step` = (masks, forward, backward): this
+    module's for GCNModel / SAGEModel, engine_gat's for GATModel - the range fallback, the empty graph and the release of the kept
+    activations are the same for all three."""
+
     @staticmethod
-    def forward(ctx, model, views, x, e_raw, names, *params):
-        from . import train
+    def forward(ctx, model, views, x, e_raw, names, step, *params):
         ops = hip_ops
-        sc = scales_for(views, model.directed)
-        masks = [None] * len(model.gnn.convs)
-        if model.kind == "sage":   # one mask per layer, drawn once: a forward that is run again as bf16x6 drops the same elements
-            H = model.node_encoder.linear2.out_features   # (train.dropout_mask is looked up here, at call time: tests substitute known masks)
-            masks = [train.dropout_mask(views.num_nodes, H, conv.feat_drop.p, x.device) if conv.feat_drop.p > 0 else None
-                     for conv in model.gnn.convs]
+        draw, fwd, _ = step
+        masks = draw(model, views, x)
         bf16x6 = ops._TUNING.get(10, 0) == 1
-        logits, kept = _step_forward(ops, model, views, sc, x, e_raw, masks)
+        logits, kept = fwd(ops, model, views, x, e_raw, masks)
         if not bf16x6 and getattr(model, "range_check", True) and not bool(torch.isfinite(logits).all()):
             bf16x6 = True   # fp16x3's operand range did not hold (forward_in_range): the step runs as bf16x6
             with ops.bf16x6_arithmetic():
-                logits, kept = _step_forward(ops, model, views, sc, x, e_raw, masks)
-        ctx.model, ctx.views, ctx.sc, ctx.names, ctx.kept, ctx.inputs, ctx.bf16x6 = model, views, sc, names, kept, (x, e_raw), bf16x6
+                logits, kept = fwd(ops, model, views, x, e_raw, masks)
+        ctx.model, ctx.views, ctx.names, ctx.step, ctx.kept, ctx.inputs, ctx.bf16x6 = model, views, names, step, kept, (x, e_raw), bf16x6
         return logits.unsqueeze(1)
 
     @staticmethod
@@ -303,31 +344,25 @@ class _BaselineStep(torch.autograd.Function):
         if ctx.kept is None:
             raise RuntimeError("the activations of this training step were released by its first backward(); "
                                "retain_graph=True is not supported - run the forward again")
-        model, views = ctx.model, ctx.views
+        model, views, bwd = ctx.model, ctx.views, ctx.step[2]
         if views.num_edges == 0:   # nothing was scored: no parameter has a gradient
             grads = [torch.zeros_like(p) for _, p in model.named_parameters()]
         else:
             if ctx.bf16x6:
                 with hip_ops.bf16x6_arithmetic():
-                    g = _step_backward(hip_ops, model, views, ctx.sc, *ctx.inputs, ctx.kept, dlogits)
+                    g = bwd(hip_ops, model, views, *ctx.inputs, ctx.kept, dlogits)
             else:
-                g = _step_backward(hip_ops, model, views, ctx.sc, *ctx.inputs, ctx.kept, dlogits)
+                g = bwd(hip_ops, model, views, *ctx.inputs, ctx.kept, dlogits)
             grads = [g[n].contiguous() for n in ctx.names]
         ctx.kept = None
-        return (None, None, None, None, None) + tuple(grads)
+        return (None, None, None, None, None, None) + tuple(grads)
 
 
-def train_forward(model, graph, x, e):
-    """The training step of GCNModel / SAGEModel (the reference's train.py:138-145 runs `model(g, x, e)` in train mode; here that call keeps
-    raising and this is the explicit entry, as train.train_forward is the symmetric model's): logits [E,1] on the compute device, with
-    autograd history to model.parameters().  `graph` as for the model's call; views of a reversed graph (GraphViews.reversed) are the
-    model of the swapped edge list."""
-    kind = getattr(model, "kind", None)
-    if kind == "gat":
-        raise NotImplementedError("train mode of GATModel is not built (its edge-softmax backward is another kernel): "
-                                  "engine_baselines.train_forward serves GCNModel and SAGEModel")
-    if kind not in KINDS:
-        raise TypeError(f"engine_baselines.train_forward serves GCNModel and SAGEModel, not {type(model).__name__}")
+_STEP = (_draw_masks, _step_forward, _step_backward)
+
+
+def run_train_step(model, graph, x, e, step):
+    """What train_forward and engine_gat.train_forward share: the refusals, the views, the inputs on the compute device, the step."""
     from .train import TRAIN_SCORE_HIDDEN
     device = engine.compute_device(x, e)
     names = [n for n, _ in model.named_parameters()]
@@ -341,16 +376,30 @@ def train_forward(model, graph, x, e):
         raise ValueError(f"x has {x.shape[0]} rows for {views.num_nodes} nodes, e has {e.shape[0]} rows for {views.num_edges} edges")
     xd = x.detach().to(device=device, dtype=torch.float32).contiguous()
     ed = e.detach().to(device=device, dtype=torch.float32).contiguous()
-    out = _BaselineStep.apply(model, views, xd, ed, names, *params)
+    out = _BaselineStep.apply(model, views, xd, ed, names, step, *params)
     views.check_range()   # a fresh graph's deferred endpoint check, after the whole forward has been enqueued
     return out
+
+
+def train_forward(model, graph, x, e):
+    """The training step of GCNModel / SAGEModel (the reference's train.py:138-145 runs `model(g, x, e)` in train mode; here that call keeps
+    raising and this is the explicit entry, as train.train_forward is the symmetric model's): logits [E,1] on the compute device, with
+    autograd history to model.parameters().  `graph` as for the model's call; views of a reversed graph (GraphViews.reversed) are the
+    model of the swapped edge list."""
+    kind = getattr(model, "kind", None)
+    if kind == "gat":
+        raise NotImplementedError("the training step of GATModel is engine_gat.train_forward (its edge-softmax backward is another "
+                                  "kernel): engine_baselines.train_forward serves GCNModel and SAGEModel")
+    if kind not in KINDS:
+        raise TypeError(f"engine_baselines.train_forward serves GCNModel and SAGEModel, not {type(model).__name__}")
+    return run_train_step(model, graph, x, e, _STEP)
 
 
 def model_forward(model, graph, x, e, prepared=Prepared, stack=run_stack):
     """models/full_graph.py:65-75 / :109-119 on the MI355X (and, with engine_gat's `prepared` and `stack`, :87-97)."""
     if model.training:
-        raise NotImplementedError(f"{type(model).__name__} is built for eval mode only: call .eval() (train mode of the GCN / SAGE / GAT "
-                                  "baselines is not served)")
+        raise NotImplementedError(f"{type(model).__name__} is built for eval mode only: call .eval() (the training step of the GCN / SAGE / "
+                                  "GAT baselines is the explicit entry train_forward of engine_baselines / engine_gat)")
     out_device = x.device
     device = engine.compute_device(x, e)
     prep = engine.prepared_for(model, device, prepared)

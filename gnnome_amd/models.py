@@ -154,8 +154,9 @@ class GATModel(_BaselineModel):
     GAT_processor (layers/processor.py:49-70: DGL's GATConv with 3 heads, nn.Linear(3H, H) on the concatenated heads, a ReLU between
     layers), ScorePredictor.  Same constructor and state_dict keys (`gnn.convs.N.{attn_l, attn_r, bias, fc.weight}`,
     `gnn.linears.N.{weight, bias}`, the encoders' and the predictor's as for GCNModel), same call; g', the scorer, `normalization`, the
-    built widths and eval mode as for GCNModel.  Train mode is not built for this model: the call raises, and
-    engine_baselines.train_forward refuses it (the edge softmax's backward is another kernel).
+    built widths and eval mode as for GCNModel.  The call serves eval mode only, as GCNModel's; the training step is the explicit entry
+    engine_gat.train_forward(model, graph, x, e) (its backward runs on gnnome_node_attention_sum_bwd_f32; feat_drop as one scaled keep-mask
+    per layer on the layer's input), which trainer.train(model_class=GATModel) calls.  engine_baselines.train_forward refuses this model.
 
     Per layer (gnnome_amd/engine_gat.py): ONE projection on [fc.weight ; attn_l fc ; attn_r fc] gives feat, el and er as column blocks of
     a [N, 3H + 64] table, the edge softmax and the weighted sum are the kernel gnnome_node_attention_sum_f32 over the graph's own in- and

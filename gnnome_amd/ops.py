@@ -774,6 +774,102 @@ def node_attention_sum(feat, views, el, er, bias=None, negative_slope=0.2, both=
     return out
 
 
+def _attention_lists(views):
+    """(in-list, out-list) of the graph the views stand for: views of a reversed graph exchange the two."""
+    lists = [(views.in_ptr, views.srt_src), (views.out_ptr, views.out_dst)]
+    if views.transposed:
+        lists.reverse()
+    return lists
+
+
+def node_attention_sum_stats(feat, views, el, er, bias=None, negative_slope=0.2, both=False, out=None, stats=None):
+    """The training form of node_attention_sum (gnnome_node_attention_sum_stats_f32): -> (out, stats), out with node_attention_sum's bits,
+    stats [N, 8] = per node m0 m1 m2 0 | 1/den0 1/den1 1/den2 0 - the per-head maximum of the scores over N'(i) and the reciprocal of the
+    softmax denominator, what node_attention_sum_bwd recomputes the weights from."""
+    lib = _lib.load()
+    feat, ldf = _rows(feat, "node_attention_sum_stats.feat")
+    el, ld_el = _rows(el, "node_attention_sum_stats.el")
+    er, ld_er = _rows(er, "node_attention_sum_stats.er")
+    n, width = feat.shape
+    heads = 3
+    if n != views.num_nodes:
+        raise ValueError(f"node_attention_sum_stats: feat has {n} rows for {views.num_nodes} nodes")
+    if width % heads or el.shape != (n, 4) or er.shape != (n, 4) or el.device != feat.device or er.device != feat.device:
+        raise ValueError(f"node_attention_sum_stats: feat is [N, 3H], el and er are [N, 4] (three heads and a pad) on feat's device; got "
+                         f"{tuple(feat.shape)}, {tuple(el.shape)}, {tuple(er.shape)}")
+    if out is None:
+        out = torch.empty((n, width), dtype=torch.float32, device=feat.device)
+    out, ldo = _rows(out, "node_attention_sum_stats.out")
+    if out.shape != feat.shape or out.device != feat.device:
+        raise ValueError(f"node_attention_sum_stats: out is {tuple(out.shape)} on {out.device}, feat is {tuple(feat.shape)} on {feat.device}")
+    if stats is None:
+        stats = torch.empty((n, 8), dtype=torch.float32, device=feat.device)
+    stats, lds = _rows(stats, "node_attention_sum_stats.stats")
+    if stats.shape != (n, 8) or stats.device != feat.device:
+        raise ValueError(f"node_attention_sum_stats: stats is {tuple(stats.shape)} on {stats.device}, expected {(n, 8)} on {feat.device}")
+    if bias is not None and (_f32(bias, "node_attention_sum_stats.bias").shape != (width,) or not bias.is_contiguous()):
+        raise ValueError("node_attention_sum_stats: bias is one contiguous float per output column")
+    (ptr_a, idx_a), (ptr_b, idx_b) = _attention_lists(views)
+    with _on(feat.device):
+        _lib.check(lib.gnnome_node_attention_sum_stats_f32(_ptr(feat), ldf, _ptr(el), ld_el, _ptr(er), ld_er, width // heads, heads, n,
+                                                           _ptr(ptr_a), _ptr(idx_a), _ptr(ptr_b) if both else None,
+                                                           _ptr(idx_b) if both else None, float(negative_slope), _ptr(bias), _ptr(out), ldo,
+                                                           _ptr(stats), lds, _stream(feat.device)), "node_attention_sum_stats_f32")
+    return out, stats
+
+
+def node_attention_sum_bwd(g, views, feat, el, er, out, stats, bias=None, negative_slope=0.2, both=False, dP=None):
+    """The gradient of node_attention_sum with respect to feat, el and er (gnnome_node_attention_sum_bwd_f32) -> (dfeat [N, 3H], del [N, 4],
+    der [N, 4]; pad column 0), from g = d out and the forward's feat, el, er, out (with its bias), bias and stats (node_attention_sum_stats).
+    Per head and edge j -> i of the self-looped (`both`: doubled) graph: a the forward's softmax weight, D[i] = g[i] . (out[i] - bias),
+    dx = a * (x > 0 ? 1 : negative_slope) * (g[i] . feat[j] - D[i]); dfeat[j] = sum a g[i], del[j] = sum dx over the edges that leave j,
+    der[i] = sum dx over the edges that enter i.  dP: a [N, 3H + 64] table laid out like the projection (feat | el, pad | er, pad | zeros) -
+    the three results are then its column blocks and its remaining 56 columns are zeroed here, by the host; None: three fresh tensors.
+    g, feat, el, er, out may be column blocks of wider tables.  Views of a reversed graph exchange the roles of the two lists."""
+    lib = _lib.load()
+    g, ldg = _rows(g, "node_attention_sum_bwd.g")
+    feat, ldf = _rows(feat, "node_attention_sum_bwd.feat")
+    el, ld_el = _rows(el, "node_attention_sum_bwd.el")
+    er, ld_er = _rows(er, "node_attention_sum_bwd.er")
+    out, ldo = _rows(out, "node_attention_sum_bwd.out")
+    stats, lds = _rows(stats, "node_attention_sum_bwd.stats")
+    n, width = g.shape
+    heads = 3
+    if n != views.num_nodes:
+        raise ValueError(f"node_attention_sum_bwd: g has {n} rows for {views.num_nodes} nodes")
+    shapes = (("feat", feat, (n, width)), ("out", out, (n, width)), ("el", el, (n, 4)), ("er", er, (n, 4)), ("stats", stats, (n, 8)))
+    for name, t, shape in shapes:
+        if t.shape != shape or t.device != g.device:
+            raise ValueError(f"node_attention_sum_bwd: {name} is {tuple(t.shape)} on {t.device}, expected {shape} on {g.device} "
+                             "(g, feat, out [N, 3H]; el, er [N, 4]; stats [N, 8])")
+    if width % heads:
+        raise ValueError(f"node_attention_sum_bwd: g is [N, heads * H], got {tuple(g.shape)} for {heads} heads")
+    if bias is not None and (_f32(bias, "node_attention_sum_bwd.bias").shape != (width,) or not bias.is_contiguous()):
+        raise ValueError("node_attention_sum_bwd: bias is one contiguous float per output column")
+    if dP is None:
+        dfeat = torch.empty((n, width), dtype=torch.float32, device=g.device)
+        del_, der = (torch.empty((n, 4), dtype=torch.float32, device=g.device) for _ in range(2))
+    else:
+        if dP.shape != (n, width + 64) or dP.device != g.device:
+            raise ValueError(f"node_attention_sum_bwd: dP is {tuple(dP.shape)} on {dP.device}, expected {(n, width + 64)} on {g.device}")
+        dfeat, del_, der = dP[:, :width], dP[:, width:width + 4], dP[:, width + 4:width + 8]
+        dP[:, width + 8:].zero_()
+    dfeat, ld_df = _rows(dfeat, "node_attention_sum_bwd.dfeat")
+    del_, ld_dl = _rows(del_, "node_attention_sum_bwd.del")
+    der, ld_dr = _rows(der, "node_attention_sum_bwd.der")
+    work = torch.empty((n, 16), dtype=torch.float32, device=g.device)
+    (ptr_a, idx_a), (ptr_b, idx_b) = _attention_lists(views)
+    with _on(g.device):
+        rc = lib.gnnome_node_attention_sum_bwd_f32(_ptr(g), ldg, _ptr(feat), ldf, _ptr(el), ld_el, _ptr(er), ld_er, _ptr(out), ldo, _ptr(bias),
+                                                   _ptr(stats), lds, width // heads, heads, n, _ptr(ptr_a), _ptr(idx_a), _ptr(ptr_b),
+                                                   _ptr(idx_b), 1 if both else 0, float(negative_slope), _ptr(dfeat), ld_df, _ptr(del_), ld_dl,
+                                                   _ptr(der), ld_dr, _ptr(work), _stream(g.device))
+    if rc != 0:   # a refusal that the caller keeps (its traceback holds this frame) must not keep the results' device memory alive
+        del dfeat, del_, der, work
+    _lib.check(rc, "node_attention_sum_bwd_f32")
+    return dfeat, del_, der
+
+
 def relu_rows(x):
     """x <- relu(x) in place (gnnome_relu_rows_f32; NaN stays NaN); x may be a column block of a wider table."""
     x, ld = _rows(x, "relu_rows.x")

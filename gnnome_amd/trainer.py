@@ -281,11 +281,14 @@ def _edge_src_dst(views):
 
 
 def _model_step(model, views, x, e):
-    """`model(views, x, e)` - except for GCNModel / SAGEModel in train mode, whose call refuses train mode and whose training step is the
-    explicit entry engine_baselines.train_forward."""
+    """`model(views, x, e)` - except for GCNModel / SAGEModel / GATModel in train mode, whose call refuses train mode and whose training
+    step is the explicit entry engine_baselines.train_forward (GATModel: engine_gat.train_forward)."""
     if model.training and getattr(model, "kind", None) in ("gcn", "sage"):
         from . import engine_baselines
         return engine_baselines.train_forward(model, views, x, e)
+    if model.training and getattr(model, "kind", None) == "gat":
+        from . import engine_gat
+        return engine_gat.train_forward(model, views, x, e)
     return model(views, x, e)
 
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 28
+#define GNNOME_ABI_VERSION 29
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -339,6 +339,43 @@ int gnnome_relu_mul_rows_f32(float* x, int ld, const float* mult, int ld_mult, i
 int gnnome_node_attention_sum_f32(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er, int hidden,
                                   int heads, int64_t num_nodes, const int32_t* in_ptr, const int32_t* srt_src, const int32_t* out_ptr,
                                   const int32_t* out_dst, float negative_slope, const float* bias, float* out, int ld_out, void* stream);
+
+/* The TRAINING FORM of gnnome_node_attention_sum_f32: the same arguments and, bit for bit, the same `out` (one kernel template, the
+ * statistics behind a compile-time flag), plus per node a row of 8 floats in `stats` (row stride ld_stats >= 8, a multiple of 4; 16-byte
+ * aligned; distinct from feat, el, er and out):  m0 m1 m2 0 | 1/den0 1/den1 1/den2 0  - per head the maximum of the leaky-relu scores over
+ * N'(i) and the reciprocal of the sum of exp(s - m) that divided the numerator.  A weight of the forward is then
+ * exp2((s - m) * log2(e)) * (1/den) again, which is how gnnome_node_attention_sum_bwd_f32 recomputes it. */
+int gnnome_node_attention_sum_stats_f32(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er, int hidden,
+                                        int heads, int64_t num_nodes, const int32_t* in_ptr, const int32_t* srt_src, const int32_t* out_ptr,
+                                        const int32_t* out_dst, float negative_slope, const float* bias, float* out, int ld_out, float* stats,
+                                        int ld_stats, void* stream);
+
+/* ---- the attention sum's gradient with respect to feat, el and er ----------------------------------------
+ * Given g = d out [N, heads*hidden] and the forward's feat, el, er, out (= A, with its bias), bias (NULL as in the forward) and stats,
+ * for every head k and every edge p = (j -> i) of g', loops included:
+ *   x_p = el[j,k] + er[i,k]     a_p = exp2((leaky_relu(x_p) - m[i,k]) * log2(e)) * inv_den[i,k]
+ *   D[i,k]       = g[i,k,:] . (out[i,k,:] - bias[k,:])
+ *   dx_p         = a_p * (x_p > 0 ? 1 : negative_slope) * (g[i,k,:] . feat[j,k,:] - D[i,k])
+ *   dfeat[j,k,:] = sum_{p: src(p) = j} a_p g[dst(p),k,:]     del[j,k] = sum_{p: src(p) = j} dx_p     der[i,k] = sum_{p: dst(p) = i} dx_p
+ * Replaces what torch autograd runs in the reference's training loop (train.py:328-330) for DGL's GATConv(hidden, hidden, num_heads=3)
+ * of layers/processor.py:49-70 on g' (models/full_graph.py:78-97): the backward of u_mul_e_sum, edge_softmax, leaky_relu and u_add_v.
+ * d bias is the column sums of g (gnnome_colsum2_f32), not written here.
+ * dfeat is [N, heads*hidden], del and der rows of 4 floats (pad column written 0), each row-strided (multiples of 4, 16-byte aligned):
+ * they may be the column blocks of one [N, 3*hidden + 64] table laid out like the projection; the kernels write nothing but these three
+ * blocks, the table's remaining score columns are the caller's to zero.  work: num_nodes * 16 floats of scratch, 16-byte aligned (per
+ * destination er | m | 1/den | D, written by the first launch, read by the second).  No output may alias an input or another output.
+ * in_ptr and out_ptr are BOTH required (the per-destination walk reads the in-list, the per-source walk the out-list): `both` != 0
+ * selects the doubled graph of directed=False, not a NULL out_ptr; srt_src and out_dst may be NULL for a graph without edges.
+ * hidden in {64,128,256}, heads == 3, anything else GNNOME_EINVAL; num_nodes == 0 returns at once.
+ * Two launches, one wave per node each (per destination: D, der and the work row; per source: dfeat and del), the forward's lane mapping,
+ * no atomics, fp32; the association is fixed and a function of the graph alone (the loop's term, then the lists ascending; lists above
+ * 4096 items in fixed 128-item blocks - csrc/node_attention_bwd.hip), so two runs leave equal bits; a node without edges gets
+ * dfeat = g bit for bit.  A hub is walked by its own wave: about three milliseconds per 10^5 items per launch (an estimate). */
+int gnnome_node_attention_sum_bwd_f32(const float* g, int ld_g, const float* feat, int ld_feat, const float* el, int ld_el, const float* er,
+                                      int ld_er, const float* out, int ld_out, const float* bias, const float* stats, int ld_stats, int hidden,
+                                      int heads, int64_t num_nodes, const int32_t* in_ptr, const int32_t* srt_src, const int32_t* out_ptr,
+                                      const int32_t* out_dst, int both, float negative_slope, float* dfeat, int ld_dfeat, float* del, int ld_del,
+                                      float* der, int ld_der, float* work, void* stream);
 
 /* ---- streaming aggregation (round 5) -----------------------------------------------------------------
  * The same node update as gnnome_node_aggregate_f32 with norm_kind = GNNOME_NORM_AFFINE (gated_gcn_full.py:111-114, :124-127,
