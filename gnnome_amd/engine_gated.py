@@ -17,7 +17,11 @@ Train mode goes through the symmetric model's training step (train._TrainStep): 
 symmetric model's attribute names, SHARING the Parameter objects, and gives every layer a zero A_3 (plain zero tensors, no
 Parameters: never updated, absent from state_dict).  That is exact for every real parameter and for dh, because A3h = 0
 makes bwd = +0, d bwd / d sigma = 0 and A_3^T dA3h = 0.  It COSTS WHAT THE SYMMETRIC STEP COSTS - the out-edge pass and the
-fifth projection block are computed on zeros; a one-direction backward kernel is not built.
+fifth projection block are computed on zeros.  That is the default (`GatedGCNModel.training_step = "symmetric"`), for directed=True.
+
+`training_step = "in_edge"` selects the step of this model's own (train_forward_in_edge, below): a [N,4H] projection, the train-form
+gate, gnnome_node_aggregate_in_raw_f32 forward and gnnome_node_aggregate_in_bwd_f32 backward (csrc/node_aggregate_in_bwd.hip) - no
+A_3, no out-edge half, no Tb / Ub tables - and directed=False on the doubled edge list.
 """
 import torch
 import torch.nn.functional as F
@@ -216,10 +220,21 @@ def forward_in_range(ops, prep, views, x, e, xd, ed, directed, check=True):
 # module entry points
 # ---------------------------------------------------------------------------------------------------
 
+TRAINING_STEPS = ("symmetric", "in_edge")
+
+
+def training_step_of(model):
+    kind = getattr(model, "training_step", "symmetric")
+    if kind not in TRAINING_STEPS:
+        raise ValueError(f"training_step={kind!r} not in {TRAINING_STEPS}")
+    return kind
+
+
 def model_forward(model, graph, x, e):
     """models/full_graph.py:42-53 on the MI355X."""
     if model.training:
-        return train_forward(model, graph, x, e).to(x.device)
+        step = train_forward_in_edge if training_step_of(model) == "in_edge" else train_forward
+        return step(model, graph, x, e).to(x.device)
     out_device = x.device
     device = engine.compute_device(x, e)
     prep = engine.prepared_for(model, device, Prepared)
@@ -334,5 +349,231 @@ def train_forward(model, graph, x, e):
     xd = x.detach().to(device=device, dtype=torch.float32).contiguous()
     ed = e.detach().to(device=device, dtype=torch.float32).contiguous()
     out = _TrainStep.apply(adapter, WholeGraph(views), xd, ed, adapter.names, *params)
+    views.check_range()
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# train mode, training_step = "in_edge": the one-direction step
+# ---------------------------------------------------------------------------------------------------
+
+def _cat4(conv):
+    """(Wcat [4H,H], bcat [4H]) = A_1 | A_2 | B_1 | B_2 of one layer; B_3's bias rides on the B2h rows (prepare_layer)."""
+    Wcat = torch.cat([conv.A_1.weight, conv.A_2.weight, conv.B_1.weight, conv.B_2.weight], 0).detach().contiguous()
+    bcat = torch.cat([conv.A_1.bias, conv.A_2.bias, conv.B_1.bias, conv.B_2.bias + conv.B_3.bias], 0).detach().contiguous()
+    return Wcat, bcat
+
+
+class _StepGraph:
+    """Where one in-edge step runs: `sh` (train.WholeGraph) over the views the STACK runs on - the graph's in-edge views, or the doubled
+    ones of directed=False - `enc_gather`, the original edge id each of the stack's sorted rows encodes, and the views and rows that are
+    scored (`score_gather` = None: every row of the stack, as it lies)."""
+
+    def __init__(self, views, directed, doubled=doubled_for, ops=hip_ops):
+        """doubled, ops: the builder of the doubled graph and the backend (the tests run the step's host logic on a torch backend)."""
+        from .train import WholeGraph
+        self.score_views = views
+        if directed:
+            self.sh, self.enc_gather, self.score_gather = WholeGraph(views, ops), views.srt_eid, None
+        else:
+            dbl = doubled(views)
+            self.sh, self.enc_gather, self.score_gather = WholeGraph(dbl.views, ops), dbl.enc_gather, dbl.score_gather
+
+
+class _InEdgeStep(torch.autograd.Function):
+    """One training step of GatedGCNModel (gated_gcn_full.py:182-230 in train mode, full_graph.py:42-53) as ONE autograd node whose inputs
+    are the model's parameters - train._TrainStep's shape on the one-direction kernels.  fp32 storage, single process."""
+
+    @staticmethod
+    def forward(ctx, model, sg, x, e_raw, names, *params):
+        from . import train
+        sh = sg.sh
+        ops, views = sh.ops, sh.views
+        convs = model.gnn.convs
+        layer_norm = len(convs) > 0 and isinstance(convs[0].bn_e, torch.nn.LayerNorm)
+        H = model.node_encoder.linear2.out_features
+        n, E2 = views.num_nodes, views.num_edges
+        d = lambda t: t.detach().contiguous()  # noqa: E731
+        ne, ee = model.node_encoder, model.edge_encoder
+        node_gather = getattr(views, "node_gather", None)   # views over renumbered nodes read x (caller's numbering) through it
+        h = ops.encode(x, d(ne.linear1.weight), d(ne.linear1.bias), d(ne.linear2.weight), d(ne.linear2.bias),
+                       **({} if node_gather is None else dict(gather=node_gather, rows=n)))
+        # directed=False: the encoded e fed twice - row p of the doubled sorted order encodes original edge enc_gather[p]
+        e = ops.encode(e_raw, d(ee.linear1.weight), d(ee.linear1.bias), d(ee.linear2.weight), d(ee.linear2.bias), gather=sg.enc_gather, rows=E2)
+        saved = []
+        for conv in convs:
+            Wcat, bcat = _cat4(conv)
+            P = ops.linear(h, Wcat, bcat)   # [N,4H] = A1h|A2h|B1h|B2h (gated_gcn_full.py:194-199)
+            A1, A2, B1, B2 = (P[:, i * H:(i + 1) * H] for i in range(4))
+            mean_e = rstd_e = sc_e = sh_e = mean_h = rstd_h = sc_h = sh_h = None
+            path, xe, stats = train._raw_gate(sh, conv, e, B1, B2, layer_norm, torch.float32)
+            if layer_norm:
+                e_new = ops.ln_relu_res(xe, d(conv.bn_e.weight), d(conv.bn_e.bias), e)
+            else:   # bn_e is applied ONCE per layer (gated_gcn_full.py:207): one momentum update; directed=False: statistics over all 2E rows
+                if path == "moments":
+                    mean_e, rstd_e, sc_e, sh_e = train._bn_train_fused(sh, conv.bn_e, stats, updates=1)
+                else:
+                    mean_e, rstd_e, sc_e, sh_e = train._bn_train(sh, conv.bn_e, stats[0], stats[1], E2, E2, updates=1)
+                e_new = ops.bn_relu_res(xe, sc_e, sh_e, e)
+            v, hf, rdf = ops.node_aggregate_in_raw(e_new, A1, A2, views)
+            if layer_norm:
+                h_next = ops.ln_relu_res(v, d(conv.bn_h.weight), d(conv.bn_h.bias), h)
+            else:
+                if train._can_fuse_bn(sh, conv.bn_h):
+                    mean_h, rstd_h, sc_h, sh_h = train._bn_train_fused(sh, conv.bn_h, ops.batch_moments(v), updates=1)
+                else:
+                    m_h, v_h = ops.batch_stats(v)
+                    mean_h, rstd_h, sc_h, sh_h = train._bn_train(sh, conv.bn_h, m_h, v_h, n, n, updates=1)
+                h_next = ops.bn_relu_res(v, sc_h, sh_h, h)
+            mask = None
+            if conv.dropout > 0.0:
+                mask = train.dropout_mask(n, H, conv.dropout, x.device)
+                h_next = ops.mul23(h_next, mask, mask)[0]
+            saved.append(dict(h=h, P=P, e=e, xe=xe, e_new=e_new, v=v, hf=hf, rdf=rdf, mask=mask, Wcat=Wcat, mean_e=mean_e, rstd_e=rstd_e,
+                              sc_e=sc_e, sh_e=sh_e, mean_h=mean_h, rstd_h=rstd_h, sc_h=sc_h, sh_h=sh_h))
+            h, e = h_next, e_new
+
+        pred = model.predictor
+        hs = pred.W1.out_features
+        W1 = d(pred.W1.weight)
+        W_nodes = torch.cat([W1[:, :H], W1[:, H:2 * H]], 0).contiguous()
+        b_nodes = torch.cat([torch.zeros_like(pred.W1.bias), pred.W1.bias]).detach().contiguous()
+        PQ = ops.linear(h, W_nodes, b_nodes)
+        # directed=False: the ORIGINAL graph is scored with the rows of the first E edge ids (full_graph.py:51)
+        e_sc = e if sg.score_gather is None else ops.gather_rows(e, sg.score_gather)
+        E = sg.score_views.num_edges
+        z1 = torch.empty((E, hs), dtype=torch.float32, device=h.device)
+        logits = torch.empty(E, dtype=torch.float32, device=h.device)
+        ops.edge_score(e_sc, PQ[:, :hs], PQ[:, hs:], sg.score_views, W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias),
+                       d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1)), logits, num_edges=E, z1_out=z1)
+        ctx.model, ctx.sg, ctx.names, ctx.saved = model, sg, names, saved
+        ctx.tail = dict(h=h, e_sc=e_sc, z1=z1, W1=W1, W_nodes=W_nodes, x=x, e_raw=e_raw)
+        return logits.unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        from . import train
+        model, sg, saved, tail = ctx.model, ctx.sg, ctx.saved, ctx.tail
+        if saved is None:
+            raise RuntimeError("the activations of this training step were released by its first backward(); "
+                               "retain_graph=True is not supported - run the forward again")
+        sh = sg.sh
+        ops, views, sv = sh.ops, sh.views, sg.score_views
+        H = model.node_encoder.linear2.out_features
+        n, E2 = views.num_nodes, views.num_edges
+        d = lambda t: t.detach().contiguous()  # noqa: E731
+        dev = dlogits.device
+        g = {}
+
+        # ---- scorer (score_predictor.py:12-17), over the scored views
+        pred = model.predictor
+        hs = pred.W1.out_features
+        dl = dlogits.reshape(-1).contiguous().float()
+        dz1, dz2, u = ops.score_tail_bwd(tail["z1"], dl, sv, d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)))
+        g["predictor.W2.weight"] = ops.wgrad(dz2, tail["z1"])
+        g["predictor.W2.bias"] = ops.colsum2(dz2)[0]
+        g["predictor.W3.weight"] = ops.colsum2(u)[0].reshape(1, 32)
+        g["predictor.W3.bias"] = dl.sum().reshape(1)
+        W1 = tail["W1"]
+        de = ops.linear(dz1, W1[:, 2 * H:].t().contiguous(), None)       # d e_final of the scored rows
+        gW1e = ops.wgrad(dz1, tail["e_sc"])
+        d_ps = ops.segment_sum(dz1, sv.out_ptr, sv.out_pos, n)           # gathered by srt_src in the forward
+        d_qd = ops.segment_sum(dz1, sv.in_ptr, None, n)                  # gathered by srt_dst
+        dPQ = torch.cat([d_ps, d_qd], 1)
+        g["predictor.W1.bias"] = ops.colsum2(d_qd)[0]
+        gWn = ops.wgrad(dPQ, tail["h"])                                  # [2hs, H]
+        g["predictor.W1.weight"] = torch.cat([gWn[:hs], gWn[hs:], gW1e], 1)
+        dh = ops.linear(dPQ, tail["W_nodes"].t().contiguous(), None)     # [N,H]
+        if sg.score_gather is not None:   # directed=False: the scorer's de goes back to the rows it read, the reverse copies get none
+            de = ops.scatter_add_rows(de, sg.score_gather, torch.zeros((E2, H), dtype=torch.float32, device=dev))
+
+        # ---- layers, last to first (gated_gcn_full.py:182-230)
+        for li in range(len(saved) - 1, -1, -1):
+            s, conv, pfx = saved[li], model.gnn.convs[li], f"gnn.convs.{li}."
+            A2, W3t = s["P"][:, H:2 * H], d(conv.B_3.weight).t().contiguous()
+            if s["mask"] is not None:
+                dh = ops.mul23(dh, s["mask"], s["mask"])[0]
+            # h' = relu(norm_h(v)) + h_in
+            dv = torch.empty((n, H), dtype=torch.float32, device=dev)
+            if s["sc_h"] is None:
+                _, g[pfx + "bn_h.weight"], g[pfx + "bn_h.bias"] = ops.ln_bwd(dh, s["v"], d(conv.bn_h.weight), d(conv.bn_h.bias), out=dv)
+            else:
+                g[pfx + "bn_h.weight"], g[pfx + "bn_h.bias"] = train._bn_bwd(sh, dh, s["v"], s["sc_h"], s["sh_h"], s["mean_h"], s["rstd_h"], n, n, dv)
+            # v = A1h + fwd: the two node tables, then de += ... over the in-lists and dA2h over the out-lists
+            Tf, Uf = ops.mul23(dv, s["rdf"], s["hf"])
+            dA2 = ops.node_aggregate_in_bwd(s["e_new"], Tf, Uf, A2, views, de)
+            # e' = relu(norm_e(xe)) + e_in ;  xe = B1h[src] + B2h[dst] + e_in W3^T
+            amax_dxe = None
+            if s["sc_e"] is None:
+                dxe = torch.empty_like(de)
+                _, g[pfx + "bn_e.weight"], g[pfx + "bn_e.bias"] = ops.ln_bwd(de, s["xe"], d(conv.bn_e.weight), d(conv.bn_e.bias), out=dxe)
+            elif ops.can_fuse_bn_bwd_dgrad(de, W3t, s["xe"]):
+                # BatchNorm backward and d e_in = d e' + dxe W3 in one pass over the edges, as in the symmetric step
+                g[pfx + "bn_e.weight"], g[pfx + "bn_e.bias"], c1, c2 = train._bn_bwd(sh, de, s["xe"], s["sc_e"], s["sh_e"], s["mean_e"], s["rstd_e"],
+                                                                                     E2, E2, None, apply=False)
+                if train.SCALED_WGRAD and hasattr(ops, "can_dgrad_amax") and ops.can_dgrad_amax(de, s["xe"]):
+                    amax_dxe = torch.empty(1, dtype=torch.int32, device=dev)
+                dxe = ops.bn_bwd_dgrad(de, s["xe"], s["sc_e"], s["sh_e"], s["sc_e"], c1, c2, s["mean_e"], s["rstd_e"], W3t, rows_once=E2,
+                                       **({"amax": amax_dxe} if amax_dxe is not None else {}))
+                W3t = None
+            else:
+                dxe = torch.empty_like(de)
+                g[pfx + "bn_e.weight"], g[pfx + "bn_e.bias"] = train._bn_bwd(sh, de, s["xe"], s["sc_e"], s["sh_e"], s["mean_e"], s["rstd_e"],
+                                                                             E2, E2, dxe)
+            if W3t is not None:
+                ops.linear(dxe, W3t, None, out=de, accumulate=True)   # d e_in = d e' + dxe W3
+            dB2, dB1 = ops.segment_sum2(dxe, views, n)   # B2h was gathered by srt_dst (the in-lists), B1h by srt_src (the out-lists): one launch
+            parts = [dv, dA2, dB1, dB2]
+            names = ("A_1", "A_2", "B_1", "B_2")
+            WcatT = s["Wcat"].t().contiguous()
+            if ops.can_use_blocks(parts):   # the four [N,H] gradients stay where their kernels left them
+                dh = ops.linear_blocks(parts, WcatT, dh, accumulate=True)
+                gWcat, gbcat = ops.wgrad_blocks(parts, s["h"])            # [4H, H], [4H]
+                for k, name in enumerate(names):
+                    g[pfx + name + ".bias"] = gbcat[k * H:(k + 1) * H]
+            else:
+                dP = torch.cat(parts, 1)
+                dh = ops.linear(dP, WcatT, None, out=dh, accumulate=True)
+                for k, name in enumerate(names):
+                    g[pfx + name + ".bias"] = ops.colsum2(parts[k])[0]
+                gWcat = ops.wgrad(dP, s["h"])
+            for k, name in enumerate(names):
+                g[pfx + name + ".weight"] = gWcat[k * H:(k + 1) * H]
+            g[pfx + "B_3.weight"] = ops.wgrad(dxe, s["e"], amax=amax_dxe) if amax_dxe is not None else ops.wgrad(dxe, s["e"])
+            g[pfx + "B_3.bias"] = g[pfx + "B_2.bias"].clone()   # every edge has exactly one destination: sum_p dxe[p] = sum_i dB2[i]
+            saved[li] = s = None
+
+        # ---- encoders (full_graph.py:44-45); directed=False: the 2E rows of de reach each original edge's features twice, summed by the products
+        train.encoder_bwd(ops, g, dh, tail["x"], getattr(views, "node_gather", None), n, model.node_encoder.linear1, model.node_encoder.linear2,
+                          "node_encoder.linear1", "node_encoder.linear2")
+        train.encoder_bwd(ops, g, de, tail["e_raw"], sg.enc_gather, E2, model.edge_encoder.linear1, model.edge_encoder.linear2,
+                          "edge_encoder.linear1", "edge_encoder.linear2")
+        ctx.saved = ctx.tail = None
+        return (None, None, None, None, None) + tuple(g[name].contiguous() for name in ctx.names)
+
+
+def train_forward_in_edge(model, graph, x, e):
+    """`model(graph, x, e)` in train mode through the one-direction step (`GatedGCNModel.training_step = "in_edge"`), both `directed`
+    values; logits [E,1] on the compute device, differentiable with respect to the model's parameters.  Served: fp32 storage, both
+    norms, the built widths; a single process (multi-GPU shards are not)."""
+    from .train import TRAIN_SCORE_HIDDEN
+    check_arithmetic(model)
+    if getattr(model, "activation_storage", "fp32") != "fp32":
+        raise ValueError(f'training_step="in_edge" keeps activations as "fp32"; activation_storage={model.activation_storage!r} is served by '
+                         'training_step="symmetric"')
+    if getattr(model, "recompute_gate", False):
+        raise ValueError('training_step="in_edge" keeps the gate output; recompute_gate is served by training_step="symmetric"')
+    built_width(model.node_encoder.linear2.out_features)
+    built_width(model.predictor.W1.out_features, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")
+    device = engine.compute_device(x, e)
+    names, params = zip(*model.named_parameters())
+    if any(p.device != device for p in params):
+        raise RuntimeError("training needs the model on the compute device: call model.to(device) first")
+    views = views_for(graph, device, node_order="input")
+    if x.shape[0] != views.num_nodes or e.shape[0] != views.num_edges:
+        raise ValueError(f"x has {x.shape[0]} rows for {views.num_nodes} nodes, e has {e.shape[0]} rows for {views.num_edges} edges")
+    xd = x.detach().to(device=device, dtype=torch.float32).contiguous()
+    ed = e.detach().to(device=device, dtype=torch.float32).contiguous()
+    out = _InEdgeStep.apply(model, _StepGraph(in_edge_views(views), bool(model.directed)), xd, ed, list(names), *params)
     views.check_range()
     return out

@@ -64,12 +64,15 @@ class GatedGCNModel(nn.Module):
     list and scores the original graph (full_graph.py:47-51).  Built widths only: hidden_features in {64, 128, 256},
     hidden_edge_scores in {32, 64, 128}; `arithmetic` "auto" / "fast" (the matrix-core kernels) - "reference" raises.
 
-    Train mode (directed=True) goes through the SYMMETRIC model's training step with a zero A_3 per layer - zero tensors, not
-    Parameters, never updated: exact for every parameter this model has, and it costs what the symmetric step costs (the out-edge
-    pass and the fifth projection block run on zeros); a one-direction backward is not built."""
+    Train mode, `training_step = "symmetric"` (the default; directed=True only): the SYMMETRIC model's training step with a zero A_3 per
+    layer - zero tensors, not Parameters, never updated: exact for every parameter this model has, and it costs what the symmetric step
+    costs (the out-edge pass and the fifth projection block run on zeros).  `training_step = "in_edge"` (set it on the instance or on a
+    subclass): the one-direction step - a [N,4H] projection, gnnome_node_aggregate_in_raw_f32 and its backward
+    gnnome_node_aggregate_in_bwd_f32 - for both `directed` values; fp32 storage, no recompute_gate.  Any other value raises ValueError."""
     arithmetic = "auto"
     activation_storage = "fp32"
     range_check = True
+    training_step = "symmetric"
 
     def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, num_layers, hidden_edge_scores,
                  normalization, dropout=None, directed=True):

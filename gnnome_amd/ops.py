@@ -1052,6 +1052,37 @@ def node_aggregate_raw(e, A1h, A2h, A3h, views, mode, num_nodes, rows_alloc=None
     return (v, a0, a1, a2, a3) if mode == 1 else (a0, a2)
 
 
+def node_aggregate_in_raw(e, A1h, A2h, views, num_nodes=None):
+    """-> (v, fwd, rden): the GatedGCN layer's aggregation without the node epilogue (gnnome_node_aggregate_in_raw_f32) - mode 1 of
+    node_aggregate_raw over the in-edges alone: v = A1h + fwd, fwd = sum_in s*A2h[src] / (sum_in s + 1e-6), rden = 1 / (sum_in s + 1e-6)."""
+    A1h, ldn = _rows(A1h, "node_aggregate_in_raw.A1h")
+    A2h, l2 = _rows(A2h, "node_aggregate_in_raw.A2h")
+    assert ldn == l2
+    e = _dense(e, "node_aggregate_in_raw.e")
+    H, dev = A2h.shape[1], A2h.device
+    n = views.num_nodes if num_nodes is None else num_nodes
+    v, fwd, rden = (torch.empty((n, H), dtype=torch.float32, device=dev) for _ in range(3))
+    _call("gnnome_node_aggregate_in_raw_f32", dev, _ptr(e), H, n, _ptr(A1h), _ptr(A2h), ldn, _ptr(views.in_ptr), _ptr(views.srt_src),
+          _ptr(v), _ptr(fwd), _ptr(rden))
+    return v, fwd, rden
+
+
+def node_aggregate_in_bwd(e, Tf, Uf, A2h, views, de, out=None):
+    """The gradient of node_aggregate_in_raw (gnnome_node_aggregate_in_bwd_f32) from Tf = dv*rden, Uf = Tf*fwd (mul23):
+    de += s(1-s) * (Tf[dst]*A2h[src] - Uf[dst]) in place; returns dA2h[N,H] = sum over out-edges of s * Tf[dst]."""
+    A2h, ldn = _rows(A2h, "node_aggregate_in_bwd.A2h")
+    e, de = _dense(e, "node_aggregate_in_bwd.e"), _dense(de, "node_aggregate_in_bwd.de")
+    Tf, Uf = _dense(Tf, "node_aggregate_in_bwd.Tf"), _dense(Uf, "node_aggregate_in_bwd.Uf")
+    H, n = e.shape[1], views.num_nodes
+    if Tf.shape != (n, H) or Uf.shape != (n, H) or de.shape != e.shape or e.shape[0] != views.num_edges:
+        raise ValueError(f"node_aggregate_in_bwd: shapes e{tuple(e.shape)} de{tuple(de.shape)} Tf{tuple(Tf.shape)} Uf{tuple(Uf.shape)} "
+                         f"for {n} nodes and {views.num_edges} edges")
+    dA2h = torch.empty((n, H), dtype=torch.float32, device=e.device) if out is None else _dense(out, "node_aggregate_in_bwd.out")
+    _call("gnnome_node_aggregate_in_bwd_f32", e.device, _ptr(e), e.shape[0], H, n, _ptr(Tf), _ptr(Uf), _ptr(A2h), ldn, _ptr(views.in_ptr),
+          _ptr(views.srt_src), _ptr(views.out_ptr), _ptr(views.out_pos), _ptr(views.out_dst), _ptr(de), _ptr(dA2h))
+    return dA2h
+
+
 _COL_WS = {}
 
 

@@ -344,7 +344,9 @@ def train(train_set, valid_set, out=None, hyperparameters=None, overfit=False, d
     configs/hyperparameters.py by the reference's key names.  `trace` (for tests): a list that receives the initial state dict and
     one dict per step (graph, mask fraction, the step's full-graph node and edge ids, its edges, loss and counts; the first training
     step's gradients) - it copies to the host per step.  `model_class`: the model to train, SymGatedGCNModel, GatedGCNModel, GCNModel or
-    SAGEModel (same constructor arguments)."""
+    SAGEModel (same constructor arguments).  A GatedGCNModel subclass that sets `training_step = "in_edge"` (and, if it wants the doubled
+    graph, passes directed=False to the base constructor) trains through `_model_step` like any other model: its own call selects the
+    one-direction step (engine_gated.train_forward_in_edge)."""
     hp = hyperparameters_with(hyperparameters)
     seed = hp["seed"] if seed is None else seed
     dropout = hp["dropout"] if dropout is None else dropout

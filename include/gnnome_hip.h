@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 29
+#define GNNOME_ABI_VERSION 30
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -263,6 +263,32 @@ int gnnome_node_aggregate_in_range_f32(const float* e, int hidden, int64_t num_n
                                        const float* A1h, const float* A2h, int ld_node, const int32_t* in_ptr, const int32_t* srt_src,
                                        const float* h_in, int ld_h, float* h_out, int norm_kind, const float* norm_scale,
                                        const float* norm_shift, void* stream);
+
+/* The same aggregation WITHOUT the node epilogue, with the two node tables its backward needs - the train-mode forward of the GatedGCN
+ * layer, gated_gcn_full.py:212-215 (sigmoid, the update_all pair, the divide) and :217 (the sum with A1h); the one-direction form of mode 1
+ * of gnnome_node_aggregate_raw_f32.  For every node i < num_nodes:
+ *   aux0[i,:]  = fwd = sum_{p in in(i)} s_p * A2h[srt_src[p],:] / (sum_{p in in(i)} s_p + 1e-6)
+ *   aux1[i,:]  = 1 / (sum_{p in in(i)} s_p + 1e-6)
+ *   v_out[i,:] = A1h[i,:] + fwd
+ * v_out, aux0, aux1 dense [num_nodes, H]; everything else as for gnnome_node_aggregate_in_f32 (same lane mapping and association:
+ * lists above 4096 items in fixed 128-item blocks).  On nodes of at most 4096 in-edges the three outputs equal mode 1's with an all-zero
+ * A3h table bit for bit. */
+int gnnome_node_aggregate_in_raw_f32(const float* e, int hidden, int64_t num_nodes, const float* A1h, const float* A2h, int ld_node,
+                                     const int32_t* in_ptr, const int32_t* srt_src, float* v_out, float* aux0, float* aux1,
+                                     void* stream);
+
+/* The gradient of that aggregation - what torch autograd and DGL's backward kernels run for gated_gcn_full.py:212-215 under
+ * loss.backward() (train.py:329).  Tf = dv * aux1 and Uf = Tf * aux0 are dense [num_nodes, H] (gnnome_mul23_f32), s_p = sigmoid(e[p,:]):
+ *   de[p,:]   += s_p (1 - s_p) * (Tf[dst_p,:] * A2h[srt_src[p],:] - Uf[dst_p,:])       every edge p   (dst_p: the node whose in-list holds p)
+ *   dA2h[j,:]  = sum_{q in out(j)} s_{out_pos[q]} * Tf[out_dst[q],:]                    every node j   (dense [num_nodes, H], overwritten)
+ * - the first half of gnnome_agg_edge_bwd_f32 and aux2 of mode 2 of gnnome_node_aggregate_raw_f32.  Two launches (one wave per
+ * destination, one wave per source), no atomics, no scratch, fp32; the association depends on the graph alone (lists above 4096 items in
+ * fixed 128-item blocks).  hidden in {64,128,256}; ld_node: the row stride of A2h.  num_nodes == 0: a no-op; num_edges == 0: dA2h is
+ * zeroed and de is not touched.  de must not alias e. */
+int gnnome_node_aggregate_in_bwd_f32(const float* e, int64_t num_edges, int hidden, int64_t num_nodes, const float* Tf, const float* Uf,
+                                     const float* A2h, int ld_node, const int32_t* in_ptr, const int32_t* srt_src,
+                                     const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, float* de, float* dA2h,
+                                     void* stream);
 
 /* ---- unweighted, degree-normalised neighbour sum: the message passing of GCNModel and SAGEModel -------
  * For every node i < num_nodes:
