@@ -113,6 +113,9 @@ SIGNATURES = {
     "gnnome_gate_center_f32": [_p, _l, _i, _p, _p, _i, _p, _p, _p, _i, _p, _p],
     "gnnome_greedy_walks_workspace_bytes": [_l, _i, ctypes.POINTER(_sz)],
     "gnnome_greedy_walks": [_p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _sz, _p],
+    "gnnome_greedy_walks_opts": [_p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _sz, ctypes.c_float, _i, _l,
+                                 _p],
+    "gnnome_candidate_table": [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p],
     "gnnome_mark_walk_visited": [_p, _p, _p, _l, _p, _p],
     "gnnome_overlap_workspace_bytes": [ctypes.POINTER(_sz)],
     "gnnome_overlap_edit_distance": [_p, _p, _l, _p, _i, _p, _p, _p, _l, _p, _p, _p, _sz, _p],
@@ -152,7 +155,7 @@ SIGNATURES = {
     "gnnome_pr_curve_ap": [_p, _p, _l, _p, _p, _sz, _p],
 }
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 
 # the parameter blocks of gnnome_model_forward_f32 (include/gnnome_hip.h), field for field

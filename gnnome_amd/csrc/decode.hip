@@ -25,6 +25,25 @@
 // on a tie among fewer than 64 candidates lane 0 replays that introselect over the candidates in LDS (nth0_libstdcxx;
 // checked against torch.topk on 40k random tied lists), so the walks are the reference's walks on ties as well
 // (tests/test_decode.py, golden case "ties").
+//
+// The reference's two decoder switches (inference.py:26-28), through gnnome_greedy_walks_opts; gnnome_greedy_walks is that entry
+// with both off and runs the kernel instantiation without them (OPTS = false: the code of the entry before the switches).
+//
+//   early_stopping / p_threshold  inference.py:98-100, :142-145   in the RANKED branch only (a list of 2 or more with an admissible
+//       successor): if every admissible successor's log-probability is below log(p_threshold) the walk ends at the current node,
+//       which is already in the walk and in the visited set; nothing is added to the sum.  "all below" is "the maximum below", and
+//       the maximum is what the ranking reduction leaves in every lane.  The reference compares an fp32 tensor with the Python
+//       double math.log(p_threshold); torch rounds the double to fp32 and compares in fp32, so `stop_logp` is that fp32 value and a
+//       log-probability EQUAL to it does not stop the walk.  -infinity is "off": nothing is below it.  A single successor (:84-91)
+//       is taken however improbable its edge is.
+//   RANDOM                        inference.py:102-104, :147-149  after the early-stopping test, position j of the n admissible
+//       successors in list order is taken and ITS log-probability added.  DELIBERATE DIVERGENCE: the reference draws
+//       torch.randint from the CPU generator once per step, candidate after candidate - a stream no wave can replay.  Here
+//           key = candidate << 32 | half << 31 | step      half 0 = forward, 1 = backward; step = the iteration of the walk loop
+//           u   = mix64(seed + (key + 1) * 0x9E3779B97F4A7C15)    the (key + 1)-th output of splitmix64 seeded with `seed`
+//           j   = ((u >> 32) * n) >> 32
+//       a pure function of its four arguments: the same seed gives the same walks whatever the scheduling
+//       (tests/decode_switch_statement.py states it on Python integers).
 #include "common.h"
 
 namespace gnnome {
@@ -39,6 +58,26 @@ struct WalkGraph {
     const uint8_t* visited;     // [N]    nodes consumed by earlier contigs (inference.py:173, :334)
     int64_t num_nodes;
 };
+
+struct WalkOpts {
+    float stop_logp;   // fp32(log(p_threshold)); -INFINITY = early stopping off
+    int random;        // 0 = rank (torch.topk), 1 = the seeded draw
+    uint64_t seed;
+    uint32_t cand, half;
+};
+
+// The finaliser of splitmix64.
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ int walk_draw(const WalkOpts& o, int step, int n) {
+    const uint64_t key = ((uint64_t)o.cand << 32) | ((uint64_t)o.half << 31) | (uint64_t)(uint32_t)step;
+    const uint64_t u = mix64(o.seed + (key + 1ull) * 0x9E3779B97F4A7C15ull);
+    return (int)(((u >> 32) * (uint64_t)(uint32_t)n) >> 32);
+}
 
 constexpr int kTieCap = 64;   // torch.topk(k = 1) takes std::nth_element below 64 candidates, std::partial_sort (= first maximum) from 64 up
 
@@ -108,9 +147,10 @@ __device__ __forceinline__ bool bit_test(const uint32_t* bits, int node) {
 // Returns the number of nodes written to `out`; `sum` accumulates the chosen log-probabilities in fp32 in walk order
 // like the reference's `sumLogProb +=`, `plen` the prefix lengths of the contig's edges: of the edges walked (forward),
 // or of their mates (nb ^ 1 -> cur ^ 1) when MATES (the backward half is reversed and complemented afterwards, :157).
-template <bool MATES>
+// OPTS: the early-stopping test and the random choice of `opt` (header of this file); without it `opt` is not read.
+template <bool MATES, bool OPTS>
 __device__ int greedy_walk(const WalkGraph& g, uint32_t* bits, int start, int s, int d, int32_t* out, int cap, float& sum,
-                           int64_t& plen, int& status, int& last, float* tie_v, int* tie_p) {
+                           int64_t& plen, int& status, int& last, float* tie_v, int* tie_p, const WalkOpts& opt) {
     const int lane = threadIdx.x & 63;
     int current = start, len = 0;
     last = start;
@@ -176,7 +216,25 @@ __device__ int greedy_walk(const WalkGraph& g, uint32_t* bits, int start, int s,
                 }
             }
             if (best_pos == 0x7fffffff) break;   // :93-94 every successor is visited
-            if (n_best > 1 && n_cand < kTieCap) {
+            if (OPTS && best < opt.stop_logp) break;   // :98-100 every admissible successor is improbable (fp32 compare, wave-uniform)
+            if (OPTS && opt.random) {            // :102-104 the j-th admissible successor in list order, j drawn from (seed, c, half, step)
+                const int j = walk_draw(opt, len - 1, n_cand);
+                int seen = 0;
+                for (int base = 0; base < deg; base += 64) {   // the first pass again, up to the chunk that holds position j
+                    const int i = base + lane;
+                    const bool ok = i < deg && !excluded(g.succ_nbr[row + i]);
+                    const unsigned long long mask = __ballot(ok);
+                    const int here = __popcll(mask);
+                    if (j < seen + here) {
+                        const bool hit = ok && seen + __popcll(mask & ((1ull << lane) - 1ull)) == j;
+                        const int from = __ffsll((long long)__ballot(hit)) - 1;   // exactly one lane
+                        best_pos = __shfl(i, from);
+                        best = __shfl(hit ? g.logp[g.succ_eid[row + i]] : 0.f, from);
+                        break;
+                    }
+                    seen += here;
+                }
+            } else if (n_best > 1 && n_cand < kTieCap) {
                 __syncthreads();                 // (one wave per block) the LDS writes above are in place
                 if (lane == 0) nth0_libstdcxx(tie_v, tie_p, n_cand);
                 __syncthreads();
@@ -213,11 +271,13 @@ __device__ int greedy_walk(const WalkGraph& g, uint32_t* bits, int start, int s,
 }
 
 // One wave per candidate start edge (src, dst, eid): inference.py:161-165 (run_greedy_both_ways) + :29-36.
+template <bool OPTS>
 __global__ __launch_bounds__(64) void k_greedy_walks(WalkGraph g, const int32_t* __restrict__ cand_src, const int32_t* __restrict__ cand_dst,
                                                      const int32_t* __restrict__ cand_eid, int num_cand, uint32_t* bitmaps,
                                                      int64_t words_per_cand, int32_t* walks_f, int32_t* walks_b, int64_t cap,
                                                      int32_t* len_f, int32_t* len_b, float* sum_f, float* sum_b,
-                                                     int64_t* contig_len, int32_t* status_out) {
+                                                     int64_t* contig_len, int32_t* status_out, float stop_logp, int random,
+                                                     uint64_t seed) {
     const int c = blockIdx.x;
     if (c >= num_cand) return;
     const int s = cand_src[c], d = cand_dst[c];
@@ -228,8 +288,10 @@ __global__ __launch_bounds__(64) void k_greedy_walks(WalkGraph g, const int32_t*
     __shared__ float tie_v[kTieCap];
     __shared__ int tie_p[kTieCap];
     int last = d, last_b = 0;
-    const int lf = greedy_walk<false>(g, bits, d, s, d, walks_f + (int64_t)c * cap, (int)cap, sf, plen, status, last, tie_v, tie_p);
-    const int lb = greedy_walk<true>(g, bits, s ^ 1, s, d, walks_b + (int64_t)c * cap, (int)cap, sb, plen, status, last_b, tie_v, tie_p);
+    WalkOpts opt{stop_logp, random, seed, (uint32_t)c, 0u};
+    const int lf = greedy_walk<false, OPTS>(g, bits, d, s, d, walks_f + (int64_t)c * cap, (int)cap, sf, plen, status, last, tie_v, tie_p, opt);
+    opt.half = 1u;
+    const int lb = greedy_walk<true, OPTS>(g, bits, s ^ 1, s, d, walks_b + (int64_t)c * cap, (int)cap, sb, plen, status, last_b, tie_v, tie_p, opt);
     if ((threadIdx.x & 63) == 0) {
         len_f[c] = lf;
         len_b[c] = lb;
@@ -238,6 +300,36 @@ __global__ __launch_bounds__(64) void k_greedy_walks(WalkGraph g, const int32_t*
         contig_len[c] = plen + g.read_len[last];
         status_out[c] = status;
     }
+}
+
+// The figures the reference prints for every candidate (inference.py:267-296), one thread per candidate, in the doubles Python
+// computes them in: sumLogProb = sum_f.item() + sum_b.item(), mean = sum / (len_walk - 2), scaled = mean / sqrt(len_contig), each one
+// correctly rounded IEEE operation.  table[7, P] rows: src, dst, len_walk, len_contig, sumLogProb, meanLogProb, meanLogProb_scaled.
+__global__ void k_candidate_table(const int32_t* __restrict__ cand_src, const int32_t* __restrict__ cand_dst, const int32_t* __restrict__ len_f,
+                                  const int32_t* __restrict__ len_b, const float* __restrict__ sum_f, const float* __restrict__ sum_b,
+                                  const int64_t* __restrict__ contig_len, int num_cand, double* __restrict__ table) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= num_cand) return;
+    const int s = cand_src[c], d = cand_dst[c];
+    int len_walk = len_f[c] + len_b[c];
+    int64_t len_contig = contig_len[c];
+    double sum = __dadd_rn((double)sum_f[c], (double)sum_b[c]), mean = 0.0, scaled = 0.0;
+    if (s == d) len_walk = 1;                                   // :271-272
+    if (len_walk > 2) {                                         // :273-280
+        mean = __ddiv_rn(sum, (double)(len_walk - 2));
+        if (len_contig > 0) scaled = __ddiv_rn(mean, __dsqrt_rn((double)len_contig));
+    } else if (len_walk < 2) {                                  // :289-294 a self-loop start edge: everything 0
+        len_contig = 0;
+        sum = 0.0;
+    }                                                           // :281-288 len_walk == 2: mean 0, scaled 0 / sqrt(len_contig) = 0
+    const int64_t p = num_cand;
+    table[c] = (double)s;
+    table[p + c] = (double)d;
+    table[2 * p + c] = (double)len_walk;
+    table[3 * p + c] = (double)len_contig;
+    table[4 * p + c] = sum;
+    table[5 * p + c] = mean;
+    table[6 * p + c] = scaled;
 }
 
 // After a walk has been chosen (inference.py:304-334): every node of the walk and its mate, plus the nodes the walk
@@ -277,13 +369,15 @@ extern "C" int gnnome_greedy_walks_workspace_bytes(int64_t num_nodes, int num_ca
     return GNNOME_OK;
 }
 
-extern "C" int gnnome_greedy_walks(const int32_t* succ_ptr, const int32_t* succ_nbr, const int32_t* succ_eid, const float* logp,
-                                   const int32_t* prefix_len, const int32_t* read_len, const uint8_t* visited, int64_t num_nodes,
-                                   const int32_t* cand_src, const int32_t* cand_dst, const int32_t* cand_eid, int num_candidates,
-                                   int32_t* walks_f, int32_t* walks_b, int64_t capacity, int32_t* len_f, int32_t* len_b, float* sum_f,
-                                   float* sum_b, int64_t* contig_len, int32_t* status, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
+extern "C" int gnnome_greedy_walks_opts(const int32_t* succ_ptr, const int32_t* succ_nbr, const int32_t* succ_eid, const float* logp,
+                                        const int32_t* prefix_len, const int32_t* read_len, const uint8_t* visited, int64_t num_nodes,
+                                        const int32_t* cand_src, const int32_t* cand_dst, const int32_t* cand_eid, int num_candidates,
+                                        int32_t* walks_f, int32_t* walks_b, int64_t capacity, int32_t* len_f, int32_t* len_b, float* sum_f,
+                                        float* sum_b, int64_t* contig_len, int32_t* status, void* workspace, size_t workspace_bytes,
+                                        float stop_logp, int choice_mode, int64_t seed, void* stream) {
     using namespace gnnome;
+    GN_REQUIRE(choice_mode == 0 || choice_mode == 1, "greedy_walks: choice_mode is 0 (rank) or 1 (random)");
+    GN_REQUIRE(stop_logp == stop_logp, "greedy_walks: stop_logp is NaN (fp32 log(p_threshold), or -infinity for off)");
     GN_REQUIRE(num_nodes >= 0 && num_candidates >= 0 && capacity >= 1, "greedy_walks: bad sizes");
     if (num_candidates == 0) return GNNOME_OK;
     GN_REQUIRE(num_nodes % 2 == 0, "greedy_walks: nodes come in (read, reverse complement) pairs, N must be even");
@@ -296,8 +390,35 @@ extern "C" int gnnome_greedy_walks(const int32_t* succ_ptr, const int32_t* succ_
     hipStream_t s = (hipStream_t)stream;
     GN_HIP(hipMemsetAsync(workspace, 0, (size_t)num_candidates * (size_t)words * sizeof(uint32_t), s));
     WalkGraph g{succ_ptr, succ_nbr, succ_eid, logp, prefix_len, read_len, visited, num_nodes};
-    hipLaunchKernelGGL(k_greedy_walks, dim3((unsigned)num_candidates), dim3(64), 0, s, g, cand_src, cand_dst, cand_eid, num_candidates,
-                       (uint32_t*)workspace, words, walks_f, walks_b, capacity, len_f, len_b, sum_f, sum_b, contig_len, status);
+    // both switches off: the instantiation without them - the walk code as it was before they existed, bit for bit and cycle for cycle
+    const bool opts = choice_mode != 0 || stop_logp > -INFINITY;
+    hipLaunchKernelGGL(opts ? k_greedy_walks<true> : k_greedy_walks<false>, dim3((unsigned)num_candidates), dim3(64), 0, s, g, cand_src,
+                       cand_dst, cand_eid, num_candidates, (uint32_t*)workspace, words, walks_f, walks_b, capacity, len_f, len_b, sum_f, sum_b,
+                       contig_len, status, stop_logp, choice_mode, (uint64_t)seed);
+    GN_LAUNCH_CHECK();
+    return GNNOME_OK;
+}
+
+extern "C" int gnnome_greedy_walks(const int32_t* succ_ptr, const int32_t* succ_nbr, const int32_t* succ_eid, const float* logp,
+                                   const int32_t* prefix_len, const int32_t* read_len, const uint8_t* visited, int64_t num_nodes,
+                                   const int32_t* cand_src, const int32_t* cand_dst, const int32_t* cand_eid, int num_candidates,
+                                   int32_t* walks_f, int32_t* walks_b, int64_t capacity, int32_t* len_f, int32_t* len_b, float* sum_f,
+                                   float* sum_b, int64_t* contig_len, int32_t* status, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    return gnnome_greedy_walks_opts(succ_ptr, succ_nbr, succ_eid, logp, prefix_len, read_len, visited, num_nodes, cand_src, cand_dst, cand_eid,
+                                    num_candidates, walks_f, walks_b, capacity, len_f, len_b, sum_f, sum_b, contig_len, status, workspace,
+                                    workspace_bytes, -INFINITY, 0, 0, stream);
+}
+
+extern "C" int gnnome_candidate_table(const int32_t* cand_src, const int32_t* cand_dst, const int32_t* len_f, const int32_t* len_b,
+                                      const float* sum_f, const float* sum_b, const int64_t* contig_len, int num_candidates, double* table,
+                                      void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_candidates >= 0, "candidate_table: bad size");
+    if (num_candidates == 0) return GNNOME_OK;
+    GN_REQUIRE(cand_src && cand_dst && len_f && len_b && sum_f && sum_b && contig_len && table, "candidate_table: null pointer");
+    hipLaunchKernelGGL(k_candidate_table, dim3((unsigned)((num_candidates + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cand_src, cand_dst,
+                       len_f, len_b, sum_f, sum_b, contig_len, num_candidates, table);
     GN_LAUNCH_CHECK();
     return GNNOME_OK;
 }

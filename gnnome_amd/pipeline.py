@@ -47,29 +47,34 @@ def _read(path, similarity, parser, device, long_overlaps=False):
 
 
 def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto", device=None, scores=None, sampler=None, parser="host",
-             long_overlaps=False):
+             long_overlaps=False, early_stopping=False, p_threshold=0.06, random_walks=False, seed=None):
     """-> (walks, scores, graph dict).  `scores` overrides the model (inference.py:426-432: saved predictions / labels).
     parser: how a GFA path is read (gfa.read_gfa's parser=; with "device" the graph's tensors stay on the device).
-    long_overlaps: gfa.read_gfa's keyword - True lets a GFA with overlaps beyond 65 536 bases (ultra-long ONT reads) through."""
+    long_overlaps: gfa.read_gfa's keyword - True lets a GFA with overlaps beyond 65 536 bases (ultra-long ONT reads) through.
+    early_stopping, p_threshold, random_walks, seed: decode.decode_contigs' keywords (the reference's decoder switches,
+    inference.py:26-28); the ablation's constant scores are scores=decode.constant_scores(g)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     g = gfa_or_graph if isinstance(gfa_or_graph, dict) else _read(gfa_or_graph, similarity, parser, device, long_overlaps)
     if scores is None:
         scores = score_graph(g, model, device)
     prefix = g["prefix_length"].masked_fill(g["prefix_length"] < 0, 0)      # inference.py:461
     dg = decode.DecodeGraph(g["src"], g["dst"], g["num_nodes"], prefix, g["read_length"], device=device).set_scores(scores)
-    return decode.decode_contigs(dg, len_threshold, nb_paths=nb_paths, sampler=sampler), scores, g
+    walks = decode.decode_contigs(dg, len_threshold, nb_paths=nb_paths, sampler=sampler, early_stopping=early_stopping,
+                                  p_threshold=p_threshold, random_walks=random_walks, seed=seed)
+    return walks, scores, g
 
 
 def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, nb_paths=100, similarity="auto", device=None, scores=None,
                       sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, parser="host", reads_parser="host",
-                      long_overlaps=False):
+                      long_overlaps=False, early_stopping=False, p_threshold=0.06, random_walks=False, seed=None):
     """GFA -> scores -> greedy walks -> contigs spelled on the device -> FASTA at out_path (inference.py:411-489).
     -> (walks, contigs, stats); stats = quick_evaluation's figures as a dict (ref_length from the caller: NG50 and the
     reconstructed fraction are -1 without it).  Sequences: the GFA's S lines if it carries them, else `reads` (a FASTA / FASTQ
     path, plain or .gz, or a ReadStore); with neither this raises before any scoring.  Only the reads the walks touch are
     uploaded.  The prefixes are masked as pipeline.assemble masks them (inference.py:461).  parser="device" / "auto": the GFA is read
     once, by gfa.read_gfa_device, and its sequences are the packed reads that parse left on the device, restricted to the touched ones.
-    reads_parser: how a `reads` file is read (ReadStore.from_reads_file's parser=).  long_overlaps: as in assemble."""
+    reads_parser: how a `reads` file is read (ReadStore.from_reads_file's parser=).  long_overlaps, early_stopping, p_threshold,
+    random_walks, seed: as in assemble."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     gfa_path = None if isinstance(gfa_or_graph, dict) else gfa_or_graph
     if gfa_path is not None and parser != "host":
@@ -95,7 +100,7 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
         raise ValueError("no read sequences: the GFA's S lines say '*' (or a graph dict was passed) and no `reads` was given")
     g = gfa_or_graph if isinstance(gfa_or_graph, dict) else gfa.read_gfa(gfa_or_graph, similarity=similarity, long_overlaps=long_overlaps)
     walks, scores, g = assemble(g, model, len_threshold, nb_paths=nb_paths, similarity=similarity, device=device, scores=scores,
-                                sampler=sampler)
+                                sampler=sampler, early_stopping=early_stopping, p_threshold=p_threshold, random_walks=random_walks, seed=seed)
     touched = sorted({v >> 1 for w in walks for v in w})
     if source == "store":
         store = reads

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 30
+#define GNNOME_ABI_VERSION 31
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -821,6 +821,35 @@ int gnnome_greedy_walks(const int32_t* succ_ptr, const int32_t* succ_nbr, const 
                         const int32_t* cand_src, const int32_t* cand_dst, const int32_t* cand_eid, int num_candidates,
                         int32_t* walks_f, int32_t* walks_b, int64_t capacity, int32_t* len_f, int32_t* len_b, float* sum_f,
                         float* sum_b, int64_t* contig_len, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The same launch with the reference's two decoder switches (inference.py:26-28); gnnome_greedy_walks is this entry with
+ * stop_logp = -infinity, choice_mode = 0, and with those values the outputs are bit-identical to it.
+ *   stop_logp    early_stopping / p_threshold (inference.py:98-100, :142-145): fp32(log(p_threshold)), or -infinity for off.  In
+ *                the ranked branch only - a successor list of 2 or more with an admissible successor - a walk (either half) ends
+ *                at its current node when EVERY admissible successor has logp < stop_logp.  The reference compares an fp32 tensor
+ *                with a Python double, which torch rounds to fp32 first: the compare here is that fp32 compare, and a logp equal
+ *                to stop_logp does not stop.  A single successor (:84-91) is taken however improbable.  Nothing is added to the
+ *                sum at a stop; contig_len is computed as for any other end of walk; status is unchanged.
+ *   choice_mode  0 = rank (torch.topk, as above); 1 = RANDOM (inference.py:102-104, :147-149): after the early-stopping test, the
+ *                j-th of the n admissible successors in list order is taken and its own logp added.
+ *   seed         DELIBERATE DIVERGENCE from the reference, which draws torch.randint from the CPU generator once per step and
+ *                candidate after candidate - no wave can replay that stream.  Here j is a pure function of (seed, candidate index c,
+ *                half, step): key = c << 32 | half << 31 | step (half 0 forward / 1 backward; step = the iteration of that half's
+ *                walk loop, every iteration counted), u = mix64(seed + (key + 1) * 0x9E3779B97F4A7C15) with mix64 the finaliser of
+ *                splitmix64 - the (key + 1)-th output of splitmix64 seeded with `seed`, the int64 taken as its 64 bits - and
+ *                j = ((u >> 32) * n) >> 32.  The same seed gives the same walks whatever the scheduling.  Ignored in mode 0. */
+int gnnome_greedy_walks_opts(const int32_t* succ_ptr, const int32_t* succ_nbr, const int32_t* succ_eid, const float* logp,
+                             const int32_t* prefix_len, const int32_t* read_len, const uint8_t* visited, int64_t num_nodes,
+                             const int32_t* cand_src, const int32_t* cand_dst, const int32_t* cand_eid, int num_candidates,
+                             int32_t* walks_f, int32_t* walks_b, int64_t capacity, int32_t* len_f, int32_t* len_b, float* sum_f,
+                             float* sum_b, int64_t* contig_len, int32_t* status, void* workspace, size_t workspace_bytes,
+                             float stop_logp, int choice_mode, int64_t seed, void* stream);
+/* The figures the reference prints for every candidate (inference.py:267-296) from one launch's outputs, in the doubles Python
+ * computes them in.  table: double[7, P], rows src, dst, len_walk, len_contig, sumLogProb, meanLogProb, meanLogProb_scaled:
+ * len_walk = len_f + len_b, 1 for a self-loop start edge (then every figure is 0); sumLogProb = (double)sum_f + (double)sum_b;
+ * meanLogProb = sumLogProb / (len_walk - 2), 0 at len_walk 2; scaled = meanLogProb / sqrt(len_contig), 0 where len_contig <= 0. */
+int gnnome_candidate_table(const int32_t* cand_src, const int32_t* cand_dst, const int32_t* len_f, const int32_t* len_b,
+                           const float* sum_f, const float* sum_b, const int64_t* contig_len, int num_candidates, double* table,
+                           void* stream);
 /* visited[n] = visited[n^1] = 1 for every node of `walk` and for every node it jumped over: for consecutive (ss, dd),
  * succs[ss] & preds[dd] and their mates (inference.py:313-318, :334). */
 int gnnome_mark_walk_visited(const int32_t* succ_ptr, const int32_t* succ_nbr, const int32_t* walk, int64_t walk_len,
