@@ -41,6 +41,8 @@ SIGNATURES = {
     "gnnome_node_aggregate_in_range_f32": [_p, _i, _l, _l, _l, _p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _p, _p],
     "gnnome_node_aggregate_in_raw_f32": [_p, _i, _l, _p, _p, _i, _p, _p, _p, _p, _p, _p],
     "gnnome_node_aggregate_in_bwd_f32": [_p, _l, _i, _l, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "gnnome_node_aggregate_in_raw_part_f32": [_p, _i, _l, _l, _p, _p, _i, _p, _p, _p, _p, _p, _p],
+    "gnnome_node_aggregate_in_bwd_part_f32": [_p, _l, _i, _l, _l, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
     "gnnome_node_neighbour_sum_f32": [_p, _i, _i, _l, _p, _p, _p, _p, _p, _p, _p, _i, _p],
     "gnnome_relu_rows_f32": [_p, _i, _l, _i, _p],
     "gnnome_node_neighbour_sum_bwd_f32": [_p, _i, _i, _l, _p, _p, _p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p],
@@ -155,7 +157,7 @@ SIGNATURES = {
     "gnnome_pr_curve_ap": [_p, _p, _l, _p, _p, _sz, _p],
 }
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 
 # the parameter blocks of gnnome_model_forward_f32 (include/gnnome_hip.h), field for field

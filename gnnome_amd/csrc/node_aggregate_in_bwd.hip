@@ -12,6 +12,10 @@
 //       dA2h[j,:]  = sum_{q in out(j)} s_{out_pos[q]} * Tf[out_dst[q],:]                  every node j
 //     - the forward half of gnnome_agg_edge_bwd_f32 and aux2 of mode 2 of gnnome_node_aggregate_raw_f32 (tables Tb := 0, A3h := Tf).
 //
+//   gnnome_node_aggregate_in_raw_part_f32 / gnnome_node_aggregate_in_bwd_part_f32   the same two on one rank's shard of an in-edge-only
+//     destination-range partition: the kernels below launched with TWO row counts - the n_own owned destinations (which come first) and the
+//     n_local = owned + halo table rows.  See the entries at the end of the file.
+//
 // Reference lines replaced: gated_gcn_full.py:212-215 (sigmoid, DGL gspmm u_mul_e+sum and copy_e+sum, the divide) and :217 (A1h + ...)
 // in train mode, and what torch autograd + DGL's backward kernels (gsddmm / gspmm on the reversed graph) run for those lines under
 // loss.backward() (train.py:329).
@@ -292,19 +296,66 @@ static int launch_agg_in_raw(const float* e, int64_t n, const float* A1h, const 
     return GNNOME_OK;
 }
 
+// n_dst: the destinations whose in-lists are walked (Tf / Uf rows); n_src: the sources whose out-lists are walked (dA2h rows).  The whole
+// graph: both its node count.  A shard of a destination-range partition: n_dst owned rows, n_src owned + halo rows.
 template <int H>
-static int launch_agg_in_bwd(const float* e, int64_t n, const float* Tf, const float* Uf, const float* A2h, int ldn, const int32_t* in_ptr,
-                             const int32_t* ss, const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, float* de, float* dA2h,
-                             hipStream_t s) {
+static int launch_agg_in_bwd(const float* e, int64_t n_dst, int64_t n_src, const float* Tf, const float* Uf, const float* A2h, int ldn,
+                             const int32_t* in_ptr, const int32_t* ss, const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst,
+                             float* de, float* dA2h, hipStream_t s) {
     int64_t blocks;
-    if (int rc = inb_blocks(n, "node_aggregate_in_bwd", &blocks)) return rc;
-    hipLaunchKernelGGL((k_agg_in_bwd_dst<H>), dim3((unsigned)blocks), dim3(kAggInbThreads), 0, s, e, n, Tf, Uf, A2h, ldn, in_ptr, ss, de,
+    if (int rc = inb_blocks(n_dst, "node_aggregate_in_bwd", &blocks)) return rc;
+    hipLaunchKernelGGL((k_agg_in_bwd_dst<H>), dim3((unsigned)blocks), dim3(kAggInbThreads), 0, s, e, n_dst, Tf, Uf, A2h, ldn, in_ptr, ss, de,
                        (int)blocks);
     GN_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_agg_in_bwd_src<H>), dim3((unsigned)blocks), dim3(kAggInbThreads), 0, s, e, n, Tf, out_ptr, out_pos, out_dst, dA2h,
+    if (int rc = inb_blocks(n_src, "node_aggregate_in_bwd", &blocks)) return rc;
+    hipLaunchKernelGGL((k_agg_in_bwd_src<H>), dim3((unsigned)blocks), dim3(kAggInbThreads), 0, s, e, n_src, Tf, out_ptr, out_pos, out_dst, dA2h,
                        (int)blocks);
     GN_LAUNCH_CHECK();
     return GNNOME_OK;
+}
+
+// Argument checks and dispatch shared by the whole-graph entries and their partition forms (`who` names the entry in the error text).
+static int agg_in_raw_entry(const char* who, const float* e, int hidden, int64_t num_nodes, const float* A1h, const float* A2h, int ld_node,
+                            const int32_t* in_ptr, const int32_t* srt_src, float* v_out, float* aux0, float* aux1, void* stream) {
+    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "%s: hidden=%d not in {64,128,256}", who, hidden);
+    if (num_nodes == 0) return GNNOME_OK;
+    // e / srt_src may be NULL for a graph without edges (never dereferenced then)
+    GN_REQUIRE(A1h && A2h && in_ptr && v_out && aux0 && aux1, "%s: null pointer", who);
+    GN_REQUIRE(ld_node >= hidden && ld_node % 4 == 0, "%s: bad strides", who);
+    GN_REQUIRE(((uintptr_t)A1h % 16 == 0) && ((uintptr_t)A2h % 16 == 0) && ((uintptr_t)e % 16 == 0) && ((uintptr_t)v_out % 16 == 0) &&
+                   ((uintptr_t)aux0 % 16 == 0) && ((uintptr_t)aux1 % 16 == 0),
+               "%s: tensors must be 16-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    switch (hidden) {
+        case 64: return launch_agg_in_raw<64>(e, num_nodes, A1h, A2h, ld_node, in_ptr, srt_src, v_out, aux0, aux1, s);
+        case 128: return launch_agg_in_raw<128>(e, num_nodes, A1h, A2h, ld_node, in_ptr, srt_src, v_out, aux0, aux1, s);
+        default: return launch_agg_in_raw<256>(e, num_nodes, A1h, A2h, ld_node, in_ptr, srt_src, v_out, aux0, aux1, s);
+    }
+}
+
+static int agg_in_bwd_entry(const char* who, const float* e, int64_t num_edges, int hidden, int64_t n_dst, int64_t n_src, const float* Tf,
+                            const float* Uf, const float* A2h, int ld_node, const int32_t* in_ptr, const int32_t* srt_src,
+                            const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, float* de, float* dA2h, void* stream) {
+    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "%s: hidden=%d not in {64,128,256}", who, hidden);
+    if (n_src == 0) return GNNOME_OK;
+    GN_REQUIRE(dA2h && (uintptr_t)dA2h % 16 == 0, "%s: dA2h is null or not 16-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    if (num_edges == 0) {   // no edge: every out-list is empty and de has no rows
+        GN_HIP(hipMemsetAsync(dA2h, 0, (size_t)n_src * hidden * sizeof(float), s));
+        return GNNOME_OK;
+    }
+    GN_REQUIRE(n_dst > 0, "%s: %lld edges but no destination row", who, (long long)num_edges);
+    GN_REQUIRE(e && Tf && Uf && A2h && in_ptr && srt_src && out_ptr && out_pos && out_dst && de, "%s: null pointer", who);
+    GN_REQUIRE(ld_node >= hidden && ld_node % 4 == 0, "%s: bad strides", who);
+    GN_REQUIRE(((uintptr_t)e % 16 == 0) && ((uintptr_t)Tf % 16 == 0) && ((uintptr_t)Uf % 16 == 0) && ((uintptr_t)A2h % 16 == 0) &&
+                   ((uintptr_t)de % 16 == 0),
+               "%s: tensors must be 16-byte aligned", who);
+    GN_REQUIRE(de != e && dA2h != Tf && dA2h != Uf, "%s: outputs must not alias inputs", who);
+    switch (hidden) {
+        case 64: return launch_agg_in_bwd<64>(e, n_dst, n_src, Tf, Uf, A2h, ld_node, in_ptr, srt_src, out_ptr, out_pos, out_dst, de, dA2h, s);
+        case 128: return launch_agg_in_bwd<128>(e, n_dst, n_src, Tf, Uf, A2h, ld_node, in_ptr, srt_src, out_ptr, out_pos, out_dst, de, dA2h, s);
+        default: return launch_agg_in_bwd<256>(e, n_dst, n_src, Tf, Uf, A2h, ld_node, in_ptr, srt_src, out_ptr, out_pos, out_dst, de, dA2h, s);
+    }
 }
 
 }  // namespace gnnome
@@ -314,20 +365,7 @@ extern "C" int gnnome_node_aggregate_in_raw_f32(const float* e, int hidden, int6
                                                 void* stream) {
     using namespace gnnome;
     GN_REQUIRE(num_nodes >= 0, "node_aggregate_in_raw: negative node count");
-    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "node_aggregate_in_raw: hidden=%d not in {64,128,256}", hidden);
-    if (num_nodes == 0) return GNNOME_OK;
-    // e / srt_src may be NULL for a graph without edges (never dereferenced then)
-    GN_REQUIRE(A1h && A2h && in_ptr && v_out && aux0 && aux1, "node_aggregate_in_raw: null pointer");
-    GN_REQUIRE(ld_node >= hidden && ld_node % 4 == 0, "node_aggregate_in_raw: bad strides");
-    GN_REQUIRE(((uintptr_t)A1h % 16 == 0) && ((uintptr_t)A2h % 16 == 0) && ((uintptr_t)e % 16 == 0) && ((uintptr_t)v_out % 16 == 0) &&
-                   ((uintptr_t)aux0 % 16 == 0) && ((uintptr_t)aux1 % 16 == 0),
-               "node_aggregate_in_raw: tensors must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    switch (hidden) {
-        case 64: return launch_agg_in_raw<64>(e, num_nodes, A1h, A2h, ld_node, in_ptr, srt_src, v_out, aux0, aux1, s);
-        case 128: return launch_agg_in_raw<128>(e, num_nodes, A1h, A2h, ld_node, in_ptr, srt_src, v_out, aux0, aux1, s);
-        default: return launch_agg_in_raw<256>(e, num_nodes, A1h, A2h, ld_node, in_ptr, srt_src, v_out, aux0, aux1, s);
-    }
+    return agg_in_raw_entry("node_aggregate_in_raw", e, hidden, num_nodes, A1h, A2h, ld_node, in_ptr, srt_src, v_out, aux0, aux1, stream);
 }
 
 extern "C" int gnnome_node_aggregate_in_bwd_f32(const float* e, int64_t num_edges, int hidden, int64_t num_nodes, const float* Tf,
@@ -336,23 +374,32 @@ extern "C" int gnnome_node_aggregate_in_bwd_f32(const float* e, int64_t num_edge
                                                 void* stream) {
     using namespace gnnome;
     GN_REQUIRE(num_nodes >= 0 && num_edges >= 0, "node_aggregate_in_bwd: negative node or edge count");
-    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "node_aggregate_in_bwd: hidden=%d not in {64,128,256}", hidden);
-    if (num_nodes == 0) return GNNOME_OK;
-    GN_REQUIRE(dA2h && (uintptr_t)dA2h % 16 == 0, "node_aggregate_in_bwd: dA2h is null or not 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    if (num_edges == 0) {   // no edge: every out-list is empty and de has no rows
-        GN_HIP(hipMemsetAsync(dA2h, 0, (size_t)num_nodes * hidden * sizeof(float), s));
-        return GNNOME_OK;
-    }
-    GN_REQUIRE(e && Tf && Uf && A2h && in_ptr && srt_src && out_ptr && out_pos && out_dst && de, "node_aggregate_in_bwd: null pointer");
-    GN_REQUIRE(ld_node >= hidden && ld_node % 4 == 0, "node_aggregate_in_bwd: bad strides");
-    GN_REQUIRE(((uintptr_t)e % 16 == 0) && ((uintptr_t)Tf % 16 == 0) && ((uintptr_t)Uf % 16 == 0) && ((uintptr_t)A2h % 16 == 0) &&
-                   ((uintptr_t)de % 16 == 0),
-               "node_aggregate_in_bwd: tensors must be 16-byte aligned");
-    GN_REQUIRE(de != e && dA2h != Tf && dA2h != Uf, "node_aggregate_in_bwd: outputs must not alias inputs");
-    switch (hidden) {
-        case 64: return launch_agg_in_bwd<64>(e, num_nodes, Tf, Uf, A2h, ld_node, in_ptr, srt_src, out_ptr, out_pos, out_dst, de, dA2h, s);
-        case 128: return launch_agg_in_bwd<128>(e, num_nodes, Tf, Uf, A2h, ld_node, in_ptr, srt_src, out_ptr, out_pos, out_dst, de, dA2h, s);
-        default: return launch_agg_in_bwd<256>(e, num_nodes, Tf, Uf, A2h, ld_node, in_ptr, srt_src, out_ptr, out_pos, out_dst, de, dA2h, s);
-    }
+    return agg_in_bwd_entry("node_aggregate_in_bwd", e, num_edges, hidden, num_nodes, num_nodes, Tf, Uf, A2h, ld_node, in_ptr, srt_src, out_ptr,
+                            out_pos, out_dst, de, dA2h, stream);
+}
+
+// ---- the partition forms: num_nodes_out destination rows (a rank's owned nodes, which come first), num_nodes_local table rows (owned + halo).
+// The kernels are the ones above - same lane mapping, same association - launched over the rows that have work: the raw form and the
+// backward's destination launch over the num_nodes_out owned rows (no wave per halo row, no [num_nodes_local, H] output nobody reads), the
+// backward's source launch over all num_nodes_local rows.
+
+extern "C" int gnnome_node_aggregate_in_raw_part_f32(const float* e, int hidden, int64_t num_nodes_out, int64_t num_nodes_local, const float* A1h,
+                                                     const float* A2h, int ld_node, const int32_t* in_ptr, const int32_t* srt_src, float* v_out,
+                                                     float* aux0, float* aux1, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_nodes_out >= 0 && num_nodes_out <= num_nodes_local, "node_aggregate_in_raw_part: %lld destination rows of %lld local rows",
+               (long long)num_nodes_out, (long long)num_nodes_local);
+    return agg_in_raw_entry("node_aggregate_in_raw_part", e, hidden, num_nodes_out, A1h, A2h, ld_node, in_ptr, srt_src, v_out, aux0, aux1, stream);
+}
+
+extern "C" int gnnome_node_aggregate_in_bwd_part_f32(const float* e, int64_t num_edges, int hidden, int64_t num_nodes_out, int64_t num_nodes_local,
+                                                     const float* Tf, const float* Uf, const float* A2h, int ld_node, const int32_t* in_ptr,
+                                                     const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_pos,
+                                                     const int32_t* out_dst, float* de, float* dA2h, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_edges >= 0 && num_nodes_out >= 0 && num_nodes_out <= num_nodes_local,
+               "node_aggregate_in_bwd_part: %lld edges, %lld destination rows of %lld local rows", (long long)num_edges, (long long)num_nodes_out,
+               (long long)num_nodes_local);
+    return agg_in_bwd_entry("node_aggregate_in_bwd_part", e, num_edges, hidden, num_nodes_out, num_nodes_local, Tf, Uf, A2h, ld_node, in_ptr,
+                            srt_src, out_ptr, out_pos, out_dst, de, dA2h, stream);
 }

@@ -25,7 +25,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import engine
+from . import engine, engine_gated
 from . import ops as hip_ops
 
 
@@ -61,11 +61,20 @@ def split_by_degree(deg, num_nodes, world):
     return bounds
 
 
+def _checked_bounds(bounds, num_nodes, world):
+    bounds = [int(b) for b in bounds]
+    if len(bounds) != world + 1 or bounds[0] != 0 or bounds[-1] != num_nodes or any(a > b for a, b in zip(bounds[:-1], bounds[1:])):
+        raise ValueError(f"bounds={bounds}: expected {world + 1} ascending node ids from 0 to {num_nodes}")
+    return bounds
+
+
 def partition_census(src, dst, num_nodes, world, bounds=None):
     """What PartitionedGraph.from_global would give every rank of a `world`-way destination-range partition, computed in one
     process without a process group (planning: which world size a graph wants; tools/partition_stats.py):
     per rank the owned nodes, local edges (incident to an owned node), owned in-edges (the ones it scores), halo rows it
-    receives and rows it sends per layer.  Pure index arithmetic over the edge list, O(E) per rank."""
+    receives and rows it sends per layer.  Pure index arithmetic over the edge list, O(E) per rank.
+    The `in_edge_*` counts are those of from_global(..., in_edges_only=True), the partition a GatedGCNModel runs on: its local edges
+    are the owned in-edges, its halo the distinct non-owned SOURCES of those."""
     src, dst = torch.as_tensor(src).long(), torch.as_tensor(dst).long()
     bounds = split_by_incident_edges(src, dst, num_nodes, world) if bounds is None else list(bounds)
     bt = torch.tensor(bounds[1:-1], device=src.device, dtype=torch.long)
@@ -82,9 +91,14 @@ def partition_census(src, dst, num_nodes, world, bounds=None):
     recv = torch.bincount(holder, minlength=world)
     send = torch.bincount(owner, minlength=world)
     link = torch.bincount(owner * world + holder, minlength=world * world).view(world, world)   # rows owner -> holder
+    pair_in = torch.unique(rd[cut] * num_nodes + src[cut])        # in-edge-only partition: (holder, source) pairs of the cut in-edges
+    recv_in = torch.bincount(pair_in // num_nodes, minlength=world)
+    send_in = torch.bincount(torch.bucketize(pair_in % num_nodes, bt, right=True), minlength=world)
     for p in range(world):
         ranks.append({"rank": p, "owned_nodes": bounds[p + 1] - bounds[p], "local_edges": int(local[p]), "owned_in_edges": int(owned_in[p]),
-                      "halo_rows": int(recv[p]), "rows_sent_per_layer": int(send[p]), "largest_link_rows": int(link[p].max())})
+                      "halo_rows": int(recv[p]), "rows_sent_per_layer": int(send[p]), "largest_link_rows": int(link[p].max()),
+                      "in_edge_local_edges": int(owned_in[p]), "in_edge_halo_rows": int(recv_in[p]),
+                      "in_edge_rows_sent_per_layer": int(send_in[p])})
     e = int(src.numel())
     return {"world": world, "num_nodes": num_nodes, "num_edges": e, "bounds": bounds, "cut_edges": int(cut.sum()),
             "cut_fraction": float(cut.sum()) / max(e, 1), "edge_replication": float(local.sum()) / max(e, 1),
@@ -96,6 +110,7 @@ class PartitionedGraph:
 
     def __init__(self):
         self.rank = self.world = 0
+        self.in_edges_only = False  # True: the local graph holds the in-edges of the owned nodes only (the partition of a one-direction model)
         self.lo = self.hi = self.n_own = self.n_local = self.num_edges_global = 0
         self.bounds = None
         self.node_gid = None        # int64 [n_local]  global id of local node (owned first, then halo ascending)
@@ -111,33 +126,45 @@ class PartitionedGraph:
         self.score_index = None     # int64 [E_global]: where global edge id k sits in the flattened [world, score_pad] gather
 
     @classmethod
-    def from_global(cls, src, dst, num_nodes, rank, world, device, ops=hip_ops, group=None, node_perm=None):
+    def from_global(cls, src, dst, num_nodes, rank, world, device, ops=hip_ops, group=None, node_perm=None, in_edges_only=False,
+                    bounds=None):
         """Build from the full edge list (every rank holds it in this harness, as inference.py holds the
         whole DGLGraph).  The plan is computed on `device` (masks, unique, searchsorted over the E-sized edge list: 0.9 s per
         rank on the host at 10M edges) + one all_to_all of halo requests.
         node_perm (int64[N], the same on every rank; gnnome_amd.node_order.locality_order): the RANGES are cut in the renumbered
-        node order - for graphs whose ids do not follow the layout; local_node_rows still takes rows in the caller's numbering."""
+        node order - for graphs whose ids do not follow the layout; local_node_rows still takes rows in the caller's numbering.
+        in_edges_only: the partition of a ONE-DIRECTION model (GatedGCNModel): the local graph holds the owned nodes, their in-edges -
+        in global edge-id order within each destination run, so every owned node's sum has the whole graph's association - and as
+        halo the distinct non-owned sources; no out-edge of an owned node into another range is kept, so every local edge is scored
+        here (n_score = all of them) and halo nodes have empty in-lists.
+        bounds: the range boundaries [0, ..., N] (the same on every rank) instead of split_by_incident_edges's."""
         self = cls()
+        self.in_edges_only = bool(in_edges_only)
         src, dst = torch.as_tensor(src).to(device).long(), torch.as_tensor(dst).to(device).long()
         if node_perm is not None:
             self._set_node_perm(node_perm, num_nodes, device)
             src, dst = self.node_perm[src], self.node_perm[dst]
         self.rank, self.world, self.num_edges_global = rank, world, int(src.numel())
-        self.bounds = split_by_incident_edges(src, dst, num_nodes, world)
+        self.bounds = split_by_incident_edges(src, dst, num_nodes, world) if bounds is None else _checked_bounds(bounds, num_nodes, world)
         lo, hi = self.bounds[rank], self.bounds[rank + 1]
-        keep = ((dst >= lo) & (dst < hi)) | ((src >= lo) & (src < hi))
+        keep = (dst >= lo) & (dst < hi)
+        if not self.in_edges_only:
+            keep |= (src >= lo) & (src < hi)
         self.edge_gid = torch.nonzero(keep).squeeze(1)
         return self._build(src[keep], dst[keep], device, ops, group)
 
     @classmethod
-    def from_slices(cls, src_slice, dst_slice, num_nodes, rank, world, device, ops=hip_ops, group=None, node_perm=None):
+    def from_slices(cls, src_slice, dst_slice, num_nodes, rank, world, device, ops=hip_ops, group=None, node_perm=None, in_edges_only=False,
+                    bounds=None):
         """Build from a rank's SLICE of the edge list: rank r holds the edges with global ids [off_r, off_r + m_r), the slices in
         rank order making up the whole list (a reader that splits its input file G ways; no rank ever holds all E endpoints).
         Degrees are all-reduced ([N] int64) for the range boundaries, then every edge travels once to the owner of its
         destination and, when that is another rank, once to the owner of its source (one all_to_all of (src, dst, id) triples).
         The ids a rank receives arrive ascending - peer blocks in rank order, each ascending - so the local edge order, and with
-        it every later array, equals from_global's.  The same route moves edge features: shuffle_edge_rows(e_slice)."""
+        it every later array, equals from_global's.  The same route moves edge features: shuffle_edge_rows(e_slice).
+        in_edges_only, bounds: as for from_global; an edge then travels to the owner of its destination only."""
         self = cls()
+        self.in_edges_only = bool(in_edges_only)
         src = torch.as_tensor(src_slice).to(device).long()
         dst = torch.as_tensor(dst_slice).to(device).long()
         if node_perm is not None:   # (as from_global: ranges over renumbered nodes; the permutation itself needs the whole graph once)
@@ -154,11 +181,11 @@ class PartitionedGraph:
         if not alone:
             all_reduce_sum(deg, group)
         self.global_degrees = deg        # [2, N] int64 of the WHOLE graph: what inference.py:416-420 z-scores into x
-        self.bounds = split_by_degree(deg[0] + deg[1], num_nodes, world)
+        self.bounds = split_by_degree(deg[0] + deg[1], num_nodes, world) if bounds is None else _checked_bounds(bounds, num_nodes, world)
         bt = torch.tensor(self.bounds[1:-1], device=device, dtype=torch.long)
         owner_d, owner_s = torch.bucketize(dst, bt, right=True), torch.bucketize(src, bt, right=True)
         gid = torch.arange(offset, offset + src.numel(), device=device)
-        second = owner_s != owner_d
+        second = (owner_s != owner_d) if not self.in_edges_only else torch.zeros_like(owner_s, dtype=torch.bool)
         to_rank = torch.cat([owner_d, owner_s[second]])
         which = torch.cat([torch.arange(src.numel(), device=device), torch.nonzero(second).squeeze(1)])
         order = torch.argsort(to_rank * (self.num_edges_global + 1) + gid[which])     # by receiving rank, then by global id
@@ -456,10 +483,25 @@ def _project(ops, lw, h, n_own, xchg):
     return P
 
 
+def _check_partition_kind(prep, part):
+    """True for a GatedGCNModel's weights.  The one-direction model runs on the in-edge-only partition, the symmetric model on the one
+    that also keeps the out-edges of the owned nodes: the other combination would silently drop or double terms, so it raises."""
+    gated = isinstance(prep, engine_gated.Prepared)
+    if gated and not prep.directed:
+        raise NotImplementedError("GatedGCNModel with directed=False is not served on partitions (the doubled edge list is not partitioned)")
+    if gated != bool(getattr(part, "in_edges_only", False)):
+        raise ValueError("GatedGCNModel runs on PartitionedGraph.from_global(..., in_edges_only=True), SymGatedGCNModel on the default "
+                         f"partition; got in_edges_only={getattr(part, 'in_edges_only', False)}")
+    return gated
+
+
 def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result=True):
     """The rank-local kernel sequence.  x_local: [n_local, F] features of owned+halo nodes, e_local:
     [e_local, F] features of local edges in local edge-id order.  Returns logits[E_global] (complete on
-    every rank after the all_reduce when `reduce_result`)."""
+    every rank after the all_reduce when `reduce_result`).
+    prep = engine_gated.Prepared (a GatedGCNModel): engine_gated's eval sequence per layer - the [n_local,4H] projection, the same gate,
+    gnnome_node_aggregate_in_f32 over the owned rows - on an in-edge-only partition (PartitionedGraph.from_global(..., in_edges_only=True))."""
+    gated = _check_partition_kind(prep, part)
     views, n_own = part.views, part.n_own
     xchg = HaloExchange(part, ops, group)
     H = prep.hidden
@@ -470,6 +512,11 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result
         if li > 0:
             xchg.start(h)
         P = _project(ops, lw, h, n_own, xchg)
+        if gated:   # A1h|A2h|B1h|B2h: no A_3 block, no out-edge half (the halo rows of h' are written by the next exchange)
+            A1, A2, B1, B2 = (P[:, i * H:(i + 1) * H] for i in range(4))
+            e = engine.gate(ops, lw, views, e, B1, B2, (e_local, prep.enc_edge), scratch)
+            h = ops.node_aggregate_in(e, A1, A2, views, h, lw.norm, lw.scale_h, lw.shift_h, num_nodes_out=n_own)
+            continue
         A1, A2, A3, B1, B2 = (P[:, i * H:(i + 1) * H] for i in range(5))
         e = engine.gate(ops, lw, views, e, B1, B2, (e_local, prep.enc_edge), scratch)
         h = ops.node_aggregate(e, A1, A2, A3, views, h, lw.norm, lw.scale_h, lw.shift_h, num_nodes_out=n_own)
@@ -506,6 +553,8 @@ class CapturedPartitionedForward:
         if runner.prep is None:
             raise RuntimeError("CapturedPartitionedForward is for eval-mode inference")
         ops, prep, part = runner.ops, runner.prep, runner.part
+        if isinstance(prep, engine_gated.Prepared):
+            raise NotImplementedError("CapturedPartitionedForward is built for SymGatedGCNModel; a GatedGCNModel runs the eager forward()")
         self.part, self.group, self.ops = part, runner.group, ops
         self.alone = alone = _alone(part.world)
         dev = runner.x.device
@@ -576,7 +625,16 @@ class PartitionedRunner:
         already selected (part.local_node_rows), for callers that never hold the [N,F] table on this device; e_global[E,F] or
         e_local (part.local_edge_rows / part.shuffle_edge_rows) likewise."""
         self.ops, self.part, self.group, self.model = ops, part, group, model
-        self.prep = None if model.training else engine.prepared_for(model, device, engine.Prepared)
+        from .models import GatedGCNModel
+        self.gated = isinstance(model, GatedGCNModel)   # (engine_gated.py): the in-edge-only partition, its own kernel sequences
+        if self.gated:
+            if not model.directed:
+                raise NotImplementedError("GatedGCNModel with directed=False is not served on partitions (the doubled edge list is not partitioned)")
+            if not part.in_edges_only:
+                raise ValueError("GatedGCNModel runs on an in-edge-only partition: PartitionedGraph.from_global(..., in_edges_only=True)")
+        elif part.in_edges_only:
+            raise ValueError("an in-edge-only partition serves GatedGCNModel; SymGatedGCNModel needs the out-edges of the owned nodes too")
+        self.prep = None if model.training else engine.prepared_for(model, device, engine_gated.Prepared if self.gated else engine.Prepared)
         rows = part.local_node_rows(x_global) if x_local is None else x_local
         self.x = rows.to(device=device, dtype=torch.float32).contiguous()
         erows = part.local_edge_rows(e_global) if e_local is None else e_local
@@ -600,4 +658,10 @@ class PartitionedRunner:
         """train mode: logits[E,1] with autograd history; after loss.backward() every rank holds the whole graph's
         parameter gradients (already summed over ranks), so identical optimizers stay in step without a DDP wrapper."""
         from .train import train_forward_on
+        if self.gated:
+            # GatedGCNModel: the one-direction step on the shard; the symmetric-step adapter (zero A_3) is not served on partitions
+            if engine_gated.training_step_of(self.model) != "in_edge":
+                raise NotImplementedError('a partitioned GatedGCNModel trains with training_step = "in_edge"; this model has training_step = '
+                                          f'{self.model.training_step!r}')
+            return engine_gated.train_forward_in_edge_on(self.model, PartitionShard(self.part, self.ops, self.group), self.x, self.e)
         return train_forward_on(self.model, PartitionShard(self.part, self.ops, self.group), self.x, self.e)

@@ -21,7 +21,9 @@ fifth projection block are computed on zeros.  That is the default (`GatedGCNMod
 
 `training_step = "in_edge"` selects the step of this model's own (train_forward_in_edge, below): a [N,4H] projection, the train-form
 gate, gnnome_node_aggregate_in_raw_f32 forward and gnnome_node_aggregate_in_bwd_f32 backward (csrc/node_aggregate_in_bwd.hip) - no
-A_3, no out-edge half, no Tb / Ub tables - and directed=False on the doubled edge list.
+A_3, no out-edge half, no Tb / Ub tables - and directed=False on the doubled edge list.  The same step runs one rank's rows of an
+in-edge-only destination-range partition (train_forward_in_edge_on over dist.PartitionShard; directed=True) on the partition forms
+gnnome_node_aggregate_in_raw_part_f32 / gnnome_node_aggregate_in_bwd_part_f32; eval mode on a partition is dist.run_partitioned.
 """
 import torch
 import torch.nn.functional as F
@@ -82,6 +84,7 @@ class Prepared:
 
         check_arithmetic(model)
         self.device = device
+        self.directed = bool(getattr(model, "directed", True))   # (dist.run_partitioned refuses directed=False up front)
         self.hidden = built_width(model.node_encoder.linear2.out_features)
         self.enc_node = tuple(dev(t) for t in (model.node_encoder.linear1.weight, model.node_encoder.linear1.bias,
                                                model.node_encoder.linear2.weight, model.node_encoder.linear2.bias))
@@ -372,17 +375,31 @@ class _StepGraph:
     def __init__(self, views, directed, doubled=doubled_for, ops=hip_ops):
         """doubled, ops: the builder of the doubled graph and the backend (the tests run the step's host logic on a torch backend)."""
         from .train import WholeGraph
-        self.score_views = views
+        self.score_views = self.seg_views = views   # seg_views: whose in- / out-lists the scorer's node gathers are transposed over
+        self.num_scored = views.num_edges
         if directed:
             self.sh, self.enc_gather, self.score_gather = WholeGraph(views, ops), views.srt_eid, None
         else:
             dbl = doubled(views)
             self.sh, self.enc_gather, self.score_gather = WholeGraph(dbl.views, ops), dbl.enc_gather, dbl.score_gather
 
+    @classmethod
+    def on_shard(cls, shard):
+        """One rank's rows of an in-edge-only destination-range partition (dist.PartitionShard; directed=True): the stack runs on the
+        local views, every local edge is an owned in-edge and is scored here, into this rank's piece of the logits."""
+        self = object.__new__(cls)
+        self.sh, self.enc_gather, self.score_gather = shard, shard.views.srt_eid, None
+        self.score_views, self.seg_views, self.num_scored = shard.score_views, shard.views, shard.e_own
+        return self
+
 
 class _InEdgeStep(torch.autograd.Function):
     """One training step of GatedGCNModel (gated_gcn_full.py:182-230 in train mode, full_graph.py:42-53) as ONE autograd node whose inputs
-    are the model's parameters - train._TrainStep's shape on the one-direction kernels.  fp32 storage, single process."""
+    are the model's parameters - train._TrainStep's shape on the one-direction kernels.  fp32 storage.  A single process (train.WholeGraph),
+    or one rank of an in-edge-only destination-range partition (dist.PartitionShard, directed=True): n_own owned rows first, halo rows of h
+    refreshed before every projection, BatchNorm statistics over the owned rows merged across ranks, the halo rows of dh - which carry this
+    rank's PARTIAL gradients, as do the halo rows of dA2h / dB1h - returned to their owners once per layer, parameter gradients summed over ranks.
+    The single-process case issues exactly the calls it issued before shards were served."""
 
     @staticmethod
     def forward(ctx, model, sg, x, e_raw, names, *params):
@@ -393,17 +410,28 @@ class _InEdgeStep(torch.autograd.Function):
         layer_norm = len(convs) > 0 and isinstance(convs[0].bn_e, torch.nn.LayerNorm)
         H = model.node_encoder.linear2.out_features
         n, E2 = views.num_nodes, views.num_edges
+        n_own = sh.n_own
+        whole = sh.alone and n_own == n   # the single-process case; otherwise a shard: rows [n_own, n) are halo rows
         d = lambda t: t.detach().contiguous()  # noqa: E731
         ne, ee = model.node_encoder, model.edge_encoder
         node_gather = getattr(views, "node_gather", None)   # views over renumbered nodes read x (caller's numbering) through it
         h = ops.encode(x, d(ne.linear1.weight), d(ne.linear1.bias), d(ne.linear2.weight), d(ne.linear2.bias),
-                       **({} if node_gather is None else dict(gather=node_gather, rows=n)))
+                       **({} if node_gather is None else dict(gather=node_gather, rows=n)))   # (a shard's halo rows of layer 0 come from x)
         # directed=False: the encoded e fed twice - row p of the doubled sorted order encodes original edge enc_gather[p]
         e = ops.encode(e_raw, d(ee.linear1.weight), d(ee.linear1.bias), d(ee.linear2.weight), d(ee.linear2.bias), gather=sg.enc_gather, rows=E2)
         saved = []
-        for conv in convs:
+        for li, conv in enumerate(convs):
             Wcat, bcat = _cat4(conv)
-            P = ops.linear(h, Wcat, bcat)   # [N,4H] = A1h|A2h|B1h|B2h (gated_gcn_full.py:194-199)
+            if whole:
+                P = ops.linear(h, Wcat, bcat)   # [N,4H] = A1h|A2h|B1h|B2h (gated_gcn_full.py:194-199)
+            else:
+                if li > 0:
+                    sh.halo_start(h)
+                P = torch.empty((n, 4 * H), dtype=torch.float32, device=x.device)
+                ops.linear(h[:n_own], Wcat, bcat, out=P[:n_own])    # owned rows while the halo rows are in flight
+                sh.halo_finish()
+                if n > n_own:
+                    ops.linear(h[n_own:], Wcat, bcat, out=P[n_own:])
             A1, A2, B1, B2 = (P[:, i * H:(i + 1) * H] for i in range(4))
             mean_e = rstd_e = sc_e = sh_e = mean_h = rstd_h = sc_h = sh_h = None
             path, xe, stats = train._raw_gate(sh, conv, e, B1, B2, layer_norm, torch.float32)
@@ -413,22 +441,32 @@ class _InEdgeStep(torch.autograd.Function):
                 if path == "moments":
                     mean_e, rstd_e, sc_e, sh_e = train._bn_train_fused(sh, conv.bn_e, stats, updates=1)
                 else:
-                    mean_e, rstd_e, sc_e, sh_e = train._bn_train(sh, conv.bn_e, stats[0], stats[1], E2, E2, updates=1)
+                    # (a shard: every local edge is an owned in-edge, each edge of the graph on exactly one rank)
+                    mean_e, rstd_e, sc_e, sh_e = train._bn_train(sh, conv.bn_e, stats[0], stats[1], sh.e_own, sh.e_global, updates=1)
                 e_new = ops.bn_relu_res(xe, sc_e, sh_e, e)
-            v, hf, rdf = ops.node_aggregate_in_raw(e_new, A1, A2, views)
+            # v, hf, rdf: the owned rows
+            v, hf, rdf = ops.node_aggregate_in_raw(e_new, A1, A2, views) if whole else ops.node_aggregate_in_raw_part(e_new, A1, A2, views, n_own)
+            # a shard keeps n rows of h: the owned ones are written here, the halo rows by the next exchange
+            h_rows = None if whole else torch.empty((n, H), dtype=torch.float32, device=x.device)
+            into = {} if whole else dict(out=h_rows[:n_own])
             if layer_norm:
-                h_next = ops.ln_relu_res(v, d(conv.bn_h.weight), d(conv.bn_h.bias), h)
+                h_next = ops.ln_relu_res(v, d(conv.bn_h.weight), d(conv.bn_h.bias), h[:n_own], **into)
             else:
                 if train._can_fuse_bn(sh, conv.bn_h):
                     mean_h, rstd_h, sc_h, sh_h = train._bn_train_fused(sh, conv.bn_h, ops.batch_moments(v), updates=1)
                 else:
                     m_h, v_h = ops.batch_stats(v)
-                    mean_h, rstd_h, sc_h, sh_h = train._bn_train(sh, conv.bn_h, m_h, v_h, n, n, updates=1)
-                h_next = ops.bn_relu_res(v, sc_h, sh_h, h)
+                    mean_h, rstd_h, sc_h, sh_h = train._bn_train(sh, conv.bn_h, m_h, v_h, n_own, sh.n_global, updates=1)
+                h_next = ops.bn_relu_res(v, sc_h, sh_h, h[:n_own], **into)
             mask = None
             if conv.dropout > 0.0:
-                mask = train.dropout_mask(n, H, conv.dropout, x.device)
-                h_next = ops.mul23(h_next, mask, mask)[0]
+                mask = train.dropout_mask(n_own, H, conv.dropout, x.device)
+                if whole:
+                    h_next = ops.mul23(h_next, mask, mask)[0]
+                else:
+                    h_rows[:n_own].copy_(ops.mul23(h_rows[:n_own], mask, mask)[0])
+            if not whole:
+                h_next = h_rows
             saved.append(dict(h=h, P=P, e=e, xe=xe, e_new=e_new, v=v, hf=hf, rdf=rdf, mask=mask, Wcat=Wcat, mean_e=mean_e, rstd_e=rstd_e,
                               sc_e=sc_e, sh_e=sh_e, mean_h=mean_h, rstd_h=rstd_h, sc_h=sc_h, sh_h=sh_h))
             h, e = h_next, e_new
@@ -438,14 +476,22 @@ class _InEdgeStep(torch.autograd.Function):
         W1 = d(pred.W1.weight)
         W_nodes = torch.cat([W1[:, :H], W1[:, H:2 * H]], 0).contiguous()
         b_nodes = torch.cat([torch.zeros_like(pred.W1.bias), pred.W1.bias]).detach().contiguous()
+        if not whole:
+            sh.halo_start(h)
+            sh.halo_finish()
         PQ = ops.linear(h, W_nodes, b_nodes)
         # directed=False: the ORIGINAL graph is scored with the rows of the first E edge ids (full_graph.py:51)
         e_sc = e if sg.score_gather is None else ops.gather_rows(e, sg.score_gather)
-        E = sg.score_views.num_edges
+        E = sg.num_scored
         z1 = torch.empty((E, hs), dtype=torch.float32, device=h.device)
-        logits = torch.empty(E, dtype=torch.float32, device=h.device)
-        ops.edge_score(e_sc, PQ[:, :hs], PQ[:, hs:], sg.score_views, W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias),
-                       d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1)), logits, num_edges=E, z1_out=z1)
+        w_tail = (W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1)))
+        if sh.alone:
+            logits = torch.empty(E, dtype=torch.float32, device=h.device)
+            ops.edge_score(e_sc, PQ[:, :hs], PQ[:, hs:], sg.score_views, *w_tail, logits, num_edges=E, z1_out=z1)
+        else:   # one contiguous piece per rank in sorted order; finish_logits all-gathers and un-permutes them
+            piece = torch.empty(sh.part.score_pad, dtype=torch.float32, device=h.device)
+            ops.edge_score(e_sc, PQ[:, :hs], PQ[:, hs:], sg.score_views, *w_tail, piece, num_edges=E, scatter_to_edge_id=False, z1_out=z1)
+            logits = sh.finish_logits(piece)
         ctx.model, ctx.sg, ctx.names, ctx.saved = model, sg, names, saved
         ctx.tail = dict(h=h, e_sc=e_sc, z1=z1, W1=W1, W_nodes=W_nodes, x=x, e_raw=e_raw)
         return logits.unsqueeze(1)
@@ -461,9 +507,14 @@ class _InEdgeStep(torch.autograd.Function):
         ops, views, sv = sh.ops, sh.views, sg.score_views
         H = model.node_encoder.linear2.out_features
         n, E2 = views.num_nodes, views.num_edges
+        n_own = sh.n_own
+        whole = sh.alone and n_own == n
         d = lambda t: t.detach().contiguous()  # noqa: E731
         dev = dlogits.device
         g = {}
+        # A shard: rows that also live on another rank (halo nodes) carry PARTIAL gradients here.  Everything below is linear in the incoming
+        # gradient, so the per-rank parameter gradients sum to the whole graph's (sum_ranks at the end), and the halo rows of dh go back to
+        # their owners once per layer (halo_bwd_start / halo_bwd_finish), which add them in ascending rank order.
 
         # ---- scorer (score_predictor.py:12-17), over the scored views
         pred = model.predictor
@@ -473,12 +524,13 @@ class _InEdgeStep(torch.autograd.Function):
         g["predictor.W2.weight"] = ops.wgrad(dz2, tail["z1"])
         g["predictor.W2.bias"] = ops.colsum2(dz2)[0]
         g["predictor.W3.weight"] = ops.colsum2(u)[0].reshape(1, 32)
-        g["predictor.W3.bias"] = dl.sum().reshape(1)
+        g["predictor.W3.bias"] = (dl if sh.alone else dl[sv.srt_eid.long()]).sum().reshape(1)   # (a shard: the edges scored here)
         W1 = tail["W1"]
         de = ops.linear(dz1, W1[:, 2 * H:].t().contiguous(), None)       # d e_final of the scored rows
         gW1e = ops.wgrad(dz1, tail["e_sc"])
-        d_ps = ops.segment_sum(dz1, sv.out_ptr, sv.out_pos, n)           # gathered by srt_src in the forward
-        d_qd = ops.segment_sum(dz1, sv.in_ptr, None, n)                  # gathered by srt_dst
+        seg = sg.seg_views
+        d_ps = ops.segment_sum(dz1, seg.out_ptr, seg.out_pos, n)         # gathered by srt_src in the forward
+        d_qd = ops.segment_sum(dz1, seg.in_ptr, None, n)                 # gathered by srt_dst
         dPQ = torch.cat([d_ps, d_qd], 1)
         g["predictor.W1.bias"] = ops.colsum2(d_qd)[0]
         gWn = ops.wgrad(dPQ, tail["h"])                                  # [2hs, H]
@@ -488,20 +540,30 @@ class _InEdgeStep(torch.autograd.Function):
             de = ops.scatter_add_rows(de, sg.score_gather, torch.zeros((E2, H), dtype=torch.float32, device=dev))
 
         # ---- layers, last to first (gated_gcn_full.py:182-230)
+        if saved:
+            sh.halo_bwd_start(dh)   # the halo rows travel under the kernels that do not read dh (the scorer's weight gradients above are done)
         for li in range(len(saved) - 1, -1, -1):
             s, conv, pfx = saved[li], model.gnn.convs[li], f"gnn.convs.{li}."
             A2, W3t = s["P"][:, H:2 * H], d(conv.B_3.weight).t().contiguous()
+            sh.halo_bwd_finish(dh)
             if s["mask"] is not None:
-                dh = ops.mul23(dh, s["mask"], s["mask"])[0]
-            # h' = relu(norm_h(v)) + h_in
-            dv = torch.empty((n, H), dtype=torch.float32, device=dev)
+                if whole:
+                    dh = ops.mul23(dh, s["mask"], s["mask"])[0]
+                else:
+                    dh[:n_own].copy_(ops.mul23(dh[:n_own], s["mask"], s["mask"])[0])
+            # h' = relu(norm_h(v)) + h_in      (owned rows; a halo row's dv is zero)
+            dv = (torch.empty if n == n_own else torch.zeros)((n, H), dtype=torch.float32, device=dev)
             if s["sc_h"] is None:
-                _, g[pfx + "bn_h.weight"], g[pfx + "bn_h.bias"] = ops.ln_bwd(dh, s["v"], d(conv.bn_h.weight), d(conv.bn_h.bias), out=dv)
+                _, g[pfx + "bn_h.weight"], g[pfx + "bn_h.bias"] = ops.ln_bwd(dh[:n_own], s["v"], d(conv.bn_h.weight), d(conv.bn_h.bias), out=dv[:n_own])
             else:
-                g[pfx + "bn_h.weight"], g[pfx + "bn_h.bias"] = train._bn_bwd(sh, dh, s["v"], s["sc_h"], s["sh_h"], s["mean_h"], s["rstd_h"], n, n, dv)
+                g[pfx + "bn_h.weight"], g[pfx + "bn_h.bias"] = train._bn_bwd(sh, dh[:n_own], s["v"], s["sc_h"], s["sh_h"], s["mean_h"], s["rstd_h"],
+                                                                             sh.n_global, n_own, dv[:n_own])
             # v = A1h + fwd: the two node tables, then de += ... over the in-lists and dA2h over the out-lists
-            Tf, Uf = ops.mul23(dv, s["rdf"], s["hf"])
-            dA2 = ops.node_aggregate_in_bwd(s["e_new"], Tf, Uf, A2, views, de)
+            Tf, Uf = ops.mul23(dv[:n_own], s["rdf"], s["hf"])
+            if whole:
+                dA2 = ops.node_aggregate_in_bwd(s["e_new"], Tf, Uf, A2, views, de)
+            else:   # [n, H]: a halo source's row is this rank's partial sum over the local edges
+                dA2 = ops.node_aggregate_in_bwd_part(s["e_new"], Tf, Uf, A2, views, de, n_own)
             # e' = relu(norm_e(xe)) + e_in ;  xe = B1h[src] + B2h[dst] + e_in W3^T
             amax_dxe = None
             if s["sc_e"] is None:
@@ -510,16 +572,16 @@ class _InEdgeStep(torch.autograd.Function):
             elif ops.can_fuse_bn_bwd_dgrad(de, W3t, s["xe"]):
                 # BatchNorm backward and d e_in = d e' + dxe W3 in one pass over the edges, as in the symmetric step
                 g[pfx + "bn_e.weight"], g[pfx + "bn_e.bias"], c1, c2 = train._bn_bwd(sh, de, s["xe"], s["sc_e"], s["sh_e"], s["mean_e"], s["rstd_e"],
-                                                                                     E2, E2, None, apply=False)
+                                                                                     sh.e_global, sh.e_own, None, apply=False)
                 if train.SCALED_WGRAD and hasattr(ops, "can_dgrad_amax") and ops.can_dgrad_amax(de, s["xe"]):
                     amax_dxe = torch.empty(1, dtype=torch.int32, device=dev)
-                dxe = ops.bn_bwd_dgrad(de, s["xe"], s["sc_e"], s["sh_e"], s["sc_e"], c1, c2, s["mean_e"], s["rstd_e"], W3t, rows_once=E2,
+                dxe = ops.bn_bwd_dgrad(de, s["xe"], s["sc_e"], s["sh_e"], s["sc_e"], c1, c2, s["mean_e"], s["rstd_e"], W3t, rows_once=sh.e_own,
                                        **({"amax": amax_dxe} if amax_dxe is not None else {}))
                 W3t = None
             else:
                 dxe = torch.empty_like(de)
                 g[pfx + "bn_e.weight"], g[pfx + "bn_e.bias"] = train._bn_bwd(sh, de, s["xe"], s["sc_e"], s["sh_e"], s["mean_e"], s["rstd_e"],
-                                                                             E2, E2, dxe)
+                                                                             sh.e_global, sh.e_own, dxe)
             if W3t is not None:
                 ops.linear(dxe, W3t, None, out=de, accumulate=True)   # d e_in = d e' + dxe W3
             dB2, dB1 = ops.segment_sum2(dxe, views, n)   # B2h was gathered by srt_dst (the in-lists), B1h by srt_src (the out-lists): one launch
@@ -528,12 +590,16 @@ class _InEdgeStep(torch.autograd.Function):
             WcatT = s["Wcat"].t().contiguous()
             if ops.can_use_blocks(parts):   # the four [N,H] gradients stay where their kernels left them
                 dh = ops.linear_blocks(parts, WcatT, dh, accumulate=True)
+                if li > 0:
+                    sh.halo_bwd_start(dh)   # (layer 0's halo rows of h came from x: their dh stays here, for the node encoder's gradients)
                 gWcat, gbcat = ops.wgrad_blocks(parts, s["h"])            # [4H, H], [4H]
                 for k, name in enumerate(names):
                     g[pfx + name + ".bias"] = gbcat[k * H:(k + 1) * H]
             else:
                 dP = torch.cat(parts, 1)
                 dh = ops.linear(dP, WcatT, None, out=dh, accumulate=True)
+                if li > 0:
+                    sh.halo_bwd_start(dh)
                 for k, name in enumerate(names):
                     g[pfx + name + ".bias"] = ops.colsum2(parts[k])[0]
                 gWcat = ops.wgrad(dP, s["h"])
@@ -549,22 +615,14 @@ class _InEdgeStep(torch.autograd.Function):
         train.encoder_bwd(ops, g, de, tail["e_raw"], sg.enc_gather, E2, model.edge_encoder.linear1, model.edge_encoder.linear2,
                           "edge_encoder.linear1", "edge_encoder.linear2")
         ctx.saved = ctx.tail = None
-        return (None, None, None, None, None) + tuple(g[name].contiguous() for name in ctx.names)
+        return (None, None, None, None, None) + tuple(sh.sum_ranks([g[name].contiguous() for name in ctx.names]))
 
 
 def train_forward_in_edge(model, graph, x, e):
     """`model(graph, x, e)` in train mode through the one-direction step (`GatedGCNModel.training_step = "in_edge"`), both `directed`
     values; logits [E,1] on the compute device, differentiable with respect to the model's parameters.  Served: fp32 storage, both
-    norms, the built widths; a single process (multi-GPU shards are not)."""
-    from .train import TRAIN_SCORE_HIDDEN
-    check_arithmetic(model)
-    if getattr(model, "activation_storage", "fp32") != "fp32":
-        raise ValueError(f'training_step="in_edge" keeps activations as "fp32"; activation_storage={model.activation_storage!r} is served by '
-                         'training_step="symmetric"')
-    if getattr(model, "recompute_gate", False):
-        raise ValueError('training_step="in_edge" keeps the gate output; recompute_gate is served by training_step="symmetric"')
-    built_width(model.node_encoder.linear2.out_features)
-    built_width(model.predictor.W1.out_features, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")
+    norms, the built widths; a single process (one rank of a partition: train_forward_in_edge_on)."""
+    _check_in_edge_step(model)
     device = engine.compute_device(x, e)
     names, params = zip(*model.named_parameters())
     if any(p.device != device for p in params):
@@ -577,3 +635,33 @@ def train_forward_in_edge(model, graph, x, e):
     out = _InEdgeStep.apply(model, _StepGraph(in_edge_views(views), bool(model.directed)), xd, ed, list(names), *params)
     views.check_range()
     return out
+
+
+def train_forward_in_edge_on(model, shard, x_local, e_local):
+    """The one-direction step over one rank's rows of an in-edge-only destination-range partition (dist.PartitionShard over
+    PartitionedGraph.from_global(..., in_edges_only=True)); x_local / e_local: the input features of the shard's nodes (owned, then halo)
+    and edges (local edge-id order).  Returns logits[E_global, 1], complete on every rank; after backward() every rank holds the whole
+    graph's parameter gradients.  directed=True and training_step="in_edge" only (dist.PartitionedRunner.train_forward checks both)."""
+    _check_in_edge_step(model)
+    if not model.directed:
+        raise NotImplementedError("GatedGCNModel with directed=False is not served on partitions (the doubled edge list is not partitioned)")
+    if not getattr(shard.part, "in_edges_only", False):
+        raise ValueError("GatedGCNModel runs on an in-edge-only partition: build it with PartitionedGraph.from_global(..., in_edges_only=True)")
+    names, params = zip(*model.named_parameters())
+    if any(p.device != x_local.device for p in params):
+        raise RuntimeError("training needs the model on the compute device: call model.to(device) first")
+    if x_local.shape[0] != shard.n_local or e_local.shape[0] != shard.e_local:
+        raise ValueError(f"x has {x_local.shape[0]} rows for {shard.n_local} local nodes, e has {e_local.shape[0]} rows for {shard.e_local} local edges")
+    return _InEdgeStep.apply(model, _StepGraph.on_shard(shard), x_local, e_local, list(names), *params)
+
+
+def _check_in_edge_step(model):
+    from .train import TRAIN_SCORE_HIDDEN
+    check_arithmetic(model)
+    if getattr(model, "activation_storage", "fp32") != "fp32":
+        raise ValueError(f'training_step="in_edge" keeps activations as "fp32"; activation_storage={model.activation_storage!r} is served by '
+                         'training_step="symmetric"')
+    if getattr(model, "recompute_gate", False):
+        raise ValueError('training_step="in_edge" keeps the gate output; recompute_gate is served by training_step="symmetric"')
+    built_width(model.node_encoder.linear2.out_features)
+    built_width(model.predictor.W1.out_features, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")

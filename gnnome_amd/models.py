@@ -68,7 +68,10 @@ class GatedGCNModel(nn.Module):
     layer - zero tensors, not Parameters, never updated: exact for every parameter this model has, and it costs what the symmetric step
     costs (the out-edge pass and the fifth projection block run on zeros).  `training_step = "in_edge"` (set it on the instance or on a
     subclass): the one-direction step - a [N,4H] projection, gnnome_node_aggregate_in_raw_f32 and its backward
-    gnnome_node_aggregate_in_bwd_f32 - for both `directed` values; fp32 storage, no recompute_gate.  Any other value raises ValueError."""
+    gnnome_node_aggregate_in_bwd_f32 - for both `directed` values; fp32 storage, no recompute_gate.  Any other value raises ValueError.
+
+    Multi-GPU (gnnome_amd/dist.py): eval mode and the "in_edge" step run on a destination-range partition built with
+    PartitionedGraph.from_global(..., in_edges_only=True), directed=True only; "symmetric" raises NotImplementedError there."""
     arithmetic = "auto"
     activation_storage = "fp32"
     range_check = True

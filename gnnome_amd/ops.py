@@ -1083,6 +1083,42 @@ def node_aggregate_in_bwd(e, Tf, Uf, A2h, views, de, out=None):
     return dA2h
 
 
+def node_aggregate_in_raw_part(e, A1h, A2h, views, n_own):
+    """node_aggregate_in_raw on one rank's shard of an in-edge-only partition (gnnome_node_aggregate_in_raw_part_f32): `views` is the local
+    graph (n_own owned nodes first, then the halo), A1h / A2h have a row per LOCAL node; -> (v, fwd, rden), [n_own, H] each."""
+    A1h, ldn = _rows(A1h, "node_aggregate_in_raw_part.A1h")
+    A2h, l2 = _rows(A2h, "node_aggregate_in_raw_part.A2h")
+    assert ldn == l2
+    e = _dense(e, "node_aggregate_in_raw_part.e")
+    H, dev, n_own = A2h.shape[1], A2h.device, int(n_own)
+    if A2h.shape[0] != views.num_nodes or A1h.shape[0] < n_own or e.shape[0] != views.num_edges:
+        raise ValueError(f"node_aggregate_in_raw_part: shapes e{tuple(e.shape)} A1h{tuple(A1h.shape)} A2h{tuple(A2h.shape)} for {n_own} owned of "
+                         f"{views.num_nodes} local nodes and {views.num_edges} edges")
+    v, fwd, rden = (torch.empty((n_own, H), dtype=torch.float32, device=dev) for _ in range(3))
+    _call("gnnome_node_aggregate_in_raw_part_f32", dev, _ptr(e), H, n_own, views.num_nodes, _ptr(A1h), _ptr(A2h), ldn, _ptr(views.in_ptr),
+          _ptr(views.srt_src), _ptr(v), _ptr(fwd), _ptr(rden))
+    return v, fwd, rden
+
+
+def node_aggregate_in_bwd_part(e, Tf, Uf, A2h, views, de, n_own, out=None):
+    """node_aggregate_in_bwd on one rank's shard (gnnome_node_aggregate_in_bwd_part_f32): Tf, Uf [n_own, H]; de += ... over the local edges in
+    place; returns dA2h[n_local, H] - the halo rows are this rank's partial sums, which the halo transpose adds at their owners."""
+    A2h, ldn = _rows(A2h, "node_aggregate_in_bwd_part.A2h")
+    e, de = _dense(e, "node_aggregate_in_bwd_part.e"), _dense(de, "node_aggregate_in_bwd_part.de")
+    Tf, Uf = _dense(Tf, "node_aggregate_in_bwd_part.Tf"), _dense(Uf, "node_aggregate_in_bwd_part.Uf")
+    H, n, n_own = e.shape[1], views.num_nodes, int(n_own)
+    if (Tf.shape != (n_own, H) or Uf.shape != (n_own, H) or de.shape != e.shape or e.shape[0] != views.num_edges or A2h.shape[0] != n
+            or not 0 <= n_own <= n):
+        raise ValueError(f"node_aggregate_in_bwd_part: shapes e{tuple(e.shape)} de{tuple(de.shape)} Tf{tuple(Tf.shape)} Uf{tuple(Uf.shape)} "
+                         f"A2h{tuple(A2h.shape)} for {n_own} owned of {n} local nodes and {views.num_edges} edges")
+    dA2h = torch.empty((n, H), dtype=torch.float32, device=e.device) if out is None else _dense(out, "node_aggregate_in_bwd_part.out")
+    if dA2h.shape != (n, H):
+        raise ValueError(f"node_aggregate_in_bwd_part: out{tuple(dA2h.shape)} for {n} local nodes")
+    _call("gnnome_node_aggregate_in_bwd_part_f32", e.device, _ptr(e), e.shape[0], H, n_own, n, _ptr(Tf), _ptr(Uf), _ptr(A2h), ldn,
+          _ptr(views.in_ptr), _ptr(views.srt_src), _ptr(views.out_ptr), _ptr(views.out_pos), _ptr(views.out_dst), _ptr(de), _ptr(dA2h))
+    return dA2h
+
+
 _COL_WS = {}
 
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNNOME_ABI_VERSION 31
+#define GNNOME_ABI_VERSION 32
 
 #define GNNOME_OK 0
 #define GNNOME_EINVAL (-1)    /* bad argument (null pointer, unsupported width, bad stride)      */
@@ -289,6 +289,30 @@ int gnnome_node_aggregate_in_bwd_f32(const float* e, int64_t num_edges, int hidd
                                      const float* A2h, int ld_node, const int32_t* in_ptr, const int32_t* srt_src,
                                      const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, float* de, float* dA2h,
                                      void* stream);
+
+/* The PARTITION FORMS of the two entries above: one rank's rows of the train-mode GatedGCN layer (layers/gated_gcn_full.py:182-230:
+ * its aggregation lines :212-217 and what autograd runs for them) on a destination-range partition that keeps, per rank, the in-edges
+ * of its owned nodes only.  Local node ids put the num_nodes_out OWNED nodes first, then the halo (the distinct non-owned sources) up to
+ * num_nodes_local; every local edge ends in an owned node, so in_ptr[num_nodes_out] = num_edges and a halo node has no in-list.
+ *
+ * raw:  v_out / aux0 / aux1 dense [num_nodes_out, H] for the owned rows only; A1h rows < num_nodes_out are read, A2h[srt_src[p]] is
+ *       gathered from the num_nodes_local-row table.  The in-lists and their order are the whole graph's (the partition keeps the global
+ *       edge-id order within a destination run), so an owned row equals gnnome_node_aggregate_in_raw_f32's row on the whole graph bit for bit.
+ * bwd:  Tf, Uf dense [num_nodes_out, H].  The destination launch (de += ..., the Tf / Uf consumer) runs over the num_nodes_out owned rows;
+ *       the source launch runs over ALL num_nodes_local rows and walks out_ptr / out_pos / out_dst of the LOCAL edges (out_ptr has
+ *       num_nodes_local + 1 entries, out_dst[q] < num_nodes_out), so dA2h is dense [num_nodes_local, H] and a halo source's row is this
+ *       rank's PARTIAL sum: the owner adds its own row and the partials it receives in ascending rank order (the halo transpose), which
+ *       makes the final row a function of the graph and the world size alone.
+ * Same kernels, lane mapping and association as the whole-graph entries (lists above 4096 items in fixed 128-item blocks, no atomics, no
+ * per-edge table); no wave is spent on a halo destination and no [num_nodes_local, H] output is written that nobody reads.
+ * num_nodes_out <= num_nodes_local is required; with num_nodes_out == num_nodes_local both are the whole-graph entries. */
+int gnnome_node_aggregate_in_raw_part_f32(const float* e, int hidden, int64_t num_nodes_out, int64_t num_nodes_local, const float* A1h,
+                                          const float* A2h, int ld_node, const int32_t* in_ptr, const int32_t* srt_src, float* v_out,
+                                          float* aux0, float* aux1, void* stream);
+int gnnome_node_aggregate_in_bwd_part_f32(const float* e, int64_t num_edges, int hidden, int64_t num_nodes_out, int64_t num_nodes_local,
+                                          const float* Tf, const float* Uf, const float* A2h, int ld_node, const int32_t* in_ptr,
+                                          const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst,
+                                          float* de, float* dA2h, void* stream);
 
 /* ---- unweighted, degree-normalised neighbour sum: the message passing of GCNModel and SAGEModel -------
  * For every node i < num_nodes:
