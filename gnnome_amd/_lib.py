@@ -46,6 +46,8 @@ SIGNATURES = {
     "gnnome_node_neighbour_sum_f32": [_p, _i, _i, _l, _p, _p, _p, _p, _p, _p, _p, _i, _p],
     "gnnome_relu_rows_f32": [_p, _i, _l, _i, _p],
     "gnnome_node_neighbour_sum_bwd_f32": [_p, _i, _i, _l, _p, _p, _p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p],
+    "gnnome_node_neighbour_sum_part_f32": [_p, _i, _i, _l, _l, _p, _l, _p, _p, _p, _p, _p, _p, _p, _i, _p],
+    "gnnome_node_neighbour_sum_bwd_part_f32": [_p, _i, _i, _l, _l, _p, _l, _p, _p, _p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p],
     "gnnome_relu_mul_rows_f32": [_p, _i, _p, _i, _l, _i, _i, _p],
     "gnnome_node_attention_sum_f32": [_p, _i, _p, _i, _p, _i, _i, _i, _l, _p, _p, _p, _p, ctypes.c_float, _p, _p, _i, _p],
     "gnnome_node_attention_sum_stats_f32": [_p, _i, _p, _i, _p, _i, _i, _i, _l, _p, _p, _p, _p, ctypes.c_float, _p, _p, _i, _p, _i, _p],
@@ -204,7 +206,10 @@ def load():
             "(or __graft_entry__.build()). gnnome_amd has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:   # a library older than the binding: entries are also ADDED under one ABI number, so the number alone does not tell
+            raise GnnomeHipError(f"{LIB_PATH} does not export {name}: it was built from an older tree; rebuild") from None
         fn.argtypes = argtypes
         fn.restype = ctypes.c_char_p if name == "gnnome_last_error" else _i
     got = lib.gnnome_abi_version()

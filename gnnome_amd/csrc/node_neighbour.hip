@@ -27,10 +27,29 @@
 // about a millisecond per 10^5 neighbours (an ESTIMATE from node_aggregate_in's per-wave row rate, not a measurement), during which
 // the rest of the chip works on the other nodes.
 //
+// gnnome_node_neighbour_sum_part_f32: the same sum on one rank's shard of a destination-range partition (models/full_graph.py:56-75 and
+// :100-119, layers/processor.py:35-46 and :73-84, per rank): tables of num_nodes_local rows, owned rows first; the rows < num_nodes_out
+// are computed - all of them by the kernel above, or the rows of a LIST by k_node_neighbour_sum_rows, whose wave takes its node from the
+// list instead of the block index (interior rows under the halo exchange, boundary rows after it).  Both run neighbour_sum_row, so a row's
+// bits depend on its lists and the table rows they name alone: equal to the whole-graph entry's at any world size and under any split.
+//
 // gnnome_relu_rows_f32: the ReLU between two layers of those models (processor.py:44, :82), in place on row-strided rows, NaN kept.
 #include "node_neighbour.h"   // the lane mapping and the association above, shared with node_neighbour_bwd.hip
 
 namespace gnnome {
+
+// one node's row: the sum of node_neighbour.h, dscale, the store by lane group 0 (node: wave-uniform)
+template <int H, bool SS>
+__device__ __forceinline__ void neighbour_sum_row(const float* __restrict__ h, int ldh, int64_t node, const int32_t* __restrict__ in_ptr,
+                                                  const int32_t* __restrict__ srt_src, const int32_t* __restrict__ out_ptr,
+                                                  const int32_t* __restrict__ out_dst, const float* __restrict__ sscale,
+                                                  const float* __restrict__ dscale, float* __restrict__ out, int ldo, int lane) {
+    constexpr int LPR = H / 4;
+    const int group = lane / LPR, c = (lane % LPR) * 4;
+    f32x4 v = nbr_node_sum<H, SS>(h, ldh, sscale, node, in_ptr, srt_src, out_ptr, out_dst, lane, group, c);
+    if (dscale != nullptr) v *= dscale[node];
+    if (group == 0) *reinterpret_cast<f32x4*>(out + node * ldo + c) = v;
+}
 
 template <int H, bool SS>
 __global__ __launch_bounds__(kNbrThreads) void k_node_neighbour_sum(const float* __restrict__ h, int ldh, int64_t num_nodes,
@@ -38,29 +57,49 @@ __global__ __launch_bounds__(kNbrThreads) void k_node_neighbour_sum(const float*
                                                                     const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_dst,
                                                                     const float* __restrict__ sscale, const float* __restrict__ dscale,
                                                                     float* __restrict__ out, int ldo, int total_blocks) {
-    constexpr int LPR = H / 4;
     // the wave index read as a scalar: the node and everything loaded through it (the list bounds, its scales) live in scalar registers
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t node = (int64_t)xcd_remap(blockIdx.x, total_blocks) * (kNbrThreads / 64) + wave;
     if (node >= num_nodes) return;
-    const int group = lane / LPR, c = (lane % LPR) * 4;
-
-    f32x4 v = nbr_node_sum<H, SS>(h, ldh, sscale, node, in_ptr, srt_src, out_ptr, out_dst, lane, group, c);
-    if (dscale != nullptr) v *= dscale[node];
-    if (group == 0) *reinterpret_cast<f32x4*>(out + node * ldo + c) = v;
+    neighbour_sum_row<H, SS>(h, ldh, node, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ldo, lane);
 }
 
+// The row-list form (gnnome_node_neighbour_sum_part_f32 with rows != NULL): wave w of the launch computes node rows[w] - a scalar load
+// through the wave index - and nothing else; the row's bits depend on its own lists alone, so they are the kernel's above.
+template <int H, bool SS>
+__global__ __launch_bounds__(kNbrThreads) void k_node_neighbour_sum_rows(const float* __restrict__ h, int ldh, const int32_t* __restrict__ rows,
+                                                                         int64_t num_rows, const int32_t* __restrict__ in_ptr,
+                                                                         const int32_t* __restrict__ srt_src, const int32_t* __restrict__ out_ptr,
+                                                                         const int32_t* __restrict__ out_dst, const float* __restrict__ sscale,
+                                                                         const float* __restrict__ dscale, float* __restrict__ out, int ldo,
+                                                                         int total_blocks) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t w = (int64_t)xcd_remap(blockIdx.x, total_blocks) * (kNbrThreads / 64) + wave;
+    if (w >= num_rows) return;
+    neighbour_sum_row<H, SS>(h, ldh, (int64_t)rows[w], in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ldo, lane);
+}
+
+// n waves: the nodes [0, n) (rows == NULL) or the n listed ones
 template <int H>
-static int launch_neighbour_sum(const float* h, int ldh, int64_t n, const int32_t* in_ptr, const int32_t* srt_src, const int32_t* out_ptr,
-                                const int32_t* out_dst, const float* sscale, const float* dscale, float* out, int ldo, hipStream_t s) {
+static int launch_neighbour_sum(const float* h, int ldh, int64_t n, const int32_t* rows, const int32_t* in_ptr, const int32_t* srt_src,
+                                const int32_t* out_ptr, const int32_t* out_dst, const float* sscale, const float* dscale, float* out, int ldo,
+                                hipStream_t s) {
     const int64_t blocks = (n + (kNbrThreads / 64) - 1) / (kNbrThreads / 64);
     GN_REQUIRE(blocks < (1ll << 31), "node_neighbour_sum: too many nodes");
-    if (sscale != nullptr)
-        hipLaunchKernelGGL((k_node_neighbour_sum<H, true>), dim3((unsigned)blocks), dim3(kNbrThreads), 0, s, h, ldh, n, in_ptr, srt_src, out_ptr,
-                           out_dst, sscale, dscale, out, ldo, (int)blocks);
+    const dim3 grid((unsigned)blocks), block(kNbrThreads);
+    if (rows != nullptr) {
+        if (sscale != nullptr)
+            hipLaunchKernelGGL((k_node_neighbour_sum_rows<H, true>), grid, block, 0, s, h, ldh, rows, n, in_ptr, srt_src, out_ptr, out_dst, sscale,
+                               dscale, out, ldo, (int)blocks);
+        else
+            hipLaunchKernelGGL((k_node_neighbour_sum_rows<H, false>), grid, block, 0, s, h, ldh, rows, n, in_ptr, srt_src, out_ptr, out_dst, sscale,
+                               dscale, out, ldo, (int)blocks);
+    } else if (sscale != nullptr)
+        hipLaunchKernelGGL((k_node_neighbour_sum<H, true>), grid, block, 0, s, h, ldh, n, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ldo,
+                           (int)blocks);
     else
-        hipLaunchKernelGGL((k_node_neighbour_sum<H, false>), dim3((unsigned)blocks), dim3(kNbrThreads), 0, s, h, ldh, n, in_ptr, srt_src, out_ptr,
-                           out_dst, sscale, dscale, out, ldo, (int)blocks);
+        hipLaunchKernelGGL((k_node_neighbour_sum<H, false>), grid, block, 0, s, h, ldh, n, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ldo,
+                           (int)blocks);
     GN_LAUNCH_CHECK();
     return GNNOME_OK;
 }
@@ -82,13 +121,11 @@ __global__ __launch_bounds__(kReluThreads) void k_relu_rows(float* __restrict__ 
 
 }  // namespace gnnome
 
-extern "C" int gnnome_node_neighbour_sum_f32(const float* h, int ld_h, int hidden, int64_t num_nodes, const int32_t* in_ptr,
-                                             const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_dst, const float* sscale,
-                                             const float* dscale, float* out, int ld_out, void* stream) {
+// what both entries check and launch: `waves` nodes - [0, waves) or the listed rows - of tables with any number of rows
+static int neighbour_sum_entry(const float* h, int ld_h, int hidden, int64_t waves, const int32_t* rows, const int32_t* in_ptr,
+                               const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_dst, const float* sscale, const float* dscale,
+                               float* out, int ld_out, void* stream) {
     using namespace gnnome;
-    GN_REQUIRE(num_nodes >= 0, "node_neighbour_sum: negative node count");
-    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "node_neighbour_sum: hidden=%d not in {64,128,256}", hidden);
-    if (num_nodes == 0) return GNNOME_OK;
     // srt_src / out_dst may be NULL for a graph without edges (never dereferenced then); out_ptr == NULL selects the directed form
     GN_REQUIRE(h && in_ptr && out, "node_neighbour_sum: null pointer");
     GN_REQUIRE(ld_h >= hidden && ld_h % 4 == 0 && ld_out >= hidden && ld_out % 4 == 0, "node_neighbour_sum: bad strides");
@@ -96,10 +133,38 @@ extern "C" int gnnome_node_neighbour_sum_f32(const float* h, int ld_h, int hidde
     GN_REQUIRE(out != h, "node_neighbour_sum: out must not alias h");
     hipStream_t s = (hipStream_t)stream;
     switch (hidden) {
-        case 64: return launch_neighbour_sum<64>(h, ld_h, num_nodes, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, s);
-        case 128: return launch_neighbour_sum<128>(h, ld_h, num_nodes, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, s);
-        default: return launch_neighbour_sum<256>(h, ld_h, num_nodes, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, s);
+        case 64: return launch_neighbour_sum<64>(h, ld_h, waves, rows, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, s);
+        case 128: return launch_neighbour_sum<128>(h, ld_h, waves, rows, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, s);
+        default: return launch_neighbour_sum<256>(h, ld_h, waves, rows, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, s);
     }
+}
+
+extern "C" int gnnome_node_neighbour_sum_f32(const float* h, int ld_h, int hidden, int64_t num_nodes, const int32_t* in_ptr,
+                                             const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_dst, const float* sscale,
+                                             const float* dscale, float* out, int ld_out, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_nodes >= 0, "node_neighbour_sum: negative node count");
+    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "node_neighbour_sum: hidden=%d not in {64,128,256}", hidden);
+    if (num_nodes == 0) return GNNOME_OK;
+    return neighbour_sum_entry(h, ld_h, hidden, num_nodes, nullptr, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, stream);
+}
+
+// One rank's shard of a destination-range partition that keeps every edge with an owned end (models/full_graph.py:56-75, :100-119;
+// layers/processor.py:35-46, :73-84 per rank): the tables and lists have num_nodes_local rows, owned rows first; rows < num_nodes_out are
+// computed - all of them, or the listed ones.  Same kernels' row code, so an owned row has the whole-graph entry's bits (header).
+extern "C" int gnnome_node_neighbour_sum_part_f32(const float* h, int ld_h, int hidden, int64_t num_nodes_out, int64_t num_nodes_local,
+                                                  const int32_t* rows, int64_t num_rows, const int32_t* in_ptr, const int32_t* srt_src,
+                                                  const int32_t* out_ptr, const int32_t* out_dst, const float* sscale, const float* dscale,
+                                                  float* out, int ld_out, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_nodes_out >= 0 && num_nodes_out <= num_nodes_local, "node_neighbour_sum_part: %lld destination rows of %lld local rows",
+               (long long)num_nodes_out, (long long)num_nodes_local);
+    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "node_neighbour_sum_part: hidden=%d not in {64,128,256}", hidden);
+    GN_REQUIRE(rows == nullptr || (num_rows >= 0 && num_rows <= num_nodes_out), "node_neighbour_sum_part: %lld listed rows of %lld destination rows",
+               (long long)num_rows, (long long)num_nodes_out);
+    const int64_t waves = rows != nullptr ? num_rows : num_nodes_out;
+    if (waves == 0) return GNNOME_OK;
+    return neighbour_sum_entry(h, ld_h, hidden, waves, rows, in_ptr, srt_src, out_ptr, out_dst, sscale, dscale, out, ld_out, stream);
 }
 
 extern "C" int gnnome_relu_rows_f32(float* x, int ld, int64_t rows, int hidden, void* stream) {

@@ -20,6 +20,11 @@
 // THE EPILOGUE IS FOUR SEPARATE ROUNDINGS in the order above, written with __fmul_rn / __fadd_rn, which the compiler never contracts:
 // oscale * s + add is NOT an fma here, so the result equals the four element-wise fp32 passes it replaces bit for bit.
 //
+// gnnome_node_neighbour_sum_bwd_part_f32: the same on one rank's shard (models/full_graph.py:56-75, :100-119; layers/processor.py:35-46,
+// :73-84, per rank), as gnnome_node_neighbour_sum_part_f32: g and rscale have num_nodes_local rows - the halo rows of g FETCHED from their
+// owners, a forward-direction exchange -, the epilogue's operands and out the owned rows; all owned rows, or the rows of a list
+// (k_node_neighbour_sum_bwd_rows).  The owned nodes' out- and in-lists are complete on the default partition, so no partial sums exist.
+//
 // gnnome_relu_mul_rows_f32: x <- relu(x) * mult in place on row-strided rows (relu = 0: x <- x * mult), NaN kept - SAGE's feat_drop
 // applied where the ReLU already touches the row.  The keep-mask is 0 or 1/(1-p) >= 1, so the stored x_d > 0 exactly where the ReLU
 // passed AND the mask kept: the backward gates on the stored row itself (`y` above) and no pre-dropout copy is saved.
@@ -27,18 +32,30 @@
 
 namespace gnnome {
 
+struct NbrBwdArgs {
+    const float* g;
+    int ldg;
+    int64_t n;               // waves: the nodes [0, n), or the n listed rows
+    const int32_t* rows;     // NULL, or the row list of gnnome_node_neighbour_sum_bwd_part_f32
+    const int32_t *out_ptr, *out_dst, *in_ptr, *srt_src;
+    const float *rscale, *oscale, *add;
+    int ld_add;
+    const float* mult;
+    int ld_mult;
+    const float* y;
+    int ld_y;
+    float* out;
+    int ldo;
+};
+
+// one node's row: the sum of node_neighbour.h, then the epilogue on lane group 0 and its store (node: wave-uniform)
 template <int H, bool SS>
-__global__ __launch_bounds__(kNbrThreads) void k_node_neighbour_sum_bwd(const float* __restrict__ g, int ldg, int64_t num_nodes,
-                                                                        const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_dst,
-                                                                        const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ srt_src,
-                                                                        const float* __restrict__ rscale, const float* __restrict__ oscale,
-                                                                        const float* add, int ld_add, const float* mult, int ld_mult,
-                                                                        const float* y, int ld_y, float* out, int ldo, int total_blocks) {
+__device__ __forceinline__ void neighbour_sum_bwd_row(const float* __restrict__ g, int ldg, int64_t node, const int32_t* __restrict__ out_ptr,
+                                                      const int32_t* __restrict__ out_dst, const int32_t* __restrict__ in_ptr,
+                                                      const int32_t* __restrict__ srt_src, const float* __restrict__ rscale,
+                                                      const float* __restrict__ oscale, const float* add, int ld_add, const float* mult,
+                                                      int ld_mult, const float* y, int ld_y, float* out, int ldo, int lane) {
     constexpr int LPR = H / 4;
-    // (the wave index as a scalar: see k_node_neighbour_sum)
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t node = (int64_t)xcd_remap(blockIdx.x, total_blocks) * (kNbrThreads / 64) + wave;
-    if (node >= num_nodes) return;
     const int group = lane / LPR, c = (lane % LPR) * 4;
 
     f32x4 v = nbr_node_sum<H, SS>(g, ldg, rscale, node, out_ptr, out_dst, in_ptr, srt_src, lane, group, c);
@@ -66,26 +83,41 @@ __global__ __launch_bounds__(kNbrThreads) void k_node_neighbour_sum_bwd(const fl
     *reinterpret_cast<f32x4*>(out + node * ldo + c) = v;
 }
 
-struct NbrBwdArgs {
-    const float* g;
-    int ldg;
-    int64_t n;
-    const int32_t *out_ptr, *out_dst, *in_ptr, *srt_src;
-    const float *rscale, *oscale, *add;
-    int ld_add;
-    const float* mult;
-    int ld_mult;
-    const float* y;
-    int ld_y;
-    float* out;
-    int ldo;
-};
+template <int H, bool SS>
+__global__ __launch_bounds__(kNbrThreads) void k_node_neighbour_sum_bwd(const float* __restrict__ g, int ldg, int64_t num_nodes,
+                                                                        const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_dst,
+                                                                        const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ srt_src,
+                                                                        const float* __restrict__ rscale, const float* __restrict__ oscale,
+                                                                        const float* add, int ld_add, const float* mult, int ld_mult,
+                                                                        const float* y, int ld_y, float* out, int ldo, int total_blocks) {
+    // (the wave index as a scalar: see k_node_neighbour_sum)
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t node = (int64_t)xcd_remap(blockIdx.x, total_blocks) * (kNbrThreads / 64) + wave;
+    if (node >= num_nodes) return;
+    neighbour_sum_bwd_row<H, SS>(g, ldg, node, out_ptr, out_dst, in_ptr, srt_src, rscale, oscale, add, ld_add, mult, ld_mult, y, ld_y, out, ldo, lane);
+}
+
+// The row-list form (gnnome_node_neighbour_sum_bwd_part_f32 with rows != NULL): wave w of the launch computes node rows[w], as
+// k_node_neighbour_sum_rows does
+template <int H, bool SS>
+__global__ __launch_bounds__(kNbrThreads) void k_node_neighbour_sum_bwd_rows(const NbrBwdArgs a, int total_blocks) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t w = (int64_t)xcd_remap(blockIdx.x, total_blocks) * (kNbrThreads / 64) + wave;
+    if (w >= a.n) return;
+    neighbour_sum_bwd_row<H, SS>(a.g, a.ldg, (int64_t)a.rows[w], a.out_ptr, a.out_dst, a.in_ptr, a.srt_src, a.rscale, a.oscale, a.add, a.ld_add,
+                                 a.mult, a.ld_mult, a.y, a.ld_y, a.out, a.ldo, lane);
+}
 
 template <int H>
 static int launch_neighbour_sum_bwd(const NbrBwdArgs& a, hipStream_t s) {
     const int64_t blocks = (a.n + (kNbrThreads / 64) - 1) / (kNbrThreads / 64);
     GN_REQUIRE(blocks < (1ll << 31), "node_neighbour_sum_bwd: too many nodes");
-    if (a.rscale != nullptr)
+    if (a.rows != nullptr) {
+        if (a.rscale != nullptr)
+            hipLaunchKernelGGL((k_node_neighbour_sum_bwd_rows<H, true>), dim3((unsigned)blocks), dim3(kNbrThreads), 0, s, a, (int)blocks);
+        else
+            hipLaunchKernelGGL((k_node_neighbour_sum_bwd_rows<H, false>), dim3((unsigned)blocks), dim3(kNbrThreads), 0, s, a, (int)blocks);
+    } else if (a.rscale != nullptr)
         hipLaunchKernelGGL((k_node_neighbour_sum_bwd<H, true>), dim3((unsigned)blocks), dim3(kNbrThreads), 0, s, a.g, a.ldg, a.n, a.out_ptr, a.out_dst,
                            a.in_ptr, a.srt_src, a.rscale, a.oscale, a.add, a.ld_add, a.mult, a.ld_mult, a.y, a.ld_y, a.out, a.ldo, (int)blocks);
     else
@@ -118,6 +150,28 @@ static bool table_ok(const void* p, int ld, int hidden) { return ld >= hidden &&
 
 }  // namespace gnnome
 
+// what both entries check and launch: `waves` nodes - [0, waves) or the listed rows - of tables with any number of rows
+static int neighbour_sum_bwd_entry(const float* g, int ld_g, int hidden, int64_t waves, const int32_t* rows, const int32_t* out_ptr,
+                                   const int32_t* out_dst, const int32_t* in_ptr, const int32_t* srt_src, int both, const float* rscale,
+                                   const float* oscale, const float* add, int ld_add, const float* mult, int ld_mult, const float* y, int ld_y,
+                                   float* out, int ld_out, void* stream) {
+    using namespace gnnome;
+    // out_dst / srt_src may be NULL for a graph without edges (never dereferenced then); in_ptr is read with `both` only
+    GN_REQUIRE(g && out && out_ptr && (!both || in_ptr), "node_neighbour_sum_bwd: null pointer");
+    GN_REQUIRE(table_ok(g, ld_g, hidden) && table_ok(out, ld_out, hidden) && (!add || table_ok(add, ld_add, hidden)) &&
+                   (!mult || table_ok(mult, ld_mult, hidden)) && (!y || table_ok(y, ld_y, hidden)),
+               "node_neighbour_sum_bwd: g, add, mult, y and out are 16-byte aligned tables with row strides >= hidden that are multiples of 4");
+    GN_REQUIRE(out != g && out != add, "node_neighbour_sum_bwd: out must not alias g or add");
+    const NbrBwdArgs a{g, ld_g, waves, rows, out_ptr, out_dst, both ? in_ptr : nullptr, both ? srt_src : nullptr, rscale, oscale, add, ld_add,
+                       mult, ld_mult, y, ld_y, out, ld_out};
+    hipStream_t s = (hipStream_t)stream;
+    switch (hidden) {
+        case 64: return launch_neighbour_sum_bwd<64>(a, s);
+        case 128: return launch_neighbour_sum_bwd<128>(a, s);
+        default: return launch_neighbour_sum_bwd<256>(a, s);
+    }
+}
+
 extern "C" int gnnome_node_neighbour_sum_bwd_f32(const float* g, int ld_g, int hidden, int64_t num_nodes, const int32_t* out_ptr,
                                                  const int32_t* out_dst, const int32_t* in_ptr, const int32_t* srt_src, int both,
                                                  const float* rscale, const float* oscale, const float* add, int ld_add, const float* mult,
@@ -126,20 +180,27 @@ extern "C" int gnnome_node_neighbour_sum_bwd_f32(const float* g, int ld_g, int h
     GN_REQUIRE(num_nodes >= 0, "node_neighbour_sum_bwd: negative node count");
     GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "node_neighbour_sum_bwd: hidden=%d not in {64,128,256}", hidden);
     if (num_nodes == 0) return GNNOME_OK;
-    // out_dst / srt_src may be NULL for a graph without edges (never dereferenced then); in_ptr is read with `both` only
-    GN_REQUIRE(g && out && out_ptr && (!both || in_ptr), "node_neighbour_sum_bwd: null pointer");
-    GN_REQUIRE(table_ok(g, ld_g, hidden) && table_ok(out, ld_out, hidden) && (!add || table_ok(add, ld_add, hidden)) &&
-                   (!mult || table_ok(mult, ld_mult, hidden)) && (!y || table_ok(y, ld_y, hidden)),
-               "node_neighbour_sum_bwd: g, add, mult, y and out are 16-byte aligned tables with row strides >= hidden that are multiples of 4");
-    GN_REQUIRE(out != g && out != add, "node_neighbour_sum_bwd: out must not alias g or add");
-    const NbrBwdArgs a{g, ld_g, num_nodes, out_ptr, out_dst, both ? in_ptr : nullptr, both ? srt_src : nullptr, rscale, oscale, add, ld_add,
-                       mult, ld_mult, y, ld_y, out, ld_out};
-    hipStream_t s = (hipStream_t)stream;
-    switch (hidden) {
-        case 64: return launch_neighbour_sum_bwd<64>(a, s);
-        case 128: return launch_neighbour_sum_bwd<128>(a, s);
-        default: return launch_neighbour_sum_bwd<256>(a, s);
-    }
+    return neighbour_sum_bwd_entry(g, ld_g, hidden, num_nodes, nullptr, out_ptr, out_dst, in_ptr, srt_src, both, rscale, oscale, add, ld_add, mult,
+                                   ld_mult, y, ld_y, out, ld_out, stream);
+}
+
+// One rank's shard (see gnnome_node_neighbour_sum_part_f32): g and rscale have num_nodes_local rows - the halo rows of g fetched from
+// their owners -, the lists num_nodes_local + 1 bounds; oscale, add, mult, y and out are touched at the computed rows (< num_nodes_out) only.
+extern "C" int gnnome_node_neighbour_sum_bwd_part_f32(const float* g, int ld_g, int hidden, int64_t num_nodes_out, int64_t num_nodes_local,
+                                                      const int32_t* rows, int64_t num_rows, const int32_t* out_ptr, const int32_t* out_dst,
+                                                      const int32_t* in_ptr, const int32_t* srt_src, int both, const float* rscale,
+                                                      const float* oscale, const float* add, int ld_add, const float* mult, int ld_mult,
+                                                      const float* y, int ld_y, float* out, int ld_out, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_nodes_out >= 0 && num_nodes_out <= num_nodes_local, "node_neighbour_sum_bwd_part: %lld destination rows of %lld local rows",
+               (long long)num_nodes_out, (long long)num_nodes_local);
+    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "node_neighbour_sum_bwd_part: hidden=%d not in {64,128,256}", hidden);
+    GN_REQUIRE(rows == nullptr || (num_rows >= 0 && num_rows <= num_nodes_out),
+               "node_neighbour_sum_bwd_part: %lld listed rows of %lld destination rows", (long long)num_rows, (long long)num_nodes_out);
+    const int64_t waves = rows != nullptr ? num_rows : num_nodes_out;
+    if (waves == 0) return GNNOME_OK;
+    return neighbour_sum_bwd_entry(g, ld_g, hidden, waves, rows, out_ptr, out_dst, in_ptr, srt_src, both, rscale, oscale, add, ld_add, mult,
+                                   ld_mult, y, ld_y, out, ld_out, stream);
 }
 
 extern "C" int gnnome_relu_mul_rows_f32(float* x, int ld, const float* mult, int ld_mult, int64_t rows, int hidden, int relu, void* stream) {

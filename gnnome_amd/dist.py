@@ -17,6 +17,10 @@ inference.py:388).  This is the north_star's scheme:
     sorted order; ONE all_gather of the pieces (E*4/G bytes each, padded to the largest) and one index_select
     through a map built with the plan put them into global edge-id order (SURVEY.md 8e "Scorer").
 
+GatedGCNModel runs on the in-edge-only form of the partition (engine_gated.py); GCNModel and SAGEModel on the default one, with one
+exchange of h and one forward-direction exchange of its gradient per layer and neighbour sums bit-equal to the single-rank run
+(engine_baselines.py, "destination-range partitions"); GATModel is refused.
+
 All tensor math goes through an `ops` namespace exactly like engine.run_stack: the product passes
 gnnome_amd.ops (HIP); the CPU/gloo tests pass the checker backend to exercise this host logic.
 """
@@ -124,6 +128,7 @@ class PartitionedGraph:
         self.node_perm = self.node_gather = None   # optional renumbering the ranges were cut in (caller's id -> internal id, and back)
         self.score_pad = 0          # rows of the padded logits piece every rank contributes to the all_gather
         self.score_index = None     # int64 [E_global]: where global edge id k sits in the flattened [world, score_pad] gather
+        self._baseline = {}         # directed -> engine_baselines.PartitionPlan (scales of all local rows, lists, interior / boundary rows)
 
     @classmethod
     def from_global(cls, src, dst, num_nodes, rank, world, device, ops=hip_ops, group=None, node_perm=None, in_edges_only=False,
@@ -359,19 +364,27 @@ class HaloExchange:
 
     def __init__(self, part, ops, group=None):
         self.part, self.ops, self.group, self.work, self._keep, self._bwd = part, ops, group, None, None, None
+        self._into = None   # the strided halo rows a dense receive buffer is copied into by finish() (see start)
 
     def start(self, h):
         p = self.part
         if _alone(p.world):
             return
         packed = self.ops.gather_rows(h, p.send_idx)
-        self._keep = packed
-        self.work = all_to_all_rows(h[p.n_own:], packed, p.recv_counts, p.send_counts, self.group, async_op=True)
+        into, self._into = h[p.n_own:], None
+        if not into.is_contiguous():
+            # a column block of a wider table (SAGEModel's h | m, dT): all_to_all_single writes dense memory only, so the rows are received
+            # into a dense [halo, H] buffer and finish() copies them in - one more [halo, H] read + write per such exchange
+            self._into, into = into, torch.empty(into.shape, dtype=h.dtype, device=h.device)
+        self._keep = (packed, into)   # (both stay alive until the collective is done)
+        self.work = all_to_all_rows(into, packed, p.recv_counts, p.send_counts, self.group, async_op=True)
 
     def finish(self):
         if self.work is not None:
             self.work.wait()
-        self.work, self._keep = None, None
+        if self._into is not None:
+            self._into.copy_(self._keep[1])
+        self.work, self._keep, self._into = None, None, None
 
     def transpose(self, dh):
         """Backward of start/finish: the halo rows of dh return to their owners, which add them to their own rows
@@ -501,6 +514,9 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result
     every rank after the all_reduce when `reduce_result`).
     prep = engine_gated.Prepared (a GatedGCNModel): engine_gated's eval sequence per layer - the [n_local,4H] projection, the same gate,
     gnnome_node_aggregate_in_f32 over the owned rows - on an in-edge-only partition (PartitionedGraph.from_global(..., in_edges_only=True))."""
+    from . import engine_baselines
+    if isinstance(prep, engine_baselines.Prepared):   # GCNModel / SAGEModel: engine_baselines' sequence on the default partition
+        return engine_baselines.run_partitioned(ops, prep, part, x_local, e_local, group)
     gated = _check_partition_kind(prep, part)
     views, n_own = part.views, part.n_own
     xchg = HaloExchange(part, ops, group)
@@ -555,6 +571,8 @@ class CapturedPartitionedForward:
         ops, prep, part = runner.ops, runner.prep, runner.part
         if isinstance(prep, engine_gated.Prepared):
             raise NotImplementedError("CapturedPartitionedForward is built for SymGatedGCNModel; a GatedGCNModel runs the eager forward()")
+        if not isinstance(prep, engine.Prepared):
+            raise NotImplementedError("CapturedPartitionedForward is built for SymGatedGCNModel; a GCNModel / SAGEModel runs the eager forward()")
         self.part, self.group, self.ops = part, runner.group, ops
         self.alone = alone = _alone(part.world)
         dev = runner.x.device
@@ -620,21 +638,35 @@ class _ScoreViews:
 class PartitionedRunner:
     """Holds one rank's partition, weights and inputs on its GPU; forward() = one whole-graph scoring pass."""
 
-    def __init__(self, model, part, x_global, e_global, device, ops=hip_ops, group=None, x_local=None, e_local=None):
+    def __init__(self, model, part, x_global, e_global, device, ops=hip_ops, group=None, x_local=None, e_local=None, split=None):
         """x_global[N,F]: the node features of the whole graph (this rank keeps its owned + halo rows), or x_local: those rows
         already selected (part.local_node_rows), for callers that never hold the [N,F] table on this device; e_global[E,F] or
-        e_local (part.local_edge_rows / part.shuffle_edge_rows) likewise."""
+        e_local (part.local_edge_rows / part.shuffle_edge_rows) likewise.
+        split (GCNModel / SAGEModel only): True = the neighbour sums as interior rows under the halo exchange + boundary rows after it,
+        False = one launch after it, None = engine_baselines.PARTITION_SPLIT; equal bits either way."""
         self.ops, self.part, self.group, self.model = ops, part, group, model
+        from . import engine_baselines
         from .models import GatedGCNModel
+        kind = getattr(model, "kind", None)             # GCNModel "gcn", SAGEModel "sage", GATModel "gat" (engine_baselines.py, engine_gat.py)
+        self.baseline = kind in engine_baselines.KINDS
         self.gated = isinstance(model, GatedGCNModel)   # (engine_gated.py): the in-edge-only partition, its own kernel sequences
-        if self.gated:
+        if kind == "gat":
+            raise NotImplementedError("GATModel is not served on partitions: its edge softmax needs every destination's complete in-list "
+                                      "per head and its backward a second exchange - the follow-up to the GCNModel / SAGEModel partition")
+        if split is not None and not self.baseline:
+            raise ValueError("split= selects the launch form of GCNModel / SAGEModel's neighbour sums; the gated models have none")
+        self.split = split
+        if self.baseline:
+            engine_baselines.check_partition(model, part)
+        elif self.gated:
             if not model.directed:
                 raise NotImplementedError("GatedGCNModel with directed=False is not served on partitions (the doubled edge list is not partitioned)")
             if not part.in_edges_only:
                 raise ValueError("GatedGCNModel runs on an in-edge-only partition: PartitionedGraph.from_global(..., in_edges_only=True)")
         elif part.in_edges_only:
             raise ValueError("an in-edge-only partition serves GatedGCNModel; SymGatedGCNModel needs the out-edges of the owned nodes too")
-        self.prep = None if model.training else engine.prepared_for(model, device, engine_gated.Prepared if self.gated else engine.Prepared)
+        prepared = engine_baselines.Prepared if self.baseline else engine_gated.Prepared if self.gated else engine.Prepared
+        self.prep = None if model.training else engine.prepared_for(model, device, prepared)
         rows = part.local_node_rows(x_global) if x_local is None else x_local
         self.x = rows.to(device=device, dtype=torch.float32).contiguous()
         erows = part.local_edge_rows(e_global) if e_local is None else e_local
@@ -652,12 +684,20 @@ class PartitionedRunner:
         if getattr(self, "_captured", None) is not None:
             return self._captured()
         with torch.no_grad():
+            if self.baseline:
+                from . import engine_baselines
+                return engine_baselines.forward_partitioned(self.ops, self.model, self.prep, self.part, self.x, self.e, self.group,
+                                                          split=self.split).unsqueeze(1)
             return run_partitioned(self.ops, self.prep, self.part, self.x, self.e, self.group).unsqueeze(1)
 
     def train_forward(self):
         """train mode: logits[E,1] with autograd history; after loss.backward() every rank holds the whole graph's
         parameter gradients (already summed over ranks), so identical optimizers stay in step without a DDP wrapper."""
         from .train import train_forward_on
+        if self.baseline:   # GCNModel / SAGEModel: engine_baselines' step on the shard (one exchange of h and one of its gradient per layer)
+            from . import engine_baselines
+            return engine_baselines.train_forward_on(self.model, PartitionShard(self.part, self.ops, self.group), self.x, self.e,
+                                                     split=self.split)
         if self.gated:
             # GatedGCNModel: the one-direction step on the shard; the symmetric-step adapter (zero A_3) is not served on partitions
             if engine_gated.training_step_of(self.model) != "in_edge":

@@ -26,6 +26,9 @@ the layer's product):
 the scorer's and the encoders' backward on the symmetric step's kernels.  No atomics anywhere: two steps from equal state leave equal
 gradient bits.  A forward whose logits are not all finite left fp16x3's operand range and is run again as bf16x6, like forward_in_range
 (one host sync per step; `model.range_check = False` drops it); its backward then runs as bf16x6 too.
+
+Several GPUs: the last section of this file - the same two sequences on one rank of a destination-range partition (dist.PartitionedRunner),
+on gnnome_node_neighbour_sum_part_f32 / _bwd_part_f32.
 """
 import torch
 
@@ -98,6 +101,7 @@ class Prepared:
 
         self.device, self.kind = device, model.kind
         assert self.kind in KINDS
+        self.directed = bool(model.directed)   # (read by the partitioned forward, which dist.run_partitioned reaches with the weights alone)
         self.hidden = built_width(model.node_encoder.linear2.out_features)
         self.enc_node = tuple(dev(t) for t in (model.node_encoder.linear1.weight, model.node_encoder.linear1.bias,
                                                model.node_encoder.linear2.weight, model.node_encoder.linear2.bias))
@@ -413,3 +417,387 @@ def model_forward(model, graph, x, e, prepared=Prepared, stack=run_stack):
                                   run_stack=stack)
     views.check_range()   # a fresh graph's deferred endpoint check, after the whole forward has been enqueued
     return logits.unsqueeze(1).to(out_device)
+
+
+# ---------------------------------------------------------------------------------------------------
+# destination-range partitions (gnnome_amd/dist.py): one rank's rows of the same two sequences
+# ---------------------------------------------------------------------------------------------------
+# GCN and SAGE have no normalisation layer and no per-edge activation, so nothing but node rows crosses ranks.  On the DEFAULT partition
+# (every edge with an owned end) an owned node's in- and out-list are complete, so with the halo rows of the layer's input fetched (one
+# exchange, the symmetric model's) the rank computes its owned rows with the whole graph's association: the neighbour sums are BIT-EQUAL
+# to the single-rank run at any world size.  The same holds backward once the halo rows of the incoming gradient are fetched - a
+# FORWARD-direction exchange of g, no halo transpose and no partial sums in the convolution stack.  Only the scorer's node gradient
+# (halo_bwd) and the parameter gradients (sum_ranks, once, at the end) are summed across ranks.
+# The rows split into INTERIOR (no list entry is a halo id: launched while the exchange is in flight) and BOUNDARY (launched after it)
+# through the row-list form of the part entries; PARTITION_SPLIT selects that or one unsplit launch after the exchange - equal bits.
+
+# the default of every split= argument below (dist.PartitionedRunner(..., split=)): not measured on two devices yet
+# (tools/baseline_partition_time.py), so it is the unsplit launch
+PARTITION_SPLIT = False
+MAX_EXACT_DEGREE = 1 << 24   # the largest degree of g' accepted: every integer up to 2^24 is a float32, in + out + 1 formed in float32 included
+
+
+class ShardLists:
+    """What the part entries read of a shard: the local in-lists as GraphViews built them (ascending edge id: the whole graph's order) and
+    the local out-lists RE-SORTED into the whole graph's order - ascending GLOBAL far-end id, then edge id; GraphViews orders them by
+    local id, which puts the halo after the owned nodes."""
+    __slots__ = ("num_nodes", "num_edges", "in_ptr", "srt_src", "out_ptr", "out_dst", "transposed")
+
+    def __init__(self, views, node_gid):
+        self.num_nodes, self.num_edges, self.transposed = views.num_nodes, views.num_edges, False
+        self.in_ptr, self.srt_src, self.out_ptr = views.in_ptr, views.srt_src, views.out_ptr
+        counts = (views.out_ptr[1:] - views.out_ptr[:-1]).long()
+        owner = torch.repeat_interleave(torch.arange(views.num_nodes, device=counts.device), counts)
+        far = node_gid.to(counts.device)[views.out_dst.long()]
+        bound = int(node_gid.max()) + 1 if node_gid.numel() else 1
+        order = torch.sort(owner * bound + far, stable=True).indices    # (ties - parallel edges - keep their edge-id order)
+        self.out_dst = views.out_dst[order].contiguous()
+
+
+class PartitionPlan:
+    """One (partition, directed): the scale vectors of ALL local rows - Scales' formulas on the whole graph's degrees, the halo rows'
+    fetched once from their owners -, the lists, and the interior / boundary rows of the forward and of the backward launch."""
+    __slots__ = ("lists", "din_rsqrt", "dout_rsqrt", "din_inv", "rows_fwd", "rows_bwd")
+
+    def __init__(self, ops, part, directed, group=None):
+        from .dist import HaloExchange
+        views, n_own, n_local = part.views, part.n_own, part.n_local
+        dev = views.in_ptr.device
+        # the owned rows' degrees are complete locally: the partition keeps every edge with an owned end
+        deg = torch.zeros((n_local, 4), dtype=torch.float32, device=dev)   # in | out | 0 | 0 (rows of four floats: what gather_rows moves)
+        own_in = (views.in_ptr[1:n_own + 1] - views.in_ptr[:n_own])
+        own_out = (views.out_ptr[1:n_own + 1] - views.out_ptr[:n_own])
+        # the degrees of g' are formed in float32 (here and in Scales): in + 1, out + 1, or in + out + 1 - refused where the largest of them
+        # passes 2^24, up to which every integer and every such sum is exact (a halo row's is refused by its owner, which makes the same plan)
+        top = 0 if not n_own else int((own_in.long() + own_out.long()).max()) + 1 if not directed else max(int(own_in.max()), int(own_out.max())) + 1
+        if top > MAX_EXACT_DEGREE:
+            raise ValueError(f"a node of degree {top} in the self-looped{'' if directed else ', doubled'} graph: degrees cross ranks and are "
+                             f"summed as float32, exact up to {MAX_EXACT_DEGREE}")
+        deg[:n_own, 0], deg[:n_own, 1] = own_in.float(), own_out.float()
+        xchg = HaloExchange(part, ops, group)
+        xchg.start(deg)
+        xchg.finish()
+        din, dout = deg[:, 0], deg[:, 1]
+        if directed:
+            din, dout = din + 1.0, dout + 1.0
+        else:
+            din = dout = din + dout + 1.0
+        self.din_rsqrt, self.dout_rsqrt = din.pow(-0.5).contiguous(), dout.pow(-0.5).contiguous()
+        self.din_inv = (1.0 / din).contiguous()
+        self.lists = ShardLists(views, part.node_gid)
+        halo_in = _rows_with_halo(views.in_ptr, views.srt_src, n_own)
+        halo_out = _rows_with_halo(views.out_ptr, views.out_dst, n_own)
+        both = not directed
+        self.rows_fwd = _split_rows(halo_in | halo_out if both else halo_in)     # the forward walks the in-list (both: and the out-list)
+        self.rows_bwd = _split_rows(halo_in | halo_out if both else halo_out)    # the backward the out-list (both: and the in-list)
+
+
+def _rows_with_halo(ptr, idx, n_own):
+    """bool[n_own]: the list of row i names an id >= n_own."""
+    hit = torch.cat([torch.zeros(1, dtype=torch.int64, device=idx.device), torch.cumsum((idx >= n_own).long(), 0)])
+    p = ptr[:n_own + 1].long()
+    return (hit[p[1:]] - hit[p[:-1]]) > 0
+
+
+def _split_rows(boundary):
+    """-> (interior, boundary) int32 row lists, ascending."""
+    return torch.nonzero(~boundary).squeeze(1).int().contiguous(), torch.nonzero(boundary).squeeze(1).int().contiguous()
+
+
+def plan_for(ops, part, directed, group=None):
+    """Made once per (partition, directed) - a COLLECTIVE the first time (the halo rows' degrees): every rank calls it at the same place."""
+    hit = part._baseline.get(bool(directed))
+    if hit is None:
+        hit = part._baseline[bool(directed)] = PartitionPlan(ops, part, bool(directed), group)
+    return hit
+
+
+def check_partition(model, part):
+    """The refusals of GCNModel / SAGEModel on a partition, before anything is allocated."""
+    if getattr(part, "in_edges_only", False):
+        raise ValueError(f"{type(model).__name__} runs on the default partition, not in_edges_only=True: GraphConv scales every source by its "
+                         "OUT-degree and the backward walks the owned nodes' out-lists, which an in-edge-only partition does not hold")
+    if part.views.transposed:
+        raise NotImplementedError(f"{type(model).__name__} on a partition runs on the forward orientation of the graph")
+    if part.n_own == 0 or part.n_score == 0:
+        raise NotImplementedError("a rank without owned nodes or owned in-edges (graph too small for this world size)")
+    built_width(model.node_encoder.linear2.out_features)
+
+
+def _sum_launch(ops, xchg_finish, split, rows, call):
+    """The layer's neighbour-sum launch around the end of the halo exchange: interior rows under it and boundary rows after it, or one
+    launch after it.  call(rows) launches the part entry for a row list (None: every owned row)."""
+    if split and rows[1].numel():
+        call(rows[0])
+        xchg_finish()
+        call(rows[1])
+    else:
+        xchg_finish()
+        call(None)
+
+
+def _gcn_layer_part(ops, plan, n_own, h, both, split, finish):
+    a = torch.empty((n_own, h.shape[1]), dtype=torch.float32, device=h.device)
+    _sum_launch(ops, finish, split, plan.rows_fwd, lambda rows: ops.node_neighbour_sum_part(
+        h, plan.lists, n_own, sscale=plan.dout_rsqrt, dscale=plan.din_rsqrt, both=both, out=a, rows=rows))
+    return a
+
+
+def _sage_layer_part(ops, plan, n_own, T, both, split, finish):
+    H = T.shape[1] // 2
+    _sum_launch(ops, finish, split, plan.rows_fwd, lambda rows: ops.node_neighbour_sum_part(
+        T[:, :H], plan.lists, n_own, dscale=plan.din_inv, both=both, out=T[:, H:], rows=rows))
+
+
+def _score_part(ops, part, group, e, h, pw_nodes, w_tail, z1_out=None):
+    """The symmetric model's scorer on the owned in-edges (dist.run_partitioned's tail): h [n_local,H] with its halo rows fetched ->
+    logits[E_global] in edge-id order, complete on every rank."""
+    from .dist import _ScoreViews, _alone
+    W_nodes, b_nodes, planes = pw_nodes
+    hs = W_nodes.shape[0] // 2
+    PQ = ops.linear(h, W_nodes, b_nodes, planes=planes)
+    sv = _ScoreViews(part.views, part.srt_geid)
+    kw = {} if z1_out is None else dict(z1_out=z1_out)
+    if _alone(part.world):
+        logits = torch.empty(part.num_edges_global, dtype=torch.float32, device=h.device)
+        ops.edge_score(e, PQ[:, :hs], PQ[:, hs:], sv, *w_tail, logits, num_edges=part.n_score, **kw)
+        return logits
+    piece = torch.empty(part.score_pad, dtype=torch.float32, device=h.device)
+    ops.edge_score(e, PQ[:, :hs], PQ[:, hs:], sv, *w_tail, piece, num_edges=part.n_score, scatter_to_edge_id=False, **kw)
+    return part.assemble_logits(piece, group)
+
+
+def run_partitioned(ops, prep, part, x_local, e_local, group=None, directed=None, split=None):
+    """run_stack on one rank: x_local [n_local,F] (owned, then halo), e_local [e_local,F] in local edge-id order -> logits[E_global].
+    Per layer: the halo rows of the layer's input (layer 0's come straight from x), the neighbour sum over the owned rows, the product
+    and the ReLU on the owned rows; one more exchange of the last h, then the scorer on the owned in-edges."""
+    from .dist import HaloExchange
+    split = PARTITION_SPLIT if split is None else split
+    directed = prep.directed if directed is None else bool(directed)
+    if getattr(part, "in_edges_only", False):
+        raise ValueError("GCNModel / SAGEModel run on the default partition, not in_edges_only=True (the sources' out-degrees and the owned "
+                         "nodes' out-lists are not there)")
+    views, n_own, n_local, H = part.views, part.n_own, part.n_local, prep.hidden
+    plan = plan_for(ops, part, directed, group)
+    both = not directed
+    xchg = HaloExchange(part, ops, group)
+    h = ops.encode(x_local, *prep.enc_node)
+    e = ops.encode(e_local, *prep.enc_edge, gather=views.srt_eid[:part.n_score], rows=part.n_score)   # the scored rows, sorted order
+    L = len(prep.layers)
+    new = lambda cols: torch.empty((n_local, cols), dtype=torch.float32, device=h.device)  # noqa: E731
+    if prep.kind == "gcn":
+        for i, lw in enumerate(prep.layers):
+            if i > 0:
+                xchg.start(h)
+            a = _gcn_layer_part(ops, plan, n_own, h, both, split, xchg.finish)
+            h = new(H)
+            ops.linear(a, lw.W, lw.bias, out=h[:n_own], planes=lw.planes)
+            if i + 1 < L:
+                ops.relu_rows(h[:n_own])
+    elif L:
+        tables = [new(2 * H) for _ in range(min(L, 2))]
+        tables[0][:, :H].copy_(h)
+        for i, lw in enumerate(prep.layers):
+            T = tables[i % 2]
+            if i > 0:
+                xchg.start(T[:, :H])
+            _sage_layer_part(ops, plan, n_own, T, both, split, xchg.finish)
+            if i + 1 == L:
+                h = new(H)
+                ops.linear(T[:n_own], lw.W, lw.bias, out=h[:n_own], planes=lw.planes)
+                break
+            nxt = tables[(i + 1) % 2]
+            ops.linear(T[:n_own], lw.W, lw.bias, out=nxt[:n_own, :H], planes=lw.planes)
+            ops.relu_rows(nxt[:n_own, :H])
+    if L:
+        xchg.start(h)
+        xchg.finish()
+    pw = prep.predictor
+    return _score_part(ops, part, group, e, h, (pw["W_nodes"], pw["b_nodes"], pw.get("planes")),
+                       (pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"]))
+
+
+def _any_rank(flag, part, group):
+    """True on every rank when `flag` is True on one: the fp16x3 -> bf16x6 decision must not differ between ranks."""
+    from .dist import _alone, all_reduce_sum
+    if _alone(part.world):
+        return bool(flag)
+    return bool(all_reduce_sum(flag.reshape(1).to(torch.float32), group) > 0)
+
+
+def forward_partitioned(ops, model, prep, part, x_local, e_local, group=None, split=None):
+    """forward_in_range on a partition: logits that are not all finite left fp16x3's operand range and the forward is run again as bf16x6 -
+    decided on the all-reduced flag, so every rank takes the same route; checked on every call (no cache: the inputs are the runner's)."""
+    directed = bool(model.directed)
+    if prep.force_bf16x6:
+        with ops.bf16x6_arithmetic():
+            return run_partitioned(ops, prep, part, x_local, e_local, group, directed, split)
+    logits = run_partitioned(ops, prep, part, x_local, e_local, group, directed, split)
+    if getattr(ops, "_TUNING", {}).get(10, 0) == 1 or not getattr(model, "range_check", True):
+        return logits
+    if not _any_rank(~torch.isfinite(logits).all(), part, group):
+        return logits
+    with ops.bf16x6_arithmetic():
+        return run_partitioned(ops, prep, part, x_local, e_local, group, directed, split)
+
+
+def _part_step_forward(ops, model, sh, x, e_raw, masks, split):
+    """_step_forward on a shard -> (logits[E_global], what the backward reads).  Owned rows: the products, the ReLU, the masks; all local
+    rows: the layer inputs the neighbour sum gathers from."""
+    d = lambda t: t.detach().contiguous()  # noqa: E731
+    part, views, n_own, n_local = sh.part, sh.views, sh.n_own, sh.n_local
+    kind, both, convs = model.kind, not model.directed, model.gnn.convs
+    plan = plan_for(ops, part, model.directed, sh.group)
+    ne, ee = model.node_encoder, model.edge_encoder
+    h = ops.encode(x, d(ne.linear1.weight), d(ne.linear1.bias), d(ne.linear2.weight), d(ne.linear2.bias))
+    e = ops.encode(e_raw, d(ee.linear1.weight), d(ee.linear1.bias), d(ee.linear2.weight), d(ee.linear2.bias), gather=views.srt_eid[:sh.e_own],
+                   rows=sh.e_own)
+    H, L = h.shape[1], len(convs)
+    new = lambda cols: torch.empty((n_local, cols), dtype=torch.float32, device=h.device)  # noqa: E731
+    layers = []
+    if kind == "gcn":
+        for i, conv in enumerate(convs):
+            if i > 0:
+                sh.halo_start(h)
+            a = _gcn_layer_part(ops, plan, n_own, h, both, split, sh.halo_finish)
+            layers.append(dict(a=a, y=h if i > 0 else None))
+            h = new(H)
+            ops.linear(a, _conv_weight(conv, kind), d(conv.bias), out=h[:n_own])
+            if i + 1 < L:
+                ops.relu_rows(h[:n_own])
+    elif L:
+        T = new(2 * H)
+        T[:, :H].copy_(h)
+        if masks[0] is not None:
+            ops.relu_mul_rows(T[:n_own, :H], masks[0], relu=False)
+        for i, conv in enumerate(convs):
+            if i > 0 or masks[0] is not None:   # (a dropped layer-0 input: the halo rows are the OWNERS' dropped rows, not what x encodes to)
+                sh.halo_start(T[:, :H])
+            _sage_layer_part(ops, plan, n_own, T, both, split, sh.halo_finish)
+            layers.append(dict(T=T, mask=masks[i]))
+            if i + 1 == L:
+                h = new(H)
+                ops.linear(T[:n_own], _conv_weight(conv, kind), d(conv.bias), out=h[:n_own])
+                break
+            nxt = new(2 * H)
+            ops.linear(T[:n_own], _conv_weight(conv, kind), d(conv.bias), out=nxt[:n_own, :H])
+            if masks[i + 1] is not None:
+                ops.relu_mul_rows(nxt[:n_own, :H], masks[i + 1])
+            else:
+                ops.relu_rows(nxt[:n_own, :H])
+            T = nxt
+    if L:
+        sh.halo_start(h)
+        sh.halo_finish()
+    pred = model.predictor
+    hs = pred.W1.out_features
+    W1 = d(pred.W1.weight)
+    W_nodes = torch.cat([W1[:, :H], W1[:, H:2 * H]], 0).contiguous()
+    b_nodes = torch.cat([torch.zeros_like(pred.W1.bias), pred.W1.bias]).detach().contiguous()
+    z1 = torch.empty((sh.e_own, hs), dtype=torch.float32, device=h.device)
+    logits = _score_part(ops, part, sh.group, e, h, (W_nodes, b_nodes, None),
+                         (W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1))), z1_out=z1)
+    return logits, dict(h=h, e=e, z1=z1, W1=W1, W_nodes=W_nodes, layers=layers)
+
+
+def _part_step_backward(ops, model, sh, x, e_raw, kept, dlogits, split):
+    """_step_backward on a shard -> {parameter name: this rank's share of the gradient}.  Per layer dW, db and dIn = dY W on the owned
+    rows, then the halo rows of the gradient table are FETCHED (the forward's exchange, on g) and the backward kernel runs over the owned
+    rows: every owned row's dY' is complete and has the single-rank run's association.  Only the scorer's node gradient returns partial
+    rows to their owners (halo_bwd)."""
+    from .train import encoder_bwd, score_backward_on_shard
+    d = lambda t: t.detach().contiguous()  # noqa: E731
+    part, views, n_own, n_local, e_own = sh.part, sh.views, sh.n_own, sh.n_local, sh.e_own
+    kind, both, convs = model.kind, not model.directed, model.gnn.convs
+    plan = plan_for(ops, part, model.directed, sh.group)
+    pred = model.predictor
+    H = kept["h"].shape[1]
+    dev = dlogits.device
+    g = {}
+    # ---- scorer: train._TrainStep.backward's, on the e_own encoded rows (the layers never touch e); dh's halo rows are partial sums
+    dh, de = score_backward_on_shard(ops, pred, sh, g, dlogits, kept["z1"], kept["e"], kept["h"], kept["W1"], kept["W_nodes"], e_own)
+    sh.halo_bwd(dh)
+    dY = dh[:n_own]
+    # ---- layers, last to first (layers/processor.py:42-46, :80-84)
+    for i in range(len(convs) - 1, -1, -1):
+        conv, s, pfx = convs[i], kept["layers"][i], f"gnn.convs.{i}."
+        g[pfx + "bias"] = ops.colsum2(dY)[0]
+        out = torch.empty((n_own, H), dtype=torch.float32, device=dev)
+        if kind == "gcn":
+            g[pfx + "weight"] = ops.wgrad(s["a"], dY)
+            dA = torch.empty((n_local, H), dtype=torch.float32, device=dev)
+            ops.linear(dY, d(conv.weight), None, out=dA[:n_own])
+            sh.halo_start(dA)
+            _sum_launch(ops, sh.halo_finish, split, plan.rows_bwd, lambda rows: ops.node_neighbour_sum_bwd_part(
+                dA, plan.lists, n_own, rscale=plan.din_rsqrt, oscale=plan.dout_rsqrt, both=both, y=s["y"], out=out, rows=rows))
+        else:
+            gW = ops.wgrad(dY, s["T"][:n_own])
+            g[pfx + "fc_self.weight"], g[pfx + "fc_neigh.weight"] = gW[:, :H], gW[:, H:]
+            dT = torch.empty((n_local, 2 * H), dtype=torch.float32, device=dev)
+            ops.linear(dY, _conv_weight(conv, kind).t().contiguous(), None, out=dT[:n_own])
+            sh.halo_start(dT[:, H:])
+            _sum_launch(ops, sh.halo_finish, split, plan.rows_bwd, lambda rows: ops.node_neighbour_sum_bwd_part(
+                dT[:, H:], plan.lists, n_own, rscale=plan.din_inv, both=both, add=dT[:, :H], mult=s["mask"],
+                y=s["T"][:, :H] if i > 0 else None, out=out, rows=rows))
+        dY = out
+        kept["layers"][i] = s = None
+    # ---- encoders (models/full_graph.py:63-64): every node row's gradient is complete at its owner, every scored edge's at its scorer
+    ne, ee = model.node_encoder, model.edge_encoder
+    encoder_bwd(ops, g, dY.contiguous(), x[:n_own], None, n_own, ne.linear1, ne.linear2, "node_encoder.linear1", "node_encoder.linear2")
+    encoder_bwd(ops, g, de, e_raw, views.srt_eid[:e_own], e_own, ee.linear1, ee.linear2, "edge_encoder.linear1", "edge_encoder.linear2")
+    return g
+
+
+class _PartitionedBaselineStep(torch.autograd.Function):
+    """_BaselineStep on one rank of a destination-range partition (dist.PartitionShard): the same step, the range fallback decided on the
+    all-reduced flag, the parameter gradients summed over ranks once at the end."""
+
+    @staticmethod
+    def forward(ctx, model, sh, x, e_raw, names, split, *params):
+        from . import train
+        ops = sh.ops
+        masks = [None] * len(model.gnn.convs)
+        if model.kind == "sage":   # feat_drop's masks of the OWNED rows (train.dropout_mask is looked up at call time, as _draw_masks does)
+            H = model.node_encoder.linear2.out_features
+            masks = [train.dropout_mask(sh.n_own, H, conv.feat_drop.p, x.device) if conv.feat_drop.p > 0 else None for conv in model.gnn.convs]
+        bf16x6 = getattr(ops, "_TUNING", {}).get(10, 0) == 1
+        logits, kept = _part_step_forward(ops, model, sh, x, e_raw, masks, split)
+        if not bf16x6 and getattr(model, "range_check", True) and _any_rank(~torch.isfinite(logits).all(), sh.part, sh.group):
+            bf16x6 = True
+            with ops.bf16x6_arithmetic():
+                logits, kept = _part_step_forward(ops, model, sh, x, e_raw, masks, split)
+        ctx.model, ctx.sh, ctx.names, ctx.kept, ctx.inputs, ctx.bf16x6, ctx.split = model, sh, names, kept, (x, e_raw), bf16x6, split
+        return logits.unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        if ctx.kept is None:
+            raise RuntimeError("the activations of this training step were released by its first backward(); "
+                               "retain_graph=True is not supported - run the forward again")
+        model, sh = ctx.model, ctx.sh
+        ops = sh.ops
+        if ctx.bf16x6:
+            with ops.bf16x6_arithmetic():
+                g = _part_step_backward(ops, model, sh, *ctx.inputs, ctx.kept, dlogits, ctx.split)
+        else:
+            g = _part_step_backward(ops, model, sh, *ctx.inputs, ctx.kept, dlogits, ctx.split)
+        ctx.kept = None
+        return (None, None, None, None, None, None) + tuple(sh.sum_ranks([g[n].contiguous() for n in ctx.names]))
+
+
+def train_forward_on(model, shard, x_local, e_local, split=None):
+    """The training step of GCNModel / SAGEModel over one rank's rows (dist.PartitionShard over the default partition): x_local / e_local
+    are the input features of the shard's nodes (owned, then halo) and edges (local edge-id order).  Returns logits[E_global, 1], complete
+    on every rank; after backward() every rank holds the whole graph's parameter gradients."""
+    from .train import TRAIN_SCORE_HIDDEN
+    if getattr(model, "kind", None) not in KINDS:
+        raise TypeError(f"engine_baselines.train_forward_on serves GCNModel and SAGEModel, not {type(model).__name__}")
+    check_partition(model, shard.part)
+    built_width(model.predictor.W1.out_features, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")
+    names, params = zip(*model.named_parameters())
+    if any(p.device != x_local.device for p in params):
+        raise RuntimeError("training needs the model on the compute device: call model.to(device) first")
+    if x_local.shape[0] != shard.n_local or e_local.shape[0] != shard.e_local:
+        raise ValueError(f"x has {x_local.shape[0]} rows for {shard.n_local} local nodes, e has {e_local.shape[0]} rows for {shard.e_local} local edges")
+    split = PARTITION_SPLIT if split is None else bool(split)
+    return _PartitionedBaselineStep.apply(model, shard, x_local, e_local, list(names), split, *params)

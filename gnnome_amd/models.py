@@ -125,7 +125,9 @@ class GCNModel(_BaselineModel):
     Built widths only: hidden_features in {64, 128, 256}, hidden_edge_scores in {32, 64, 128}.  The call serves eval mode only: in train
     mode it raises NotImplementedError.  The training step is the explicit entry engine_baselines.train_forward(model, graph, x, e)
     (logits with autograd history to the parameters; its backward runs on gnnome_node_neighbour_sum_bwd_f32), which
-    trainer.train(model_class=GCNModel) calls."""
+    trainer.train(model_class=GCNModel) calls.  On several GPUs: dist.PartitionedRunner over the default destination-range partition, eval
+    mode (forward) and the training step (train_forward), on the partition forms of the two kernels; an in-edge-only partition and the
+    captured forward are refused (DESIGN 7c "Partitions")."""
     kind = "gcn"
 
     def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, num_layers, hidden_edge_scores,
@@ -145,7 +147,8 @@ class SAGEModel(_BaselineModel):
     One divergence: the reference's default dropout=None reaches nn.Dropout(None) and fails at construction; here None means 0.0.
     feat_drop is the identity in eval mode; the training step (engine_baselines.train_forward, as for GCNModel - the call itself refuses
     train mode) draws one scaled keep-mask per layer through train.dropout_mask and applies it to the layer's input before both the self
-    and the neighbour path, as DGL's SAGEConv does."""
+    and the neighbour path, as DGL's SAGEConv does.  On a partition (dist.PartitionedRunner, as for GCNModel) the masks are drawn for the
+    owned rows and the halo rows of every layer's input, layer 0's included, are the owners' dropped rows."""
     kind = "sage"
 
     def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, num_layers, hidden_edge_scores,

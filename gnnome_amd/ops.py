@@ -916,6 +916,75 @@ def node_neighbour_sum_bwd(g, views, rscale=None, oscale=None, both=False, add=N
     return out
 
 
+def _part_rows(rows, n_own, device, what):
+    """(pointer, count) of a row list: None = the rows 0 .. n_own."""
+    if rows is None:
+        return None, 0
+    _i32(rows, what + ".rows")
+    if rows.dim() != 1 or not rows.is_contiguous() or rows.device != device or rows.numel() > n_own:
+        raise ValueError(f"{what}: rows is a contiguous int32 list of at most {n_own} distinct owned row ids on {device}")
+    return _ptr(rows), int(rows.numel())
+
+
+def node_neighbour_sum_part(h, views, n_own, sscale=None, dscale=None, both=False, out=None, rows=None):
+    """node_neighbour_sum on one rank's shard of the default partition (gnnome_node_neighbour_sum_part_f32): `views` is the local graph
+    (n_own owned nodes first, then the halo; every edge with an owned end), h and sscale have a row per LOCAL node, dscale and out
+    ([n_own, H], or more rows) are touched at the computed rows only.  rows: None = the rows 0 .. n_own, or an int32 list of distinct
+    owned row ids - exactly those are written.  An owned row has the bits of node_neighbour_sum on the whole graph."""
+    h, ldh = _rows(h, "node_neighbour_sum_part.h")
+    n, hidden = h.shape
+    n_own = int(n_own)
+    if n != views.num_nodes or not 0 <= n_own <= n or views.transposed:
+        raise ValueError(f"node_neighbour_sum_part: h has {n} rows for {n_own} owned of {views.num_nodes} local nodes (forward orientation)")
+    if out is None:
+        out = torch.empty((n_own, hidden), dtype=torch.float32, device=h.device)
+    out, ldo = _rows(out, "node_neighbour_sum_part.out")
+    if out.shape[0] < n_own or out.shape[1] != hidden or out.device != h.device:
+        raise ValueError(f"node_neighbour_sum_part: out is {tuple(out.shape)} on {out.device} for {n_own} owned rows of width {hidden} on {h.device}")
+    for name, t, need in (("sscale", sscale, n), ("dscale", dscale, n_own)):
+        if t is not None and (_f32(t, "node_neighbour_sum_part." + name).dim() != 1 or t.numel() < need or not t.is_contiguous()):
+            raise ValueError(f"node_neighbour_sum_part: {name} is one contiguous float per node, at least {need}")
+    rp, nr = _part_rows(rows, n_own, h.device, "node_neighbour_sum_part")
+    if rows is not None and nr == 0:   # (an empty tensor has no pointer to hand over: the entry would read NULL as "every row")
+        return out
+    _call("gnnome_node_neighbour_sum_part_f32", h.device, _ptr(h), ldh, hidden, n_own, n, rp, nr, _ptr(views.in_ptr), _ptr(views.srt_src),
+          _ptr(views.out_ptr) if both else None, _ptr(views.out_dst) if both else None, _ptr(sscale), _ptr(dscale), _ptr(out), ldo)
+    return out
+
+
+def node_neighbour_sum_bwd_part(g, views, n_own, rscale=None, oscale=None, both=False, add=None, y=None, mult=None, out=None, rows=None):
+    """node_neighbour_sum_bwd on one rank's shard (gnnome_node_neighbour_sum_bwd_part_f32): g and rscale have a row per LOCAL node (the halo
+    rows of g fetched from their owners); oscale, add, y, mult and out ([n_own, H], or more rows) are touched at the computed rows only.
+    rows as for node_neighbour_sum_part.  An owned row has the bits of node_neighbour_sum_bwd on the whole graph."""
+    g, ldg = _rows(g, "node_neighbour_sum_bwd_part.g")
+    n, hidden = g.shape
+    n_own = int(n_own)
+    if n != views.num_nodes or not 0 <= n_own <= n or views.transposed:
+        raise ValueError(f"node_neighbour_sum_bwd_part: g has {n} rows for {n_own} owned of {views.num_nodes} local nodes (forward orientation)")
+    if out is None:
+        out = torch.empty((n_own, hidden), dtype=torch.float32, device=g.device)
+    tables = {"out": out, "add": add, "mult": mult, "y": y}
+    lds = {}
+    for name, t in tables.items():
+        if t is None:
+            lds[name] = 0
+            continue
+        t, lds[name] = _rows(t, "node_neighbour_sum_bwd_part." + name)
+        if t.shape[0] < n_own or t.shape[1] != hidden or t.device != g.device:
+            raise ValueError(f"node_neighbour_sum_bwd_part: {name} is {tuple(t.shape)} on {t.device} for {n_own} owned rows of width {hidden} "
+                             f"on {g.device}")
+    for name, t, need in (("rscale", rscale, n), ("oscale", oscale, n_own)):
+        if t is not None and (_f32(t, "node_neighbour_sum_bwd_part." + name).dim() != 1 or t.numel() < need or not t.is_contiguous()):
+            raise ValueError(f"node_neighbour_sum_bwd_part: {name} is one contiguous float per node, at least {need}")
+    rp, nr = _part_rows(rows, n_own, g.device, "node_neighbour_sum_bwd_part")
+    if rows is not None and nr == 0:
+        return out
+    _call("gnnome_node_neighbour_sum_bwd_part_f32", g.device, _ptr(g), ldg, hidden, n_own, n, rp, nr, _ptr(views.out_ptr), _ptr(views.out_dst),
+          _ptr(views.in_ptr) if both else None, _ptr(views.srt_src) if both else None, 1 if both else 0, _ptr(rscale), _ptr(oscale),
+          _ptr(add), lds["add"], _ptr(mult), lds["mult"], _ptr(y), lds["y"], _ptr(out), lds["out"])
+    return out
+
+
 def relu_mul_rows(x, mult, relu=True):
     """x <- relu(x) * mult in place (gnnome_relu_mul_rows_f32; NaN stays NaN), relu=False: x <- x * mult.  x and mult may be column blocks of
     wider tables.  mult=None is refused: relu_rows is the ReLU alone."""

@@ -244,6 +244,35 @@ def encoder_bwd(ops, g, dout, inp, gather, rows, l1, l2, pfx1, pfx2):
     g[pfx1 + ".bias"] = ops.colsum2(dt)[0] if dt.shape[1] in (16, 32, 64) else dt.sum(0)
 
 
+def score_backward_on_shard(ops, pred, sh, g, dlogits, z1, e, h, W1, W_nodes, e_rows):
+    """The scorer's backward (score_predictor.py:12-17) over a shard's owned in-edges - sorted positions [0, e_own) - shared by the
+    symmetric step below and the partitioned step of GCNModel / SAGEModel (engine_baselines.py): the predictor's gradients into g ->
+    (dh [n_local,H], whose halo rows hold this rank's PARTIAL sums, de = the gradient of the first e_rows encoded edge rows).
+    z1 [e_own,hs] as the forward kept it, e the encoded rows the scorer read (e_rows of them: e_local where the layers carry every local
+    edge, e_own where they never touch e), h [n_local,H] the last layer's output, W1 / W_nodes as the forward split them."""
+    d = lambda t: t.detach().contiguous()  # noqa: E731
+    views, n_local, e_own, e_local = sh.views, sh.n_local, sh.e_own, sh.e_local
+    H, hs = h.shape[1], pred.W1.out_features
+    dl = dlogits.reshape(-1).contiguous().float()
+    dz1, dz2, u = ops.score_tail_bwd(z1, dl, sh.score_views, d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)))
+    g["predictor.W2.weight"] = ops.wgrad(dz2, z1)
+    g["predictor.W2.bias"] = ops.colsum2(dz2)[0]
+    g["predictor.W3.weight"] = ops.colsum2(u)[0].reshape(1, pred.W3.in_features)
+    g["predictor.W3.bias"] = (dl if sh.alone else dl[sh.score_views.srt_eid.long()]).sum().reshape(1)
+    if e_local > e_own:   # the local edges that end in another range are scored by their destinations' owners
+        dz1 = torch.cat([dz1, torch.zeros((e_local - e_own, hs), dtype=torch.float32, device=dl.device)], 0)
+    dz1_e = dz1 if e_rows == dz1.shape[0] else dz1[:e_rows]
+    de = ops.linear(dz1_e, W1[:, 2 * H:].t().contiguous(), None)
+    gW1e = ops.wgrad(dz1_e, e)
+    d_ps = ops.segment_sum(dz1, views.out_ptr, views.out_pos, n_local)   # gathered by srt_src in the forward
+    d_qd = ops.segment_sum(dz1, views.in_ptr, None, n_local)             # gathered by srt_dst
+    dPQ = torch.cat([d_qd, d_ps], 1) if views.transposed else torch.cat([d_ps, d_qd], 1)
+    g["predictor.W1.bias"] = ops.colsum2(dPQ[:, hs:].contiguous())[0]
+    gWn = ops.wgrad(dPQ, h)                                              # [2hs, H]
+    g["predictor.W1.weight"] = torch.cat([gWn[:hs], gWn[hs:], gW1e], 1)
+    return ops.linear(dPQ, W_nodes.t().contiguous(), None), de
+
+
 class _TrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, sh, x, e_raw, names, *params):
@@ -368,26 +397,8 @@ class _TrainStep(torch.autograd.Function):
         # at the end), and halo_bwd returns the halo rows' share of dh to the owners once per layer.
 
         # ---- scorer (score_predictor.py:12-17): the owned in-edges, positions [0, e_own)
-        pred = model.predictor
-        hs = pred.W1.out_features
-        dl = dlogits.reshape(-1).contiguous().float()
-        dz1, dz2, u = ops.score_tail_bwd(tail["z1"], dl, sh.score_views, d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)))
-        g["predictor.W2.weight"] = ops.wgrad(dz2, tail["z1"])
-        g["predictor.W2.bias"] = ops.colsum2(dz2)[0]
-        g["predictor.W3.weight"] = ops.colsum2(u)[0].reshape(1, 32)
-        g["predictor.W3.bias"] = (dl if sh.alone else dl[sh.score_views.srt_eid.long()]).sum().reshape(1)
-        if e_local > e_own:
-            dz1 = torch.cat([dz1, torch.zeros((e_local - e_own, hs), dtype=torch.float32, device=dev)], 0)
-        W1 = tail["W1"]
-        de = ops.linear(dz1, W1[:, 2 * H:].t().contiguous(), None)           # d e_final  [e_local,H]
-        gW1e = ops.wgrad(dz1, tail["e"])
-        d_ps = ops.segment_sum(dz1, views.out_ptr, views.out_pos, n_local)   # gathered by srt_src in the forward
-        d_qd = ops.segment_sum(dz1, views.in_ptr, None, n_local)             # gathered by srt_dst
-        dPQ = torch.cat([d_qd, d_ps], 1) if views.transposed else torch.cat([d_ps, d_qd], 1)
-        g["predictor.W1.bias"] = ops.colsum2(dPQ[:, hs:].contiguous())[0]
-        gWn = ops.wgrad(dPQ, tail["h"])                                      # [2hs, H]
-        g["predictor.W1.weight"] = torch.cat([gWn[:hs], gWn[hs:], gW1e], 1)
-        dh = ops.linear(dPQ, tail["W_nodes"].t().contiguous(), None)         # [n_local,H]
+        dh, de = score_backward_on_shard(ops, model.predictor, sh, g, dlogits, tail["z1"], tail["e"], tail["h"], tail["W1"], tail["W_nodes"],
+                                         e_local)   # d e_final [e_local,H], dh [n_local,H]
 
         # ---- layers, last to first (gated_gcn_full.py:82-142)
         # the halo rows of dh travel back to their owners while the kernels that do not read dh run (round 6): the predictor's and, per layer, the

@@ -29,6 +29,9 @@
 extern "C" {
 #endif
 
+/* Raised when an existing entry changes its signature or meaning.  32 also covers gnnome_node_neighbour_sum_part_f32 and
+ * gnnome_node_neighbour_sum_bwd_part_f32, which were ADDED without touching any other entry: a caller built against 32 keeps working, and
+ * the Python binding resolves every entry by name when it loads the library, so a library that predates them is refused there, by name. */
 #define GNNOME_ABI_VERSION 32
 
 #define GNNOME_OK 0
@@ -359,6 +362,35 @@ int gnnome_node_neighbour_sum_bwd_f32(const float* g, int ld_g, int hidden, int6
                                       const int32_t* in_ptr, const int32_t* srt_src, int both, const float* rscale, const float* oscale,
                                       const float* add, int ld_add, const float* mult, int ld_mult, const float* y, int ld_y, float* out,
                                       int ld_out, void* stream);
+
+/* ---- the two neighbour sums on one rank's shard of a destination-range partition --------------------------
+ * GCNModel (models/full_graph.py:56-75, layers/processor.py:35-46) and SAGEModel (full_graph.py:100-119, processor.py:73-84) per rank.
+ * The shard is the DEFAULT partition: num_nodes_out owned nodes first, then the halo, every edge with an owned end kept - so an owned
+ * node's in-list AND out-list are complete, in the whole graph's order.  h / g, sscale / rscale are [num_nodes_local] tables (the halo
+ * rows fetched from their owners), in_ptr and out_ptr have num_nodes_local + 1 entries, neighbour ids are < num_nodes_local.  out,
+ * dscale / oscale, add, mult and y are read and written at the computed rows (< num_nodes_out) only: no wave is spent on a halo row
+ * and no [num_nodes_local, H] output exists.  num_nodes_out <= num_nodes_local is required (GNNOME_EINVAL otherwise, as for a NULL
+ * required pointer or a hidden outside {64,128,256}).
+ * rows: NULL - the rows 0 .. num_nodes_out, num_rows ignored - or int32[num_rows] DISTINCT owned row ids (the caller's contract, as
+ * in_ptr is): the launch computes exactly those rows, one wave per listed row, and leaves every other output row untouched;
+ * num_rows == 0 launches nothing and returns GNNOME_OK.  A rank launches its INTERIOR rows (no list entry is a halo id) while the
+ * halo exchange is in flight and its BOUNDARY rows after it.
+ * BIT EQUALITY: the device code, lane mapping and association are the whole-graph entries' (csrc/node_neighbour.h is the single copy);
+ * the bits of a row depend on that row's lists and the table rows they name alone.  So with num_nodes_out == num_nodes_local and
+ * rows == NULL the result is the whole-graph entry's bit for bit, any split into row lists gives the unsplit result bit for bit, and
+ * an owned row of a shard whose tables hold the whole graph's rows equals the whole-graph entry's row at any world size - forward,
+ * and backward once the halo rows of g have been fetched.  Per layer a rank therefore needs ONE forward exchange (h) and ONE
+ * forward-direction exchange of g in the backward, each of the size of the symmetric model's halo exchange; no halo transpose, no
+ * partial sums.  No atomics; lists above 4096 items in the fixed 128-item blocks. */
+int gnnome_node_neighbour_sum_part_f32(const float* h, int ld_h, int hidden, int64_t num_nodes_out, int64_t num_nodes_local,
+                                       const int32_t* rows, int64_t num_rows, const int32_t* in_ptr, const int32_t* srt_src,
+                                       const int32_t* out_ptr, const int32_t* out_dst, const float* sscale, const float* dscale, float* out,
+                                       int ld_out, void* stream);
+int gnnome_node_neighbour_sum_bwd_part_f32(const float* g, int ld_g, int hidden, int64_t num_nodes_out, int64_t num_nodes_local,
+                                           const int32_t* rows, int64_t num_rows, const int32_t* out_ptr, const int32_t* out_dst,
+                                           const int32_t* in_ptr, const int32_t* srt_src, int both, const float* rscale, const float* oscale,
+                                           const float* add, int ld_add, const float* mult, int ld_mult, const float* y, int ld_y,
+                                           float* out, int ld_out, void* stream);
 
 /* x[r, 0..hidden) <- relu(x[r, 0..hidden)) * mult[r, 0..hidden) in place for r < rows (relu == 0: x <- x * mult, the encoder's output
  * has no ReLU): SAGEConv's feat_drop (processor.py:77) on a layer's input, applied where the ReLU of :82 touches the row.  mult is the
