@@ -23,6 +23,12 @@ The families:
                     lists, hubs at node 0 and at node n - 1
     many_hubs(k)    k hubs of 4100 - 4400 items at every MANY_HUBS_STRIDE-th node id, written in shuffled order; every hub edge
                     joins a hub to a non-hub node
+    tails(n, e, k)  (not in FAMILIES: no probes) tiny graphs whose highest-numbered nodes have no edge and whose last in-list ends at
+                    position E - 1, for the aggregation backward's clamped index requests
+
+Two exact recipes: exact_inputs / exact_sums (gates of GATE_ON / GATE_OFF: integer node sums) and, for the aggregation's BACKWARD, the
+HALVES recipe exact_backward_inputs / exact_backward / exact_backward_bound (a third gate value GATE_HALF = 0 with a sigmoid of exactly
+0.5: every output a multiple of 1/4), described where they are defined.
 """
 import numpy as np
 import torch
@@ -206,3 +212,100 @@ def exact_segment_sums(s, d, X, n, dtype=torch.int64):
     """(sum of X rows over every node's in-list, over its out-list), rows per sorted position."""
     zeros = torch.zeros((n, X.shape[1]), dtype=dtype, device=X.device)
     return zeros.index_add(0, d.long(), X.to(dtype)), zeros.index_add(0, s.long(), X.to(dtype))
+
+
+# ---------------------------------------------------------------------------------------------- the halves recipe
+#
+# The exact recipe above never tests a gradient term: at a device sigmoid of exactly 1 or 0 the factor s (1 - s) of the aggregation's
+# backward vanishes.  A THIRD gate value, 0, is to give a device sigmoid of exactly 0.5 (exp(-0) = 1, 1 + 1 = 2, rcp(2) = 0.5 - the
+# premise the device tests open with) and s (1 - s) = 0.25.  With small INTEGER tables, de0, xe and mean, scale in {1, 2} and shift an odd
+# multiple of 0.5, every output of the backward
+#     sum_in[i]  = sum_{p: d_p = i} s_p Tb[s_p]                    sum_out[i] = sum_{p: s_p = i} s_p Tf[d_p]
+#     de'[p]     = de0[p] + s_p (1 - s_p) (Tf[d_p] A2[s_p] - Uf[d_p] + Tb[s_p] A3[d_p] - Ub[s_p])
+#     s1 = sum_p de'[p] m_p                                        s2 = sum_p de'[p] m_p (xe[p] - mean),   m_p = (xe[p] scale + shift > 0)
+# is a multiple of 1/4, and as long as the sum of the ABSOLUTE values of a sum's terms stays below 2^24 quarters (exact_backward_bound) so
+# is every partial sum, in every order, with or without fma contraction: the fp32 result has ONE possible bit pattern.  xe scale + shift is
+# exact and never 0, so the relu mask does not depend on how the expression is rounded either; the integer xe is its own bfloat16 copy.
+GATE_HALF = 0.0
+BACKWARD_MAX = 2          # tables, de0, xe and mean are integers in [-BACKWARD_MAX, BACKWARD_MAX]
+NODE_TABLES = ("Tf", "Uf", "Tb", "Ub", "A2", "A3")
+
+
+def exact_backward_inputs(num_edges, n, hidden, seed):
+    """The inputs of the halves recipe as a dict: gates [E, H] of GATE_HALF (about half of them) / GATE_ON / GATE_OFF, mixed within rows;
+    Tf, Uf, Tb, Ub, A2, A3 [n, H], de0 and xe [E, H], mean [H]: integers in [-BACKWARD_MAX, BACKWARD_MAX]; scale [H] in {1, 2}; shift [H] an
+    odd multiple of 0.5.  Edge rows are per SORTED position, node rows per internal node id."""
+    g = torch.Generator().manual_seed(seed)
+    kind = torch.randint(0, 4, (num_edges, hidden), generator=g, dtype=torch.int8)
+    gates = torch.full((num_edges, hidden), GATE_HALF)
+    gates[kind == 2], gates[kind == 3] = GATE_ON, GATE_OFF
+    ints = lambda *shape: torch.randint(-BACKWARD_MAX, BACKWARD_MAX + 1, shape, generator=g).float()  # noqa: E731
+    out = dict(gates=gates, **{k: ints(n, hidden) for k in NODE_TABLES}, de0=ints(num_edges, hidden), xe=ints(num_edges, hidden))
+    out["scale"] = torch.randint(1, 3, (hidden,), generator=g).float()
+    out["shift"] = torch.randint(-3, 3, (hidden,), generator=g).float() + 0.5
+    out["mean"] = ints(hidden)
+    return out
+
+
+def _quarters(s, d, t):
+    """The integer parts of the statement, int64, in the units that make them integers: q = 4 sigmoid (0 / 2 / 4), half = [s (1 - s) = 1/4],
+    the relu mask m, the bracket of de' and the tables gathered at the endpoints."""
+    i64 = lambda x: x.round().long()  # noqa: E731
+    gates = t["gates"]
+    known = (gates == GATE_ON) | (gates == GATE_OFF) | (gates == GATE_HALF)
+    assert bool(known.all()), "a gate that is none of GATE_ON / GATE_OFF / GATE_HALF"
+    q = 4 * (gates == GATE_ON).long() + 2 * (gates == GATE_HALF).long()
+    tb_s, ub_s, a2_s = i64(t["Tb"])[s], i64(t["Ub"])[s], i64(t["A2"])[s]
+    tf_d, uf_d, a3_d = i64(t["Tf"])[d], i64(t["Uf"])[d], i64(t["A3"])[d]
+    m = (2 * i64(t["xe"]) * i64(t["scale"]) + i64(2 * t["shift"]) > 0).long()
+    return q, (q == 2).long(), m, (tf_d, a2_s, uf_d, tb_s, a3_d, ub_s)
+
+
+def exact_backward(s, d, t, n):
+    """The statement of the aggregation's backward on the sorted endpoint arrays (s, d) and the inputs `t` of exact_backward_inputs, in
+    int64 quarters, returned as float64: dict(sum_in, sum_out [n, H], de [E, H], s1, s2 [H]).  On the device the inputs are on."""
+    s, d = s.long(), d.long()
+    q, half, m, (tf_d, a2_s, uf_d, tb_s, a3_d, ub_s) = _quarters(s, d, t)
+    zeros = torch.zeros((n, q.shape[1]), dtype=torch.int64, device=q.device)
+    de = 4 * t["de0"].round().long() + half * (tf_d * a2_s - uf_d + tb_s * a3_d - ub_s)
+    xc = t["xe"].round().long() - t["mean"].round().long()
+    out = dict(sum_in=zeros.index_add(0, d, q * tb_s), sum_out=zeros.index_add(0, s, q * tf_d), de=de, s1=(de * m).sum(0), s2=(de * m * xc).sum(0))
+    return {k: v.double() / 4.0 for k, v in out.items()}
+
+
+def exact_backward_bound(s, d, t, n):
+    """The condition of the halves recipe: per output, the largest sum of the absolute values of the terms of one of its sums, in quarters
+    (every product counted factor by factor, so that a kernel may also distribute them).  All below EXACT_LIMIT = 2^24: every partial sum
+    any kernel may form is an fp32 value."""
+    s, d = s.long(), d.long()
+    q, half, m, (tf_d, a2_s, uf_d, tb_s, a3_d, ub_s) = _quarters(s, d, t)
+    zeros = torch.zeros((n, q.shape[1]), dtype=torch.int64, device=q.device)
+    de = 4 * t["de0"].round().long().abs() + half * ((tf_d * a2_s).abs() + uf_d.abs() + (tb_s * a3_d).abs() + ub_s.abs())
+    xc = t["xe"].round().long().abs() + t["mean"].round().long().abs()
+    big = lambda v: int(v.max()) if v.numel() else 0  # noqa: E731
+    return dict(sum_in=big(zeros.index_add(0, d, (q * tb_s).abs())), sum_out=big(zeros.index_add(0, s, (q * tf_d).abs())), de=big(de),
+                s1=big((de * m).sum(0)), s2=big((de * m * xc).sum(0)))
+
+
+# The clamp and tail cases of the fused backward (k_agg_bwd_fused requests the first 64 neighbour ids of both lists of every node before it
+# knows the lists' lengths, clamped to position E - 1): the HIGHEST-numbered nodes have no edge at all (in_ptr[node] = out_ptr[node] = E: every
+# prefetch of theirs is clamped), the last node that has in-edges ends its list at position E - 1, n is no multiple of the 4 nodes of a
+# workgroup, E goes down to 1.  (n, E, items in the last in-list)
+TAILS = ((1, 1, 1), (1, 3, 3), (5, 1, 1), (5, 2, 1), (5, 9, 4), (33, 1, 1), (33, 40, 5), (33, 200, 70), (33, 131, 64))
+
+
+def tails(n, num_edges, last_list, seed=14):
+    """n nodes of which the highest min(3, n - 1) are isolated; the highest-numbered node that is not gets `last_list` in-edges, the other
+    edges fall anywhere among the nodes that may have edges (self-loops and parallel edges included)."""
+    rng = np.random.default_rng(seed + 1000 * n + num_edges)
+    active = max(1, n - 3)
+    src = rng.integers(0, active, size=num_edges)
+    dst = rng.integers(0, active, size=num_edges)
+    dst[:last_list] = active - 1
+    if active > 1:
+        dst[last_list:] = rng.integers(0, active - 1, size=num_edges - last_list)
+    order = rng.permutation(num_edges)
+    src, dst = src[order], dst[order]
+    return dict(src=torch.from_numpy(src.astype(np.int32)), dst=torch.from_numpy(dst.astype(np.int32)), n=n, active=active, last_list=last_list,
+                in_degree=torch.bincount(torch.from_numpy(dst), minlength=n), out_degree=torch.bincount(torch.from_numpy(src), minlength=n), hubs=[],
+                spec={}, probe_src=None, probe_on=None, probe_off=None)

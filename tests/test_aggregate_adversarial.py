@@ -6,6 +6,15 @@ gated sum is an integer below 2^24 with the same fp32 bits in any order, so a lo
 difference at any list length (a hub of 10^4 items hides one item inside every rounding bar).  The first assertions of each exact test
 are the premise: one-item probe nodes must give exactly 1.0 and exactly 0.0.
 
+The HALVES recipe (test_exact_backward and the tests after it) extends this to the aggregation's BACKWARD, whose gradient term carries
+s (1 - s) and vanishes at both of those gates: a third gate value, GATE_HALF = 0, whose device sigmoid is exactly 0.5 (the premise those
+tests open with: a one-item probe gives 0.5), small integer tables, de0, xe and mean, scale in {1, 2}, shift an odd multiple of 0.5.  Then
+both node sums, de' per sorted position and the BatchNorm statistics s1, s2 are multiples of 1/4 whose sums of |terms| stay below 2^24
+quarters (asserted on the CPU in tests/test_aggregate_graphs.py and again for the inputs of each device test): ONE fp32 bit pattern, in any
+order of the additions and with or without fma contraction, for agg_bwd_fused (all five outputs, fp32 and bf16 xe, the amax slot), for
+agg_edge_bwd_stats / agg_edge_bwd, for the variants behind set_tuning(4, 88 / 77) and for node_aggregate_in_bwd - on the list lengths,
+the hubs, and ag.TAILS (trailing nodes without edges: the clamp of the indices requested ahead).
+
 REAL-VALUED checks: inputs drawn as in test_hip_parity.test_node_aggregate, against the checker (tests/cpu_ops.py) in float64 at that
 file's bar (_assert_close: 1e-5 max(scale, 1)), plus the bit-level promises: two runs, num_nodes_out, node ranges, the single-wave
 path, the tuning variants documented as "the same bits".
@@ -38,12 +47,12 @@ class _Form:
     reversed views the stored arrays swapped), internal node ids, and the role swaps a caller of transposed views makes."""
 
     def __init__(self, name, form):
-        g = ag.graph(name)
+        g = ag.graph(name) if isinstance(name, str) else name      # (a graph of its own, as ag.tails() makes them: plain form, no probes)
         self.g, self.n, self.form = g, g["n"], form
         src, dst = g["src"].to(dev()), g["dst"].to(dev())
         perm = None
         if form == "perm":
-            perm = torch.randperm(self.n, generator=torch.Generator().manual_seed(len(name)))
+            perm = torch.randperm(self.n, generator=torch.Generator().manual_seed(len(name)))       # (named graphs only)
         self.build = lambda: (ops.GraphViews(src, dst, self.n, node_perm=perm).reversed() if form == "reversed"
                               else ops.GraphViews(src, dst, self.n, node_perm=perm))
         self.views = self.build()
@@ -54,9 +63,11 @@ class _Form:
         self.inner = (lambda v: int(perm[v])) if perm is not None else int
         self.hubs = sorted(self.inner(h) for h in g["hubs"])
         self.e = ss.numel()
-        in_ptr = self.views.in_ptr.cpu()
-        self.pos_on, self.pos_off = int(in_ptr[self.inner(g["probe_on"])]), int(in_ptr[self.inner(g["probe_off"])])
-        self.probe_src, self.probe_on, self.probe_off = (self.inner(g[k]) for k in ("probe_src", "probe_on", "probe_off"))
+        self.pos_on = self.pos_off = self.probe_src = self.probe_on = self.probe_off = None
+        if g["probe_on"] is not None:
+            in_ptr = self.views.in_ptr.cpu()
+            self.pos_on, self.pos_off = int(in_ptr[self.inner(g["probe_on"])]), int(in_ptr[self.inner(g["probe_off"])])
+            self.probe_src, self.probe_on, self.probe_off = (self.inner(g[k]) for k in ("probe_src", "probe_on", "probe_off"))
 
     def swap(self, a, b):
         return (b, a) if self.t else (a, b)
@@ -272,3 +283,188 @@ def test_split_hubs_are_a_function_of_the_graph(name, hidden):
         assert torch.equal(outs[0][1][~hub], single[1][~hub]), form
         for again in outs[1:]:
             assert torch.equal(again[0], outs[0][0]) and torch.equal(again[1], outs[0][1]), form
+
+
+# ---------------------------------------------------------------------------------------------- the halves recipe: the backward, exact
+
+BWD_KEYS = ("sum_in", "sum_out", "de", "s1", "s2")
+
+
+def _halves_case(f, hidden, seed):
+    """The halves inputs on the device with the probe wired in (probe_src's rows of both node-sum tables are 1, the probe edges' gates are
+    GATE_HALF / GATE_OFF in every channel), and the int64 statement of all five outputs as float32 - after the recipe's CONDITION has been
+    asserted for exactly these inputs."""
+    t = ag.exact_backward_inputs(f.e, f.n, hidden, seed)
+    if f.pos_on is not None:
+        t["gates"][f.pos_on], t["gates"][f.pos_off] = ag.GATE_HALF, ag.GATE_OFF
+        t["Tb"][f.probe_src], t["Tf"][f.probe_src] = 1.0, 1.0
+    t = {k: v.to(dev()) for k, v in t.items()}
+    gs, gd = f.s.to(dev()), f.d.to(dev())
+    bound = ag.exact_backward_bound(gs, gd, t, f.n)
+    assert max(bound.values()) < ag.EXACT_LIMIT, bound
+    want = {k: v.float() for k, v in ag.exact_backward(gs, gd, t, f.n).items()}
+    return t, want
+
+
+def _assert_half_premise(f, t, hidden):
+    """sigmoid(GATE_HALF) is exactly 0.5 on the device: a node with ONE in-edge of that gate and a table row of 1.0 has a node sum of 0.5
+    (mode 2 of node_aggregate_raw, the entry test_exact_sums checks) - on the graph's own probe, or on a one-edge graph where it has none."""
+    if f.pos_on is not None:
+        a_in, a_out = f.raw2(t["gates"], t["Tb"], t["Tf"])
+        probed = (a_out if f.t else a_in)[f.probe_on].cpu()
+    else:
+        one = ops.GraphViews(torch.zeros(1, dtype=torch.int32, device=dev()), torch.ones(1, dtype=torch.int32, device=dev()), 2)
+        ones = torch.ones(2, hidden, device=dev())
+        probed = ops.node_aggregate_raw(torch.full((1, hidden), ag.GATE_HALF, device=dev()), None, ones, ones, one, 2, 2)[0][1].cpu()
+    print(f"probe sum: gate {ag.GATE_HALF} x table row 1.0 -> {probed[0].item()!r}")
+    assert torch.equal(probed, torch.full((hidden,), 0.5)), ("sigmoid(GATE_HALF) is not exactly 0.5", probed)
+
+
+def _kernel_tables(f, t):
+    """The six node tables in the roles the KERNEL gives the stored arrays (reversed views: a caller's source-side table is the kernel's
+    destination-side one) -> (Tf, Uf, Tb, Ub, A2h, A3h)."""
+    return (t["Tb"], t["Ub"], t["Tf"], t["Uf"], t["A3"], t["A2"]) if f.t else (t["Tf"], t["Uf"], t["Tb"], t["Ub"], t["A2"], t["A3"])
+
+
+def _fused(f, t, xe, amax=None):
+    out = ops.agg_bwd_fused(t["gates"], *_kernel_tables(f, t), f.views, t["de0"].clone(), xe, t["scale"], t["shift"], t["mean"], f.n, amax=amax)
+    return dict(zip(BWD_KEYS, f.swap(out[0], out[1]) + tuple(out[2:])))
+
+
+def _edge_stats(f, t, xe):
+    de, s1, s2 = ops.agg_edge_bwd_stats(t["gates"], *_kernel_tables(f, t), f.views, t["de0"].clone(), xe, t["scale"], t["shift"], t["mean"])
+    return dict(de=de, s1=s1, s2=s2)
+
+
+def _where_edge(f, got, want):
+    bad = torch.nonzero((got != want).any(1)).flatten()
+    p = int(bad[0])
+    cols = torch.nonzero(got[p] != want[p]).flatten()[:4]
+    return (f"{bad.numel()} de' rows differ, first sorted position {p} of {f.e} = edge ({int(f.s[p])} -> {int(f.d[p])}), channels {cols.tolist()}: "
+            f"got {got[p, cols].tolist()} want {want[p, cols].tolist()}")
+
+
+def _where_columns(got, want):
+    bad = torch.nonzero(got != want).flatten()
+    c = int(bad[0])
+    return f"{bad.numel()} columns differ, first {c}: got {got[c].item()!r} want {want[c].item()!r} (difference {got[c].item() - want[c].item()!r})"
+
+
+def _assert_outputs(f, got, want, what):
+    for k in got:
+        if torch.equal(got[k], want[k]):
+            continue
+        where = _where_edge(f, got[k], want[k]) if k == "de" else _where(got[k], want[k]) if got[k].dim() == 2 else _where_columns(got[k], want[k])
+        raise AssertionError((f.form, what, k, where))
+
+
+def _bits(x):
+    return x.float().reshape(1).view(torch.int32)
+
+
+def _check_backward_entries(f, t, want, hidden):
+    """Every entry that forms the aggregation's backward, against the statement, bit for bit."""
+    x16 = t["xe"].to(torch.bfloat16)
+    assert torch.equal(x16.float(), t["xe"])
+    top = torch.maximum(want["sum_in"].abs().max(), want["sum_out"].abs().max())
+    first = _fused(f, t, t["xe"])
+    _assert_outputs(f, first, want, "agg_bwd_fused")
+    # a second run, into an amax slot preset to 0: the same bits, and exactly the bits of max(|sum_in|, |sum_out|) in the slot
+    slot = torch.zeros(1, dtype=torch.int32, device=dev())
+    again = _fused(f, t, t["xe"], amax=slot)
+    _assert_outputs(f, again, first, "agg_bwd_fused, second run")
+    assert torch.equal(slot, _bits(top)), (f.form, "amax", slot.view(torch.float32).item(), top.item())
+    # xe as bfloat16, into a slot preset ABOVE the maximum: left unchanged
+    above = _bits(top + 1.0).clone()
+    _assert_outputs(f, _fused(f, t, x16, amax=above), want, "agg_bwd_fused, bf16 xe")
+    assert torch.equal(above, _bits(top + 1.0)), (f.form, "amax preset above the maximum", above.view(torch.float32).item())
+    edge_want = {k: want[k] for k in ("de", "s1", "s2")}
+    _assert_outputs(f, _edge_stats(f, t, t["xe"]), edge_want, "agg_edge_bwd_stats")
+    _assert_outputs(f, _edge_stats(f, t, x16), edge_want, "agg_edge_bwd_stats, bf16 xe")
+    de = ops.agg_edge_bwd(t["gates"], *_kernel_tables(f, t), f.views, t["de0"].clone())
+    _assert_outputs(f, dict(de=de), edge_want, "agg_edge_bwd")
+
+
+@pytest.mark.parametrize("name,hidden", SMALL)
+def test_exact_backward(name, hidden):
+    """The HALVES recipe (tests/aggregate_graphs.py): gates of GATE_ON / GATE_OFF / GATE_HALF = 0, small integer tables, de0, xe and mean,
+    scale in {1, 2}, shift an odd multiple of 0.5.  Premise, asserted first: the device sigmoid of 0 is exactly 0.5 - a one-item probe
+    gives 0.5.  Then s (1 - s) is 1/4 or 0, all five outputs of the backward - both node sums, de' per sorted position, s1, s2 - are
+    multiples of 1/4 whose partial sums stay below 2^24 quarters (asserted for these very inputs), and every kernel that forms them
+    must return the ONE fp32 bit pattern of the int64 statement: agg_bwd_fused (fp32 and bf16 xe, twice, with the amax slot),
+    agg_edge_bwd_stats (fp32 and bf16 xe) and agg_edge_bwd."""
+    for form in FORMS:
+        f = _Form(name, form)
+        t, want = _halves_case(f, hidden, seed=hidden + len(name))
+        _assert_half_premise(f, t, hidden)
+        _check_backward_entries(f, t, want, hidden)
+
+
+@pytest.mark.parametrize("hidden", [64, 128, 256])
+def test_exact_backward_on_the_clamp_and_tail_graphs(hidden):
+    """The halves recipe (premise first: sigmoid(0) = 0.5 exactly) on ag.TAILS: the highest-numbered nodes have no edge, so every index
+    the fused kernel requests ahead for them is clamped to position E - 1; the last in-list ends AT E - 1; n in {1, 5, 33} is no multiple
+    of a workgroup's four nodes; E goes down to 1."""
+    for n, e, last in ag.TAILS:
+        f = _Form(ag.tails(n, e, last), "plain")
+        t, want = _halves_case(f, hidden, seed=n + e)
+        if (n, e) == ag.TAILS[0][:2]:
+            _assert_half_premise(f, t, hidden)
+        try:
+            _check_backward_entries(f, t, want, hidden)
+        except AssertionError as err:
+            raise AssertionError((f"tails n={n} E={e} last in-list {last}",) + err.args) from None
+
+
+@pytest.mark.parametrize("hidden", [64, 128, 256])
+def test_exact_backward_of_the_kernel_variants_kept_for_measurements(hidden):
+    """The halves recipe (premise first) on the two variants still built behind set_tuning(4, .): 88 = the fused kernel's first form
+    <2, 4, 4> (other step sizes: 8 / 4 / 2 in-edge and 16 / 8 / 4 out-edge items at H = 64 / 128 / 256, an uncut grid), 77 = the edge pass
+    with cached loads."""
+    f = _Form("lists", "plain")
+    t, want = _halves_case(f, hidden, seed=hidden + 5)
+    _assert_half_premise(f, t, hidden)
+    edge_want = {k: want[k] for k in ("de", "s1", "s2")}
+    try:
+        ops.set_tuning(4, 88)
+        _assert_outputs(f, _fused(f, t, t["xe"]), want, "agg_bwd_fused <2,4,4>")
+        _assert_outputs(f, _fused(f, t, t["xe"].to(torch.bfloat16)), want, "agg_bwd_fused <2,4,4>, bf16 xe")
+        ops.set_tuning(4, 77)
+        _assert_outputs(f, _edge_stats(f, t, t["xe"]), edge_want, "agg_edge_bwd_stats, cached loads")
+        _assert_outputs(f, _edge_stats(f, t, t["xe"].to(torch.bfloat16)), edge_want, "agg_edge_bwd_stats, cached loads, bf16 xe")
+    finally:
+        ops.set_tuning(4, 0)
+
+
+@pytest.mark.parametrize("name,hidden", SMALL)
+def test_exact_in_edge_backward(name, hidden):
+    """node_aggregate_in_bwd on the halves recipe (premise first): its de' is the statement with Tb = Ub = A3 = 0, its dA2h the statement's
+    sum_out."""
+    f = _Form(name, "plain")
+    t, _ = _halves_case(f, hidden, seed=hidden + len(name) + 1)
+    _assert_half_premise(f, t, hidden)
+    zero = torch.zeros_like(t["Tb"])
+    t0 = dict(t, Tb=zero, Ub=zero, A3=zero)
+    want = {k: v.float() for k, v in ag.exact_backward(f.s.to(dev()), f.d.to(dev()), t0, f.n).items()}
+    de = t["de0"].clone()
+    dA2h = ops.node_aggregate_in_bwd(t["gates"], t["Tf"], t["Uf"], t["A2"], f.views, de)
+    _assert_outputs(f, dict(de=de, sum_out=dA2h), want, "node_aggregate_in_bwd")
+
+
+@pytest.mark.parametrize("name,hidden", SMALL)
+def test_exact_segment_sums_with_amax_and_one_list_at_a_time(name, hidden):
+    """Integer rows (the exact recipe's X): segment_sum2 with the amax slot - the same sums, the bits of their largest |element| in a slot
+    preset to 0, a slot preset above it unchanged - and segment_sum over in_ptr and over out_ptr / out_pos."""
+    for form in FORMS:
+        f = _Form(name, form)
+        X = ag.exact_inputs(f.e, f.n, hidden, seed=hidden + len(name))[3].to(dev())
+        w_in, w_out = (w.float() for w in ag.exact_segment_sums(f.s.to(dev()), f.d.to(dev()), X, f.n))
+        top = torch.maximum(w_in.abs().max(), w_out.abs().max())
+        for preset in (torch.zeros((), device=dev()), top + 1.0):
+            slot = _bits(preset).clone()
+            seg_in, seg_out = f.swap(*ops.segment_sum2(X, f.views, f.n, amax=slot))
+            assert torch.equal(seg_in, w_in) and torch.equal(seg_out, w_out), (form, "segment_sum2 with amax", _where(torch.cat([seg_in, seg_out], 1), torch.cat([w_in, w_out], 1)))
+            assert torch.equal(slot, _bits(torch.maximum(top, preset))), (form, "amax", slot.view(torch.float32).item(), top.item())
+        one_in, one_out = f.swap(ops.segment_sum(X, f.views.in_ptr, None, f.n), ops.segment_sum(X, f.views.out_ptr, f.views.out_pos, f.n))
+        assert torch.equal(one_in, w_in), (form, "segment_sum over in_ptr", _where(one_in, w_in))
+        assert torch.equal(one_out, w_out), (form, "segment_sum over out_ptr / out_pos", _where(one_out, w_out))
