@@ -107,7 +107,11 @@ constexpr int kGranuleBytes = 32768;   // (K = 64: 16 KB - two column blocks, as
 // K in {64, 128, 256}; 4 waves; two granule slots.  PROBE (measurement only; gnnome_set_tuning(2, 20) + gnnome_set_tuning(1, mask)): 1 no stores, 2 no MFMAs,
 // 4 no DMA inside the loop, 8 no quad transpose (all four: wrong results), 16 (right results) no prefetch of the next row tile; 32 (right results): wave 0's cycle counters to gnnome_debug_gate_profile's
 // buffer ([workgroups][8] int64)
-template <int K, int PROBE = 0>
+// NTS (K = 128; off with gnnome_set_tuning(12, 1); the same bits): P leaves through nontemporal stores.  Its next reader is another kernel, after more traffic than
+// any cache here holds, and the vector-memory counter is ONE in-order counter: every wait for a granule or a row tile is a wait for the older stores too.  At
+// N = 1e5 the launch takes 67 against 74 us, an iteration 6050 against 8200 cycles (5750 with no stores at all), a CU's first / second workgroup
+// ends at 45 / 57 against 60 / 70 us (profiles/project128_*).
+template <int K, int PROBE = 0, bool NTS = false>
 __global__ __launch_bounds__(256, 2) void k_node_project(const float* __restrict__ A, int64_t M, int lda, const unsigned char* __restrict__ planes,
                                                           const float* __restrict__ bias, int Nout, float* __restrict__ C, int ldc, int64_t total_units,
                                                           long long* prof, int xp) {
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void k_node_project(const float* __restrict
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    long long t_start = 0, t_wait = 0, t_load = 0, r_start = 0;   // PROBE 32
+    long long t_start = 0, t_wait = 0, t_load = 0, r_start = 0, t_bar = 0, t_pro = 0;   // PROBE 32
     if (PROBE & 32) { t_start = __builtin_readcyclecounter(); r_start = __builtin_amdgcn_s_memrealtime(); }
     // this workgroup's run of units: unit u = (row tile u / gpt, granule u % gpt); an XCD's workgroups take neighbouring runs
     const int gpt = Nout / (32 * BPG);
@@ -217,8 +221,15 @@ __global__ __launch_bounds__(256, 2) void k_node_project(const float* __restrict
         } else {
             wait_vm<NSTORE>();   // granule n is in (this wave's pieces); the stores of iteration n - 1 may still be on their way
         }
+        long long t_vm = 0;
+        if (PROBE & 32) t_vm = __builtin_readcyclecounter();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's pieces of granule n are in; every wave is through with granule n - 1
-        if ((PROBE & 32) && !fresh) t_wait += __builtin_readcyclecounter() - t_in;
+        if (PROBE & 32) {
+            const long long t_now = __builtin_readcyclecounter();
+            if (!fresh) t_wait += t_now - t_in;
+            t_bar += t_now - t_vm;
+            if (n == 0) t_pro = t_now - t_start;
+        }
 
         // the next unit, and its granule on the way into the other slot
         int g_next = g + 1;
@@ -282,7 +293,10 @@ __global__ __launch_bounds__(256, 2) void k_node_project(const float* __restrict
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const f32x4 y = E[r] + bq;
-                if (!(PROBE & 1)) *reinterpret_cast<f32x4*>(crow[r] + 32 * cb) = y;
+                if (!(PROBE & 1)) {
+                    if constexpr (NTS) __builtin_nontemporal_store(y, reinterpret_cast<f32x4*>(crow[r] + 32 * cb));
+                    else *reinterpret_cast<f32x4*>(crow[r] + 32 * cb) = y;
+                }
                 else if (y[0] == 123.456f) crow[r][0] = y[1];
             }
         }
@@ -299,17 +313,19 @@ __global__ __launch_bounds__(256, 2) void k_node_project(const float* __restrict
         p[3] = r_start;                    // 100 MHz clock at the start
         p[4] = __builtin_amdgcn_s_memrealtime();
         p[5] = count;
+        p[6] = t_pro;                      // from the kernel's entry to the far side of the first barrier: the first granule and the first row tile are in
+        p[7] = t_bar;                      // of [0] + [2] (and the first iteration's wait): at the barrier alone, every iteration
     }
     wait_vm<0>();   // nothing of this workgroup's is on its way into LDS when the slots are handed on
 }
 
-template <int K, int PROBE>
+template <int K, int PROBE, bool NTS = false>
 static int launch_project(const float* A, int64_t M, int lda, const void* planes, const float* bias, int Nout, float* C, int ldc, hipStream_t s) {
     constexpr int BPG = K == 256 ? 1 : 2;
     const int64_t tiles = (M + 127) / 128, units = tiles * (Nout / (32 * BPG));
     const int64_t slots = 2 * persistent_grid();   // workgroups that are resident together: two per CU
     const int grid = (int)(units < slots ? units : slots);
-    hipLaunchKernelGGL((k_node_project<K, PROBE>), dim3(grid), dim3(256), 0, s, A, M, lda, (const unsigned char*)planes, bias, Nout, C, ldc, units,
+    hipLaunchKernelGGL((k_node_project<K, PROBE, NTS>), dim3(grid), dim3(256), 0, s, A, M, lda, (const unsigned char*)planes, bias, Nout, C, ldc, units,
                        (PROBE & 32) ? gate_profile_buffer() : nullptr, tuning(kTuneGateExperiment));
     GN_LAUNCH_CHECK();
     return GNNOME_OK;
@@ -326,6 +342,12 @@ int weight_planes_launch(const float* W, int ldw, int Nout, int K, void* planes,
 
 int project_launch(const float* A, int64_t M, int K, int lda, const void* planes, const float* bias, int Nout, float* C, int ldc, hipStream_t s) {
     const int probe = (K != 64 && tuning(kTuneLinearVariant) == 20) ? (tuning(kTuneGateAblation) & 63) : 0;
+    // K = 128: nontemporal stores unless key 12 asks for the schedule before them (the same bits); the ablation probes keep that one, the cycle counters take either
+    if (K == 128 && tuning(kTuneProjectSchedule) != 1) {
+        if (probe == 32) return launch_project<128, 32, true>(A, M, lda, planes, bias, Nout, C, ldc, s);
+        if (probe == 33) return launch_project<128, 33, true>(A, M, lda, planes, bias, Nout, C, ldc, s);
+        if (probe == 0) return launch_project<128, 0, true>(A, M, lda, planes, bias, Nout, C, ldc, s);
+    }
 #define GN_PROBE(P) \
     if (probe == P) return K == 128 ? launch_project<128, P>(A, M, lda, planes, bias, Nout, C, ldc, s) : launch_project<256, P>(A, M, lda, planes, bias, Nout, C, ldc, s);
     GN_PROBE(1) GN_PROBE(2) GN_PROBE(3) GN_PROBE(4) GN_PROBE(7) GN_PROBE(8) GN_PROBE(16) GN_PROBE(32) GN_PROBE(33) GN_PROBE(34) GN_PROBE(35) GN_PROBE(39)

@@ -77,7 +77,10 @@ const char* gnnome_last_error(void);
  *   key 7 also: 9 / 10 two nodes per wave (U = 4 / 2), 11-13 persistent contiguous chunks (measured negatives),
  *                             16 the item loop before the lean one (accumulate_items_split; the same bits, every mode)
  *   key 11 aggregation addressing: 1 = row addresses in 64 bits per item at every size (default: 32-bit byte offsets wherever a step's
- *                             rows lie below 4 GiB; the same bits) */
+ *                             rows lie below 4 GiB; the same bits)
+ *   key 12 node projection schedule (gnnome_linear_planes_f32 at K = 128): 0 the shipped default, 1 the schedule before it (plain stores for P, where the
+ *                             default stores nontemporally) - the same bits, the A/B partner and the bit oracle of
+ *                             tests/test_node_project_schedule.py */
 int gnnome_set_tuning(int key, int value);
 
 /* Measurement only: when set to a device buffer of 256 x 8 int64, every launch of the edge-tile kernel leaves, per
