@@ -53,6 +53,12 @@ SIGNATURES = {
     "gnnome_node_attention_sum_stats_f32": [_p, _i, _p, _i, _p, _i, _i, _i, _l, _p, _p, _p, _p, ctypes.c_float, _p, _p, _i, _p, _i, _p],
     "gnnome_node_attention_sum_bwd_f32": [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _i, _i, _i, _l, _p, _p, _p, _p, _i, ctypes.c_float,
                                           _p, _i, _p, _i, _p, _i, _p, _p],
+    "gnnome_node_attention_sum_part_f32": [_p, _i, _p, _i, _p, _i, _i, _i, _l, _l, _p, _p, _p, _p, ctypes.c_float, _p, _p, _i, _p],
+    "gnnome_node_attention_sum_stats_part_f32": [_p, _i, _p, _i, _p, _i, _i, _i, _l, _l, _p, _p, _p, _p, ctypes.c_float, _p, _p, _i, _p, _i, _p],
+    "gnnome_node_attention_sum_bwd_dst_part_f32": [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _i, _i, _i, _l, _l, _p, _p, _p, _p, _i,
+                                                   ctypes.c_float, _p, _i, _p, _p],
+    "gnnome_node_attention_sum_bwd_src_part_f32": [_p, _i, _p, _i, _p, _i, _p, _i, _i, _l, _l, _p, _p, _p, _p, _i, ctypes.c_float, _p, _i, _p, _i,
+                                                   _p],
     "gnnome_stream_schedule_sizes": [_l, _l, _i, ctypes.POINTER(_l), ctypes.POINTER(_sz)],
     "gnnome_build_stream_schedule": [_l, _l, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p],
     "gnnome_node_aggregate_stream_f32": [_p, _i, _l, _l, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p,

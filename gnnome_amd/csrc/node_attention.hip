@@ -42,6 +42,11 @@
 // gnnome_node_attention_sum_stats_f32 is the TRAINING FORM: the same kernel template with two more arguments (k_node_attention_sum<H,
 // float*, int>) also leaves, per node, the row m0 m1 m2 0 | 1/den0 1/den1 1/den2 0 that the backward (node_attention_bwd.hip)
 // recomputes every weight from.  The plain entry's kernels k_node_attention_sum<H> keep their arguments and their code.
+//
+// gnnome_node_attention_sum_part_f32 / _stats_part_f32 (end of this file): the two forms over the num_nodes_out OWNED rows of one rank's
+// shard of a destination-range partition - feat and el tables of num_nodes_local rows, er / out / stats touched below num_nodes_out.  The
+// kernel reads its own node's er and writes its own node's out and stats, and reads feat / el wherever a list points, so the part entries
+// are these kernels launched over the owned rows: one copy of the row code, and an owned row's bits are the whole-graph entry's.
 #include "node_attention.h"   // the constants and the score, shared with node_attention_bwd.hip
 
 namespace gnnome {
@@ -291,5 +296,33 @@ extern "C" int gnnome_node_attention_sum_stats_f32(const float* feat, int ld_fea
                                                    const int32_t* out_ptr, const int32_t* out_dst, float negative_slope, const float* bias,
                                                    float* out, int ld_out, float* stats, int ld_stats, void* stream) {
     return attention_sum_checked(feat, ld_feat, el, ld_el, er, ld_er, hidden, heads, num_nodes, in_ptr, srt_src, out_ptr, out_dst,
+                                 negative_slope, bias, out, ld_out, true, stats, ld_stats, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------- one rank's shard
+// The same two kernels over the num_nodes_out owned rows of a shard (include/gnnome_hip.h, "the attention sum on one rank's shard"): a
+// wave reads er, and writes out and stats, at its own node's row - below num_nodes_out - and reads feat / el at whatever local id a list
+// names, the halo rows included.  Nothing but the launch bound differs from the whole-graph entries, so the row code is theirs.
+
+extern "C" int gnnome_node_attention_sum_part_f32(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er,
+                                                  int hidden, int heads, int64_t num_nodes_out, int64_t num_nodes_local, const int32_t* in_ptr,
+                                                  const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_dst, float negative_slope,
+                                                  const float* bias, float* out, int ld_out, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_nodes_out >= 0 && num_nodes_out <= num_nodes_local, "node_attention_sum_part: %lld destination rows of %lld local rows",
+               (long long)num_nodes_out, (long long)num_nodes_local);
+    return attention_sum_checked(feat, ld_feat, el, ld_el, er, ld_er, hidden, heads, num_nodes_out, in_ptr, srt_src, out_ptr, out_dst,
+                                 negative_slope, bias, out, ld_out, false, nullptr, 0, stream);
+}
+
+extern "C" int gnnome_node_attention_sum_stats_part_f32(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er,
+                                                        int hidden, int heads, int64_t num_nodes_out, int64_t num_nodes_local,
+                                                        const int32_t* in_ptr, const int32_t* srt_src, const int32_t* out_ptr,
+                                                        const int32_t* out_dst, float negative_slope, const float* bias, float* out, int ld_out,
+                                                        float* stats, int ld_stats, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_nodes_out >= 0 && num_nodes_out <= num_nodes_local, "node_attention_sum_stats_part: %lld destination rows of %lld local rows",
+               (long long)num_nodes_out, (long long)num_nodes_local);
+    return attention_sum_checked(feat, ld_feat, el, ld_el, er, ld_er, hidden, heads, num_nodes_out, in_ptr, srt_src, out_ptr, out_dst,
                                  negative_slope, bias, out, ld_out, true, stats, ld_stats, stream);
 }

@@ -43,6 +43,15 @@
 // remaining 56 score columns are ZEROED BY THE HOST (ops.node_attention_sum_bwd, engine_gat's step: once per table).
 // HUBS: walked by their own wave in both kernels, as in the forward: about three milliseconds per 10^5 items per walk (the forward's
 // ESTIMATE, not a measurement).
+//
+// gnnome_node_attention_sum_bwd_dst_part_f32 / _bwd_src_part_f32: the two launches as SEPARATE entries over the owned rows of one rank's
+// shard of a destination-range partition (the default one: both lists of an owned node complete, in the whole graph's order).  The
+// destination walk needs g, out, stats and er of its own node only and feat / el of the neighbours - local rows, halo included; the source
+// walk needs g and the 64-byte work row of every DESTINATION its node points at, and a halo destination's are its owner's: the caller
+// fetches the halo rows of g (under the destination phase, which does not read them) and of work between the two entries.  Both entries
+// launch the kernels below with num_nodes = the owned rows - no second statement of the row code, so an owned row has the whole-graph
+// entry's bits, and the two phases on a whole table are that entry, work included.  Every edge's term of dfeat[j] / del[j] is computed
+// by j's owner and its term of der[i] by i's: nothing is summed across ranks.
 #include "node_attention.h"
 
 namespace gnnome {
@@ -387,22 +396,71 @@ struct AttBwdArgs {
     float* work;
 };
 
+constexpr int kAttPhaseDst = 1, kAttPhaseSrc = 2;   // the two launches; the whole-graph entry runs both, a part entry one
+
+// a.n = the rows computed (one wave each): every node for the whole-graph entry, the owned rows of a shard for the part entries - the same
+// two kernels either way, which index feat / el (and, the source walk, g / work) at whatever local row a list names
 template <int H>
-static int launch_attention_sum_bwd(const AttBwdArgs& a, hipStream_t s) {
+static int launch_attention_sum_bwd(const AttBwdArgs& a, int phases, hipStream_t s) {
     const int64_t blocks = (a.n + (kAttThreads / 64) - 1) / (kAttThreads / 64);
     GN_REQUIRE(blocks < (1ll << 31), "node_attention_sum_bwd: too many nodes");
-    hipLaunchKernelGGL((k_att_bwd_dst<H>), dim3((unsigned)blocks), dim3(kAttThreads), 0, s, a.g, a.ldg, a.feat, a.ldf, a.el, a.ld_el, a.er, a.ld_er,
-                       a.out, a.ldo, a.bias, a.stats, a.ld_stats, a.n, a.in_ptr, a.srt_src, a.both ? a.out_ptr : nullptr,
-                       a.both ? a.out_dst : nullptr, a.slope, a.der, a.ld_der, a.work, (int)blocks);
-    GN_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_att_bwd_src<H>), dim3((unsigned)blocks), dim3(kAttThreads), 0, s, a.g, a.ldg, a.feat, a.ldf, a.el, a.ld_el, a.work, a.n,
-                       a.out_ptr, a.out_dst, a.both ? a.in_ptr : nullptr, a.both ? a.srt_src : nullptr, a.slope, a.dfeat, a.ld_dfeat, a.del,
-                       a.ld_del, (int)blocks);
-    GN_LAUNCH_CHECK();
+    if (phases & kAttPhaseDst) {
+        hipLaunchKernelGGL((k_att_bwd_dst<H>), dim3((unsigned)blocks), dim3(kAttThreads), 0, s, a.g, a.ldg, a.feat, a.ldf, a.el, a.ld_el, a.er,
+                           a.ld_er, a.out, a.ldo, a.bias, a.stats, a.ld_stats, a.n, a.in_ptr, a.srt_src, a.both ? a.out_ptr : nullptr,
+                           a.both ? a.out_dst : nullptr, a.slope, a.der, a.ld_der, a.work, (int)blocks);
+        GN_LAUNCH_CHECK();
+    }
+    if (phases & kAttPhaseSrc) {
+        hipLaunchKernelGGL((k_att_bwd_src<H>), dim3((unsigned)blocks), dim3(kAttThreads), 0, s, a.g, a.ldg, a.feat, a.ldf, a.el, a.ld_el, a.work,
+                           a.n, a.out_ptr, a.out_dst, a.both ? a.in_ptr : nullptr, a.both ? a.srt_src : nullptr, a.slope, a.dfeat, a.ld_dfeat,
+                           a.del, a.ld_del, (int)blocks);
+        GN_LAUNCH_CHECK();
+    }
     return GNNOME_OK;
 }
 
 }  // namespace gnnome
+
+// The argument checks of the three entries, then the launch(es).  `what` names the entry in the error text; a phase that does not read or
+// write a table is not asked for it (its pointer is NULL and its stride unused).
+static int attention_sum_bwd_checked(const gnnome::AttBwdArgs& a, int hidden, int heads, int phases, const char* what, void* stream) {
+    using namespace gnnome;
+    const bool dst = phases & kAttPhaseDst, src = phases & kAttPhaseSrc;
+    GN_REQUIRE(a.n >= 0, "%s: negative node count", what);
+    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "%s: hidden=%d not in {64,128,256}", what, hidden);
+    GN_REQUIRE(heads == kAttHeads, "%s: heads=%d, built for %d (layers/processor.py:50)", what, heads, kAttHeads);
+    if (a.n == 0) return GNNOME_OK;
+    // both walks need both pointer arrays (the destination walk reads the in-list, the source walk the out-list), so `both` is a flag
+    // here and not a NULL out_ptr; srt_src / out_dst may be NULL for a graph without edges (never dereferenced then)
+    GN_REQUIRE(a.g && a.feat && a.el && a.work && (dst ? a.in_ptr != nullptr : a.out_ptr != nullptr), "%s: null pointer", what);
+    GN_REQUIRE(!a.both || (a.in_ptr && a.out_ptr), "%s: null pointer", what);
+    if (dst) GN_REQUIRE(a.er && a.out && a.stats && a.der, "%s: null pointer", what);
+    if (src) GN_REQUIRE(a.out_ptr && a.dfeat && a.del, "%s: null pointer", what);
+    const int width = kAttHeads * hidden;
+    GN_REQUIRE(a.ldg >= width && a.ldg % 4 == 0 && a.ldf >= width && a.ldf % 4 == 0 && (!dst || (a.ldo >= width && a.ldo % 4 == 0)) &&
+                   (!src || (a.ld_dfeat >= width && a.ld_dfeat % 4 == 0)),
+               "%s: bad strides of g / feat / out / dfeat (>= 3 * hidden, multiples of 4)", what);
+    GN_REQUIRE(a.ld_el >= 4 && a.ld_el % 4 == 0 && (!dst || (a.ld_er >= 4 && a.ld_er % 4 == 0 && a.ld_der >= 4 && a.ld_der % 4 == 0 &&
+                                                              a.ld_stats >= kAttStatsRow && a.ld_stats % 4 == 0)) &&
+                   (!src || (a.ld_del >= 4 && a.ld_del % 4 == 0)),
+               "%s: el, er, del and der are rows of 4 floats, stats rows of 8, row strides multiples of 4", what);
+    const void* all[] = {a.g, a.feat, a.el, a.er, a.out, a.bias, a.stats, a.dfeat, a.del, a.der, a.work};
+    for (const void* p : all) GN_REQUIRE((uintptr_t)p % 16 == 0, "%s: every table must be 16-byte aligned", what);
+    // (the source phase READS work: it is an output of the destination phase alone)
+    const void* ins[] = {a.g, a.feat, a.el, a.er, a.out, a.stats, a.bias, dst ? nullptr : (const void*)a.work};
+    const void* outs[] = {a.dfeat, a.del, a.der, dst ? (const void*)a.work : nullptr};
+    for (int i = 0; i < 4; ++i) {
+        if (outs[i] == nullptr) continue;
+        for (const void* p : ins) GN_REQUIRE(outs[i] != p, "%s: an output must not alias an input", what);
+        for (int k = i + 1; k < 4; ++k) GN_REQUIRE(outs[i] != outs[k], "%s: the outputs must not alias each other", what);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    switch (hidden) {
+        case 64: return launch_attention_sum_bwd<64>(a, phases, s);
+        case 128: return launch_attention_sum_bwd<128>(a, phases, s);
+        default: return launch_attention_sum_bwd<256>(a, phases, s);
+    }
+}
 
 extern "C" int gnnome_node_attention_sum_bwd_f32(const float* g, int ld_g, const float* feat, int ld_feat, const float* el, int ld_el,
                                                  const float* er, int ld_er, const float* out, int ld_out, const float* bias, const float* stats,
@@ -411,34 +469,40 @@ extern "C" int gnnome_node_attention_sum_bwd_f32(const float* g, int ld_g, const
                                                  float negative_slope, float* dfeat, int ld_dfeat, float* del, int ld_del, float* der, int ld_der,
                                                  float* work, void* stream) {
     using namespace gnnome;
-    GN_REQUIRE(num_nodes >= 0, "node_attention_sum_bwd: negative node count");
-    GN_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256, "node_attention_sum_bwd: hidden=%d not in {64,128,256}", hidden);
-    GN_REQUIRE(heads == kAttHeads, "node_attention_sum_bwd: heads=%d, built for %d (layers/processor.py:50)", heads, kAttHeads);
-    if (num_nodes == 0) return GNNOME_OK;
-    // both walks need both pointer arrays (the destination walk reads the in-list, the source walk the out-list), so `both` is a flag
-    // here and not a NULL out_ptr; srt_src / out_dst may be NULL for a graph without edges (never dereferenced then)
-    GN_REQUIRE(g && feat && el && er && out && stats && in_ptr && out_ptr && dfeat && del && der && work, "node_attention_sum_bwd: null pointer");
-    const int width = kAttHeads * hidden;
-    GN_REQUIRE(ld_g >= width && ld_g % 4 == 0 && ld_feat >= width && ld_feat % 4 == 0 && ld_out >= width && ld_out % 4 == 0 &&
-                   ld_dfeat >= width && ld_dfeat % 4 == 0,
-               "node_attention_sum_bwd: bad strides of g / feat / out / dfeat (>= 3 * hidden, multiples of 4)");
-    GN_REQUIRE(ld_el >= 4 && ld_el % 4 == 0 && ld_er >= 4 && ld_er % 4 == 0 && ld_del >= 4 && ld_del % 4 == 0 && ld_der >= 4 && ld_der % 4 == 0 &&
-                   ld_stats >= kAttStatsRow && ld_stats % 4 == 0,
-               "node_attention_sum_bwd: el, er, del and der are rows of 4 floats, stats rows of 8, row strides multiples of 4");
-    const void* all[] = {g, feat, el, er, out, bias, stats, dfeat, del, der, work};
-    for (const void* p : all) GN_REQUIRE((uintptr_t)p % 16 == 0, "node_attention_sum_bwd: every table must be 16-byte aligned");
-    const void* ins[] = {g, feat, el, er, out, stats, bias};
-    const void* outs[] = {dfeat, del, der, work};
-    for (int i = 0; i < 4; ++i) {
-        for (const void* p : ins) GN_REQUIRE(outs[i] != p, "node_attention_sum_bwd: an output must not alias an input");
-        for (int k = i + 1; k < 4; ++k) GN_REQUIRE(outs[i] != outs[k], "node_attention_sum_bwd: the outputs must not alias each other");
-    }
     const AttBwdArgs a{g,       ld_g,    feat,    ld_feat, el,        ld_el,          er,    ld_er,    out, ld_out, bias, stats, ld_stats, num_nodes,
                        in_ptr,  srt_src, out_ptr, out_dst, both != 0, negative_slope, dfeat, ld_dfeat, del, ld_del, der,  ld_der, work};
-    hipStream_t s = (hipStream_t)stream;
-    switch (hidden) {
-        case 64: return launch_attention_sum_bwd<64>(a, s);
-        case 128: return launch_attention_sum_bwd<128>(a, s);
-        default: return launch_attention_sum_bwd<256>(a, s);
-    }
+    return attention_sum_bwd_checked(a, hidden, heads, kAttPhaseDst | kAttPhaseSrc, "node_attention_sum_bwd", stream);
+}
+
+// ---------------------------------------------------------------------------------------------------- one rank's shard: the two phases
+// On a destination-range partition (include/gnnome_hip.h, "the attention sum on one rank's shard") a collective sits between the two
+// launches - the halo rows of `work` are their owners' to compute - so each is an entry of its own.  Both are k_att_bwd_dst / k_att_bwd_src
+// launched over the num_nodes_out owned rows: the kernels index their own node's rows below num_nodes_out and a neighbour's at whatever
+// local id the list names, which is all a shard asks of them.
+
+extern "C" int gnnome_node_attention_sum_bwd_dst_part_f32(const float* g, int ld_g, const float* feat, int ld_feat, const float* el, int ld_el,
+                                                          const float* er, int ld_er, const float* out, int ld_out, const float* bias,
+                                                          const float* stats, int ld_stats, int hidden, int heads, int64_t num_nodes_out,
+                                                          int64_t num_nodes_local, const int32_t* in_ptr, const int32_t* srt_src,
+                                                          const int32_t* out_ptr, const int32_t* out_dst, int both, float negative_slope,
+                                                          float* der, int ld_der, float* work, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_nodes_out >= 0 && num_nodes_out <= num_nodes_local, "node_attention_sum_bwd_dst_part: %lld destination rows of %lld local rows",
+               (long long)num_nodes_out, (long long)num_nodes_local);
+    const AttBwdArgs a{g,      ld_g,    feat,    ld_feat, el,        ld_el,          er,      ld_er, out,     ld_out, bias, stats, ld_stats, num_nodes_out,
+                       in_ptr, srt_src, out_ptr, out_dst, both != 0, negative_slope, nullptr, 0,     nullptr, 0,      der,  ld_der, work};
+    return attention_sum_bwd_checked(a, hidden, heads, kAttPhaseDst, "node_attention_sum_bwd_dst_part", stream);
+}
+
+extern "C" int gnnome_node_attention_sum_bwd_src_part_f32(const float* g, int ld_g, const float* feat, int ld_feat, const float* el, int ld_el,
+                                                          const float* work, int hidden, int heads, int64_t num_nodes_out,
+                                                          int64_t num_nodes_local, const int32_t* out_ptr, const int32_t* out_dst,
+                                                          const int32_t* in_ptr, const int32_t* srt_src, int both, float negative_slope,
+                                                          float* dfeat, int ld_dfeat, float* del, int ld_del, void* stream) {
+    using namespace gnnome;
+    GN_REQUIRE(num_nodes_out >= 0 && num_nodes_out <= num_nodes_local, "node_attention_sum_bwd_src_part: %lld source rows of %lld local rows",
+               (long long)num_nodes_out, (long long)num_nodes_local);
+    const AttBwdArgs a{g,      ld_g,    feat,    ld_feat, el,        ld_el,          nullptr, 0,        nullptr, 0,      nullptr, nullptr, 0, num_nodes_out,
+                       in_ptr, srt_src, out_ptr, out_dst, both != 0, negative_slope, dfeat,   ld_dfeat, del,     ld_del, nullptr, 0, const_cast<float*>(work)};
+    return attention_sum_bwd_checked(a, hidden, heads, kAttPhaseSrc, "node_attention_sum_bwd_src_part", stream);
 }

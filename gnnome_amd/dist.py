@@ -19,7 +19,11 @@ inference.py:388).  This is the north_star's scheme:
 
 GatedGCNModel runs on the in-edge-only form of the partition (engine_gated.py); GCNModel and SAGEModel on the default one, with one
 exchange of h and one forward-direction exchange of its gradient per layer and neighbour sums bit-equal to the single-rank run
-(engine_baselines.py, "destination-range partitions"); GATModel is refused.
+(engine_baselines.py, "destination-range partitions"); GATModel on the default one too, through GATPartitionedRunner: one exchange of h
+per layer forward, the halo rows of the projection made locally, and two forward-direction exchanges per layer backward - dA's halo rows
+and the 64-byte work rows between the two phases of the attention sum's backward (engine_gat.py, "destination-range partitions").
+PartitionedRunner itself keeps refusing GATModel and names that class.  The GAT path has run as processes sharing one GPU and as CPU
+ranks over gloo only - never on two devices.
 
 All tensor math goes through an `ops` namespace exactly like engine.run_stack: the product passes
 gnnome_amd.ops (HIP); the CPU/gloo tests pass the checker backend to exercise this host logic.
@@ -420,6 +424,14 @@ class HaloExchange:
         dh[p.n_own:].zero_()
 
 
+def check_shard(part):
+    """What a PartitionShard refuses (GATPartitionedRunner raises the same, in the same words, before it allocates anything)."""
+    if part.views.transposed:
+        raise NotImplementedError("partitioned training runs on the forward orientation of the graph")
+    if part.n_own == 0 or part.n_score == 0:
+        raise NotImplementedError("a rank without owned nodes or owned in-edges (graph too small for this world size)")
+
+
 class PartitionShard:
     """One rank's rows of a training step over a destination-range partition (see gnnome_amd.train.WholeGraph for
     the interface; SURVEY.md 8e "Training additions"):
@@ -429,10 +441,7 @@ class PartitionShard:
         buffer); halo rows of dh are scatter-added back to their owners once per layer."""
 
     def __init__(self, part, ops=hip_ops, group=None):
-        if part.views.transposed:
-            raise NotImplementedError("partitioned training runs on the forward orientation of the graph")
-        if part.n_own == 0 or part.n_score == 0:
-            raise NotImplementedError("a rank without owned nodes or owned in-edges (graph too small for this world size)")
+        check_shard(part)
         self.part, self.ops, self.group, self.world = part, ops, group, part.world
         self.alone = _alone(part.world)     # False under GNNOME_FORCE_COLLECTIVES=1: one rank, every collective issued
         self.views = part.views
@@ -651,8 +660,9 @@ class PartitionedRunner:
         self.baseline = kind in engine_baselines.KINDS
         self.gated = isinstance(model, GatedGCNModel)   # (engine_gated.py): the in-edge-only partition, its own kernel sequences
         if kind == "gat":
-            raise NotImplementedError("GATModel is not served on partitions: its edge softmax needs every destination's complete in-list "
-                                      "per head and its backward a second exchange - the follow-up to the GCNModel / SAGEModel partition")
+            raise NotImplementedError("GATModel is not served on partitions by PartitionedRunner: its backward makes a second exchange per "
+                                      "layer and it takes no split= - use dist.GATPartitionedRunner (same inputs, same forward() / "
+                                      "train_forward())")
         if split is not None and not self.baseline:
             raise ValueError("split= selects the launch form of GCNModel / SAGEModel's neighbour sums; the gated models have none")
         self.split = split
@@ -705,3 +715,39 @@ class PartitionedRunner:
                                           f'{self.model.training_step!r}')
             return engine_gated.train_forward_in_edge_on(self.model, PartitionShard(self.part, self.ops, self.group), self.x, self.e)
         return train_forward_on(self.model, PartitionShard(self.part, self.ops, self.group), self.x, self.e)
+
+
+class GATPartitionedRunner:
+    """PartitionedRunner for GATModel: one rank's default partition, weights and inputs on its GPU; the same inputs, the same forward()
+    and train_forward().  A class of its own because the sequence is: no split= (the interior / boundary launch was never measured to
+    pay), two exchanges per layer in the backward, the halo rows of the projection made locally (engine_gat.py, "destination-range
+    partitions").  directed=False is served: the partition keeps both lists of every owned node and the kernels take `both`."""
+
+    def __init__(self, model, part, x_global, e_global, device, ops=hip_ops, group=None, x_local=None, e_local=None):
+        """x_global / e_global, or x_local / e_local already selected: as for PartitionedRunner.  Every refusal is raised before anything
+        is allocated on the device."""
+        from . import engine_gat
+        engine_gat.check_partition(model, part)
+        self.ops, self.part, self.group, self.model = ops, part, group, model
+        self.prep = None if model.training else engine.prepared_for(model, device, engine_gat.Prepared)
+        rows = part.local_node_rows(x_global) if x_local is None else x_local
+        self.x = rows.to(device=device, dtype=torch.float32).contiguous()
+        erows = part.local_edge_rows(e_global) if e_local is None else e_local
+        self.e = erows.to(device=device, dtype=torch.float32).contiguous()
+
+    def capture(self):
+        raise NotImplementedError("CapturedPartitionedForward is built for SymGatedGCNModel; a GATModel runs the eager forward()")
+
+    def forward(self):
+        """eval mode: logits[E,1] of one whole-graph scoring pass, complete on every rank."""
+        from . import engine_gat
+        if self.prep is None:
+            raise RuntimeError("built from a model in train mode: use train_forward()")
+        with torch.no_grad():
+            return engine_gat.forward_partitioned(self.ops, self.model, self.prep, self.part, self.x, self.e, self.group).unsqueeze(1)
+
+    def train_forward(self):
+        """train mode: logits[E,1] with autograd history; after loss.backward() every rank holds the whole graph's parameter gradients
+        (already summed over ranks)."""
+        from . import engine_gat
+        return engine_gat.train_forward_on(self.model, PartitionShard(self.part, self.ops, self.group), self.x, self.e)

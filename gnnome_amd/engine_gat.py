@@ -31,6 +31,9 @@ Backward, per layer from the last (dY = the gradient of the head mix's output):
     d attn_l[k] = fc_k dWp[3H+k], d attn_r[k] = fc_k dWp[3H+4+k]
 then the scorer's and the encoders' backward (engine_baselines.score_backward, encoders_backward).  No atomics anywhere: two steps from
 equal state leave equal gradient bits.
+
+Several GPUs: the last section of this file - the same two sequences on one rank of a destination-range partition
+(dist.GATPartitionedRunner), on gnnome_node_attention_sum_part_f32 / _stats_part_f32 / _bwd_dst_part_f32 / _bwd_src_part_f32.
 """
 import torch
 
@@ -246,3 +249,242 @@ def train_forward(model, graph, x, e):
     if getattr(model, "kind", None) != "gat":
         raise TypeError(f"engine_gat.train_forward serves GATModel, not {type(model).__name__}")
     return eb.run_train_step(model, graph, x, e, _STEP)
+
+
+# ---------------------------------------------------------------------------------------------------
+# destination-range partitions (gnnome_amd/dist.py, GATPartitionedRunner): one rank's rows of the same two sequences
+# ---------------------------------------------------------------------------------------------------
+# On the DEFAULT partition (every edge with an owned end) an owned node's in- and out-list are complete, so every softmax of an owned
+# destination sees all of its terms: with feat | el of the halo rows at hand the part entries of csrc/node_attention.hip compute the owned
+# rows with the whole graph's association - BIT-EQUAL to the single-rank kernel on equal tables.  The halo rows of P = h Wp^T are projected
+# LOCALLY from the exchanged halo rows of h (H floats per row, the exchange GCNModel makes) rather than exchanged themselves (3H + 64
+# floats per row, 3.25 times the bytes): redundant product rows against bytes on the link - which is cheaper is not measured.
+# Backward, per layer: every edge's term of dfeat[j] / del[j] is computed by j's owner and its term of der[i] by i's owner, so the stack
+# needs no halo transpose and no partial sums - but the source walk reads G = dA and the 64-byte work row (er | m | 1/den | D) of every
+# destination j points at, and those are their owners': TWO forward-direction exchanges per layer, G's halo rows (3H floats each, in
+# flight under the destination phase, which reads owned rows of G only) and work's (16 floats each) between the two phases.  Only the
+# scorer's node gradient (halo_bwd) and the parameter gradients (sum_ranks, once, at the end) are summed across ranks.
+# feat_drop: the OWNER applies ReLU and mask to its owned rows BEFORE the exchange, so halo rows arrive dropped and masks are drawn for
+# owned rows only; with p > 0 layer 0's dropped input is exchanged too (a local copy made from x would lack the owner's mask).
+
+def shard_lists(part):
+    """The lists the part entries read (engine_baselines.ShardLists: the out-lists in the whole graph's order), made once per partition."""
+    hit = part._baseline.get("lists")
+    if hit is None:
+        hit = part._baseline["lists"] = eb.ShardLists(part.views, part.node_gid)
+    return hit
+
+
+def check_partition(model, part):
+    """The refusals of GATModel on a partition, before anything is allocated."""
+    from .dist import check_shard
+    if getattr(model, "kind", None) != "gat":
+        raise TypeError(f"the GAT partition sequences serve GATModel, not {type(model).__name__}")
+    if getattr(part, "in_edges_only", False):
+        raise ValueError("GATModel runs on the default partition, not in_edges_only=True: its backward walks the owned nodes' out-lists "
+                         "(and directed=False its forward too), which an in-edge-only partition does not hold")
+    check_shard(part)
+    eb.built_width(model.node_encoder.linear2.out_features)
+
+
+def _project_part(ops, h, Wp, planes, n_own, finish):
+    """P [n_local, 3H + 64] = h Wp^T of ALL local rows: the owned rows while the halo rows of h are in flight, the halo rows after."""
+    P = torch.empty((h.shape[0], Wp.shape[0]), dtype=torch.float32, device=h.device)
+    ops.linear(h[:n_own], Wp, None, out=P[:n_own], planes=planes)
+    finish()
+    if h.shape[0] > n_own:
+        ops.linear(h[n_own:], Wp, None, out=P[n_own:], planes=planes)
+    return P
+
+
+def run_partitioned(ops, prep, part, x_local, e_local, group=None, directed=True):
+    """run_stack on one rank: x_local [n_local,F] (owned, then halo), e_local [e_local,F] in local edge-id order -> logits[E_global].
+    Per layer: the halo rows of the layer's input (layer 0's come straight from x), the projection of all local rows, the attention sum,
+    the head mix and the ReLU on the owned rows; one more exchange of the last h, then the scorer on the owned in-edges."""
+    from .dist import HaloExchange
+    views, n_own, n_local, H = part.views, part.n_own, part.n_local, prep.hidden
+    W = HEADS * H
+    lists = shard_lists(part)
+    xchg = HaloExchange(part, ops, group)
+    h = ops.encode(x_local, *prep.enc_node)
+    e = ops.encode(e_local, *prep.enc_edge, gather=views.srt_eid[:part.n_score], rows=part.n_score)   # the scored rows, sorted order
+    L = len(prep.layers)
+    A = torch.empty((n_own, W), dtype=torch.float32, device=h.device) if L else None
+    for i, lw in enumerate(prep.layers):
+        if i > 0:
+            xchg.start(h)
+        P = _project_part(ops, h, lw.Wp, lw.planes, n_own, xchg.finish)
+        ops.node_attention_sum_part(P[:, :W], lists, n_own, P[:, W:W + 4], P[:n_own, W + 4:W + 8], bias=lw.bias, negative_slope=lw.slope,
+                                    both=not directed, out=A)
+        h = torch.empty((n_local, H), dtype=torch.float32, device=h.device)
+        ops.linear(A, lw.W, lw.b, out=h[:n_own])
+        if i + 1 < L:
+            ops.relu_rows(h[:n_own])
+    if L:
+        xchg.start(h)
+        xchg.finish()
+    pw = prep.predictor
+    return eb._score_part(ops, part, group, e, h, (pw["W_nodes"], pw["b_nodes"], pw.get("planes")),
+                          (pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"]))
+
+
+def forward_partitioned(ops, model, prep, part, x_local, e_local, group=None):
+    """engine_baselines.forward_partitioned for this stack: logits that are not all finite left fp16x3's operand range and the forward is
+    run again as bf16x6 - decided on the all-reduced flag (eb._any_rank), so every rank takes the same route."""
+    directed = bool(model.directed)
+    if prep.force_bf16x6:
+        with ops.bf16x6_arithmetic():
+            return run_partitioned(ops, prep, part, x_local, e_local, group, directed)
+    logits = run_partitioned(ops, prep, part, x_local, e_local, group, directed)
+    if getattr(ops, "_TUNING", {}).get(10, 0) == 1 or not getattr(model, "range_check", True):
+        return logits
+    if not eb._any_rank(~torch.isfinite(logits).all(), part, group):
+        return logits
+    with ops.bf16x6_arithmetic():
+        return run_partitioned(ops, prep, part, x_local, e_local, group, directed)
+
+
+def _part_step_forward(ops, model, sh, x, e_raw, masks):
+    """_step_forward on a shard -> (logits[E_global], what the backward reads).  Kept per layer: h_d and P for the local rows; A, stats
+    and the mask for the owned rows."""
+    d = lambda t: t.detach().contiguous()  # noqa: E731
+    part, views, n_own, n_local = sh.part, sh.views, sh.n_own, sh.n_local
+    both = not model.directed
+    lists = shard_lists(part)
+    ne, ee = model.node_encoder, model.edge_encoder
+    h = ops.encode(x, d(ne.linear1.weight), d(ne.linear1.bias), d(ne.linear2.weight), d(ne.linear2.bias))
+    e = ops.encode(e_raw, d(ee.linear1.weight), d(ee.linear1.bias), d(ee.linear2.weight), d(ee.linear2.bias), gather=views.srt_eid[:sh.e_own],
+                   rows=sh.e_own)
+    H = h.shape[1]
+    W = HEADS * H
+    layers = []
+    for i, (conv, lin) in enumerate(zip(model.gnn.convs, model.gnn.linears)):
+        if masks[i] is not None:          # the owner drops its rows; the halo rows arrive dropped
+            ops.relu_mul_rows(h[:n_own], masks[i], relu=i > 0)
+        elif i > 0:
+            ops.relu_rows(h[:n_own])
+        if i > 0 or masks[0] is not None:   # (layer 0 without a mask: the halo rows are what x encodes to)
+            sh.halo_start(h)
+        Wp = fold_on_device(conv)
+        P = _project_part(ops, h, Wp, None, n_own, sh.halo_finish)
+        A, stats = ops.node_attention_sum_stats_part(P[:, :W], lists, n_own, P[:, W:W + 4], P[:n_own, W + 4:W + 8], bias=d(conv.bias),
+                                                     negative_slope=float(conv.negative_slope), both=both)
+        layers.append(dict(h_d=h, P=P, A=A, stats=stats, mask=masks[i], Wp=Wp))
+        h = torch.empty((n_local, H), dtype=torch.float32, device=h.device)
+        ops.linear(A, d(lin.weight), d(lin.bias), out=h[:n_own])
+    if layers:
+        sh.halo_start(h)
+        sh.halo_finish()
+    pred = model.predictor
+    hs = pred.W1.out_features
+    W1 = d(pred.W1.weight)
+    W_nodes = torch.cat([W1[:, :H], W1[:, H:2 * H]], 0).contiguous()
+    b_nodes = torch.cat([torch.zeros_like(pred.W1.bias), pred.W1.bias]).detach().contiguous()
+    z1 = torch.empty((sh.e_own, hs), dtype=torch.float32, device=h.device)
+    logits = eb._score_part(ops, part, sh.group, e, h, (W_nodes, b_nodes, None),
+                            (W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1))),
+                            z1_out=z1)
+    return logits, dict(h=h, e=e, z1=z1, W1=W1, W_nodes=W_nodes, layers=layers)
+
+
+def _part_step_backward(ops, model, sh, x, e_raw, kept, dlogits):
+    """_step_backward on a shard -> {parameter name: this rank's share of the gradient}.  Per layer the head mix's backward on the owned
+    rows, the exchange of G = dA's halo rows under the destination phase, the exchange of the halo work rows, the source phase, and dWp, dh
+    from the owned rows of dP.  Only the scorer's node gradient returns partial rows to their owners (halo_bwd)."""
+    from .train import encoder_bwd, score_backward_on_shard
+    d = lambda t: t.detach().contiguous()  # noqa: E731
+    views, n_own, n_local, e_own = sh.views, sh.n_own, sh.n_local, sh.e_own
+    both = not model.directed
+    lists = shard_lists(sh.part)
+    H = kept["h"].shape[1]
+    W = HEADS * H
+    dev = dlogits.device
+    g = {}
+    dh, de = score_backward_on_shard(ops, model.predictor, sh, g, dlogits, kept["z1"], kept["e"], kept["h"], kept["W1"], kept["W_nodes"], e_own)
+    sh.halo_bwd(dh)
+    dY = dh[:n_own]
+    dP = None
+    if kept["layers"]:
+        dP = torch.empty((n_own, W + SCORE_COLUMNS), dtype=torch.float32, device=dev)
+        dP[:, W + 8:].zero_()   # the 56 score columns no kernel writes: once per table
+    for i in range(len(kept["layers"]) - 1, -1, -1):
+        conv, lin, s = model.gnn.convs[i], model.gnn.linears[i], kept["layers"][i]
+        g[f"gnn.linears.{i}.weight"] = ops.wgrad(dY, s["A"])
+        g[f"gnn.linears.{i}.bias"] = sY = ops.colsum2(dY)[0]
+        G = torch.empty((n_local, W), dtype=torch.float32, device=dev)
+        ops.linear(dY, d(lin.weight).t().contiguous(), None, out=G[:n_own])
+        sh.halo_start(G)                   # 3H floats per halo row, in flight under the destination phase (which reads owned rows of G)
+        g[f"gnn.convs.{i}.bias"] = (sY.double() @ lin.weight.detach().double()).float()
+        P = s["P"]
+        work = torch.empty((n_local, 16), dtype=torch.float32, device=dev)
+        ops.node_attention_sum_bwd_dst_part(G, lists, n_own, P[:, :W], P[:, W:W + 4], P[:n_own, W + 4:W + 8], s["A"], s["stats"],
+                                            bias=d(conv.bias), negative_slope=float(conv.negative_slope), both=both,
+                                            der=dP[:, W + 4:W + 8], work=work)
+        sh.halo_finish()
+        sh.halo_start(work)                # 16 floats per halo row
+        sh.halo_finish()
+        ops.node_attention_sum_bwd_src_part(G, lists, n_own, P[:n_own, :W], P[:n_own, W:W + 4], work,
+                                            negative_slope=float(conv.negative_slope), both=both, dfeat=dP[:, :W], del_=dP[:, W:W + 4])
+        h_d = s["h_d"][:n_own]
+        for name, grad in unfold(conv, ops.wgrad(dP, h_d)).items():
+            g[f"gnn.convs.{i}.{name}"] = grad
+        dY = ops.linear(dP, s["Wp"].t().contiguous(), None)
+        if s["mask"] is not None:
+            ops.relu_mul_rows(dY, s["mask"], relu=False)
+        if i > 0:                          # h_d > 0 exactly where the ReLU passed and the mask kept
+            dY = ops.relu_bwd(dY, h_d)
+        kept["layers"][i] = s = None
+    ne, ee = model.node_encoder, model.edge_encoder
+    encoder_bwd(ops, g, dY.contiguous(), x[:n_own], None, n_own, ne.linear1, ne.linear2, "node_encoder.linear1", "node_encoder.linear2")
+    encoder_bwd(ops, g, de, e_raw, views.srt_eid[:e_own], e_own, ee.linear1, ee.linear2, "edge_encoder.linear1", "edge_encoder.linear2")
+    return g
+
+
+class _PartitionedGatStep(torch.autograd.Function):
+    """engine_baselines._PartitionedBaselineStep for GATModel: the step on one rank of a destination-range partition, the range fallback
+    decided on the all-reduced flag, the parameter gradients summed over ranks once at the end."""
+
+    @staticmethod
+    def forward(ctx, model, sh, x, e_raw, names, *params):
+        from . import train
+        ops = sh.ops
+        H = model.node_encoder.linear2.out_features   # feat_drop's masks of the OWNED rows (train.dropout_mask is looked up at call time)
+        masks = [train.dropout_mask(sh.n_own, H, conv.feat_drop.p, x.device) if conv.feat_drop.p > 0 else None for conv in model.gnn.convs]
+        bf16x6 = getattr(ops, "_TUNING", {}).get(10, 0) == 1
+        logits, kept = _part_step_forward(ops, model, sh, x, e_raw, masks)
+        if not bf16x6 and getattr(model, "range_check", True) and eb._any_rank(~torch.isfinite(logits).all(), sh.part, sh.group):
+            bf16x6 = True
+            with ops.bf16x6_arithmetic():
+                logits, kept = _part_step_forward(ops, model, sh, x, e_raw, masks)
+        ctx.model, ctx.sh, ctx.names, ctx.kept, ctx.inputs, ctx.bf16x6 = model, sh, names, kept, (x, e_raw), bf16x6
+        return logits.unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        if ctx.kept is None:
+            raise RuntimeError("the activations of this training step were released by its first backward(); "
+                               "retain_graph=True is not supported - run the forward again")
+        model, sh = ctx.model, ctx.sh
+        ops = sh.ops
+        if ctx.bf16x6:
+            with ops.bf16x6_arithmetic():
+                g = _part_step_backward(ops, model, sh, *ctx.inputs, ctx.kept, dlogits)
+        else:
+            g = _part_step_backward(ops, model, sh, *ctx.inputs, ctx.kept, dlogits)
+        ctx.kept = None
+        return (None, None, None, None, None) + tuple(sh.sum_ranks([g[n].contiguous() for n in ctx.names]))
+
+
+def train_forward_on(model, shard, x_local, e_local):
+    """The training step of GATModel over one rank's rows (dist.PartitionShard over the default partition): x_local / e_local are the input
+    features of the shard's nodes (owned, then halo) and edges (local edge-id order).  Returns logits[E_global, 1], complete on every
+    rank; after backward() every rank holds the whole graph's parameter gradients."""
+    from .train import TRAIN_SCORE_HIDDEN
+    check_partition(model, shard.part)
+    eb.built_width(model.predictor.W1.out_features, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")
+    names, params = zip(*model.named_parameters())
+    if any(p.device != x_local.device for p in params):
+        raise RuntimeError("training needs the model on the compute device: call model.to(device) first")
+    if x_local.shape[0] != shard.n_local or e_local.shape[0] != shard.e_local:
+        raise ValueError(f"x has {x_local.shape[0]} rows for {shard.n_local} local nodes, e has {e_local.shape[0]} rows for {shard.e_local} local edges")
+    return _PartitionedGatStep.apply(model, shard, x_local, e_local, list(names), *params)

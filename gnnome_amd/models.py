@@ -170,7 +170,9 @@ class GATModel(_BaselineModel):
     Per layer (gnnome_amd/engine_gat.py): ONE projection on [fc.weight ; attn_l fc ; attn_r fc] gives feat, el and er as column blocks of
     a [N, 3H + 64] table, the edge softmax and the weighted sum are the kernel gnnome_node_attention_sum_f32 over the graph's own in- and
     out-lists, then the head mix.  As for SAGEModel, dropout=None means 0.0 (the reference fails on it), and the reference's print at
-    construction is not reproduced."""
+    construction is not reproduced.  On several GPUs: dist.GATPartitionedRunner over the default destination-range partition, eval mode
+    and the training step, both `directed` values, on the partition forms of the attention kernels (DESIGN 7d "Partitions");
+    dist.PartitionedRunner refuses this model and names that class."""
     kind = "gat"
 
     def __init__(self, node_features, edge_features, hidden_features, hidden_ne_features, num_layers, hidden_edge_scores,

@@ -870,6 +870,113 @@ def node_attention_sum_bwd(g, views, feat, el, er, out, stats, bias=None, negati
     return dfeat, del_, der
 
 
+def _attention_part_tables(what, n_own, views, local, owned):
+    """The shape checks the four part front ends share: `local` tables have a row per LOCAL node, `owned` ones at least n_own rows.
+    Each is (name, tensor, columns) -> [(tensor, row stride)] in the order given."""
+    n = views.num_nodes
+    n_own = int(n_own)
+    if not 0 <= n_own <= n or views.transposed:
+        raise ValueError(f"{what}: {n_own} owned of {n} local nodes (forward orientation)")
+    device = local[0][1].device
+    got = []
+    for tables, need, kind in ((local, n, "local"), (owned, n_own, "owned")):
+        for name, t, cols in tables:
+            t, ld = _rows(t, f"{what}.{name}")
+            if (t.shape[0] != need if kind == "local" else t.shape[0] < need) or t.shape[1] != cols or t.device != device:
+                raise ValueError(f"{what}: {name} is {tuple(t.shape)} on {t.device}, expected {need} {kind} rows of {cols} columns on {device}")
+            got.append((t, ld))
+    return got
+
+
+def _attention_part_forward(what, entry, feat, views, n_own, el, er, bias, negative_slope, both, out, stats):
+    n_own, heads = int(n_own), 3
+    width = feat.shape[1]
+    if width % heads:
+        raise ValueError(f"{what}: feat is [n_local, 3H], got {tuple(feat.shape)}")
+    if out is None:
+        out = torch.empty((n_own, width), dtype=torch.float32, device=feat.device)
+    owned = [("er", er, 4), ("out", out, width)]
+    if entry.endswith("stats_part_f32"):
+        if stats is None:
+            stats = torch.empty((n_own, 8), dtype=torch.float32, device=feat.device)
+        owned.append(("stats", stats, 8))
+    tabs = _attention_part_tables(what, n_own, views, [("feat", feat, width), ("el", el, 4)], owned)
+    if bias is not None and (_f32(bias, what + ".bias").shape != (width,) or not bias.is_contiguous()):
+        raise ValueError(f"{what}: bias is one contiguous float per output column")
+    (feat, ldf), (el, ld_el), (er, ld_er), (o, ldo) = tabs[:4]
+    tail = (_ptr(tabs[4][0]), tabs[4][1]) if len(tabs) == 5 else ()
+    _call(entry, feat.device, _ptr(feat), ldf, _ptr(el), ld_el, _ptr(er), ld_er, width // heads, heads, n_own, views.num_nodes,
+          _ptr(views.in_ptr), _ptr(views.srt_src), _ptr(views.out_ptr) if both else None, _ptr(views.out_dst) if both else None,
+          float(negative_slope), _ptr(bias), _ptr(o), ldo, *tail)
+    return out, stats
+
+
+def node_attention_sum_part(feat, views, n_own, el, er, bias=None, negative_slope=0.2, both=False, out=None):
+    """node_attention_sum on one rank's shard of the default partition (gnnome_node_attention_sum_part_f32): `views` holds the local lists
+    in the whole graph's order (engine_baselines.ShardLists: n_own owned nodes first, then the halo), feat [n_local, 3H] and el [n_local, 4]
+    have a row per LOCAL node, er and out ([n_own, .], or more rows) are touched at the owned rows only.  An owned row has the bits of
+    node_attention_sum on the whole graph."""
+    return _attention_part_forward("node_attention_sum_part", "gnnome_node_attention_sum_part_f32", feat, views, n_own, el, er, bias,
+                                   negative_slope, both, out, None)[0]
+
+
+def node_attention_sum_stats_part(feat, views, n_own, el, er, bias=None, negative_slope=0.2, both=False, out=None, stats=None):
+    """node_attention_sum_stats on one rank's shard (gnnome_node_attention_sum_stats_part_f32) -> (out [n_own, 3H], stats [n_own, 8])."""
+    return _attention_part_forward("node_attention_sum_stats_part", "gnnome_node_attention_sum_stats_part_f32", feat, views, n_own, el, er,
+                                   bias, negative_slope, both, out, stats)
+
+
+def node_attention_sum_bwd_dst_part(g, views, n_own, feat, el, er, out, stats, bias=None, negative_slope=0.2, both=False, der=None, work=None):
+    """The DESTINATION phase of node_attention_sum_bwd on one rank's shard (gnnome_node_attention_sum_bwd_dst_part_f32) -> (der, work):
+    g, er, out and stats are read at the owned rows (n_own rows, or more), feat [n_local, 3H] and el [n_local, 4] at any local row; der
+    ([n_own, 4], or more rows) and the rows < n_own of work [n_local, 16] are written, work's halo rows left as they are - they are their
+    owners' to compute and the caller's to fetch before node_attention_sum_bwd_src_part."""
+    what = "node_attention_sum_bwd_dst_part"
+    n_own, heads, n = int(n_own), 3, views.num_nodes
+    width = feat.shape[1]
+    if width % heads:
+        raise ValueError(f"{what}: feat is [n_local, 3H], got {tuple(feat.shape)}")
+    if der is None:
+        der = torch.empty((n_own, 4), dtype=torch.float32, device=feat.device)
+    if work is None:
+        work = torch.empty((n, 16), dtype=torch.float32, device=feat.device)
+    if work.shape != (n, 16) or not work.is_contiguous():
+        raise ValueError(f"{what}: work is {tuple(work.shape)}, expected a contiguous {(n, 16)}")
+    tabs = _attention_part_tables(what, n_own, views, [("feat", feat, width), ("el", el, 4), ("work", work, 16)],
+                                  [("g", g, width), ("er", er, 4), ("out", out, width), ("stats", stats, 8), ("der", der, 4)])
+    if bias is not None and (_f32(bias, what + ".bias").shape != (width,) or not bias.is_contiguous()):
+        raise ValueError(f"{what}: bias is one contiguous float per output column")
+    (feat, ldf), (el, ld_el), (w, _), (g, ldg), (er, ld_er), (o, ldo), (st, lds), (dr, ld_dr) = tabs
+    _call("gnnome_node_attention_sum_bwd_dst_part_f32", feat.device, _ptr(g), ldg, _ptr(feat), ldf, _ptr(el), ld_el, _ptr(er), ld_er, _ptr(o), ldo,
+          _ptr(bias), _ptr(st), lds, width // heads, heads, n_own, n, _ptr(views.in_ptr), _ptr(views.srt_src), _ptr(views.out_ptr),
+          _ptr(views.out_dst), 1 if both else 0, float(negative_slope), _ptr(dr), ld_dr, _ptr(w))
+    return der, work
+
+
+def node_attention_sum_bwd_src_part(g, views, n_own, feat, el, work, negative_slope=0.2, both=False, dfeat=None, del_=None):
+    """The SOURCE phase on one rank's shard (gnnome_node_attention_sum_bwd_src_part_f32) -> (dfeat [n_own, 3H], del [n_own, 4]): g
+    [n_local, 3H] and work [n_local, 16] are read at ANY local row - their halo rows fetched from the owners after the destination phase -,
+    feat and el at the owned rows.  dfeat and del_ may be column blocks of a [n_own, 3H + 64] table laid out like the projection."""
+    what = "node_attention_sum_bwd_src_part"
+    n_own, heads, n = int(n_own), 3, views.num_nodes
+    width = g.shape[1]
+    if width % heads:
+        raise ValueError(f"{what}: g is [n_local, 3H], got {tuple(g.shape)}")
+    if dfeat is None:
+        dfeat = torch.empty((n_own, width), dtype=torch.float32, device=g.device)
+    if del_ is None:
+        del_ = torch.empty((n_own, 4), dtype=torch.float32, device=g.device)
+    if not work.is_contiguous():
+        raise ValueError(f"{what}: work is a contiguous [n_local, 16] table")
+    tabs = _attention_part_tables(what, n_own, views, [("g", g, width), ("work", work, 16)],
+                                  [("feat", feat, width), ("el", el, 4), ("dfeat", dfeat, width), ("del", del_, 4)])
+    (g, ldg), (w, _), (feat, ldf), (el, ld_el), (df, ld_df), (dl, ld_dl) = tabs
+    _call("gnnome_node_attention_sum_bwd_src_part_f32", g.device, _ptr(g), ldg, _ptr(feat), ldf, _ptr(el), ld_el, _ptr(w), width // heads, heads,
+          n_own, n, _ptr(views.out_ptr), _ptr(views.out_dst), _ptr(views.in_ptr), _ptr(views.srt_src), 1 if both else 0, float(negative_slope),
+          _ptr(df), ld_df, _ptr(dl), ld_dl)
+    return dfeat, del_
+
+
 def relu_rows(x):
     """x <- relu(x) in place (gnnome_relu_rows_f32; NaN stays NaN); x may be a column block of a wider table."""
     x, ld = _rows(x, "relu_rows.x")

@@ -29,8 +29,9 @@
 extern "C" {
 #endif
 
-/* Raised when an existing entry changes its signature or meaning.  32 also covers gnnome_node_neighbour_sum_part_f32 and
- * gnnome_node_neighbour_sum_bwd_part_f32, which were ADDED without touching any other entry: a caller built against 32 keeps working, and
+/* Raised when an existing entry changes its signature or meaning.  32 also covers gnnome_node_neighbour_sum_part_f32,
+ * gnnome_node_neighbour_sum_bwd_part_f32 and the four part entries of the attention sum (gnnome_node_attention_sum_part_f32, _stats_part_f32,
+ * _bwd_dst_part_f32, _bwd_src_part_f32), which were ADDED without touching any other entry: a caller built against 32 keeps working, and
  * the Python binding resolves every entry by name when it loads the library, so a library that predates them is refused there, by name. */
 #define GNNOME_ABI_VERSION 32
 
@@ -461,6 +462,55 @@ int gnnome_node_attention_sum_bwd_f32(const float* g, int ld_g, const float* fea
                                       int heads, int64_t num_nodes, const int32_t* in_ptr, const int32_t* srt_src, const int32_t* out_ptr,
                                       const int32_t* out_dst, int both, float negative_slope, float* dfeat, int ld_dfeat, float* del, int ld_del,
                                       float* der, int ld_der, float* work, void* stream);
+
+/* ---- the attention sum on one rank's shard of a destination-range partition -----------------------------
+ * GATModel (models/full_graph.py:78-97, layers/processor.py:49-70) per rank.  The shard is the DEFAULT partition, as for the two
+ * neighbour sums above: num_nodes_out owned nodes first, then the halo, every edge with an owned end kept - so an owned node's in-list
+ * AND out-list are complete, in the whole graph's order, and every softmax of an owned destination sees all of its terms.  in_ptr and
+ * out_ptr have num_nodes_local + 1 entries (the first num_nodes_out + 1 are read), neighbour ids are < num_nodes_local.
+ * num_nodes_out <= num_nodes_local is required: GNNOME_EINVAL otherwise, as for heads != 3, a hidden outside {64,128,256}, a NULL
+ * required pointer or a bad stride - the whole-graph entries' argument errors, checked before anything is launched.  num_nodes_out == 0
+ * returns at once.  Strides, alignment and aliasing rules are the whole-graph entries'.
+ *
+ * FORWARD, the two forms: feat and el are tables of num_nodes_local rows (the halo rows projected locally or fetched); er, out and
+ * stats are read and written at rows < num_nodes_out only.  No wave is spent on a halo row and no [num_nodes_local, 3*hidden] output
+ * exists.
+ *
+ * BACKWARD, the two launches of gnnome_node_attention_sum_bwd_f32 as separate entries, because on a partition a collective sits between
+ * them:
+ *   the DESTINATION phase computes D, der and the 16-float work row  er | m | 1/den | D  of the owned rows.  It reads g, out, stats and
+ *     er at owned rows, feat / el at any local row through the in-list and, with `both`, the out-list, and writes der rows and work rows
+ *     < num_nodes_out of a [num_nodes_local, 16] table - the rows at and above num_nodes_out are not touched;
+ *   the SOURCE phase computes dfeat and del of the owned rows.  It reads feat / el at owned rows and g and work at ANY local row through
+ *     the out-list and, with `both`, the in-list: the caller fills the halo rows of g and of work - from their owners, two
+ *     forward-direction exchanges of 3*hidden and of 16 floats per halo row - between the two phases.
+ * Every edge's term of dfeat[j] / del[j] is computed by j's owner and its term of der[i] by i's owner: no halo transpose, no partial sums.
+ *
+ * BIT EQUALITY: the part entries launch the whole-graph entries' kernels over the owned rows - the row code, lane mapping and
+ * association (the loop's term first, lists ascending, 128-item blocks above 4096 items) exist once, in csrc/node_attention.hip and
+ * csrc/node_attention_bwd.hip.  The bits of an owned row depend only on that row's lists and the table rows they name.  So with
+ * num_nodes_out == num_nodes_local the part entries equal the whole-graph entries bit for bit; the destination phase followed by the
+ * source phase on a whole table equals gnnome_node_attention_sum_bwd_f32, work included; and an owned row of a shard whose tables hold
+ * the whole graph's rows equals the whole-graph entry's row at any world size. */
+int gnnome_node_attention_sum_part_f32(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er, int hidden,
+                                       int heads, int64_t num_nodes_out, int64_t num_nodes_local, const int32_t* in_ptr,
+                                       const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_dst, float negative_slope,
+                                       const float* bias, float* out, int ld_out, void* stream);
+int gnnome_node_attention_sum_stats_part_f32(const float* feat, int ld_feat, const float* el, int ld_el, const float* er, int ld_er,
+                                             int hidden, int heads, int64_t num_nodes_out, int64_t num_nodes_local, const int32_t* in_ptr,
+                                             const int32_t* srt_src, const int32_t* out_ptr, const int32_t* out_dst, float negative_slope,
+                                             const float* bias, float* out, int ld_out, float* stats, int ld_stats, void* stream);
+int gnnome_node_attention_sum_bwd_dst_part_f32(const float* g, int ld_g, const float* feat, int ld_feat, const float* el, int ld_el,
+                                               const float* er, int ld_er, const float* out, int ld_out, const float* bias,
+                                               const float* stats, int ld_stats, int hidden, int heads, int64_t num_nodes_out,
+                                               int64_t num_nodes_local, const int32_t* in_ptr, const int32_t* srt_src,
+                                               const int32_t* out_ptr, const int32_t* out_dst, int both, float negative_slope, float* der,
+                                               int ld_der, float* work, void* stream);
+int gnnome_node_attention_sum_bwd_src_part_f32(const float* g, int ld_g, const float* feat, int ld_feat, const float* el, int ld_el,
+                                               const float* work, int hidden, int heads, int64_t num_nodes_out, int64_t num_nodes_local,
+                                               const int32_t* out_ptr, const int32_t* out_dst, const int32_t* in_ptr,
+                                               const int32_t* srt_src, int both, float negative_slope, float* dfeat, int ld_dfeat,
+                                               float* del, int ld_del, void* stream);
 
 /* ---- streaming aggregation (round 5) -----------------------------------------------------------------
  * The same node update as gnnome_node_aggregate_f32 with norm_kind = GNNOME_NORM_AFFINE (gated_gcn_full.py:111-114, :124-127,
