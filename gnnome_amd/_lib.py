@@ -163,6 +163,7 @@ SIGNATURES = {
     "gnnome_pr_curve_scan": [_p, _l, _p, _sz, _p, _p],
     "gnnome_pr_curve_emit": [_p, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _sz, _p],
     "gnnome_pr_curve_ap": [_p, _p, _l, _p, _p, _sz, _p],
+    "gnnome_walk_audit": [_p, _p, _p, _l, _l, _p, _p, _p, _p, _l, _p, _p, _p],
 }
 
 ABI_VERSION = 32

@@ -1868,3 +1868,28 @@ def cluster_inputs(node_ptr, nid, edge_ptr, eid, in_deg, out_deg, e, y, outer_ni
           _ptr(in_deg), _ptr(out_deg), in_deg.numel(), _ptr(e), _ptr(y), e.shape[0], _ptr(x_org), _ptr(x_rev), _ptr(e_sub), _ptr(y_sub),
           _ptr(ws), ws.numel())
     return x_org, x_rev, e_sub, y_sub
+
+
+def _i64(t, name, device):
+    if t.dtype != torch.int64 or t.dim() != 1 or t.device != device or not t.is_contiguous():
+        raise TypeError(f"{name}: expected a contiguous 1-d int64 tensor on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def walk_audit(walk_ptr, walk_nodes, walk_id, read_strand, read_start, read_end, read_chr):
+    """gnnome_walk_audit (include/gnnome_hip.h; utils/analyze.py:1-38) over flattened walks -> (flags uint8[T], counts int32[W,3]) on
+    the device, nothing synchronised.  walk_ptr int32[W+1], walk_nodes, walk_id int32[T]; the four node arrays int64[N].  Flag bits:
+    1 strand, 2 chromosome, 4 overlap, 64 a position outside its walk, 128 a node id outside [0, N) (never dereferenced)."""
+    walk_ptr, walk_nodes, walk_id = _i32(walk_ptr, "walk_audit.walk_ptr"), _i32(walk_nodes, "walk_audit.walk_nodes"), _i32(walk_id, "walk_audit.walk_id")
+    dev = walk_nodes.device
+    cols = [_i64(t, f"walk_audit.{n}", dev) for t, n in ((read_strand, "read_strand"), (read_start, "read_start"), (read_end, "read_end"),
+                                                         (read_chr, "read_chr"))]
+    W, T, N = walk_ptr.numel() - 1, walk_nodes.numel(), cols[0].numel()
+    if W < 0 or walk_ptr.dim() != 1 or walk_nodes.dim() != 1 or walk_id.shape != walk_nodes.shape or walk_ptr.device != dev or walk_id.device != dev:
+        raise ValueError("walk_audit: walk_ptr int32[W+1], walk_nodes and walk_id int32[T] on one device")
+    if any(c.numel() != N for c in cols):
+        raise ValueError("walk_audit: the four node arrays differ in length")
+    flags = torch.empty(T, dtype=torch.uint8, device=dev)
+    counts = torch.zeros((W, 3), dtype=torch.int32, device=dev)
+    _call("gnnome_walk_audit", dev, _ptr(walk_ptr), _ptr(walk_nodes), _ptr(walk_id), W, T, *(_ptr(c) for c in cols), N, _ptr(flags), _ptr(counts))
+    return flags, counts

@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import contigs as contigs_mod
-from . import decode, features, gfa, metrics
+from . import analyze, decode, features, gfa, metrics
 from .graph import views_for
 
 
@@ -145,3 +145,17 @@ def edge_report(g, model=None, scores=None, device=None):
     return {"TP": TP, "TN": TN, "FP": FP, "FN": FN, "acc": acc, "precision": precision, "recall": recall, "f1": f1,
             "acc_inv": acc_inv, "precision_inv": precision_inv, "recall_inv": recall_inv, "f1_inv": f1_inv,
             "aps": metrics.get_aps(scores, y, device=device), "aps_inverse": metrics.get_aps_inverse(scores, y, device=device)}
+
+
+def walk_report(g, walks, device=None):
+    """The walk checks of utils/analyze.py:1-38 summed over `walks` on a graph with read positions (read_gfa(training=True)): per kind -
+    strand, chromosome, overlap - the number of findings and the number of walks with at least one, copied to the host once.
+    analyze.audit_walks has the findings themselves."""
+    audit = analyze.audit_walks(g, walks, device=device)
+    counts = audit.counts.long()
+    totals = torch.cat([counts.sum(0), (counts > 0).sum(0)]).tolist()
+    kinds = ("strand", "chromosome", "overlap")
+    report = {"walks": len(audit)}
+    report.update({k: totals[i] for i, k in enumerate(kinds)})
+    report.update({"walks_with_" + k: totals[3 + i] for i, k in enumerate(kinds)})
+    return report

@@ -1313,6 +1313,27 @@ int gnnome_pr_curve_emit(const uint32_t* sorted_keys, int64_t num_edges, int64_t
 int gnnome_pr_curve_ap(const double* precision, const double* recall, int64_t num_thresholds, double* ap, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- Walk audit: the strand, chromosome and overlap checks of decoded walks ---------------------------------------------------------
+ * Replaces utils/analyze.py:1-38 (assert_strand, assert_chromosome, assert_overlap, each a Python loop with .item() round trips per
+ * step) for a whole batch of walks, as tests/walk_audit_statement.py states them.  Walks are flattened: walk w is
+ * walk_nodes[walk_ptr[w] .. walk_ptr[w+1]) (int32, walk_ptr[W+1] ascending from 0 to T), and walk_id int32[T] names the walk of every
+ * position (the caller's repeat_interleave of the walk lengths).  read_strand, read_start, read_end, read_chr: int64[num_nodes].
+ * One thread per position t of walk w, with first = walk_nodes[walk_ptr[w]]; flags uint8[T]:
+ *   bit 0  (:1-8)    t is not the walk's first position and read_strand[node] != read_strand[first]
+ *   bit 1  (:11-18)  t is not the walk's first position and read_chr[node] != read_chr[first]
+ *   bit 2  (:21-38)  t is not the walk's last position and, with d = walk_nodes[t+1], both strands are 1 and read_start[d] >
+ *                    read_end[node], or both are -1 and read_end[d] < read_start[node]  (equality, unequal strands and strand values
+ *                    other than 1 / -1 are silent; the chromosome is not looked at)
+ *   bit 6  walk_id[t] outside [0, W) or t outside [walk_ptr[w], walk_ptr[w+1]) within [0, T): the position is not examined
+ *   bit 7  the node id is outside [0, num_nodes): it is never used as an index, and no other bit of the position is set
+ * The reference's printed `walk index` is t - walk_ptr[w] - 1 for bits 0 and 1 (it enumerates walk[1:]) and t - walk_ptr[w] for bit 2.
+ * counts int32[W,3]: zeroed here, then the number of positions of walk w with bit 0, bit 1, bit 2 - summed per wavefront run of equal
+ * walk_id and added with integer atomics (exact, order-free).  num_walks, num_positions < 2^31; either being 0 returns 0 without a
+ * launch and without writing anything. */
+int gnnome_walk_audit(const int32_t* walk_ptr, const int32_t* walk_nodes, const int32_t* walk_id, int64_t num_walks, int64_t num_positions,
+                      const int64_t* read_strand, const int64_t* read_start, const int64_t* read_end, const int64_t* read_chr,
+                      int64_t num_nodes, uint8_t* flags, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
