@@ -25,6 +25,10 @@ and the 64-byte work rows between the two phases of the attention sum's backward
 PartitionedRunner itself keeps refusing GATModel and names that class.  The GAT path has run as processes sharing one GPU and as CPU
 ranks over gloo only - never on two devices.
 
+SymGatedGCNModel's pass over dgl.reverse(g) (train.py:159-170, the symmetry loss) runs on the same plan with reverse=True: owned nodes,
+scored edges, BatchNorm rows and the halo plan do not depend on the orientation, only the roles of the projection's column blocks and of
+the two lists do ("Symmetry step").  Run over gloo and on ranks sharing one GPU - never on two devices.
+
 All tensor math goes through an `ops` namespace exactly like engine.run_stack: the product passes
 gnnome_amd.ops (HIP); the CPU/gloo tests pass the checker backend to exercise this host logic.
 """
@@ -232,15 +236,18 @@ class PartitionedGraph:
             all_to_all_rows(out, packed, self._slice_recv, self._slice_send, self._group)
         return out.reshape((out.shape[0],) + tuple(rows_slice.shape[1:]))
 
-    def local_degree_features(self):
+    def local_degree_features(self, reverse=False):
         """x rows of this rank's owned + halo nodes, [zscore(in_degree) | zscore(out_degree)] of the WHOLE graph (inference.py:416-420;
-        mean and unbiased std in fp64, applied in fp32 like gnnome_degree_features_f32), from the degrees from_slices all-reduced."""
+        mean and unbiased std in fp64, applied in fp32 like gnnome_degree_features_f32), from the degrees from_slices all-reduced.
+        reverse: the two columns swapped - the x of the reversed pass (train.py:112-122,165-166; ops.degree_features): the degrees stay
+        those of the original graph, dgl.reverse copies ndata and does not recompute it."""
         if not hasattr(self, "global_degrees"):
             raise RuntimeError("local_degree_features needs a plan built by from_slices")
         d = self.global_degrees.double()
         mean, std = d.mean(1, keepdim=True), d.std(1, keepdim=True)
         local = self.global_degrees[:, self.node_gid].float()
-        return ((local - mean.float()) / std.float()).t().contiguous()
+        z = (local - mean.float()) / std.float()
+        return (z.flip(0) if reverse else z).t().contiguous()
 
     def _build(self, ls, ld, device, ops, group):
         """Everything after the rank knows its local edges (ls, ld: global endpoints, ascending global edge id)."""
@@ -425,7 +432,8 @@ class HaloExchange:
 
 
 def check_shard(part):
-    """What a PartitionShard refuses (GATPartitionedRunner raises the same, in the same words, before it allocates anything)."""
+    """What a PartitionShard refuses (GATPartitionedRunner raises the same, in the same words, before it allocates anything).  The PLAN is
+    always the forward orientation's; the reversed pass of SymGatedGCNModel is asked for with reverse=True on that plan."""
     if part.views.transposed:
         raise NotImplementedError("partitioned training runs on the forward orientation of the graph")
     if part.n_own == 0 or part.n_score == 0:
@@ -440,15 +448,20 @@ class PartitionShard:
       * backward: per-channel BatchNorm sums and, at the end, all parameter gradients are all-reduced (one flat
         buffer); halo rows of dh are scatter-added back to their owners once per layer."""
 
-    def __init__(self, part, ops=hip_ops, group=None):
+    def __init__(self, part, ops=hip_ops, group=None, reverse=False):
+        """reverse: the shard of the pass over dgl.reverse(g) (gated_gcn_full.py:99,117-127; train.py:165) - SymGatedGCNModel's step only.
+        The rows a rank owns do not depend on the orientation: the same owned nodes, the same n_score scored edges (the sorted prefix,
+        whose FORWARD destination is owned), the same halo plan, the same assembly of the logits.  Only `views` changes - the plan's own
+        arrays with the flag flipped (GraphViews.reversed: nothing is sorted or copied) - and with it the roles train._roles deals out."""
         check_shard(part)
         self.part, self.ops, self.group, self.world = part, ops, group, part.world
         self.alone = _alone(part.world)     # False under GNNOME_FORCE_COLLECTIVES=1: one rank, every collective issued
-        self.views = part.views
+        self.reverse = bool(reverse)
+        self.views = part.views.reversed() if self.reverse else part.views
         self.n_own, self.n_local = part.n_own, part.n_local
         self.e_own, self.e_local = part.n_score, part.views.num_edges
         self.n_global, self.e_global = part.bounds[-1], part.num_edges_global
-        self.score_views = _ScoreViews(part.views, part.srt_geid)
+        self.score_views = _ScoreViews(self.views, part.srt_geid)
         self._xchg = HaloExchange(part, ops, group)
 
     def halo_start(self, h):
@@ -517,17 +530,27 @@ def _check_partition_kind(prep, part):
     return gated
 
 
-def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result=True):
+def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result=True, reverse=False):
     """The rank-local kernel sequence.  x_local: [n_local, F] features of owned+halo nodes, e_local:
     [e_local, F] features of local edges in local edge-id order.  Returns logits[E_global] (complete on
     every rank after the all_reduce when `reduce_result`).
+    reverse (SymGatedGCNModel only): the pass over dgl.reverse(g) (gated_gcn_full.py:99,117-127; train.py:165) on the SAME plan - x_local
+    then holds the swapped degree columns.  Owned nodes, scored edges (the sorted prefix), halo exchange and the assembly of the logits are
+    the forward pass's; the column blocks of P change roles (A2 <-> A3, B1 <-> B2, as engine.layer_step does on a whole graph) and the
+    scorer's node halves change places (engine.score_step).
     prep = engine_gated.Prepared (a GatedGCNModel): engine_gated's eval sequence per layer - the [n_local,4H] projection, the same gate,
     gnnome_node_aggregate_in_f32 over the owned rows - on an in-edge-only partition (PartitionedGraph.from_global(..., in_edges_only=True))."""
     from . import engine_baselines
     if isinstance(prep, engine_baselines.Prepared):   # GCNModel / SAGEModel: engine_baselines' sequence on the default partition
+        if reverse:
+            raise NotImplementedError("GCNModel / SAGEModel on a partition runs on the forward orientation of the graph")
         return engine_baselines.run_partitioned(ops, prep, part, x_local, e_local, group)
     gated = _check_partition_kind(prep, part)
-    views, n_own = part.views, part.n_own
+    if gated and reverse:
+        raise NotImplementedError("GatedGCNModel on an in-edge-only partition runs on the forward orientation of the graph")
+    if part.views.transposed:   # (the plan itself is never flipped: reverse= selects the pass)
+        raise NotImplementedError("partitioned training runs on the forward orientation of the graph")
+    views, n_own = (part.views.reversed() if reverse else part.views), part.n_own
     xchg = HaloExchange(part, ops, group)
     H = prep.hidden
     h = ops.encode(x_local, *prep.enc_node)  # halo rows of layer 0 come straight from the input features
@@ -543,6 +566,8 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result
             h = ops.node_aggregate_in(e, A1, A2, views, h, lw.norm, lw.scale_h, lw.shift_h, num_nodes_out=n_own)
             continue
         A1, A2, A3, B1, B2 = (P[:, i * H:(i + 1) * H] for i in range(5))
+        if reverse:   # src <-> dst: an owned node's contiguous by-dst run holds its OUT-edges now, its out_pos run its in-edges
+            A2, A3, B1, B2 = A3, A2, B2, B1
         e = engine.gate(ops, lw, views, e, B1, B2, (e_local, prep.enc_edge), scratch)
         h = ops.node_aggregate(e, A1, A2, A3, views, h, lw.norm, lw.scale_h, lw.shift_h, num_nodes_out=n_own)
     xchg.start(h)
@@ -550,17 +575,18 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result
     hs = pw["hs"]
     xchg.finish()
     PQ = ops.linear(h, pw["W_nodes"], pw["b_nodes"], planes=pw.get("planes"))
+    Ps, Qd = (PQ[:, hs:], PQ[:, :hs]) if reverse else (PQ[:, :hs], PQ[:, hs:])   # x[src'] | x[dst'] = x[dst] | x[src]; b1 enters once either way
     score_views = _ScoreViews(views, part.srt_geid)
     if _alone(part.world) or not reduce_result:
         # scatter straight to GLOBAL edge ids: a GraphViews-like shim whose srt_eid is the global map
         logits = (torch.zeros if part.world > 1 else torch.empty)(part.num_edges_global, dtype=torch.float32, device=h.device)
         if part.n_score > 0:
-            ops.edge_score(e, PQ[:, :hs], PQ[:, hs:], score_views, pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"], logits,
+            ops.edge_score(e, Ps, Qd, score_views, pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"], logits,
                            num_edges=part.n_score)
         return logits
     piece = torch.empty(part.score_pad, dtype=torch.float32, device=h.device)
     if part.n_score > 0:
-        ops.edge_score(e, PQ[:, :hs], PQ[:, hs:], score_views, pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"], piece,
+        ops.edge_score(e, Ps, Qd, score_views, pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"], piece,
                        num_edges=part.n_score, scatter_to_edge_id=False)
     return part.assemble_logits(piece, group)
 
@@ -574,7 +600,10 @@ class CapturedPartitionedForward:
     projection of the owned rows (the halo rows of a layout-ordered graph are a few per cent of a rank's rows).
     Same kernels, same order: the logits equal run_partitioned's bit for bit.  Inputs are the runner's static x / e."""
 
-    def __init__(self, runner):
+    def __init__(self, runner, reverse=False):
+        if reverse:   # (before anything is allocated or warmed up)
+            raise NotImplementedError("CapturedPartitionedForward records the forward orientation only; the reversed pass (reverse=True) runs "
+                                      "the eager PartitionedRunner.forward(reverse=True)")
         if runner.prep is None:
             raise RuntimeError("CapturedPartitionedForward is for eval-mode inference")
         ops, prep, part = runner.ops, runner.prep, runner.part
@@ -647,12 +676,16 @@ class _ScoreViews:
 class PartitionedRunner:
     """Holds one rank's partition, weights and inputs on its GPU; forward() = one whole-graph scoring pass."""
 
-    def __init__(self, model, part, x_global, e_global, device, ops=hip_ops, group=None, x_local=None, e_local=None, split=None):
+    def __init__(self, model, part, x_global, e_global, device, ops=hip_ops, group=None, x_local=None, e_local=None, split=None,
+                 x_rev_global=None, x_rev_local=None):
         """x_global[N,F]: the node features of the whole graph (this rank keeps its owned + halo rows), or x_local: those rows
         already selected (part.local_node_rows), for callers that never hold the [N,F] table on this device; e_global[E,F] or
         e_local (part.local_edge_rows / part.shuffle_edge_rows) likewise.
         split (GCNModel / SAGEModel only): True = the neighbour sums as interior rows under the halo exchange + boundary rows after it,
-        False = one launch after it, None = engine_baselines.PARTITION_SPLIT; equal bits either way."""
+        False = one launch after it, None = engine_baselines.PARTITION_SPLIT; equal bits either way.
+        x_rev_global / x_rev_local (SymGatedGCNModel only): the node features of the REVERSED pass - the degree columns swapped
+        (train.py:165-166; part.local_degree_features(reverse=True)) - which forward(reverse=True) / train_forward(reverse=True) read.  One
+        plan, one set of views, one copy of the edge features serve both passes."""
         self.ops, self.part, self.group, self.model = ops, part, group, model
         from . import engine_baselines
         from .models import GatedGCNModel
@@ -675,22 +708,44 @@ class PartitionedRunner:
                 raise ValueError("GatedGCNModel runs on an in-edge-only partition: PartitionedGraph.from_global(..., in_edges_only=True)")
         elif part.in_edges_only:
             raise ValueError("an in-edge-only partition serves GatedGCNModel; SymGatedGCNModel needs the out-edges of the owned nodes too")
+        elif part.views.transposed:   # the reversed pass is selected by reverse=, never by flipping the plan (check_shard's words)
+            raise NotImplementedError("partitioned training runs on the forward orientation of the graph")
+        if (x_rev_global is not None or x_rev_local is not None) and (self.baseline or self.gated):
+            raise NotImplementedError(f"{type(model).__name__} on a partition runs on the forward orientation of the graph: it takes no x_rev")
         prepared = engine_baselines.Prepared if self.baseline else engine_gated.Prepared if self.gated else engine.Prepared
         self.prep = None if model.training else engine.prepared_for(model, device, prepared)
         rows = part.local_node_rows(x_global) if x_local is None else x_local
         self.x = rows.to(device=device, dtype=torch.float32).contiguous()
         erows = part.local_edge_rows(e_global) if e_local is None else e_local
         self.e = erows.to(device=device, dtype=torch.float32).contiguous()
+        self.x_rev = None
+        if x_rev_global is not None or x_rev_local is not None:
+            rows = part.local_node_rows(x_rev_global) if x_rev_local is None else x_rev_local
+            self.x_rev = rows.to(device=device, dtype=torch.float32).contiguous()
 
-    def capture(self):
-        """Record the forward as hipGraph segments between the collectives (CapturedPartitionedForward); forward() replays them."""
-        self._captured = CapturedPartitionedForward(self)
+    def capture(self, reverse=False):
+        """Record the forward as hipGraph segments between the collectives (CapturedPartitionedForward); forward() replays them.
+        reverse=True is refused there: the reversed pass stays eager."""
+        self._captured = CapturedPartitionedForward(self, reverse=reverse)
         return self
 
-    def forward(self):
-        """eval mode: logits[E,1] of one whole-graph scoring pass."""
+    def _reversed_inputs(self):
+        """x of the reversed pass, or the refusal of a model / runner that has none."""
+        if self.baseline or self.gated:
+            raise NotImplementedError(f"{type(self.model).__name__} on a partition runs on the forward orientation of the graph")
+        if self.x_rev is None:
+            raise ValueError("reverse=True reads the node features of the reversed pass: build the runner with x_rev_global= or x_rev_local=")
+        return self.x_rev
+
+    def forward(self, reverse=False):
+        """eval mode: logits[E,1] of one whole-graph scoring pass.  reverse=True (SymGatedGCNModel): the pass over dgl.reverse(g) on the
+        runner's x_rev - the `rev` logits of train.py:165-167, [E,1] in edge-id order, identical on every rank; always eager."""
         if self.prep is None:
             raise RuntimeError("built from a model in train mode: use train_forward()")
+        if reverse:
+            x_rev = self._reversed_inputs()
+            with torch.no_grad():
+                return run_partitioned(self.ops, self.prep, self.part, x_rev, self.e, self.group, reverse=True).unsqueeze(1)
         if getattr(self, "_captured", None) is not None:
             return self._captured()
         with torch.no_grad():
@@ -700,10 +755,18 @@ class PartitionedRunner:
                                                           split=self.split).unsqueeze(1)
             return run_partitioned(self.ops, self.prep, self.part, self.x, self.e, self.group).unsqueeze(1)
 
-    def train_forward(self):
+    def train_forward(self, reverse=False):
         """train mode: logits[E,1] with autograd history; after loss.backward() every rank holds the whole graph's
-        parameter gradients (already summed over ranks), so identical optimizers stay in step without a DDP wrapper."""
+        parameter gradients (already summed over ranks), so identical optimizers stay in step without a DDP wrapper.
+        reverse=True (SymGatedGCNModel): the `rev` logits.  One symmetry step (train.py:159-170) is
+            loss.symmetry_loss(r.train_forward().squeeze(-1), r.train_forward(reverse=True).squeeze(-1), y, pw, alpha).backward()
+        - two autograd nodes, each with its own shard and its own saved activations, both alive until backward(); the gradients of the two
+        passes are all-reduced per pass and accumulate in .grad, bn_e's running statistics advance four times per layer, bn_h's twice.
+        Every rank must call the two passes, and backward(), in the same order: each issues collectives."""
         from .train import train_forward_on
+        if reverse:
+            x_rev = self._reversed_inputs()
+            return train_forward_on(self.model, PartitionShard(self.part, self.ops, self.group, reverse=True), x_rev, self.e)
         if self.baseline:   # GCNModel / SAGEModel: engine_baselines' step on the shard (one exchange of h and one of its gradient per layer)
             from . import engine_baselines
             return engine_baselines.train_forward_on(self.model, PartitionShard(self.part, self.ops, self.group), self.x, self.e,
