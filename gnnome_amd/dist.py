@@ -45,7 +45,9 @@ def force_collectives():
     """GNNOME_FORCE_COLLECTIVES=1: a single-rank process group still ISSUES every collective of the partitioned path (halo
     all_to_all both ways, BatchNorm statistics all_gather, BatchNorm-backward and gradient all_reduce, logits all_gather) instead
     of taking the world == 1 shortcuts - the way a one-GPU box runs this module's RCCL calls (tests/test_hip_partition.py).
-    A one-rank collective is the identity, so the results must equal the plain path bit for bit."""
+    A one-rank collective is the identity, so the results must equal the plain path bit for bit - in training too: one rank's statistics
+    are the whole graph's, so the step keeps the single-rank BatchNorm kernels and sends their moments and backward sums through the
+    collectives (PartitionShard.sync_moments, sum_ranks) instead of merging them on the host."""
     return os.environ.get("GNNOME_FORCE_COLLECTIVES", "0") == "1"
 
 
@@ -363,6 +365,19 @@ def all_reduce_sum(t, group=None):
     return t
 
 
+def broadcast_from(t, src=0, group=None):
+    """t <- the t of the group's rank `src`, in place (trainer.train_partitioned: what rank 0 drew)."""
+    if group is not None:
+        src = dist.get_global_rank(group, src)
+    if _staged(t, group):
+        c = t.cpu()
+        dist.broadcast(c, src=src, group=group)
+        t.copy_(c)
+    else:
+        dist.broadcast(t, src=src, group=group)
+    return t
+
+
 def all_gather_rows(t, world, group=None):
     """[world, *t.shape]: every rank's t."""
     out = torch.empty(world * t.numel(), dtype=t.dtype, device="cpu" if _staged(t, group) else t.device)
@@ -490,6 +505,16 @@ class PartitionShard:
         mean_all = (n * mu).sum(0) / total
         m2_all = (m2 + n * (mu - mean_all) ** 2).sum(0)
         return mean_all.float().contiguous(), (m2_all / total).float().contiguous()
+
+    def sync_moments(self, moments):
+        """(d1, d2, center, rows) of a single-rank BatchNorm call (train._bn_train_fused; train._can_fuse_bn admits world == 1 only) through
+        the statistics' all_gather: one rank's own row comes back, the same bits, and the collective has been issued."""
+        if self.alone:
+            return moments
+        d1, d2, center, rows = moments
+        H = d1.numel()
+        row = all_gather_rows(torch.cat([d1.reshape(-1), d2.reshape(-1), center.reshape(-1)]), self.world, self.group)[0]
+        return row[:H], row[H:2 * H], row[2 * H:], rows
 
     def sum_ranks(self, tensors):
         if self.alone:
@@ -755,6 +780,13 @@ class PartitionedRunner:
                                                           split=self.split).unsqueeze(1)
             return run_partitioned(self.ops, self.prep, self.part, self.x, self.e, self.group).unsqueeze(1)
 
+    def check_train_step(self):
+        """What train_forward() refuses about the MODEL, raised without running a kernel or a collective (trainer.train_partitioned asks
+        before epoch 0): the symmetric-step adapter of GatedGCNModel (zero A_3) is not served on partitions."""
+        if self.gated and engine_gated.training_step_of(self.model) != "in_edge":
+            raise NotImplementedError('a partitioned GatedGCNModel trains with training_step = "in_edge"; this model has training_step = '
+                                      f'{self.model.training_step!r}')
+
     def train_forward(self, reverse=False):
         """train mode: logits[E,1] with autograd history; after loss.backward() every rank holds the whole graph's
         parameter gradients (already summed over ranks), so identical optimizers stay in step without a DDP wrapper.
@@ -772,10 +804,7 @@ class PartitionedRunner:
             return engine_baselines.train_forward_on(self.model, PartitionShard(self.part, self.ops, self.group), self.x, self.e,
                                                      split=self.split)
         if self.gated:
-            # GatedGCNModel: the one-direction step on the shard; the symmetric-step adapter (zero A_3) is not served on partitions
-            if engine_gated.training_step_of(self.model) != "in_edge":
-                raise NotImplementedError('a partitioned GatedGCNModel trains with training_step = "in_edge"; this model has training_step = '
-                                          f'{self.model.training_step!r}')
+            self.check_train_step()
             return engine_gated.train_forward_in_edge_on(self.model, PartitionShard(self.part, self.ops, self.group), self.x, self.e)
         return train_forward_on(self.model, PartitionShard(self.part, self.ops, self.group), self.x, self.e)
 
@@ -800,6 +829,9 @@ class GATPartitionedRunner:
 
     def capture(self):
         raise NotImplementedError("CapturedPartitionedForward is built for SymGatedGCNModel; a GATModel runs the eager forward()")
+
+    def check_train_step(self):
+        """PartitionedRunner.check_train_step: GATModel has one training step, and check_partition has passed."""
 
     def forward(self):
         """eval mode: logits[E,1] of one whole-graph scoring pass, complete on every rank."""

@@ -110,13 +110,18 @@ def induced_subgraph(graph, keep, device=None):
     the edges whose two endpoints are kept in their original order, original ids stored (MaskedGraph.nid / .eid)."""
     device = device or (graph.device if isinstance(graph, ops.GraphViews) else torch.device("cuda", torch.cuda.current_device()))
     src, dst, n = _edge_list_on(graph, device)
-    keep = keep.to(device)
+    s2, d2, nid, eid = induced_edge_list(src, dst, keep.to(device))
+    views = ops.GraphViews(s2, d2, int(nid.numel()), validate=False)
+    return MaskedGraph(s2, d2, int(nid.numel()), nid, eid, views)
+
+
+def induced_edge_list(src, dst, keep):
+    """The index arithmetic of induced_subgraph on the device of `src`, without the views: (src', dst', nid, eid) of the edges whose two
+    endpoints are kept (trainer.train_partitioned plans the masked graph from this list; every rank computes the same one)."""
     new_id = torch.cumsum(keep, 0, dtype=torch.int32) - 1
     eid = torch.nonzero(keep[src.long()] & keep[dst.long()]).squeeze(1)
     nid = torch.nonzero(keep).squeeze(1)
-    s2, d2 = new_id[src[eid].long()].contiguous(), new_id[dst[eid].long()].contiguous()
-    views = ops.GraphViews(s2, d2, int(nid.numel()), validate=False)
-    return MaskedGraph(s2, d2, int(nid.numel()), nid, eid, views)
+    return new_id[src[eid].long()].contiguous(), new_id[dst[eid].long()].contiguous(), nid, eid
 
 
 def mask_graph_strandwise(graph, fraction, device=None, keep_half=None):

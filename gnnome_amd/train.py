@@ -40,7 +40,8 @@ class WholeGraph:
     (owned nodes first, then halo; owned in-edges first, then the out-edges that end in the halo)."""
 
     world = 1
-    alone = True      # no collective is issued (a PartitionShard of one rank under GNNOME_FORCE_COLLECTIVES=1 says False)
+    alone = True      # no collective is issued (a PartitionShard of one rank under GNNOME_FORCE_COLLECTIVES=1 says False; `world` is 1 for
+                      # both, and it is `world` that selects the kernels: the two give the same bits)
 
     def __init__(self, views, ops=hip_ops):
         self.views, self.ops = views, ops
@@ -65,6 +66,9 @@ class WholeGraph:
 
     def combine_stats(self, mean, var, rows):   # per-rank (mean, biased var, row count) -> statistics of the union
         return mean, var
+
+    def sync_moments(self, moments):    # world == 1 with forced collectives: the statistics take their round trip through the collective
+        return moments
 
     def sum_ranks(self, tensors):       # element-wise sum over ranks of a list of tensors (same shapes on every rank)
         return tensors
@@ -117,12 +121,15 @@ def _bn_train(sh, bn, mean, var, n_local, rows, updates):
 def _bn_train_fused(sh, bn, moments, updates):
     """The single-rank case in one launch (gnnome_bn_train_finish_f32): no per-channel torch arithmetic, no host work."""
     track = bn.track_running_stats
+    moments = sh.sync_moments(moments)
     return sh.ops.bn_train_finish(moments, bn.weight.detach(), bn.bias.detach(), bn.running_mean if track else None,
                                   bn.running_var if track else None, bn.num_batches_tracked if track else None, bn.momentum, bn.eps, updates)
 
 
 def _can_fuse_bn(sh, bn):
-    return sh.alone and bn.momentum is not None and hasattr(sh.ops, "bn_train_finish")
+    """world == 1, not `alone`: one rank's rows are the whole graph's, so a rank that issues every collective (GNNOME_FORCE_COLLECTIVES=1)
+    takes the same kernels as the plain step - its moments go through sync_moments, a one-rank gather - and gives the same bits."""
+    return sh.world == 1 and bn.momentum is not None and hasattr(sh.ops, "bn_train_finish")
 
 
 def _bn_bwd(sh, dy, x, scale, shift, mean, rstd, rows, n_once, out, stats=None, apply=True):
@@ -133,7 +140,8 @@ def _bn_bwd(sh, dy, x, scale, shift, mean, rstd, rows, n_once, out, stats=None, 
     first n_once rows only (the owned ones)."""
     ops = sh.ops
     s1, s2 = ops.bn_bwd_stats(dy, x, scale, shift, mean) if stats is None else stats   # (stats: gathered by the producer of dy)
-    if sh.alone and hasattr(ops, "bn_bwd_terms"):
+    if sh.world == 1 and hasattr(ops, "bn_bwd_terms"):
+        s1, s2 = sh.sum_ranks([s1, s2])                     # (alone: as they are; forced collectives: a one-rank all-reduce, the same bits)
         s2h, c1, c2 = ops.bn_bwd_terms(s1, s2, rstd, rows)   # the three vectors below in one launch
     else:
         s2h = rstd * s2                                     # sum dy*m*xhat
@@ -258,7 +266,7 @@ def score_backward_on_shard(ops, pred, sh, g, dlogits, z1, e, h, W1, W_nodes, e_
     g["predictor.W2.weight"] = ops.wgrad(dz2, z1)
     g["predictor.W2.bias"] = ops.colsum2(dz2)[0]
     g["predictor.W3.weight"] = ops.colsum2(u)[0].reshape(1, pred.W3.in_features)
-    g["predictor.W3.bias"] = (dl if sh.alone else dl[sh.score_views.srt_eid.long()]).sum().reshape(1)
+    g["predictor.W3.bias"] = (dl if sh.world == 1 else dl[sh.score_views.srt_eid.long()]).sum().reshape(1)
     if e_local > e_own:   # the local edges that end in another range are scored by their destinations' owners
         dz1 = torch.cat([dz1, torch.zeros((e_local - e_own, hs), dtype=torch.float32, device=dl.device)], 0)
     dz1_e = dz1 if e_rows == dz1.shape[0] else dz1[:e_rows]

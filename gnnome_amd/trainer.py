@@ -2,6 +2,8 @@
 
     records = trainer.train(train_set, valid_set, out="run", seed=1)        # -> one record per epoch
     python -m gnnome_amd.trainer --train DIR --valid DIR --name run [--overfit] [--resume] [--dropout P] [--seed S] [--gpu I]
+    records = trainer.train_partitioned(train_set, valid_set, out="run", seed=1)   # every rank of a process group: graphs larger than one GPU
+    python -m gnnome_amd.trainer --train DIR --valid DIR --name run --gpus N [--transport nccl|gloo]
 
 Per epoch, as the reference: shuffle the training graphs; if `masking`, keep a random fraction of the reads
 (features.mask_graph_strandwise); train on the whole graph if `num_nodes_per_cluster >= N`, otherwise on the
@@ -27,6 +29,7 @@ import json
 import os
 import random
 import re
+import sys
 import time
 import types
 from datetime import datetime
@@ -172,10 +175,20 @@ def load_dataset(ds):
     return [(f"graph {i}", g) for i, g in enumerate(ds)]
 
 
-class _Graph:
-    """One dataset graph on the device, prepared once at load: the full graph's views, stored degrees, z-scored e and labels."""
+def hip_backend():
+    """The namespace the loops reach the device through - the package's own kernels: `kernels` (what dist.PartitionedRunner takes as
+    ops=), GraphViews, cluster_inputs (features.cluster_inputs), edge_loss (ops.edge_loss), stored_degrees, edge_features.
+    train_partitioned(ops=...) takes another one (the CPU tests: a torch restatement)."""
+    return types.SimpleNamespace(kernels=ops, GraphViews=ops.GraphViews, cluster_inputs=features.cluster_inputs, edge_loss=ops.edge_loss,
+                                 stored_degrees=features.stored_degrees, edge_features=features.edge_features)
 
-    def __init__(self, name, g, device):
+
+class _Graph:
+    """One dataset graph on the device, prepared once at load: the full graph's views, stored degrees, z-scored e and labels (and the
+    edge list itself, in edge-id order: train_partitioned masks and plans from it)."""
+
+    def __init__(self, name, g, device, be=None):
+        be = be or hip_backend()
         y = g.get("y") if isinstance(g, dict) else None
         if y is None:
             raise ValueError(f"graph {name}: no labels (y); build training graphs with gfa.read_gfa(..., training=True) or trainer.process")
@@ -183,7 +196,8 @@ class _Graph:
         self.num_nodes = int(g["num_nodes"])
         src = torch.as_tensor(g["src"]).to(device=device, dtype=torch.int32).contiguous()
         dst = torch.as_tensor(g["dst"]).to(device=device, dtype=torch.int32).contiguous()
-        self.views = ops.GraphViews(src, dst, self.num_nodes)
+        self.src, self.dst = src, dst
+        self.views = be.GraphViews(src, dst, self.num_nodes)
         self.num_edges = int(src.numel())
         self.y = torch.as_tensor(y).to(device=device, dtype=torch.float32).contiguous()
         if self.y.numel() != self.num_edges:
@@ -193,13 +207,13 @@ class _Graph:
         else:
             if g.get("overlap_length") is None or g.get("overlap_similarity") is None:
                 raise ValueError(f"graph {name}: needs overlap_length and overlap_similarity (or e) for the edge features")
-            self.e = features.edge_features(torch.as_tensor(g["overlap_length"]).to(device).float(),
-                                            torch.as_tensor(g["overlap_similarity"]).to(device).float())
+            self.e = be.edge_features(torch.as_tensor(g["overlap_length"]).to(device).float(),
+                                      torch.as_tensor(g["overlap_similarity"]).to(device).float())
         if g.get("in_deg") is not None and g.get("out_deg") is not None:
             self.in_deg = torch.as_tensor(g["in_deg"]).to(device=device, dtype=torch.float32).contiguous()
             self.out_deg = torch.as_tensor(g["out_deg"]).to(device=device, dtype=torch.float32).contiguous()
         else:
-            self.in_deg, self.out_deg = (t.contiguous() for t in features.stored_degrees(self.views))
+            self.in_deg, self.out_deg = (t.contiguous() for t in be.stored_degrees(self.views))
 
 
 def process(gfa, reads, out_path, device=None, maf=None, maf_chr=None, maf_parser="host"):
@@ -220,12 +234,12 @@ def process(gfa, reads, out_path, device=None, maf=None, maf_chr=None, maf_parse
 
 class _LossAndCounts(torch.autograd.Function):
     """loss.symmetry_loss / loss.bce_loss that also leaves (loss, TP, TN, FP, FN) of the org logits in a row of the device log:
-    one edge-loss kernel gives all of them (ops.edge_loss(..., need_counts=True))."""
+    one edge-loss kernel gives all of them (ops.edge_loss(..., need_counts=True); `edge_loss`: the backend's entry)."""
 
     @staticmethod
-    def forward(ctx, org, rev, labels, pos_weight, alpha, row):
+    def forward(ctx, org, rev, labels, pos_weight, alpha, row, edge_loss):
         need = org.requires_grad or (rev is not None and rev.requires_grad)
-        loss, d_org, d_rev, tfpn = ops.edge_loss(org.detach().float().contiguous(), None if rev is None else rev.detach().float().contiguous(),
+        loss, d_org, d_rev, tfpn = edge_loss(org.detach().float().contiguous(), None if rev is None else rev.detach().float().contiguous(),
                                                 labels, pos_weight, alpha, need_grad=need, need_counts=True)
         row[0].copy_(loss[0])
         row[1:5].copy_(tfpn)
@@ -235,7 +249,7 @@ class _LossAndCounts(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         d_org, d_rev = ctx.saved_tensors
-        return (None if d_org is None else g * d_org), (None if d_rev is None else g * d_rev), None, None, None, None
+        return (None if d_org is None else g * d_org), (None if d_rev is None else g * d_rev), None, None, None, None, None
 
 
 def _graph_steps(gr, hp, device, training, trace, phase, epoch):
@@ -296,7 +310,7 @@ def _run_epoch_phase(model, optimizer, graphs, hp, pos_weight, device, training,
     phase = "train" if training else "valid"
     logs, skipped, first_grads = [], 0, trace is not None and training and not any(t.get("grads") is not None for t in trace)
     alpha = float(hp["alpha"]) if hp["use_symmetry_loss"] else 0.0
-    n_trace0 = len(trace) if trace is not None else 0
+    n_trace0, n_done = len(trace) if trace is not None else 0, 0
     for gr in graphs:
         if training:
             model.train()
@@ -306,7 +320,9 @@ def _run_epoch_phase(model, optimizer, graphs, hp, pos_weight, device, training,
         for i, (views, ci) in enumerate(steps):
             org = _model_step(model, views, ci.x, ci.e).squeeze(-1)
             rev = _model_step(model, views.reversed(), ci.x_rev, ci.e).squeeze(-1) if hp["use_symmetry_loss"] else None
-            loss = _LossAndCounts.apply(org, rev, ci.y, pos_weight, alpha, log[i])
+            loss = _LossAndCounts.apply(org, rev, ci.y, pos_weight, alpha, log[i], ops.edge_loss)
+            if trace is not None:
+                trace[n_trace0 + n_done + i]["logits"] = org.detach().cpu()
             if training:
                 optimizer.zero_grad()
                 loss.backward()
@@ -315,6 +331,7 @@ def _run_epoch_phase(model, optimizer, graphs, hp, pos_weight, device, training,
                     first_grads = False
                 optimizer.step()
         logs.append(log)
+        n_done += len(steps)
     log = torch.cat(logs).cpu() if logs else torch.zeros((0, 5), dtype=torch.float64)   # the one copy to the host of the phase
     if trace is not None:
         for rec, row in zip(trace[n_trace0:], log.tolist()):
@@ -338,12 +355,41 @@ def _set_rng_state(st):
         torch.cuda.set_rng_state_all([t.cpu() for t in st["cuda"]])
 
 
+# ---- what train and train_partitioned share ----------------------------------------------------------------------------------
+
+def _optimizer_and_scheduler(model, hp):
+    optimizer = torch.optim.Adam(model.parameters(), lr=hp["lr"])
+    return optimizer, ReduceLROnPlateau(optimizer, mode="min", factor=hp["decay"], patience=hp["patience"])
+
+
+def _run_paths(out, seed, models_dir, checkpoints_dir, resumed=None):
+    """(model file, checkpoint file) of the run `out` with `seed`; resumed=num_epochs: the files a resumed run writes."""
+    out = f"{out}_seed{seed}" + ("" if resumed is None else f"_resumed-{resumed}")
+    return os.path.join(models_dir, f"model_{out}.pt"), os.path.join(checkpoints_dir, f"ckpt_{out}.pt")
+
+
+def _load_checkpoint(ckpt, model, optimizer, scheduler, loss_train, loss_valid):
+    """Model, optimizer, scheduler and the best losses out of a checkpoint -> the epoch to start from (the random state is the caller's)."""
+    model.load_state_dict(ckpt["model_state_dict"])
+    optimizer.load_state_dict(ckpt["optim_state_dict"])
+    loss_train.append(ckpt["loss_train"])
+    loss_valid.append(ckpt["loss_valid"])
+    if "scheduler_state_dict" in ckpt:
+        scheduler.load_state_dict(ckpt["scheduler_state_dict"])
+    return ckpt["epoch"] + 1
+
+
+def _checkpoint_dict(epoch, model, optimizer, scheduler, best, rng_state):
+    return {"epoch": epoch, "model_state_dict": model.state_dict(), "optim_state_dict": optimizer.state_dict(),
+            "loss_train": best[0], "loss_valid": best[1], "scheduler_state_dict": scheduler.state_dict(), "rng_state": rng_state}
+
+
 def train(train_set, valid_set, out=None, hyperparameters=None, overfit=False, dropout=None, seed=None, resume=False, device=None,
           models_dir="models", checkpoints_dir="checkpoints", trace=None, model_class=SymGatedGCNModel):
     """train.py:188-450 (see the module docstring) -> the list of epoch records.  `hyperparameters`: overrides of
     configs/hyperparameters.py by the reference's key names.  `trace` (for tests): a list that receives the initial state dict and
-    one dict per step (graph, mask fraction, the step's full-graph node and edge ids, its edges, loss and counts; the first training
-    step's gradients) - it copies to the host per step.  `model_class`: the model to train, SymGatedGCNModel, GatedGCNModel, GCNModel or
+    one dict per step (graph, mask fraction, the step's full-graph node and edge ids, its edges, its org logits, loss and counts; the
+    first training step's gradients) - it copies to the host per step.  `model_class`: the model to train, SymGatedGCNModel, GatedGCNModel, GCNModel or
     SAGEModel (same constructor arguments).  A GatedGCNModel subclass that sets `training_step = "in_edge"` (and, if it wants the doubled
     graph, passes directed=False to the base constructor) trains through `_model_step` like any other model: its own call selects the
     one-direction step (engine_gated.train_forward_in_edge)."""
@@ -363,29 +409,19 @@ def train(train_set, valid_set, out=None, hyperparameters=None, overfit=False, d
 
     model = model_class(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_ne_features"], hp["num_gnn_layers"],
                              hp["hidden_edge_scores"], hp["normalization"], dropout=dropout).to(device)
-    optimizer = torch.optim.Adam(model.parameters(), lr=hp["lr"])
-    scheduler = ReduceLROnPlateau(optimizer, mode="min", factor=hp["decay"], patience=hp["patience"])
+    optimizer, scheduler = _optimizer_and_scheduler(model, hp)
     if trace is not None:
         trace.append({"initial_state": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, "pos_weight": float(pos_weight)})
 
-    out = f"{out}_seed{seed}"
     os.makedirs(models_dir, exist_ok=True)
     os.makedirs(checkpoints_dir, exist_ok=True)
-    model_path = os.path.join(models_dir, f"model_{out}.pt")
-    ckpt_path = os.path.join(checkpoints_dir, f"ckpt_{out}.pt")
+    model_path, ckpt_path = _run_paths(out, seed, models_dir, checkpoints_dir)
     start_epoch, loss_train, loss_valid = 0, [], []
     order = list(range(len(ds_train)))
     if resume:
         ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)   # load_state_dict moves to the device
-        model_path = os.path.join(models_dir, f"model_{out}_resumed-{hp['num_epochs']}.pt")
-        ckpt_path = os.path.join(checkpoints_dir, f"ckpt_{out}_resumed-{hp['num_epochs']}.pt")
-        start_epoch = ckpt["epoch"] + 1
-        model.load_state_dict(ckpt["model_state_dict"])
-        optimizer.load_state_dict(ckpt["optim_state_dict"])
-        loss_train.append(ckpt["loss_train"])
-        loss_valid.append(ckpt["loss_valid"])
-        if "scheduler_state_dict" in ckpt:
-            scheduler.load_state_dict(ckpt["scheduler_state_dict"])
+        model_path, ckpt_path = _run_paths(out, seed, models_dir, checkpoints_dir, resumed=hp["num_epochs"])
+        start_epoch = _load_checkpoint(ckpt, model, optimizer, scheduler, loss_train, loss_valid)
         if "rng_state" in ckpt:
             _set_rng_state(ckpt["rng_state"])
             order = list(ckpt["rng_state"]["train_order"])
@@ -421,12 +457,283 @@ def train(train_set, valid_set, out=None, hyperparameters=None, overfit=False, d
         rec["lr"] = lr
         rec["seconds"] = time.perf_counter() - t0
         # after scheduler.step: the checkpoint's scheduler state is the one the next epoch starts from
-        torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optim_state_dict": optimizer.state_dict(),
-                    "loss_train": best[0], "loss_valid": best[1], "scheduler_state_dict": scheduler.state_dict(),
-                    "rng_state": _rng_state(order)}, ckpt_path)
+        torch.save(_checkpoint_dict(epoch, model, optimizer, scheduler, best, _rng_state(order)), ckpt_path)
         with open(log_path, "a") as f:
             f.write(json.dumps(rec) + "\n")
         records.append(rec)
+    return records
+
+
+# ---- the loop on destination-range partitions --------------------------------------------------------------------------------
+
+def _ranks_that_would_be_empty(src, dst, num_nodes, world, bounds, in_edges_only):
+    """(bounds, owned nodes per rank, owned in-edges per rank) of the plan PartitionedGraph.from_global would build, from the edge list
+    alone - no process group, the same on every rank (dist.partition_census's arithmetic)."""
+    from . import dist as gdist
+    src, dst = src.long(), dst.long()
+    bounds = gdist.split_by_incident_edges(src, dst, num_nodes, world) if bounds is None else gdist._checked_bounds(bounds, num_nodes, world)
+    bt = torch.tensor(bounds[1:-1], device=dst.device, dtype=torch.long)
+    owned_in = torch.bincount(torch.bucketize(dst, bt, right=True), minlength=world).tolist()
+    return bounds, [b - a for a, b in zip(bounds[:-1], bounds[1:])], owned_in
+
+
+def _partition_bounds(ctx, gr, src, dst, num_nodes, epoch, phase):
+    """The range boundaries of one (masked) graph's plan, or the collective refusal: decided from the edge list every rank holds, before the
+    first collective of the plan, so every rank raises the same ValueError and none is left waiting for a peer."""
+    bounds = None if ctx.bounds is None else ctx.bounds(src, dst, num_nodes, ctx.world)
+    bounds, nodes, in_edges = _ranks_that_would_be_empty(src, dst, num_nodes, ctx.world, bounds, ctx.in_edges_only)
+    for r in range(ctx.world):
+        if nodes[r] == 0 or in_edges[r] == 0:
+            when = "before epoch 0" if epoch is None else f"{phase} phase of epoch {epoch}"
+            raise ValueError(f"graph {gr.name}, {when}: rank {r} of world size {ctx.world} would own {nodes[r]} nodes and {in_edges[r]} "
+                             f"in-edges of the {num_nodes} nodes and {int(src.numel())} edges left (bounds {bounds}): the graph is too "
+                             "small for this world size")
+    return bounds
+
+
+def _partition_plan(ctx, src, dst, num_nodes, bounds):
+    from . import dist as gdist
+    return gdist.PartitionedGraph.from_global(src, dst, num_nodes, ctx.rank, ctx.world, ctx.device, ops=ctx.be.kernels, group=ctx.group,
+                                              in_edges_only=ctx.in_edges_only, bounds=bounds)
+
+
+def _partition_runner(ctx, model, part, ci):
+    from . import dist as gdist
+    if getattr(model, "kind", None) == "gat":
+        return gdist.GATPartitionedRunner(model, part, ci.x, ci.e, ctx.device, ops=ctx.be.kernels, group=ctx.group)
+    return gdist.PartitionedRunner(model, part, ci.x, ci.e, ctx.device, ops=ctx.be.kernels, group=ctx.group, x_rev_global=ci.x_rev)
+
+
+def _synchronize(device):
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+
+
+def _drawn_mask(ctx, gr, hp):
+    """(fraction, keep bool[N // 2]) of one graph: rank 0 draws both exactly as _graph_steps does - random.randint, then torch.rand on the
+    device - and broadcasts them in one message; no other rank draws."""
+    from . import dist as gdist
+    half = gr.num_nodes // 2
+    if gr.num_nodes % 2:
+        raise ValueError("nodes come in (read, reverse complement) pairs: N must be even")
+    msg = torch.empty(1 + half, dtype=torch.uint8, device=ctx.device)
+    if ctx.rank == 0:
+        percent = random.randint(hp["mask_frac_low"], hp["mask_frac_high"])
+        msg[0] = percent
+        msg[1:] = torch.rand(half, device=ctx.device) < percent / 100               # train.py:92
+    if not ctx.alone:
+        gdist.broadcast_from(msg, 0, ctx.group)
+    return int(msg[0]) / 100, msg[1:].bool()
+
+
+def _run_partitioned_phase(ctx, model, optimizer, graphs, hp, pos_weight, training, trace, epoch):
+    """_run_epoch_phase in the whole-graph regime, every graph as one step on its destination-range partition -> (mean metrics, steps,
+    seconds spent on plans and runners)."""
+    phase = "train" if training else "valid"
+    device, be, sym = ctx.device, ctx.be, bool(hp["use_symmetry_loss"])
+    first_grads = trace is not None and training and not any(t.get("grads") is not None for t in trace)
+    alpha = float(hp["alpha"]) if sym else 0.0
+    n_trace0 = len(trace) if trace is not None else 0
+    log = torch.zeros((len(graphs), 5), dtype=torch.float64, device=device)
+    plan_seconds = 0.0
+    for i, gr in enumerate(graphs):
+        if training:
+            model.train()
+        fraction, nid, eid, src, dst, n = None, None, None, gr.src, gr.dst, gr.num_nodes
+        if hp["masking"]:
+            fraction, keep = _drawn_mask(ctx, gr, hp)
+            src, dst, nid, eid = features.induced_edge_list(gr.src, gr.dst, keep.repeat_interleave(2))
+            n = int(nid.numel())
+        _synchronize(device)
+        t0 = time.perf_counter()
+        bounds = _partition_bounds(ctx, gr, src, dst, n, epoch, phase)
+        plan_seconds += time.perf_counter() - t0
+        whole = types.SimpleNamespace(nid=torch.arange(n, device=device), eid=torch.arange(int(src.numel()), device=device))
+        ci = be.cluster_inputs([whole], gr.in_deg, gr.out_deg, gr.e, gr.y, outer_nid=nid, outer_eid=eid, need_rev=sym)[0]
+        _synchronize(device)
+        t0 = time.perf_counter()
+        part = _partition_plan(ctx, src, dst, n, bounds)
+        runner = _partition_runner(ctx, model, part, ci)
+        _synchronize(device)
+        plan_seconds += time.perf_counter() - t0
+        if trace is not None:
+            trace.append({"phase": phase, "epoch": epoch, "graph": gr.name, "fraction": fraction, "whole": True,
+                          "nid": (whole.nid if nid is None else nid).cpu(), "eid": (whole.eid if eid is None else eid).cpu(),
+                          "src": src.cpu(), "dst": dst.cpu(), "num_nodes": n, "rank": ctx.rank, "n_own": part.n_own, "n_score": part.n_score})
+        step = runner.train_forward if training else runner.forward
+        org = step().squeeze(-1)
+        rev = step(reverse=True).squeeze(-1) if sym else None
+        loss = _LossAndCounts.apply(org, rev, ci.y, pos_weight, alpha, log[i], be.edge_loss)
+        if trace is not None:
+            trace[-1]["logits"] = org.detach().cpu()
+        if training:
+            optimizer.zero_grad()
+            loss.backward()
+            if first_grads:
+                trace[n_trace0]["grads"] = {k: p.grad.detach().cpu().clone() for k, p in model.named_parameters()}
+                first_grads = False
+            optimizer.step()
+    log = log.cpu()                                                                   # the one copy to the host of the phase
+    if trace is not None:
+        for rec, row in zip(trace[n_trace0:], log.tolist()):
+            rec.update(loss=row[0], tp=int(row[1]), tn=int(row[2]), fp=int(row[3]), fn=int(row[4]))
+    step_metrics = metrics_from_log(log)
+    if not step_metrics:
+        raise ValueError(f"{phase}: no step with edges in this epoch")
+    return average_epoch_metrics(step_metrics), len(step_metrics), plan_seconds
+
+
+def train_partitioned(train_set, valid_set, out=None, hyperparameters=None, overfit=False, dropout=None, seed=None, resume=False, device=None,
+                      models_dir="models", checkpoints_dir="checkpoints", trace=None, model_class=SymGatedGCNModel, group=None, ops=None,
+                      bounds=None):
+    """`train` with every graph on its destination-range partition (gnnome_amd.dist): every rank of an initialised torch.distributed
+    group calls it with the same arguments, every rank returns the same list of epoch records.  The whole-graph regime only
+    (num_nodes_per_cluster >= N for every graph of the datasets); clusters stay on `train`.
+
+    group: the process group (None: the default one).  ops: the backend namespace (hip_backend() by default; with another one a CPU device
+    is accepted).  bounds: a function (src, dst, num_nodes, world) -> range boundaries [0, ..., N] for the plan of each (masked) graph,
+    in place of dist.split_by_incident_edges.
+
+    Rank 0 draws every random decision of the loop - the shuffle of the training graphs, the mask fraction, the keep mask - in the order
+    `train` draws them and broadcasts it, so one seed gives the graph order and the masks of the single-device loop.  The logits and the
+    gradients (summed over ranks) are the same bits on every rank, so the optimizers, the schedulers and the records stay in step.  Only
+    rank 0 writes files; the checkpoint also holds `world` and `rng_states`, the random state of every rank (each rank's own generators
+    draw its dropout rows), and resumes at the same world size bit for bit; at another world size rank 0's state is restored, the others
+    reseed from seed + rank and the first record says "rng": "reseeded".  A refusal is decided on every rank from data all of them hold,
+    before the collectives of the graph concerned ("Training loop on partitions")."""
+    import torch.distributed as tdist
+    from . import dist as gdist
+    from .models import GatedGCNModel
+    hp = hyperparameters_with(hyperparameters)
+    seed = hp["seed"] if seed is None else seed
+    dropout = hp["dropout"] if dropout is None else dropout
+    if not tdist.is_initialized():
+        raise RuntimeError("train_partitioned: every rank of an initialised torch.distributed process group calls it")
+    rank, world = tdist.get_rank(group), tdist.get_world_size(group)
+    if ops is None:
+        be = hip_backend()
+        device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if device.type != "cuda":
+            raise ValueError("the training step runs on the MI355X: device must be a HIP device")
+    else:
+        be = ops
+        device = torch.device(device) if device is not None else torch.device("cpu")
+    if device.type == "cuda":
+        torch.cuda.set_device(device)
+    if hp["use_symmetry_loss"] and not issubclass(model_class, SymGatedGCNModel):
+        raise ValueError(f"use_symmetry_loss=True needs the reversed pass, which only SymGatedGCNModel has on a partition; "
+                         f"{model_class.__name__} trains with use_symmetry_loss=False")
+    set_seed(seed)
+    if out is None:
+        out = datetime.now().strftime("%Y-%b-%d-%H-%M-%S")
+    ds_train = [_Graph(n, g, device, be) for n, g in load_dataset(train_set)]
+    ds_valid = ds_train if overfit else [_Graph(n, g, device, be) for n, g in load_dataset(valid_set)]
+    for gr in ds_train + ([] if overfit else ds_valid):
+        if hp["num_nodes_per_cluster"] < gr.num_nodes:
+            raise ValueError(f"num_nodes_per_cluster={hp['num_nodes_per_cluster']} is smaller than the {gr.num_nodes} nodes of graph {gr.name}: "
+                             "that is the cluster regime, which trainer.train serves; train_partitioned trains on whole graphs")
+    pos_weight = torch.tensor([pos_weight_of([(g.name, g.y) for g in ds_train])], device=device)
+
+    model = model_class(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_ne_features"], hp["num_gnn_layers"],
+                        hp["hidden_edge_scores"], hp["normalization"], dropout=dropout).to(device)
+    optimizer, scheduler = _optimizer_and_scheduler(model, hp)
+    if trace is not None:
+        trace.append({"initial_state": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, "pos_weight": float(pos_weight)})
+    ctx = types.SimpleNamespace(be=be, group=group, rank=rank, world=world, device=device, bounds=bounds, alone=gdist._alone(world),
+                                in_edges_only=isinstance(model, GatedGCNModel))
+    # the runners' own refusals (a model they do not serve, a training step they do not run) surface here, on every rank, before epoch 0
+    model.train()
+    first = ds_train[0]
+    part = _partition_plan(ctx, first.src, first.dst, first.num_nodes,
+                           _partition_bounds(ctx, first, first.src, first.dst, first.num_nodes, None, "train"))
+    whole = types.SimpleNamespace(nid=torch.arange(first.num_nodes, device=device), eid=torch.arange(first.num_edges, device=device))
+    ci = be.cluster_inputs([whole], first.in_deg, first.out_deg, first.e, first.y, need_rev=bool(hp["use_symmetry_loss"]))[0]
+    _partition_runner(ctx, model, part, ci).check_train_step()
+    del part, ci, whole
+
+    model_path, ckpt_path = _run_paths(out, seed, models_dir, checkpoints_dir)
+    start_epoch, loss_train, loss_valid = 0, [], []
+    order = list(range(len(ds_train)))
+    reseeded = False
+    if rank > 0:
+        set_seed(seed + rank)        # the model above is the same on every rank; from here on a rank's generators draw its own dropout rows
+    if resume:
+        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
+        model_path, ckpt_path = _run_paths(out, seed, models_dir, checkpoints_dir, resumed=hp["num_epochs"])
+        start_epoch = _load_checkpoint(ckpt, model, optimizer, scheduler, loss_train, loss_valid)
+        states = ckpt.get("rng_states") if "world" in ckpt else ([ckpt["rng_state"]] if "rng_state" in ckpt else None)   # no `world`: train's
+        if states is not None:
+            order = list(states[0]["train_order"])
+            if len(states) == world:
+                _set_rng_state(states[rank])
+            else:
+                reseeded = True
+                if rank == 0:
+                    _set_rng_state(states[0])
+    log_path = os.path.splitext(ckpt_path)[0] + ".jsonl"
+    if rank == 0:
+        os.makedirs(models_dir, exist_ok=True)
+        os.makedirs(checkpoints_dir, exist_ok=True)
+
+    records = []
+    for epoch in range(start_epoch, hp["num_epochs"]):
+        t0 = time.perf_counter()
+        drawn = torch.zeros(len(order), dtype=torch.int64, device=device)
+        if rank == 0:
+            random.shuffle(order)                                                      # train.py:294
+            drawn.copy_(torch.tensor(order, dtype=torch.int64))
+        if not ctx.alone:
+            gdist.broadcast_from(drawn, 0, group)
+        order = drawn.tolist()
+        train_mean, n_steps, train_plan = _run_partitioned_phase(ctx, model, optimizer, [ds_train[i] for i in order], hp, pos_weight, True,
+                                                                 trace, epoch)
+        loss_train.append(train_mean["loss"])
+        lr = optimizer.param_groups[0]["lr"]
+        rec = {"epoch": epoch, **{f"train/{k}": v for k, v in train_mean.items()}, "train/steps": n_steps, "train/skipped_clusters": 0}
+        valid_plan = 0.0
+        if overfit:
+            saved = len(loss_train) == 1 or loss_train[-1] < min(loss_train[:-1])
+            scheduler.step(train_mean["loss"])
+            best = (min(loss_train), 0.0)
+        else:
+            model.eval()
+            with torch.no_grad():
+                valid_mean, v_steps, valid_plan = _run_partitioned_phase(ctx, model, None, ds_valid, hp, pos_weight, False, trace, epoch)
+            loss_valid.append(valid_mean["loss"])
+            rec.update({f"valid/{k}": v for k, v in valid_mean.items()})
+            rec.update({"valid/steps": v_steps, "valid/skipped_clusters": 0})
+            saved = len(loss_valid) == 1 or loss_valid[-1] < min(loss_valid[:-1])
+            scheduler.step(valid_mean["loss"])
+            best = (min(loss_train), min(loss_valid))
+        if saved:
+            rec["saved"] = True
+        rec["lr"] = lr
+        rec["world"] = world
+        if reseeded:
+            rec["rng"], reseeded = "reseeded", False
+        # the wall times are rank 0's on every rank: the records are equal
+        times = torch.tensor([time.perf_counter() - t0, train_plan, valid_plan], dtype=torch.float64, device=device)
+        states = [_rng_state(order)]
+        if not ctx.alone:
+            states = [None] * world
+            tdist.all_gather_object(states, _rng_state(order), group=group)
+        if rank == 0:
+            if saved:
+                torch.save(model.state_dict(), model_path)
+            ckpt = _checkpoint_dict(epoch, model, optimizer, scheduler, best, states[0])
+            ckpt.update(world=world, rng_states=states)
+            torch.save(ckpt, ckpt_path)
+        if not ctx.alone:
+            gdist.broadcast_from(times, 0, group)     # leaves rank 0 after its writes: the barrier a later read (resume) depends on
+        rec["seconds"], rec["train/plan_seconds"], rec["valid/plan_seconds"] = times.tolist()
+        if rank == 0:
+            with open(log_path, "a") as f:
+                f.write(json.dumps(rec) + "\n")
+        records.append(rec)
+    if not ctx.alone:
+        gdist.broadcast_from(torch.zeros(1, dtype=torch.int64, device=device), 0, group)   # (the last .jsonl line is written)
+    if trace is not None:
+        trace.append({"final_state": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}})
     return records
 
 
@@ -444,12 +751,78 @@ def main(argv=None):
     p.add_argument("--gpu", type=int, default=None, help="index of the GPU to train on")
     p.add_argument("--models-dir", type=str, default="models")
     p.add_argument("--checkpoints-dir", type=str, default="checkpoints")
+    p.add_argument("--gpus", type=int, default=None, help="train on destination-range partitions over this many ranks (train_partitioned)")
+    p.add_argument("--transport", choices=("nccl", "gloo"), default="nccl",
+                   help="nccl: one rank per GPU over RCCL; gloo: host-staged collectives, the ranks share one GPU (plumbing mode)")
     a = p.parse_args(argv)
+    if a.gpus is not None and not 1 <= a.gpus <= MAX_RANKS:
+        p.error(f"--gpus {a.gpus}: between 1 and {MAX_RANKS} ranks")
+    if "WORLD_SIZE" in os.environ and a.gpus is not None:        # under torch.distributed.run: join the group that was set up
+        return _rank_main(int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"]), None, a, int(os.environ.get("LOCAL_RANK", os.environ["RANK"])))
+    if a.gpus is not None and a.gpus > 1:
+        return _launch_ranks(a)
     device = torch.device("cuda", a.gpu if a.gpu is not None else torch.cuda.current_device())
     for rec in train(a.train, a.valid, out=a.name, overfit=a.overfit, dropout=a.dropout, seed=a.seed, resume=a.resume, device=device,
                      models_dir=a.models_dir, checkpoints_dir=a.checkpoints_dir):
         print(json.dumps(rec))
+    return 0
+
+
+MAX_RANKS = 16
+
+
+def _rank_main(rank, world, port, a, local_rank=None):
+    """One rank of `--gpus N`: set the device, join the group, train_partitioned; rank 0 prints the records."""
+    import torch.distributed as tdist
+    if port is not None:
+        os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    local_rank = rank if local_rank is None else local_rank
+    # gloo: host-staged collectives between ranks that share one device (--gpu, default 0); nccl: rank r on GPU r
+    device = torch.device("cuda", (a.gpu if a.gpu is not None else 0) if a.transport == "gloo" else local_rank)
+    torch.cuda.set_device(device)
+    if a.transport == "nccl":
+        tdist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
+    else:
+        tdist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        records = train_partitioned(a.train, a.valid, out=a.name, overfit=a.overfit, dropout=a.dropout, seed=a.seed, resume=a.resume,
+                                    device=device, models_dir=a.models_dir, checkpoints_dir=a.checkpoints_dir)
+        if rank == 0:
+            for rec in records:
+                print(json.dumps(rec), flush=True)
+    finally:
+        tdist.destroy_process_group()
+    return 0
+
+
+def _launch_ranks(a):
+    """`--gpus N` without a launcher: N fresh processes (spawn), started before this one touches the GPU; it only waits.  -> the first
+    non-zero exit status; when one rank fails the others are terminated (they would wait for it in a collective)."""
+    import socket
+    import torch.multiprocessing as mp
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    procs = [ctx.Process(target=_rank_main, args=(r, a.gpus, port, a)) for r in range(a.gpus)]
+    for pr in procs:
+        pr.start()
+    status = 0
+    try:
+        while status == 0 and any(pr.exitcode is None for pr in procs):
+            for pr in procs:
+                pr.join(timeout=0.2)
+                if pr.exitcode not in (None, 0):
+                    status = pr.exitcode
+                    break
+    finally:
+        for pr in procs:
+            if pr.exitcode is None:
+                pr.terminate()
+        for pr in procs:
+            pr.join()
+    return status if status != 0 else next((pr.exitcode for pr in procs if pr.exitcode), 0)
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

@@ -1,0 +1,115 @@
+"""World-size-N worker for tests/test_dist_trainer_gloo.py and tests/test_hip_trainer_partition.py: one rank of trainer.train_partitioned,
+on CPU ranks over gloo with the checker backend (tests/cpu_trainer_ops.py), or on ranks that share the test box's one GPU with the HIP
+kernels as compute (gloo, host-staged; world 1: RCCL with GNNOME_FORCE_COLLECTIVES=1).  A rank saves what the call returned - or the
+exception it raised, as text - so the test compares the ranks; run_ranks gives the whole spawn one deadline."""
+import os
+import sys
+
+import torch
+import torch.distributed as dist
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
+
+
+def odd_bounds(src, dst, num_nodes, world):
+    """dist.split_by_incident_edges with every inner boundary moved to an odd node id: the cut falls between nodes 2r and 2r + 1 of a read."""
+    from gnnome_amd import dist as gdist
+    b = gdist.split_by_incident_edges(src.long(), dst.long(), num_nodes, world)
+    return [0] + [min(x | 1, num_nodes - 1) for x in b[1:-1]] + [num_nodes]
+
+
+def worker(rank, world, port, case, out_dir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    g = torch.load(case, weights_only=False)
+    if g.get("force_collectives"):
+        os.environ["GNNOME_FORCE_COLLECTIVES"] = "1"
+    cuda = g.get("device") == "cuda"
+    if g.get("transport") == "nccl":   # RCCL on device memory: one rank per GPU (the test box has one GPU => world 1)
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        torch.cuda.set_device(rank)
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", rank))
+    else:
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        torch.set_num_threads(1)
+        from gnnome_amd import models, trainer
+        class GatedGCNInEdge(models.GatedGCNModel):
+            training_step = "in_edge"
+
+        def model_class(name):
+            return GatedGCNInEdge if name == "GatedGCNInEdge" else getattr(models, name)
+        kw = dict(g["kwargs"])
+        if cuda:
+            kw["device"] = torch.device("cuda", rank if g.get("transport") == "nccl" else 0)
+        else:
+            import cpu_trainer_ops
+            kw.update(ops=cpu_trainer_ops.BACKEND, device=torch.device("cpu"))
+        if g.get("odd_bounds"):
+            kw["bounds"] = odd_bounds
+        real_rand, calls = torch.rand, [0]
+        if rank > 0:
+            if g.get("peers_never_draw"):
+                def no_rand(*a, **k):
+                    raise AssertionError(f"rank {rank} called torch.rand: the masks are rank 0's")
+                torch.rand = no_rand
+            if g.get("peers_never_write"):
+                def no_save(obj, f, *a, **k):   # (pickling a tensor for a collective saves into a buffer: that is no file)
+                    if isinstance(f, (str, os.PathLike)):
+                        raise AssertionError(f"rank {rank} called torch.save({f}): the files are rank 0's")
+                    return torch.serialization.save(obj, f, *a, **k)
+                torch.save = no_save
+        elif g.get("empty_mask_from_draw") is not None:
+            def one_read(*a, **k):   # from the given draw on, the mask keeps read 0 alone: no rank can own an in-edge
+                calls[0] += 1
+                t = real_rand(*a, **k)
+                if calls[0] > g["empty_mask_from_draw"]:
+                    t.fill_(1.0)
+                    t[0] = 0.0
+                return t
+            torch.rand = one_read
+        out = {"rank": rank, "backend": dist.get_backend(), "results": []}
+        for call in g.get("calls", [{}]):     # one train_partitioned per entry (its keywords, "model": a class name); an error ends the list
+            call = dict(call)
+            res = {"trace": []}
+            out["results"].append(res)
+            try:
+                res["records"] = trainer.train_partitioned(g["train_set"], g["valid_set"], trace=res["trace"],
+                                                           model_class=model_class(call.pop("model", "SymGatedGCNModel")), **dict(kw, **call))
+            except (ValueError, NotImplementedError) as ex:
+                res["error"] = f"{type(ex).__name__}: {ex}"
+                if not g.get("go_on_after_error"):
+                    break
+        torch.save = torch.serialization.save
+        torch.save(out, os.path.join(out_dir, f"rank{rank}.pt"))
+    finally:
+        dist.destroy_process_group()
+
+
+def run_ranks(world, case, tmp_dir, timeout):
+    """Start `world` ranks of `worker` as fresh processes and return what each saved (dist_baseline_worker.run_ranks for this worker): the
+    spawn gets `timeout` seconds, the first rank that fails or overruns ends the others, and the caller's test fails."""
+    import socket
+    import time
+
+    import torch.multiprocessing as mp
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    os.makedirs(tmp_dir, exist_ok=True)
+    path = os.path.join(tmp_dir, "case.pt")
+    torch.save(case, path)
+    ctx = mp.spawn(worker, args=(world, port, path, str(tmp_dir)), nprocs=world, join=False)
+    deadline = time.monotonic() + timeout
+    try:
+        while not ctx.join(timeout=max(0.0, min(1.0, deadline - time.monotonic()))):   # (raises as soon as one rank has failed)
+            if time.monotonic() >= deadline:
+                raise TimeoutError(f"a rank of world {world} was still running after {timeout} s")
+    finally:
+        for p in ctx.processes:
+            if p.is_alive():
+                p.kill()
+            p.join()
+    return [torch.load(os.path.join(tmp_dir, f"rank{r}.pt"), weights_only=False) for r in range(world)]
