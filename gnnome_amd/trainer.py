@@ -25,6 +25,7 @@ Deliberate deviations from the reference:
   * the epoch records are returned and appended as JSON lines next to the checkpoint, in place of wandb.
 """
 import argparse
+import functools
 import json
 import os
 import random
@@ -306,40 +307,57 @@ def _model_step(model, views, x, e):
     return model(views, x, e)
 
 
-def _run_epoch_phase(model, optimizer, graphs, hp, pos_weight, device, training, trace, epoch):
-    phase = "train" if training else "valid"
-    logs, skipped, first_grads = [], 0, trace is not None and training and not any(t.get("grads") is not None for t in trace)
-    alpha = float(hp["alpha"]) if hp["use_symmetry_loss"] else 0.0
-    n_trace0, n_done = len(trace) if trace is not None else 0, 0
-    for gr in graphs:
-        if training:
-            model.train()
-        steps, skip = _graph_steps(gr, hp, device, training, trace, phase, epoch)
-        skipped += skip
-        log = torch.zeros((len(steps), 5), dtype=torch.float64, device=device)
-        for i, (views, ci) in enumerate(steps):
-            org = _model_step(model, views, ci.x, ci.e).squeeze(-1)
-            rev = _model_step(model, views.reversed(), ci.x_rev, ci.e).squeeze(-1) if hp["use_symmetry_loss"] else None
-            loss = _LossAndCounts.apply(org, rev, ci.y, pos_weight, alpha, log[i], ops.edge_loss)
-            if trace is not None:
-                trace[n_trace0 + n_done + i]["logits"] = org.detach().cpu()
-            if training:
-                optimizer.zero_grad()
-                loss.backward()
-                if first_grads:
-                    trace[n_trace0]["grads"] = {k: p.grad.detach().cpu().clone() for k, p in model.named_parameters()}
-                    first_grads = False
-                optimizer.step()
-        logs.append(log)
-        n_done += len(steps)
-    log = torch.cat(logs).cpu() if logs else torch.zeros((0, 5), dtype=torch.float64)   # the one copy to the host of the phase
+def _step(model, optimizer, org, rev, y, pos_weight, alpha, row, edge_loss, rec=None, grads=False):
+    """One step from its logits on: loss and counts into `row` of the device log, then - `optimizer` not None - zero_grad / backward /
+    step.  rec: the step's trace entry (gets the org logits, and with `grads` the gradients before the optimizer step).  Nothing here
+    waits for the device unless a trace is kept."""
+    loss = _LossAndCounts.apply(org, rev, y, pos_weight, alpha, row, edge_loss)
+    if rec is not None:
+        rec["logits"] = org.detach().cpu()
+    if optimizer is not None:
+        optimizer.zero_grad()
+        loss.backward()
+        if grads:
+            rec["grads"] = {k: p.grad.detach().cpu().clone() for k, p in model.named_parameters()}
+        optimizer.step()
+
+
+def _wants_grads(trace, training):
+    """The first training step of a traced run records its gradients."""
+    return trace is not None and training and not any(t.get("grads") is not None for t in trace)
+
+
+def _finish_phase(logs, trace, n_trace0, phase):
+    """The device logs of a phase -> (mean metrics, steps): the one copy to the host of the phase, and its rows into the trace."""
+    log = torch.cat(logs).cpu() if logs else torch.zeros((0, 5), dtype=torch.float64)
     if trace is not None:
         for rec, row in zip(trace[n_trace0:], log.tolist()):
             rec.update(loss=row[0], tp=int(row[1]), tn=int(row[2]), fp=int(row[3]), fn=int(row[4]))
     step_metrics = metrics_from_log(log)
     if not step_metrics:
         raise ValueError(f"{phase}: no step with edges in this epoch")
-    return average_epoch_metrics(step_metrics), len(step_metrics), skipped
+    return average_epoch_metrics(step_metrics), len(step_metrics)
+
+
+def _run_epoch_phase(run, graphs, training, epoch):
+    """One pass over `graphs` on one device, whole graphs or clusters -> (mean metrics, steps, skipped clusters, 0.0: no plan time)."""
+    hp, model, trace, phase = run.hp, run.model, run.trace, "train" if training else "valid"
+    logs, skipped, first_grads = [], 0, _wants_grads(trace, training)
+    n_trace0, n_done = len(trace) if trace is not None else 0, 0
+    for gr in graphs:
+        if training:
+            model.train()
+        steps, skip = _graph_steps(gr, hp, run.device, training, trace, phase, epoch)
+        skipped += skip
+        log = torch.zeros((len(steps), 5), dtype=torch.float64, device=run.device)
+        for i, (views, ci) in enumerate(steps):
+            org = _model_step(model, views, ci.x, ci.e).squeeze(-1)
+            rev = _model_step(model, views.reversed(), ci.x_rev, ci.e).squeeze(-1) if hp["use_symmetry_loss"] else None
+            _step(model, run.optimizer if training else None, org, rev, ci.y, run.pos_weight, run.alpha, log[i], ops.edge_loss,
+                  rec=None if trace is None else trace[n_trace0 + n_done + i], grads=first_grads and n_done + i == 0)
+        logs.append(log)
+        n_done += len(steps)
+    return (*_finish_phase(logs, trace, n_trace0, phase), skipped, 0.0)
 
 
 def _rng_state(train_order):
@@ -355,11 +373,42 @@ def _set_rng_state(st):
         torch.cuda.set_rng_state_all([t.cpu() for t in st["cuda"]])
 
 
-# ---- what train and train_partitioned share ----------------------------------------------------------------------------------
+# ---- the loop: train and train_partitioned are _set_up, _resume, their own restore of the random state, and _run_epochs -------------
+# What differs between them is a phase function (_run_epoch_phase, _run_partitioned_phase) and a description of the ranks (_OneProcess,
+# _RankGroup): who draws the order, who writes, whose random states the checkpoint holds, how the ranks agree on the times.
 
-def _optimizer_and_scheduler(model, hp):
+def _set_up(train_set, valid_set, out, hyperparameters, overfit, dropout, seed, device, models_dir, checkpoints_dir, trace, model_class,
+            be=None):
+    """Everything up to the first epoch that needs no other rank -> the run: hyperparameters, device, seed, datasets, pos_weight, model,
+    optimizer, scheduler.  be: another backend than hip_backend(), which admits a CPU device.  The generators are seeded, then the model
+    draws its parameters; nothing else draws."""
+    hp = hyperparameters_with(hyperparameters)
+    seed = hp["seed"] if seed is None else seed
+    dropout = hp["dropout"] if dropout is None else dropout
+    if device is not None:
+        device = torch.device(device)
+    else:
+        device = torch.device("cuda", torch.cuda.current_device()) if be is None else torch.device("cpu")
+    if be is None and device.type != "cuda":
+        raise ValueError("the training step runs on the MI355X: device must be a HIP device")
+    if device.type == "cuda":
+        torch.cuda.set_device(device)
+    be = be or hip_backend()
+    set_seed(seed)
+    if out is None:
+        out = datetime.now().strftime("%Y-%b-%d-%H-%M-%S")
+    ds_train = [_Graph(n, g, device, be) for n, g in load_dataset(train_set)]
+    ds_valid = ds_train if overfit else [_Graph(n, g, device, be) for n, g in load_dataset(valid_set)]
+    pos_weight = torch.tensor([pos_weight_of([(g.name, g.y) for g in ds_train])], device=device)
+    model = model_class(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_ne_features"], hp["num_gnn_layers"],
+                        hp["hidden_edge_scores"], hp["normalization"], dropout=dropout).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=hp["lr"])
-    return optimizer, ReduceLROnPlateau(optimizer, mode="min", factor=hp["decay"], patience=hp["patience"])
+    scheduler = ReduceLROnPlateau(optimizer, mode="min", factor=hp["decay"], patience=hp["patience"])
+    if trace is not None:
+        trace.append({"initial_state": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, "pos_weight": float(pos_weight)})
+    return types.SimpleNamespace(hp=hp, seed=seed, out=out, overfit=overfit, device=device, be=be, ds_train=ds_train, ds_valid=ds_valid,
+                                 pos_weight=pos_weight, alpha=float(hp["alpha"]) if hp["use_symmetry_loss"] else 0.0, model=model,
+                                 optimizer=optimizer, scheduler=scheduler, trace=trace, models_dir=models_dir, checkpoints_dir=checkpoints_dir)
 
 
 def _run_paths(out, seed, models_dir, checkpoints_dir, resumed=None):
@@ -379,9 +428,86 @@ def _load_checkpoint(ckpt, model, optimizer, scheduler, loss_train, loss_valid):
     return ckpt["epoch"] + 1
 
 
-def _checkpoint_dict(epoch, model, optimizer, scheduler, best, rng_state):
-    return {"epoch": epoch, "model_state_dict": model.state_dict(), "optim_state_dict": optimizer.state_dict(),
-            "loss_train": best[0], "loss_valid": best[1], "scheduler_state_dict": scheduler.state_dict(), "rng_state": rng_state}
+def _resume(run, resume):
+    """The files the run writes, the epoch it starts from and the losses so far, onto `run` -> the checkpoint it resumes from (None: a
+    fresh run), whose random state the caller restores."""
+    run.model_path, run.ckpt_path = _run_paths(run.out, run.seed, run.models_dir, run.checkpoints_dir)
+    run.start_epoch, run.loss_train, run.loss_valid = 0, [], []
+    if not resume:
+        return None
+    ckpt = torch.load(run.ckpt_path, map_location="cpu", weights_only=False)   # load_state_dict moves to the device
+    run.model_path, run.ckpt_path = _run_paths(run.out, run.seed, run.models_dir, run.checkpoints_dir, resumed=run.hp["num_epochs"])
+    run.start_epoch = _load_checkpoint(ckpt, run.model, run.optimizer, run.scheduler, run.loss_train, run.loss_valid)
+    return ckpt
+
+
+class _OneProcess:
+    """The ranks of `train`: one, which draws and writes and has nobody to agree with."""
+    writes = True
+    timed_fields = ("seconds",)
+
+    def shuffled(self, order):
+        random.shuffle(order)                                                          # train.py:294 shuffles the list in place
+        return order
+
+    def record_fields(self):
+        return {}
+
+    def checkpoint_rng(self, order):
+        return {"rng_state": _rng_state(order)}
+
+    def agreed(self, times):
+        return times
+
+
+def _run_epochs(run, ranks, phase, order):
+    """The epochs from run.start_epoch on -> the records.  phase(run, graphs, training, epoch) -> (mean metrics, steps, skipped clusters,
+    plan seconds); ranks: _OneProcess or _RankGroup; order: the order of the training graphs the last epoch left."""
+    hp, model, optimizer, scheduler, loss_train, loss_valid = run.hp, run.model, run.optimizer, run.scheduler, run.loss_train, run.loss_valid
+    log_path = os.path.splitext(run.ckpt_path)[0] + ".jsonl"
+    if ranks.writes:
+        os.makedirs(run.models_dir, exist_ok=True)
+        os.makedirs(run.checkpoints_dir, exist_ok=True)
+    records = []
+    for epoch in range(run.start_epoch, hp["num_epochs"]):
+        t0 = time.perf_counter()
+        order = ranks.shuffled(order)
+        train_mean, n_steps, n_skip, train_plan = phase(run, [run.ds_train[i] for i in order], True, epoch)
+        loss_train.append(train_mean["loss"])
+        lr = optimizer.param_groups[0]["lr"]
+        rec = {"epoch": epoch, **{f"train/{k}": v for k, v in train_mean.items()}, "train/steps": n_steps, "train/skipped_clusters": n_skip}
+        valid_plan = 0.0
+        if not run.overfit:
+            model.eval()
+            with torch.no_grad():
+                valid_mean, v_steps, v_skip, valid_plan = phase(run, run.ds_valid, False, epoch)
+            loss_valid.append(valid_mean["loss"])
+            rec.update({f"valid/{k}": v for k, v in valid_mean.items()})
+            rec.update({"valid/steps": v_steps, "valid/skipped_clusters": v_skip})
+        watched = loss_train if run.overfit else loss_valid
+        saved = len(watched) == 1 or watched[-1] < min(watched[:-1])                   # the first epoch saves (the reference's min([]) raises)
+        scheduler.step(watched[-1])
+        best = (min(loss_train), 0.0 if run.overfit else min(loss_valid))
+        if saved:
+            rec["saved"] = True
+        rec["lr"] = lr
+        rec.update(ranks.record_fields())
+        times = [time.perf_counter() - t0, train_plan, valid_plan]
+        rng = ranks.checkpoint_rng(order)                                              # (every rank: among ranks it is a collective)
+        if ranks.writes:
+            if saved:
+                torch.save(model.state_dict(), run.model_path)
+            # after scheduler.step: the checkpoint's scheduler state is the one the next epoch starts from
+            torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optim_state_dict": optimizer.state_dict(),
+                        "loss_train": best[0], "loss_valid": best[1], "scheduler_state_dict": scheduler.state_dict(), **rng}, run.ckpt_path)
+        # the times are the writer's, and leave it after its writes: the barrier a later read (resume) depends on
+        rec.update(zip(ranks.timed_fields, ranks.agreed(times)))
+        if ranks.writes:
+            with open(log_path, "a") as f:
+                f.write(json.dumps(rec) + "\n")
+        records.append(rec)
+    ranks.agreed([0.0])                                                                # (the last .jsonl line is written)
+    return records
 
 
 def train(train_set, valid_set, out=None, hyperparameters=None, overfit=False, dropout=None, seed=None, resume=False, device=None,
@@ -393,75 +519,13 @@ def train(train_set, valid_set, out=None, hyperparameters=None, overfit=False, d
     SAGEModel (same constructor arguments).  A GatedGCNModel subclass that sets `training_step = "in_edge"` (and, if it wants the doubled
     graph, passes directed=False to the base constructor) trains through `_model_step` like any other model: its own call selects the
     one-direction step (engine_gated.train_forward_in_edge)."""
-    hp = hyperparameters_with(hyperparameters)
-    seed = hp["seed"] if seed is None else seed
-    dropout = hp["dropout"] if dropout is None else dropout
-    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if device.type != "cuda":
-        raise ValueError("the training step runs on the MI355X: device must be a HIP device")
-    torch.cuda.set_device(device)
-    set_seed(seed)
-    if out is None:
-        out = datetime.now().strftime("%Y-%b-%d-%H-%M-%S")
-    ds_train = [_Graph(n, g, device) for n, g in load_dataset(train_set)]
-    ds_valid = ds_train if overfit else [_Graph(n, g, device) for n, g in load_dataset(valid_set)]
-    pos_weight = torch.tensor([pos_weight_of([(g.name, g.y) for g in ds_train])], device=device)
-
-    model = model_class(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_ne_features"], hp["num_gnn_layers"],
-                             hp["hidden_edge_scores"], hp["normalization"], dropout=dropout).to(device)
-    optimizer, scheduler = _optimizer_and_scheduler(model, hp)
-    if trace is not None:
-        trace.append({"initial_state": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, "pos_weight": float(pos_weight)})
-
-    os.makedirs(models_dir, exist_ok=True)
-    os.makedirs(checkpoints_dir, exist_ok=True)
-    model_path, ckpt_path = _run_paths(out, seed, models_dir, checkpoints_dir)
-    start_epoch, loss_train, loss_valid = 0, [], []
-    order = list(range(len(ds_train)))
-    if resume:
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)   # load_state_dict moves to the device
-        model_path, ckpt_path = _run_paths(out, seed, models_dir, checkpoints_dir, resumed=hp["num_epochs"])
-        start_epoch = _load_checkpoint(ckpt, model, optimizer, scheduler, loss_train, loss_valid)
-        if "rng_state" in ckpt:
-            _set_rng_state(ckpt["rng_state"])
-            order = list(ckpt["rng_state"]["train_order"])
-    log_path = os.path.splitext(ckpt_path)[0] + ".jsonl"
-
-    records = []
-    for epoch in range(start_epoch, hp["num_epochs"]):
-        t0 = time.perf_counter()
-        random.shuffle(order)                                                          # train.py:294 shuffles the list in place
-        train_mean, n_steps, n_skip = _run_epoch_phase(model, optimizer, [ds_train[i] for i in order], hp, pos_weight, device, True,
-                                                       trace, epoch)
-        loss_train.append(train_mean["loss"])
-        lr = optimizer.param_groups[0]["lr"]
-        rec = {"epoch": epoch, **{f"train/{k}": v for k, v in train_mean.items()}, "train/steps": n_steps, "train/skipped_clusters": n_skip}
-        if overfit:
-            if len(loss_train) == 1 or loss_train[-1] < min(loss_train[:-1]):     # the first epoch saves (the reference's min([]) raises)
-                torch.save(model.state_dict(), model_path)
-                rec["saved"] = True
-            scheduler.step(train_mean["loss"])
-            best = (min(loss_train), 0.0)
-        else:
-            model.eval()
-            with torch.no_grad():
-                valid_mean, v_steps, v_skip = _run_epoch_phase(model, None, ds_valid, hp, pos_weight, device, False, trace, epoch)
-            loss_valid.append(valid_mean["loss"])
-            rec.update({f"valid/{k}": v for k, v in valid_mean.items()})
-            rec.update({"valid/steps": v_steps, "valid/skipped_clusters": v_skip})
-            if len(loss_valid) == 1 or loss_valid[-1] < min(loss_valid[:-1]):
-                torch.save(model.state_dict(), model_path)
-                rec["saved"] = True
-            scheduler.step(valid_mean["loss"])
-            best = (min(loss_train), min(loss_valid))
-        rec["lr"] = lr
-        rec["seconds"] = time.perf_counter() - t0
-        # after scheduler.step: the checkpoint's scheduler state is the one the next epoch starts from
-        torch.save(_checkpoint_dict(epoch, model, optimizer, scheduler, best, _rng_state(order)), ckpt_path)
-        with open(log_path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        records.append(rec)
-    return records
+    run = _set_up(train_set, valid_set, out, hyperparameters, overfit, dropout, seed, device, models_dir, checkpoints_dir, trace, model_class)
+    ckpt = _resume(run, resume)
+    order = list(range(len(run.ds_train)))
+    if ckpt is not None and "rng_state" in ckpt:
+        _set_rng_state(ckpt["rng_state"])
+        order = list(ckpt["rng_state"]["train_order"])
+    return _run_epochs(run, _OneProcess(), _run_epoch_phase, order)
 
 
 # ---- the loop on destination-range partitions --------------------------------------------------------------------------------
@@ -526,13 +590,12 @@ def _drawn_mask(ctx, gr, hp):
     return int(msg[0]) / 100, msg[1:].bool()
 
 
-def _run_partitioned_phase(ctx, model, optimizer, graphs, hp, pos_weight, training, trace, epoch):
+def _run_partitioned_phase(ctx, run, graphs, training, epoch):
     """_run_epoch_phase in the whole-graph regime, every graph as one step on its destination-range partition -> (mean metrics, steps,
-    seconds spent on plans and runners)."""
-    phase = "train" if training else "valid"
+    0 skipped clusters, seconds spent on plans and runners)."""
+    hp, model, trace, phase = run.hp, run.model, run.trace, "train" if training else "valid"
     device, be, sym = ctx.device, ctx.be, bool(hp["use_symmetry_loss"])
-    first_grads = trace is not None and training and not any(t.get("grads") is not None for t in trace)
-    alpha = float(hp["alpha"]) if sym else 0.0
+    first_grads = _wants_grads(trace, training)
     n_trace0 = len(trace) if trace is not None else 0
     log = torch.zeros((len(graphs), 5), dtype=torch.float64, device=device)
     plan_seconds = 0.0
@@ -560,27 +623,49 @@ def _run_partitioned_phase(ctx, model, optimizer, graphs, hp, pos_weight, traini
             trace.append({"phase": phase, "epoch": epoch, "graph": gr.name, "fraction": fraction, "whole": True,
                           "nid": (whole.nid if nid is None else nid).cpu(), "eid": (whole.eid if eid is None else eid).cpu(),
                           "src": src.cpu(), "dst": dst.cpu(), "num_nodes": n, "rank": ctx.rank, "n_own": part.n_own, "n_score": part.n_score})
-        step = runner.train_forward if training else runner.forward
-        org = step().squeeze(-1)
-        rev = step(reverse=True).squeeze(-1) if sym else None
-        loss = _LossAndCounts.apply(org, rev, ci.y, pos_weight, alpha, log[i], be.edge_loss)
-        if trace is not None:
-            trace[-1]["logits"] = org.detach().cpu()
-        if training:
-            optimizer.zero_grad()
-            loss.backward()
-            if first_grads:
-                trace[n_trace0]["grads"] = {k: p.grad.detach().cpu().clone() for k, p in model.named_parameters()}
-                first_grads = False
-            optimizer.step()
-    log = log.cpu()                                                                   # the one copy to the host of the phase
-    if trace is not None:
-        for rec, row in zip(trace[n_trace0:], log.tolist()):
-            rec.update(loss=row[0], tp=int(row[1]), tn=int(row[2]), fp=int(row[3]), fn=int(row[4]))
-    step_metrics = metrics_from_log(log)
-    if not step_metrics:
-        raise ValueError(f"{phase}: no step with edges in this epoch")
-    return average_epoch_metrics(step_metrics), len(step_metrics), plan_seconds
+        forward = runner.train_forward if training else runner.forward
+        org = forward().squeeze(-1)
+        rev = forward(reverse=True).squeeze(-1) if sym else None
+        _step(model, run.optimizer if training else None, org, rev, ci.y, run.pos_weight, run.alpha, log[i], be.edge_loss,
+              rec=None if trace is None else trace[-1], grads=first_grads and i == 0)
+    return (*_finish_phase([log], trace, n_trace0, phase), 0, plan_seconds)
+
+
+class _RankGroup:
+    """The ranks of `train_partitioned`: rank 0 draws and writes, the checkpoint holds every rank's random state, the times are rank 0's."""
+    timed_fields = ("seconds", "train/plan_seconds", "valid/plan_seconds")
+
+    def __init__(self, ctx, reseeded):
+        self.ctx, self.writes, self.reseeded = ctx, ctx.rank == 0, reseeded
+
+    def _from_rank_0(self, t):
+        from . import dist as gdist
+        if not self.ctx.alone:
+            gdist.broadcast_from(t, 0, self.ctx.group)
+        return t.tolist()
+
+    def shuffled(self, order):
+        drawn = torch.zeros(len(order), dtype=torch.int64, device=self.ctx.device)
+        if self.writes:
+            random.shuffle(order)                                                      # train.py:294
+            drawn.copy_(torch.tensor(order, dtype=torch.int64))
+        return self._from_rank_0(drawn)
+
+    def record_fields(self):
+        """`world`, and in the first record after a resume at another world size "rng": "reseeded"."""
+        fields, self.reseeded = {"world": self.ctx.world, **({"rng": "reseeded"} if self.reseeded else {})}, False
+        return fields
+
+    def checkpoint_rng(self, order):
+        import torch.distributed as tdist
+        states = [_rng_state(order)]
+        if not self.ctx.alone:
+            states = [None] * self.ctx.world
+            tdist.all_gather_object(states, _rng_state(order), group=self.ctx.group)
+        return {"rng_state": states[0], "world": self.ctx.world, "rng_states": states}
+
+    def agreed(self, times):
+        return self._from_rank_0(torch.tensor(times, dtype=torch.float64, device=self.ctx.device))
 
 
 def train_partitioned(train_set, valid_set, out=None, hyperparameters=None, overfit=False, dropout=None, seed=None, resume=False, device=None,
@@ -604,46 +689,24 @@ def train_partitioned(train_set, valid_set, out=None, hyperparameters=None, over
     import torch.distributed as tdist
     from . import dist as gdist
     from .models import GatedGCNModel
-    hp = hyperparameters_with(hyperparameters)
-    seed = hp["seed"] if seed is None else seed
-    dropout = hp["dropout"] if dropout is None else dropout
     if not tdist.is_initialized():
         raise RuntimeError("train_partitioned: every rank of an initialised torch.distributed process group calls it")
     rank, world = tdist.get_rank(group), tdist.get_world_size(group)
-    if ops is None:
-        be = hip_backend()
-        device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if device.type != "cuda":
-            raise ValueError("the training step runs on the MI355X: device must be a HIP device")
-    else:
-        be = ops
-        device = torch.device(device) if device is not None else torch.device("cpu")
-    if device.type == "cuda":
-        torch.cuda.set_device(device)
+    run = _set_up(train_set, valid_set, out, hyperparameters, overfit, dropout, seed, device, models_dir, checkpoints_dir, trace, model_class,
+                  be=ops)
+    hp, model, device, be = run.hp, run.model, run.device, run.be
     if hp["use_symmetry_loss"] and not issubclass(model_class, SymGatedGCNModel):
         raise ValueError(f"use_symmetry_loss=True needs the reversed pass, which only SymGatedGCNModel has on a partition; "
                          f"{model_class.__name__} trains with use_symmetry_loss=False")
-    set_seed(seed)
-    if out is None:
-        out = datetime.now().strftime("%Y-%b-%d-%H-%M-%S")
-    ds_train = [_Graph(n, g, device, be) for n, g in load_dataset(train_set)]
-    ds_valid = ds_train if overfit else [_Graph(n, g, device, be) for n, g in load_dataset(valid_set)]
-    for gr in ds_train + ([] if overfit else ds_valid):
+    for gr in run.ds_train + ([] if overfit else run.ds_valid):
         if hp["num_nodes_per_cluster"] < gr.num_nodes:
             raise ValueError(f"num_nodes_per_cluster={hp['num_nodes_per_cluster']} is smaller than the {gr.num_nodes} nodes of graph {gr.name}: "
                              "that is the cluster regime, which trainer.train serves; train_partitioned trains on whole graphs")
-    pos_weight = torch.tensor([pos_weight_of([(g.name, g.y) for g in ds_train])], device=device)
-
-    model = model_class(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_ne_features"], hp["num_gnn_layers"],
-                        hp["hidden_edge_scores"], hp["normalization"], dropout=dropout).to(device)
-    optimizer, scheduler = _optimizer_and_scheduler(model, hp)
-    if trace is not None:
-        trace.append({"initial_state": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, "pos_weight": float(pos_weight)})
     ctx = types.SimpleNamespace(be=be, group=group, rank=rank, world=world, device=device, bounds=bounds, alone=gdist._alone(world),
                                 in_edges_only=isinstance(model, GatedGCNModel))
     # the runners' own refusals (a model they do not serve, a training step they do not run) surface here, on every rank, before epoch 0
     model.train()
-    first = ds_train[0]
+    first = run.ds_train[0]
     part = _partition_plan(ctx, first.src, first.dst, first.num_nodes,
                            _partition_bounds(ctx, first, first.src, first.dst, first.num_nodes, None, "train"))
     whole = types.SimpleNamespace(nid=torch.arange(first.num_nodes, device=device), eid=torch.arange(first.num_edges, device=device))
@@ -651,87 +714,19 @@ def train_partitioned(train_set, valid_set, out=None, hyperparameters=None, over
     _partition_runner(ctx, model, part, ci).check_train_step()
     del part, ci, whole
 
-    model_path, ckpt_path = _run_paths(out, seed, models_dir, checkpoints_dir)
-    start_epoch, loss_train, loss_valid = 0, [], []
-    order = list(range(len(ds_train)))
-    reseeded = False
     if rank > 0:
-        set_seed(seed + rank)        # the model above is the same on every rank; from here on a rank's generators draw its own dropout rows
-    if resume:
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
-        model_path, ckpt_path = _run_paths(out, seed, models_dir, checkpoints_dir, resumed=hp["num_epochs"])
-        start_epoch = _load_checkpoint(ckpt, model, optimizer, scheduler, loss_train, loss_valid)
+        set_seed(run.seed + rank)    # the model above is the same on every rank; from here on a rank's generators draw its own dropout rows
+    ckpt = _resume(run, resume)
+    order = list(range(len(run.ds_train)))
+    reseeded = False
+    if ckpt is not None:
         states = ckpt.get("rng_states") if "world" in ckpt else ([ckpt["rng_state"]] if "rng_state" in ckpt else None)   # no `world`: train's
         if states is not None:
             order = list(states[0]["train_order"])
-            if len(states) == world:
+            reseeded = len(states) != world
+            if not reseeded or rank == 0:
                 _set_rng_state(states[rank])
-            else:
-                reseeded = True
-                if rank == 0:
-                    _set_rng_state(states[0])
-    log_path = os.path.splitext(ckpt_path)[0] + ".jsonl"
-    if rank == 0:
-        os.makedirs(models_dir, exist_ok=True)
-        os.makedirs(checkpoints_dir, exist_ok=True)
-
-    records = []
-    for epoch in range(start_epoch, hp["num_epochs"]):
-        t0 = time.perf_counter()
-        drawn = torch.zeros(len(order), dtype=torch.int64, device=device)
-        if rank == 0:
-            random.shuffle(order)                                                      # train.py:294
-            drawn.copy_(torch.tensor(order, dtype=torch.int64))
-        if not ctx.alone:
-            gdist.broadcast_from(drawn, 0, group)
-        order = drawn.tolist()
-        train_mean, n_steps, train_plan = _run_partitioned_phase(ctx, model, optimizer, [ds_train[i] for i in order], hp, pos_weight, True,
-                                                                 trace, epoch)
-        loss_train.append(train_mean["loss"])
-        lr = optimizer.param_groups[0]["lr"]
-        rec = {"epoch": epoch, **{f"train/{k}": v for k, v in train_mean.items()}, "train/steps": n_steps, "train/skipped_clusters": 0}
-        valid_plan = 0.0
-        if overfit:
-            saved = len(loss_train) == 1 or loss_train[-1] < min(loss_train[:-1])
-            scheduler.step(train_mean["loss"])
-            best = (min(loss_train), 0.0)
-        else:
-            model.eval()
-            with torch.no_grad():
-                valid_mean, v_steps, valid_plan = _run_partitioned_phase(ctx, model, None, ds_valid, hp, pos_weight, False, trace, epoch)
-            loss_valid.append(valid_mean["loss"])
-            rec.update({f"valid/{k}": v for k, v in valid_mean.items()})
-            rec.update({"valid/steps": v_steps, "valid/skipped_clusters": 0})
-            saved = len(loss_valid) == 1 or loss_valid[-1] < min(loss_valid[:-1])
-            scheduler.step(valid_mean["loss"])
-            best = (min(loss_train), min(loss_valid))
-        if saved:
-            rec["saved"] = True
-        rec["lr"] = lr
-        rec["world"] = world
-        if reseeded:
-            rec["rng"], reseeded = "reseeded", False
-        # the wall times are rank 0's on every rank: the records are equal
-        times = torch.tensor([time.perf_counter() - t0, train_plan, valid_plan], dtype=torch.float64, device=device)
-        states = [_rng_state(order)]
-        if not ctx.alone:
-            states = [None] * world
-            tdist.all_gather_object(states, _rng_state(order), group=group)
-        if rank == 0:
-            if saved:
-                torch.save(model.state_dict(), model_path)
-            ckpt = _checkpoint_dict(epoch, model, optimizer, scheduler, best, states[0])
-            ckpt.update(world=world, rng_states=states)
-            torch.save(ckpt, ckpt_path)
-        if not ctx.alone:
-            gdist.broadcast_from(times, 0, group)     # leaves rank 0 after its writes: the barrier a later read (resume) depends on
-        rec["seconds"], rec["train/plan_seconds"], rec["valid/plan_seconds"] = times.tolist()
-        if rank == 0:
-            with open(log_path, "a") as f:
-                f.write(json.dumps(rec) + "\n")
-        records.append(rec)
-    if not ctx.alone:
-        gdist.broadcast_from(torch.zeros(1, dtype=torch.int64, device=device), 0, group)   # (the last .jsonl line is written)
+    records = _run_epochs(run, _RankGroup(ctx, reseeded), functools.partial(_run_partitioned_phase, ctx), order)
     if trace is not None:
         trace.append({"final_state": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}})
     return records

@@ -1,26 +1,23 @@
 """World-size-N worker for the partitioned GATModel tests: one rank of the default destination-range partition over gloo, with the checker
 backend (tests/cpu_ops_gat.py) or, with device="cuda", the HIP kernels on the one GPU the ranks share (host-staged collectives, as
-tests/dist_baseline_worker.py, whose run_ranks starts the ranks).  One run does everything a test module asks of a (graph, world) pair:
+tests/dist_baseline_worker.py).  One run does everything a test module asks of a (graph, world) pair:
 for every configuration of gat_partition_cases.CONFIGS the eval-mode forward (dropout 0) and one training step - with feat_drop masks
 handed in where dropout > 0 - and the exchanges each of them started."""
+import functools
 import os
 import sys
 
 import torch
-import torch.distributed as dist
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 
+import rank_launch  # noqa: E402
+
 
 def worker(rank, world, port, case, out_dir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    g = torch.load(case, weights_only=False)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        torch.set_num_threads(1)
+    with rank_launch.process_group(rank, world, port, case) as g:
         import torch.nn.functional as F
         import gat_partition_cases as gpc
         from gnnome_amd import dist as gdist
@@ -61,31 +58,6 @@ def worker(rank, world, port, case, out_dir):
                        grads={k: p.grad.cpu() for k, p in m.named_parameters()})
             out["configs"][(directed, dropout)] = res
         torch.save(out, os.path.join(out_dir, f"rank{rank}.pt"))
-    finally:
-        dist.destroy_process_group()
 
 
-def run_ranks(world, case, tmp_dir, timeout):
-    """dist_baseline_worker.run_ranks for this worker: `world` fresh processes under one time limit; the first rank that fails or
-    overruns ends the others and the caller's test fails."""
-    import socket
-    import time
-
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    path = os.path.join(tmp_dir, "case.pt")
-    torch.save(case, path)
-    ctx = mp.spawn(worker, args=(world, port, path, str(tmp_dir)), nprocs=world, join=False)
-    deadline = time.monotonic() + timeout
-    try:
-        while not ctx.join(timeout=max(0.0, min(1.0, deadline - time.monotonic()))):   # (raises as soon as one rank has failed)
-            if time.monotonic() >= deadline:
-                raise TimeoutError(f"a rank of world {world} was still running after {timeout} s")
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-            p.join()
-    return [torch.load(os.path.join(tmp_dir, f"rank{r}.pt"), weights_only=False) for r in range(world)]
+run_ranks = functools.partial(rank_launch.run_ranks, worker)

@@ -2,15 +2,17 @@
 the checker backend (tests/cpu_ops_gated.py) or, with device="cuda", the HIP kernels on the one GPU the ranks share (host-staged
 collectives, as tests/dist_worker.py).  One run does everything a test module asks of a (graph, world) pair: the plan from the whole
 edge list and from slices, the eval-mode forward, and one training step."""
+import functools
 import os
 import sys
 
 import torch
-import torch.distributed as dist
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
+
+import rank_launch  # noqa: E402
 
 PLAN_TENSORS = ("node_gid", "edge_gid", "srt_geid", "send_idx")
 PLAN_VALUES = ("bounds", "n_own", "n_local", "n_score", "send_counts", "recv_counts", "score_pad", "num_edges_global", "in_edges_only")
@@ -18,12 +20,7 @@ VIEW_TENSORS = ("in_ptr", "srt_src", "srt_dst", "srt_eid", "out_ptr", "out_pos",
 
 
 def worker(rank, world, port, case, out_dir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    g = torch.load(case, weights_only=False)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        torch.set_num_threads(1)
+    with rank_launch.process_group(rank, world, port, case) as g:
         import torch.nn.functional as F
         import gated_partition_graphs as gpg
         from gnnome_amd import dist as gdist
@@ -69,31 +66,6 @@ def worker(rank, world, port, case, out_dir):
                     "e_local": int(part.edge_gid.numel()), "send": part.send_counts, "recv": part.recv_counts,
                     "in_degree_local": (part.views.in_ptr[1:] - part.views.in_ptr[:-1]).cpu(), "srt_geid": part.srt_geid.cpu()},
                    os.path.join(out_dir, f"rank{rank}.pt"))
-    finally:
-        dist.destroy_process_group()
 
 
-def run_ranks(world, case, tmp_dir, timeout):
-    """Start `world` ranks of `worker` as fresh processes and return what each saved.  Every process gets `timeout` seconds (they start
-    together, so one deadline serves all); the first rank that fails or overruns ends the others, and the caller's test fails."""
-    import socket
-    import time
-
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    path = os.path.join(tmp_dir, "case.pt")
-    torch.save(case, path)
-    ctx = mp.spawn(worker, args=(world, port, path, str(tmp_dir)), nprocs=world, join=False)
-    deadline = time.monotonic() + timeout
-    try:
-        while not ctx.join(timeout=max(0.0, min(1.0, deadline - time.monotonic()))):   # (raises as soon as one rank has failed)
-            if time.monotonic() >= deadline:
-                raise TimeoutError(f"a rank of world {world} was still running after {timeout} s")
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-            p.join()
-    return [torch.load(os.path.join(tmp_dir, f"rank{r}.pt"), weights_only=False) for r in range(world)]
+run_ranks = functools.partial(rank_launch.run_ranks, worker)

@@ -3,6 +3,7 @@ SymGatedGCNModel on a destination-range partition - eval logits of run_partition
 (train.py:159-170) through PartitionedRunner.train_forward() / train_forward(reverse=True) - on CPU ranks over gloo with the checker
 backend, or on ranks that share the test box's one GPU with the HIP kernels as compute (gloo, host-staged; world 1: RCCL with
 GNNOME_FORCE_COLLECTIVES=1)."""
+import functools
 import os
 import sys
 
@@ -13,22 +14,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 
+import rank_launch  # noqa: E402
+
 
 def worker(rank, world, port, case, out_dir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    g = torch.load(case, weights_only=False)
-    if g.get("force_collectives"):
-        os.environ["GNNOME_FORCE_COLLECTIVES"] = "1"
-    cuda = g.get("device") == "cuda"
-    if g.get("transport") == "nccl":   # RCCL on device memory: one rank per GPU (the test box has one GPU => world 1)
-        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        torch.cuda.set_device(rank)
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", rank))
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        torch.set_num_threads(1)
+    with rank_launch.process_group(rank, world, port, case) as g:
+        cuda = g.get("device") == "cuda"
         import cpu_ops
         import gnnome_amd
         from gnnome_amd import dist as gdist
@@ -73,5 +64,6 @@ def worker(rank, world, port, case, out_dir):
         out["plan_untouched"] = (not part.views.transposed and
                                  edges_before == (part.views.srt_src.data_ptr(), part.views.srt_eid.data_ptr(), part.views.out_pos.data_ptr()))
         torch.save(out, os.path.join(out_dir, f"rank{rank}.pt"))
-    finally:
-        dist.destroy_process_group()
+
+
+run_ranks = functools.partial(rank_launch.run_ranks, worker)

@@ -2,6 +2,7 @@
 on CPU ranks over gloo with the checker backend (tests/cpu_trainer_ops.py), or on ranks that share the test box's one GPU with the HIP
 kernels as compute (gloo, host-staged; world 1: RCCL with GNNOME_FORCE_COLLECTIVES=1).  A rank saves what the call returned - or the
 exception it raised, as text - so the test compares the ranks; run_ranks gives the whole spawn one deadline."""
+import functools
 import os
 import sys
 
@@ -12,6 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 
+import rank_launch  # noqa: E402
+
 
 def odd_bounds(src, dst, num_nodes, world):
     """dist.split_by_incident_edges with every inner boundary moved to an odd node id: the cut falls between nodes 2r and 2r + 1 of a read."""
@@ -21,20 +24,8 @@ def odd_bounds(src, dst, num_nodes, world):
 
 
 def worker(rank, world, port, case, out_dir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    g = torch.load(case, weights_only=False)
-    if g.get("force_collectives"):
-        os.environ["GNNOME_FORCE_COLLECTIVES"] = "1"
-    cuda = g.get("device") == "cuda"
-    if g.get("transport") == "nccl":   # RCCL on device memory: one rank per GPU (the test box has one GPU => world 1)
-        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        torch.cuda.set_device(rank)
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", rank))
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        torch.set_num_threads(1)
+    with rank_launch.process_group(rank, world, port, case) as g:
+        cuda = g.get("device") == "cuda"
         from gnnome_amd import models, trainer
         class GatedGCNInEdge(models.GatedGCNModel):
             training_step = "in_edge"
@@ -84,32 +75,6 @@ def worker(rank, world, port, case, out_dir):
                     break
         torch.save = torch.serialization.save
         torch.save(out, os.path.join(out_dir, f"rank{rank}.pt"))
-    finally:
-        dist.destroy_process_group()
 
 
-def run_ranks(world, case, tmp_dir, timeout):
-    """Start `world` ranks of `worker` as fresh processes and return what each saved (dist_baseline_worker.run_ranks for this worker): the
-    spawn gets `timeout` seconds, the first rank that fails or overruns ends the others, and the caller's test fails."""
-    import socket
-    import time
-
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    os.makedirs(tmp_dir, exist_ok=True)
-    path = os.path.join(tmp_dir, "case.pt")
-    torch.save(case, path)
-    ctx = mp.spawn(worker, args=(world, port, path, str(tmp_dir)), nprocs=world, join=False)
-    deadline = time.monotonic() + timeout
-    try:
-        while not ctx.join(timeout=max(0.0, min(1.0, deadline - time.monotonic()))):   # (raises as soon as one rank has failed)
-            if time.monotonic() >= deadline:
-                raise TimeoutError(f"a rank of world {world} was still running after {timeout} s")
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-            p.join()
-    return [torch.load(os.path.join(tmp_dir, f"rank{r}.pt"), weights_only=False) for r in range(world)]
+run_ranks = functools.partial(rank_launch.run_ranks, worker)

@@ -1,5 +1,6 @@
 """World-size-N worker for tests/test_dist_gloo.py: runs gnnome_amd.dist's partition + halo exchange on CPU
 ranks (gloo) with the checker backend as the per-rank compute, and returns each rank's assembled logits."""
+import functools
 import os
 import sys
 
@@ -10,21 +11,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 
+import rank_launch  # noqa: E402
+
 
 def worker(rank, world, port, case, out_dir):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    g = torch.load(case, weights_only=False)
-    if g.get("force_collectives"):   # one rank that still issues every collective (gnnome_amd.dist.force_collectives)
-        os.environ["GNNOME_FORCE_COLLECTIVES"] = "1"
-    if g.get("transport") == "nccl":   # RCCL on device memory: one rank per GPU (the test box has one GPU => world 1)
-        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        torch.cuda.set_device(rank)
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", rank))
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        torch.set_num_threads(1)
+    with rank_launch.process_group(rank, world, port, case) as g:
         import cpu_ops
         import gnnome_amd
         from gnnome_amd import dist as gdist
@@ -102,5 +93,6 @@ def worker(rank, world, port, case, out_dir):
                     "recv": part.recv_counts, "backend": dist.get_backend(), "score_index": part.score_index is not None,
                     "sliced_equal": part_sliced_equal if g.get("sliced") else None},
                    os.path.join(out_dir, f"rank{rank}.pt"))
-    finally:
-        dist.destroy_process_group()
+
+
+run_ranks = functools.partial(rank_launch.run_ranks, worker)

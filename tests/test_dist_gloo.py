@@ -1,31 +1,19 @@
 """The N>1 path on CPU: destination-range partition, halo plan and per-layer exchange over gloo, with the
 checker backend as compute, must reproduce the single-process oracle on every rank."""
-import os
-import socket
+import functools
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 from conftest import load_golden
-from dist_worker import worker
+from dist_worker import run_ranks
 from gnnome_amd.dist import split_by_incident_edges
 from oracle.symgated_oracle import degree_features
 from gnnome_amd.synth import make_graph, random_state_dict
 from oracle.symgated_oracle import model_from_state_dict
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _run(world, case, tmp_path):
-    path = os.path.join(tmp_path, "case.pt")
-    torch.save(case, path)
-    mp.spawn(worker, args=(world, _free_port(), path, str(tmp_path)), nprocs=world, join=True)
-    return [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False) for r in range(world)]
+_run = functools.partial(run_ranks, timeout=180)   # (world, case, tmp_path) -> what each rank saved
 
 
 @pytest.mark.parametrize("world", [2, 3])

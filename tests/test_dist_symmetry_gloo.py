@@ -2,17 +2,15 @@
 gloo with the checker backend: `rev` logits against the whole-graph host sequence on views.reversed() and the reference golden G4, one
 symmetry step against the oracle's autograd on the unpartitioned graph, a hand graph with the two shapes that only the reversed pass
 exercises, the swapped degree columns of a from_slices plan, and what stays refused.  The bars are tests/test_dist_gloo.py's."""
-import os
-import socket
+import functools
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import cpu_ops
 import gnnome_amd
 from conftest import load_golden
-from dist_symmetry_worker import worker
+from dist_symmetry_worker import run_ranks
 from gnnome_amd import dist as gdist
 from gnnome_amd import engine
 from gnnome_amd.synth import random_state_dict
@@ -21,18 +19,7 @@ from test_train_host import check_grads
 CPU = torch.device("cpu")
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _run(world, case, tmp_path):
-    os.makedirs(tmp_path, exist_ok=True)
-    path = os.path.join(tmp_path, "case.pt")
-    torch.save(case, path)
-    mp.spawn(worker, args=(world, _free_port(), path, str(tmp_path)), nprocs=world, join=True)
-    return [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False) for r in range(world)]
+_run = functools.partial(run_ranks, timeout=180)   # (world, case, tmp_path) -> what each rank saved
 
 
 def _prob_diff(a, b):

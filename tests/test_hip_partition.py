@@ -3,15 +3,13 @@ MI355X, so the ranks are two processes sharing it, and the collectives go over g
 (gnnome_amd.dist._staged) instead of RCCL over xGMI: everything except the transport is the multi-GPU product path -
 partition, halo plan, per-layer exchange, owned-prefix scoring, and for training the cross-rank BatchNorm
 statistics, halo-gradient scatter-add and gradient sum."""
-import os
-import socket
+import functools
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 from conftest import load_golden
-from dist_worker import worker
+from dist_worker import run_ranks
 from gnnome_amd import ops
 from gnnome_amd.synth import random_state_dict
 from test_train_host import check_grads
@@ -19,17 +17,7 @@ from test_train_host import check_grads
 pytestmark = pytest.mark.gpu
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _run(world, case, tmp_path):
-    path = os.path.join(tmp_path, "case.pt")
-    torch.save(case, path)
-    mp.spawn(worker, args=(world, _free_port(), path, str(tmp_path)), nprocs=world, join=True)
-    return [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False) for r in range(world)]
+_run = functools.partial(run_ranks, timeout=240)   # (world, case, tmp_path) -> what each rank saved
 
 
 def test_scatter_add_rows_is_the_transpose_of_gather_rows():

@@ -2,17 +2,15 @@
 with the HIP kernels as compute (the host twin is tests/test_dist_symmetry_gloo.py).  The test box has ONE MI355X: world 1 runs over RCCL
 with GNNOME_FORCE_COLLECTIVES=1, world 2 is two processes sharing the device over gloo with host staging, as in tests/test_hip_partition.py,
 whose bars these are.  Never run on two devices."""
+import functools
 import gc
-import os
-import socket
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import gnnome_amd
 from conftest import load_golden
-from dist_symmetry_worker import worker
+from dist_symmetry_worker import run_ranks
 from gnnome_amd import dist as gdist
 from gnnome_amd import ops
 from gnnome_amd.synth import random_state_dict
@@ -25,17 +23,7 @@ def dev():
     return torch.device("cuda", 0)
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _run(world, case, tmp_path):
-    path = os.path.join(tmp_path, "case.pt")
-    torch.save(case, path)
-    mp.spawn(worker, args=(world, _free_port(), path, str(tmp_path)), nprocs=world, join=True)
-    return [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False) for r in range(world)]
+_run = functools.partial(run_ranks, timeout=240)   # (world, case, tmp_path) -> what each rank saved
 
 
 def _prob_diff(a, b):

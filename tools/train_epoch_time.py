@@ -86,10 +86,7 @@ def main():
         t0 = time.perf_counter()
         org = model(sub.views, ci.x, ci.e).squeeze(-1)
         rev = model(sub.views.reversed(), ci.x_rev, ci.e).squeeze(-1)
-        loss = trainer._LossAndCounts.apply(org, rev, ci.y, pw, hp["alpha"], log[i])
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
+        trainer._step(model, opt, org, rev, ci.y, pw, hp["alpha"], log[i], ops.edge_loss)
         torch.cuda.synchronize()
         step_ts.append(time.perf_counter() - t0)
     res["median_step_ms"] = statistics.median(step_ts[2:] or step_ts) * 1e3
