@@ -676,6 +676,10 @@ static int raw_stats_impl(const float* e_in, void* x_out, int64_t num_edges, int
     GN_REQUIRE(ld_node >= hidden && ld_node % 4 == 0 && ldw >= hidden && ldw % 4 == 0, "edge_gate_raw_stats: bad strides");
     GN_REQUIRE(((uintptr_t)e_in % 16 == 0) && ((uintptr_t)W3 % 16 == 0) && ((uintptr_t)B1h % 16 == 0) && ((uintptr_t)B2h % 16 == 0),
                "edge_gate_raw_stats: 16-byte alignment required");
+    // bf16 storage at hidden <= 128 always runs the bf16x6 edge-tile kernels, which leave kNumCUs * 8 partial rows; under another key 0
+    // gnnome_edge_gate_raw_stats_rows sizes stats_partial for the exact-fp32 kernel (kNumCUs * 1 or 2 rows), and the launch would write past it
+    GN_REQUIRE(!x16 || hidden == 256 || tuning(kTuneGateVariant) == 0 || tuning(kTuneGateVariant) == 8,
+               "edge_gate_raw_stats_x16: bf16 storage is built on the default kernels (gnnome_set_tuning key 0 = 0 or 8), got %d", tuning(kTuneGateVariant));
     hipStream_t s = (hipStream_t)stream;
     if (hidden == 256) {
         GateBfArgs a = {};

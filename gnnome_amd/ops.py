@@ -1416,8 +1416,11 @@ def _partial_sums(partial, H):
 
 
 def can_fuse_gate_moments(e, B1h, B2h, storage=torch.float32):
-    """H in {64, 128, 256}; bf16 storage at 256 (round 4) runs on the fp16x3 kernel only (not under set_tuning(10, 1))."""
+    """H in {64, 128, 256}; bf16 storage at 256 (round 4) runs on the fp16x3 kernel only (not under set_tuning(10, 1)), at 64 / 128 on the
+    default kernels only (set_tuning key 0 = 0 or 8)."""
     widths = (64, 128, 256) if storage == torch.float32 or _TUNING.get(10, 0) == 0 else (64, 128)
+    if storage != torch.float32 and e.shape[1] != 256 and _TUNING.get(0, 0) not in (0, 8):
+        return False   # bf16 storage runs the bf16x6 kernels only: under another key 0 the partial-sum rows are sized for the exact-fp32 kernel
     return (e.shape[1] in widths and e.shape[0] > 0 and B1h.stride(0) % 4 == 0 and B1h.data_ptr() % 16 == 0 and
             B2h.data_ptr() % 16 == 0)
 

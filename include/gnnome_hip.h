@@ -653,7 +653,12 @@ int gnnome_edge_gate_raw_f32(const float* e_in, float* x_out, int64_t num_edges,
  * must not alias e_in.)  Summing the rows of stats_partial (in any
  * FIXED order, e.g. gnnome_colsum2_f32) gives the sums the statistics need without a second pass over x_out.
  * center: any per-column value near the column mean (row 0 of x_out is one) - the shift keeps the second moment
- * free of cancellation. */
+ * free of cancellation.
+ * R depends on the kernel that gnnome_set_tuning key 0 selects at the time of the call: at hidden = 64 / 128, 8 rows per CU (2048) for
+ * the bf16x6 edge-tile kernels (key 0 = 0 or 8) and 2 / 1 rows per CU for the exact-fp32 kernel (every other value); at hidden = 256,
+ * 4 rows per workgroup of the plane form whatever key 0 says.  Ask for R under the key 0 the launch will run with.  The bf16-storage
+ * form (gnnome_edge_gate_raw_stats_x16) exists on the bf16x6 kernels only: at hidden = 64 / 128 under another key 0 it is refused
+ * (GNNOME_EINVAL) - R would be sized for a kernel that does not run. */
 /* x_out == NULL (hidden = 128): the statistics alone - the first pass of the two-pass training forward (round 4): the product is cheap on the
  * matrix cores (fp16x3), a written and re-read [E,H] tensor is not.  The second pass is gnnome_edge_gate_bn_f32 below. */
 int gnnome_edge_gate_raw_stats_rows(int hidden, int* rows_host);
@@ -1115,7 +1120,8 @@ int gnnome_bfs_levels(const int32_t* ptr, const int32_t* adj, int64_t num_nodes,
  * when written, widened exactly when read; every sum, product and statistic is still fp32, and the residual streams e, e', de,
  * h stay fp32 (|e| reaches several hundred with per-layer updates of order one: bf16 there would drop the updates).  Each entry
  * is its _f32 namesake with the marked tensor as uint16_t (bf16 bits), contiguous, 8-byte aligned:
- *   raw_stats: x_out (the statistics are those of the ROUNDED values);  bn_relu_res: x;  agg_edge_bwd_stats, agg_bwd_fused: xe;
+ *   raw_stats: x_out (the statistics are those of the ROUNDED values; hidden = 64 / 128: gnnome_set_tuning key 0 = 0 or 8 only, see
+ *   gnnome_edge_gate_raw_stats_rows);  bn_relu_res: x;  agg_edge_bwd_stats, agg_bwd_fused: xe;
  *   bn_bwd_dgrad: X and dxe (C += dxe W^T uses the unrounded dxe);  segment_sum2: X;  wgrad: A (lda in elements). */
 int gnnome_edge_gate_raw_stats_x16(const float* e_in, uint16_t* x_out, int64_t num_edges, int hidden, const float* B1h, const float* B2h,
                                    int ld_node, const int32_t* srt_src, const int32_t* srt_dst, const float* W3, int ldw,
