@@ -32,6 +32,7 @@ the two lists do ("Symmetry step").  Run over gloo and on r
 All tensor math goes through an `ops` namespace exactly like engine.run_stack: the product passes
 gnnome_amd.ops (HIP); the CPU/gloo tests pass the checker backend to exercise this host logic.
 """
+import functools
 import os
 
 import torch
@@ -698,6 +699,12 @@ class _ScoreViews:
         self.srt_src, self.srt_dst, self.srt_eid = views.srt_src, views.srt_dst, srt_geid
 
 
+def _local_rows(select, whole, local, device):
+    """A runner's input on its device: select(whole) - this rank's rows of the whole graph's table - or `local`, those rows already selected."""
+    rows = select(whole) if local is None else local
+    return rows.to(device=device, dtype=torch.float32).contiguous()
+
+
 class PartitionedRunner:
     """Holds one rank's partition, weights and inputs on its GPU; forward() = one whole-graph scoring pass."""
 
@@ -739,14 +746,11 @@ class PartitionedRunner:
             raise NotImplementedError(f"{type(model).__name__} on a partition runs on the forward orientation of the graph: it takes no x_rev")
         prepared = engine_baselines.Prepared if self.baseline else engine_gated.Prepared if self.gated else engine.Prepared
         self.prep = None if model.training else engine.prepared_for(model, device, prepared)
-        rows = part.local_node_rows(x_global) if x_local is None else x_local
-        self.x = rows.to(device=device, dtype=torch.float32).contiguous()
-        erows = part.local_edge_rows(e_global) if e_local is None else e_local
-        self.e = erows.to(device=device, dtype=torch.float32).contiguous()
+        self.x = _local_rows(part.local_node_rows, x_global, x_local, device)
+        self.e = _local_rows(part.local_edge_rows, e_global, e_local, device)
         self.x_rev = None
         if x_rev_global is not None or x_rev_local is not None:
-            rows = part.local_node_rows(x_rev_global) if x_rev_local is None else x_rev_local
-            self.x_rev = rows.to(device=device, dtype=torch.float32).contiguous()
+            self.x_rev = _local_rows(part.local_node_rows, x_rev_global, x_rev_local, device)
 
     def capture(self, reverse=False):
         """Record the forward as hipGraph segments between the collectives (CapturedPartitionedForward); forward() replays them.
@@ -776,8 +780,8 @@ class PartitionedRunner:
         with torch.no_grad():
             if self.baseline:
                 from . import engine_baselines
-                return engine_baselines.forward_partitioned(self.ops, self.model, self.prep, self.part, self.x, self.e, self.group,
-                                                          split=self.split).unsqueeze(1)
+                run = functools.partial(engine_baselines.run_partitioned, split=self.split)
+                return engine_baselines.forward_partitioned(self.ops, self.model, self.prep, self.part, self.x, self.e, self.group, run).unsqueeze(1)
             return run_partitioned(self.ops, self.prep, self.part, self.x, self.e, self.group).unsqueeze(1)
 
     def check_train_step(self):
@@ -822,10 +826,8 @@ class GATPartitionedRunner:
         engine_gat.check_partition(model, part)
         self.ops, self.part, self.group, self.model = ops, part, group, model
         self.prep = None if model.training else engine.prepared_for(model, device, engine_gat.Prepared)
-        rows = part.local_node_rows(x_global) if x_local is None else x_local
-        self.x = rows.to(device=device, dtype=torch.float32).contiguous()
-        erows = part.local_edge_rows(e_global) if e_local is None else e_local
-        self.e = erows.to(device=device, dtype=torch.float32).contiguous()
+        self.x = _local_rows(part.local_node_rows, x_global, x_local, device)
+        self.e = _local_rows(part.local_edge_rows, e_global, e_local, device)
 
     def capture(self):
         raise NotImplementedError("CapturedPartitionedForward is built for SymGatedGCNModel; a GATModel runs the eager forward()")
@@ -835,11 +837,12 @@ class GATPartitionedRunner:
 
     def forward(self):
         """eval mode: logits[E,1] of one whole-graph scoring pass, complete on every rank."""
-        from . import engine_gat
+        from . import engine_baselines, engine_gat
         if self.prep is None:
             raise RuntimeError("built from a model in train mode: use train_forward()")
         with torch.no_grad():
-            return engine_gat.forward_partitioned(self.ops, self.model, self.prep, self.part, self.x, self.e, self.group).unsqueeze(1)
+            return engine_baselines.forward_partitioned(self.ops, self.model, self.prep, self.part, self.x, self.e, self.group,
+                                                        engine_gat.run_partitioned).unsqueeze(1)
 
     def train_forward(self):
         """train mode: logits[E,1] with autograd history; after loss.backward() every rank holds the whole graph's parameter gradients

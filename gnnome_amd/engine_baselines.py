@@ -28,8 +28,11 @@ gradient bits.  A forward whose logits are not all finite left fp16x3's operand 
 (one host sync per step; `model.range_check = False` drops it); its backward then runs as bf16x6 too.
 
 Several GPUs: the last section of this file - the same two sequences on one rank of a destination-range partition (dist.PartitionedRunner),
-on gnnome_node_neighbour_sum_part_f32 / _bwd_part_f32.
+on gnnome_node_neighbour_sum_part_f32 / _bwd_part_f32, under the same autograd.Function: _BaselineStep is handed where the rows live
+(train.WholeGraph or dist.PartitionShard) and the sequences of that place, here and in engine_gat.
 """
+import contextlib
+
 import torch
 
 from . import engine
@@ -158,10 +161,16 @@ def run_stack(ops, prep, views, x, e_raw, directed=True):
     return logits
 
 
+def bf16x6_forced(ops):
+    """True when the caller has already selected bf16x6 (ops.set_tuning(10, 1)): nothing is left to fall back to, so no forward of this
+    module checks its logits then.  A backend that keeps no record of its tuning (a checker) has no such selection."""
+    return getattr(ops, "_TUNING", {}).get(10, 0) == 1
+
+
 def forward_in_range(ops, prep, views, x, e, xd, ed, directed, check=True, run_stack=run_stack):
     """engine_gated.forward_in_range for these stacks (run_stack: this module's, or engine_gat's): a forward whose logits are not all
     finite left fp16x3's operand range and is run again as bf16x6; checked once per set of inputs."""
-    if ops._TUNING.get(10, 0) == 1:
+    if bf16x6_forced(ops):
         return run_stack(ops, prep, views, xd, ed, directed)
     if prep.force_bf16x6 or engine._same_inputs(prep.range_failed, views, x, e):
         with ops.bf16x6_arithmetic():
@@ -188,30 +197,38 @@ def _conv_weight(conv, kind):
     return torch.cat([conv.fc_self.weight.detach(), conv.fc_neigh.weight.detach()], 1)
 
 
+def live_encoders(model):
+    """The two encoders as ops.encode reads them, from the live parameters -> ((W1, b1, W2, b2) of the node encoder, of the edge encoder)."""
+    return tuple(tuple(t.detach().contiguous() for t in (enc.linear1.weight, enc.linear1.bias, enc.linear2.weight, enc.linear2.bias))
+                 for enc in (model.node_encoder, model.edge_encoder))
+
+
+def live_predictor(pred, H):
+    """The scorer as its kernels read it, from the live parameters -> (W1, W_nodes [2 hs, H] = W1's src block over its dst block,
+    b_nodes = 0 | b1, tail = the five weight arguments of ops.edge_score)."""
+    d = lambda t: t.detach().contiguous()  # noqa: E731
+    W1 = d(pred.W1.weight)
+    W_nodes = torch.cat([W1[:, :H], W1[:, H:2 * H]], 0).contiguous()
+    b_nodes = torch.cat([torch.zeros_like(pred.W1.bias), pred.W1.bias]).detach().contiguous()
+    return W1, W_nodes, b_nodes, (W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1)))
+
+
 def encoders_forward(ops, model, views, x, e_raw):
     """The two encoders on the live parameters -> (h [N,H], e [E,H] in sorted order: what the scorer reads).  Shared with engine_gat's step."""
-    d = lambda t: t.detach().contiguous()  # noqa: E731
-    ne, ee = model.node_encoder, model.edge_encoder
-    h = engine.encode_nodes(ops, views, x, (d(ne.linear1.weight), d(ne.linear1.bias), d(ne.linear2.weight), d(ne.linear2.bias)))
-    e = ops.encode(e_raw, d(ee.linear1.weight), d(ee.linear1.bias), d(ee.linear2.weight), d(ee.linear2.bias), gather=views.srt_eid,
-                   rows=views.num_edges)
+    enc_node, enc_edge = live_encoders(model)
+    h = engine.encode_nodes(ops, views, x, enc_node)
+    e = ops.encode(e_raw, *enc_edge, gather=views.srt_eid, rows=views.num_edges)
     return h, e
 
 
 def score_forward(ops, model, views, h, e):
     """The scorer on the live parameters, keeping z1 -> (logits[E], what score_backward reads).  Shared with engine_gat's step."""
-    d = lambda t: t.detach().contiguous()  # noqa: E731
-    H = h.shape[1]
-    pred = model.predictor
-    hs = pred.W1.out_features
-    W1 = d(pred.W1.weight)
-    W_nodes = torch.cat([W1[:, :H], W1[:, H:2 * H]], 0).contiguous()
-    b_nodes = torch.cat([torch.zeros_like(pred.W1.bias), pred.W1.bias]).detach().contiguous()
+    hs = model.predictor.W1.out_features
+    W1, W_nodes, b_nodes, tail = live_predictor(model.predictor, h.shape[1])
     PQ = ops.linear(h, W_nodes, b_nodes)
     z1 = torch.empty((views.num_edges, hs), dtype=torch.float32, device=h.device)
     logits = torch.empty(views.num_edges, dtype=torch.float32, device=h.device)
-    ops.edge_score(e, PQ[:, :hs], PQ[:, hs:], views, W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)),
-                   d(pred.W3.bias.reshape(-1)), logits, z1_out=z1)
+    ops.edge_score(e, PQ[:, :hs], PQ[:, hs:], views, *tail, logits, z1_out=z1)
     return logits, dict(h=h, e=e, z1=z1, W1=W1, W_nodes=W_nodes)
 
 
@@ -248,15 +265,15 @@ def encoders_backward(ops, model, views, g, dY, de, x, e_raw):
     encoder_bwd(ops, g, de, e_raw, views.srt_eid, views.num_edges, ee.linear1, ee.linear2, "edge_encoder.linear1", "edge_encoder.linear2")
 
 
-def _draw_masks(model, views, x):
-    """One scaled keep-mask per layer, drawn once per step: a forward that is run again as bf16x6 drops the same elements."""
+def draw_masks(model, rows, x):
+    """feat_drop's scaled keep-masks [rows, H], one per layer with p > 0 (SAGEConv, GATConv; GraphConv has none: all None), drawn once
+    per step: a forward that is run again as bf16x6 drops the same elements.  rows: the step's OWNED node rows - on a shard the owner
+    drops its rows before the exchange, so the halo rows arrive dropped."""
     from . import train
-    masks = [None] * len(model.gnn.convs)
-    if model.kind == "sage":
-        H = model.node_encoder.linear2.out_features   # (train.dropout_mask is looked up here, at call time: tests substitute known masks)
-        masks = [train.dropout_mask(views.num_nodes, H, conv.feat_drop.p, x.device) if conv.feat_drop.p > 0 else None
-                 for conv in model.gnn.convs]
-    return masks
+    if model.kind == "gcn":
+        return [None] * len(model.gnn.convs)
+    H = model.node_encoder.linear2.out_features   # (train.dropout_mask is looked up here, at call time: tests substitute known masks)
+    return [train.dropout_mask(rows, H, conv.feat_drop.p, x.device) if conv.feat_drop.p > 0 else None for conv in model.gnn.convs]
 
 
 def _step_forward(ops, model, views, x, e_raw, masks):
@@ -325,22 +342,24 @@ def _step_backward(ops, model, views, x, e_raw, kept, dlogits):
 
 
 class _BaselineStep(torch.autograd.Function):
-    """One training step as ONE autograd node whose inputs are the model's parameters.  `step` = (masks, forward, backward): this
-    module's for GCNModel / SAGEModel, engine_gat's for GATModel - the range fallback, the empty graph and the release of the kept
-    activations are the same for all three."""
+    """One training step of GCNModel / SAGEModel / GATModel as ONE autograd node whose inputs are the model's parameters, on a whole graph
+    (train.WholeGraph) or on one rank of a destination-range partition (dist.PartitionShard).  `sh` says where the rows live: the backend,
+    the owned rows the masks are drawn for, whether the range fallback is decided with the other ranks, how the gradients are summed.
+    `step` = (draw, forward, backward) is the model's kernel sequence for that place (_STEP here and in engine_gat; train_forward_on's
+    for a shard); the range fallback, the empty graph and the release of the kept activations are the same for all of them."""
 
     @staticmethod
-    def forward(ctx, model, views, x, e_raw, names, step, *params):
-        ops = hip_ops
+    def forward(ctx, model, sh, x, e_raw, names, step, *params):
+        ops = sh.ops
         draw, fwd, _ = step
-        masks = draw(model, views, x)
-        bf16x6 = ops._TUNING.get(10, 0) == 1
-        logits, kept = fwd(ops, model, views, x, e_raw, masks)
-        if not bf16x6 and getattr(model, "range_check", True) and not bool(torch.isfinite(logits).all()):
+        masks = draw(model, sh.n_own, x)
+        bf16x6 = bf16x6_forced(ops)
+        logits, kept = fwd(ops, model, sh.views, x, e_raw, masks)
+        if not bf16x6 and getattr(model, "range_check", True) and _any_rank_not_finite(logits, sh.alone, sh.group):
             bf16x6 = True   # fp16x3's operand range did not hold (forward_in_range): the step runs as bf16x6
             with ops.bf16x6_arithmetic():
-                logits, kept = fwd(ops, model, views, x, e_raw, masks)
-        ctx.model, ctx.views, ctx.names, ctx.step, ctx.kept, ctx.inputs, ctx.bf16x6 = model, views, names, step, kept, (x, e_raw), bf16x6
+                logits, kept = fwd(ops, model, sh.views, x, e_raw, masks)
+        ctx.model, ctx.sh, ctx.names, ctx.step, ctx.kept, ctx.inputs, ctx.bf16x6 = model, sh, names, step, kept, (x, e_raw), bf16x6
         return logits.unsqueeze(1)
 
     @staticmethod
@@ -348,26 +367,23 @@ class _BaselineStep(torch.autograd.Function):
         if ctx.kept is None:
             raise RuntimeError("the activations of this training step were released by its first backward(); "
                                "retain_graph=True is not supported - run the forward again")
-        model, views, bwd = ctx.model, ctx.views, ctx.step[2]
-        if views.num_edges == 0:   # nothing was scored: no parameter has a gradient
+        model, sh, bwd = ctx.model, ctx.sh, ctx.step[2]
+        if sh.e_own == 0:   # nothing was scored: no parameter has a gradient (a whole graph only: a shard without scored edges is refused)
             grads = [torch.zeros_like(p) for _, p in model.named_parameters()]
         else:
-            if ctx.bf16x6:
-                with hip_ops.bf16x6_arithmetic():
-                    g = bwd(hip_ops, model, views, *ctx.inputs, ctx.kept, dlogits)
-            else:
-                g = bwd(hip_ops, model, views, *ctx.inputs, ctx.kept, dlogits)
+            with sh.ops.bf16x6_arithmetic() if ctx.bf16x6 else contextlib.nullcontext():
+                g = bwd(sh.ops, model, sh.views, *ctx.inputs, ctx.kept, dlogits)
             grads = [g[n].contiguous() for n in ctx.names]
         ctx.kept = None
-        return (None, None, None, None, None, None) + tuple(grads)
+        return (None, None, None, None, None, None) + tuple(sh.sum_ranks(grads))
 
 
-_STEP = (_draw_masks, _step_forward, _step_backward)
+_STEP = (draw_masks, _step_forward, _step_backward)
 
 
 def run_train_step(model, graph, x, e, step):
     """What train_forward and engine_gat.train_forward share: the refusals, the views, the inputs on the compute device, the step."""
-    from .train import TRAIN_SCORE_HIDDEN
+    from .train import TRAIN_SCORE_HIDDEN, WholeGraph
     device = engine.compute_device(x, e)
     names = [n for n, _ in model.named_parameters()]
     params = [p for _, p in model.named_parameters()]
@@ -380,7 +396,7 @@ def run_train_step(model, graph, x, e, step):
         raise ValueError(f"x has {x.shape[0]} rows for {views.num_nodes} nodes, e has {e.shape[0]} rows for {views.num_edges} edges")
     xd = x.detach().to(device=device, dtype=torch.float32).contiguous()
     ed = e.detach().to(device=device, dtype=torch.float32).contiguous()
-    out = _BaselineStep.apply(model, views, xd, ed, names, step, *params)
+    out = _BaselineStep.apply(model, WholeGraph(views), xd, ed, names, step, *params)
     views.check_range()   # a fresh graph's deferred endpoint check, after the whole forward has been enqueued
     return out
 
@@ -617,28 +633,53 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, directed=None
                        (pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"]))
 
 
-def _any_rank(flag, part, group):
-    """True on every rank when `flag` is True on one: the fp16x3 -> bf16x6 decision must not differ between ranks."""
-    from .dist import _alone, all_reduce_sum
-    if _alone(part.world):
-        return bool(flag)
-    return bool(all_reduce_sum(flag.reshape(1).to(torch.float32), group) > 0)
+def _any_rank_not_finite(logits, alone, group):
+    """True on every rank when the logits of one are not all finite: the fp16x3 -> bf16x6 decision must not differ between ranks.
+    alone (train.WholeGraph, dist._alone): this process's flag, read once; otherwise the all-reduced flag."""
+    from .dist import all_reduce_sum
+    finite = torch.isfinite(logits).all()
+    if alone:
+        return not bool(finite)
+    return bool(all_reduce_sum((~finite).reshape(1).to(torch.float32), group) > 0)
 
 
-def forward_partitioned(ops, model, prep, part, x_local, e_local, group=None, split=None):
-    """forward_in_range on a partition: logits that are not all finite left fp16x3's operand range and the forward is run again as bf16x6 -
-    decided on the all-reduced flag, so every rank takes the same route; checked on every call (no cache: the inputs are the runner's)."""
+def forward_partitioned(ops, model, prep, part, x_local, e_local, group, run):
+    """forward_in_range on a partition, for run = this module's run_partitioned (with its split= bound) or engine_gat's: logits that are
+    not all finite left fp16x3's operand range and the forward is run again as bf16x6 - decided on the all-reduced flag, so every rank
+    takes the same route; checked on every call (no cache: the inputs are the runner's)."""
+    from .dist import _alone
     directed = bool(model.directed)
     if prep.force_bf16x6:
         with ops.bf16x6_arithmetic():
-            return run_partitioned(ops, prep, part, x_local, e_local, group, directed, split)
-    logits = run_partitioned(ops, prep, part, x_local, e_local, group, directed, split)
-    if getattr(ops, "_TUNING", {}).get(10, 0) == 1 or not getattr(model, "range_check", True):
+            return run(ops, prep, part, x_local, e_local, group, directed)
+    logits = run(ops, prep, part, x_local, e_local, group, directed)
+    if bf16x6_forced(ops) or not getattr(model, "range_check", True):
         return logits
-    if not _any_rank(~torch.isfinite(logits).all(), part, group):
+    if not _any_rank_not_finite(logits, _alone(part.world), group):
         return logits
     with ops.bf16x6_arithmetic():
-        return run_partitioned(ops, prep, part, x_local, e_local, group, directed, split)
+        return run(ops, prep, part, x_local, e_local, group, directed)
+
+
+def encoders_backward_on_shard(ops, model, sh, g, dY, de, x, e_raw):
+    """encoders_backward on a shard (models/full_graph.py:63-64): every node row's gradient is complete at its owner, every scored edge's
+    at its scorer."""
+    from .train import encoder_bwd
+    ne, ee = model.node_encoder, model.edge_encoder
+    encoder_bwd(ops, g, dY.contiguous(), x[:sh.n_own], None, sh.n_own, ne.linear1, ne.linear2, "node_encoder.linear1", "node_encoder.linear2")
+    encoder_bwd(ops, g, de, e_raw, sh.views.srt_eid[:sh.e_own], sh.e_own, ee.linear1, ee.linear2, "edge_encoder.linear1", "edge_encoder.linear2")
+
+
+def check_step_on(model, shard, x_local, e_local):
+    """What every train_forward_on refuses once its check_partition has passed -> (names, params) of the model's parameters."""
+    from .train import TRAIN_SCORE_HIDDEN
+    built_width(model.predictor.W1.out_features, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")
+    names, params = zip(*model.named_parameters())
+    if any(p.device != x_local.device for p in params):
+        raise RuntimeError("training needs the model on the compute device: call model.to(device) first")
+    if x_local.shape[0] != shard.n_local or e_local.shape[0] != shard.e_local:
+        raise ValueError(f"x has {x_local.shape[0]} rows for {shard.n_local} local nodes, e has {e_local.shape[0]} rows for {shard.e_local} local edges")
+    return list(names), params
 
 
 def _part_step_forward(ops, model, sh, x, e_raw, masks, split):
@@ -648,10 +689,9 @@ def _part_step_forward(ops, model, sh, x, e_raw, masks, split):
     part, views, n_own, n_local = sh.part, sh.views, sh.n_own, sh.n_local
     kind, both, convs = model.kind, not model.directed, model.gnn.convs
     plan = plan_for(ops, part, model.directed, sh.group)
-    ne, ee = model.node_encoder, model.edge_encoder
-    h = ops.encode(x, d(ne.linear1.weight), d(ne.linear1.bias), d(ne.linear2.weight), d(ne.linear2.bias))
-    e = ops.encode(e_raw, d(ee.linear1.weight), d(ee.linear1.bias), d(ee.linear2.weight), d(ee.linear2.bias), gather=views.srt_eid[:sh.e_own],
-                   rows=sh.e_own)
+    enc_node, enc_edge = live_encoders(model)
+    h = ops.encode(x, *enc_node)
+    e = ops.encode(e_raw, *enc_edge, gather=views.srt_eid[:sh.e_own], rows=sh.e_own)
     H, L = h.shape[1], len(convs)
     new = lambda cols: torch.empty((n_local, cols), dtype=torch.float32, device=h.device)  # noqa: E731
     layers = []
@@ -689,14 +729,9 @@ def _part_step_forward(ops, model, sh, x, e_raw, masks, split):
     if L:
         sh.halo_start(h)
         sh.halo_finish()
-    pred = model.predictor
-    hs = pred.W1.out_features
-    W1 = d(pred.W1.weight)
-    W_nodes = torch.cat([W1[:, :H], W1[:, H:2 * H]], 0).contiguous()
-    b_nodes = torch.cat([torch.zeros_like(pred.W1.bias), pred.W1.bias]).detach().contiguous()
-    z1 = torch.empty((sh.e_own, hs), dtype=torch.float32, device=h.device)
-    logits = _score_part(ops, part, sh.group, e, h, (W_nodes, b_nodes, None),
-                         (W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1))), z1_out=z1)
+    W1, W_nodes, b_nodes, tail = live_predictor(model.predictor, H)
+    z1 = torch.empty((sh.e_own, model.predictor.W1.out_features), dtype=torch.float32, device=h.device)
+    logits = _score_part(ops, part, sh.group, e, h, (W_nodes, b_nodes, None), tail, z1_out=z1)
     return logits, dict(h=h, e=e, z1=z1, W1=W1, W_nodes=W_nodes, layers=layers)
 
 
@@ -705,9 +740,9 @@ def _part_step_backward(ops, model, sh, x, e_raw, kept, dlogits, split):
     rows, then the halo rows of the gradient table are FETCHED (the forward's exchange, on g) and the backward kernel runs over the owned
     rows: every owned row's dY' is complete and has the single-rank run's association.  Only the scorer's node gradient returns partial
     rows to their owners (halo_bwd)."""
-    from .train import encoder_bwd, score_backward_on_shard
+    from .train import score_backward_on_shard
     d = lambda t: t.detach().contiguous()  # noqa: E731
-    part, views, n_own, n_local, e_own = sh.part, sh.views, sh.n_own, sh.n_local, sh.e_own
+    part, n_own, n_local, e_own = sh.part, sh.n_own, sh.n_local, sh.e_own
     kind, both, convs = model.kind, not model.directed, model.gnn.convs
     plan = plan_for(ops, part, model.directed, sh.group)
     pred = model.predictor
@@ -741,63 +776,20 @@ def _part_step_backward(ops, model, sh, x, e_raw, kept, dlogits, split):
                 y=s["T"][:, :H] if i > 0 else None, out=out, rows=rows))
         dY = out
         kept["layers"][i] = s = None
-    # ---- encoders (models/full_graph.py:63-64): every node row's gradient is complete at its owner, every scored edge's at its scorer
-    ne, ee = model.node_encoder, model.edge_encoder
-    encoder_bwd(ops, g, dY.contiguous(), x[:n_own], None, n_own, ne.linear1, ne.linear2, "node_encoder.linear1", "node_encoder.linear2")
-    encoder_bwd(ops, g, de, e_raw, views.srt_eid[:e_own], e_own, ee.linear1, ee.linear2, "edge_encoder.linear1", "edge_encoder.linear2")
+    encoders_backward_on_shard(ops, model, sh, g, dY, de, x, e_raw)
     return g
-
-
-class _PartitionedBaselineStep(torch.autograd.Function):
-    """_BaselineStep on one rank of a destination-range partition (dist.PartitionShard): the same step, the range fallback decided on the
-    all-reduced flag, the parameter gradients summed over ranks once at the end."""
-
-    @staticmethod
-    def forward(ctx, model, sh, x, e_raw, names, split, *params):
-        from . import train
-        ops = sh.ops
-        masks = [None] * len(model.gnn.convs)
-        if model.kind == "sage":   # feat_drop's masks of the OWNED rows (train.dropout_mask is looked up at call time, as _draw_masks does)
-            H = model.node_encoder.linear2.out_features
-            masks = [train.dropout_mask(sh.n_own, H, conv.feat_drop.p, x.device) if conv.feat_drop.p > 0 else None for conv in model.gnn.convs]
-        bf16x6 = getattr(ops, "_TUNING", {}).get(10, 0) == 1
-        logits, kept = _part_step_forward(ops, model, sh, x, e_raw, masks, split)
-        if not bf16x6 and getattr(model, "range_check", True) and _any_rank(~torch.isfinite(logits).all(), sh.part, sh.group):
-            bf16x6 = True
-            with ops.bf16x6_arithmetic():
-                logits, kept = _part_step_forward(ops, model, sh, x, e_raw, masks, split)
-        ctx.model, ctx.sh, ctx.names, ctx.kept, ctx.inputs, ctx.bf16x6, ctx.split = model, sh, names, kept, (x, e_raw), bf16x6, split
-        return logits.unsqueeze(1)
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        if ctx.kept is None:
-            raise RuntimeError("the activations of this training step were released by its first backward(); "
-                               "retain_graph=True is not supported - run the forward again")
-        model, sh = ctx.model, ctx.sh
-        ops = sh.ops
-        if ctx.bf16x6:
-            with ops.bf16x6_arithmetic():
-                g = _part_step_backward(ops, model, sh, *ctx.inputs, ctx.kept, dlogits, ctx.split)
-        else:
-            g = _part_step_backward(ops, model, sh, *ctx.inputs, ctx.kept, dlogits, ctx.split)
-        ctx.kept = None
-        return (None, None, None, None, None, None) + tuple(sh.sum_ranks([g[n].contiguous() for n in ctx.names]))
 
 
 def train_forward_on(model, shard, x_local, e_local, split=None):
     """The training step of GCNModel / SAGEModel over one rank's rows (dist.PartitionShard over the default partition): x_local / e_local
     are the input features of the shard's nodes (owned, then halo) and edges (local edge-id order).  Returns logits[E_global, 1], complete
     on every rank; after backward() every rank holds the whole graph's parameter gradients."""
-    from .train import TRAIN_SCORE_HIDDEN
     if getattr(model, "kind", None) not in KINDS:
         raise TypeError(f"engine_baselines.train_forward_on serves GCNModel and SAGEModel, not {type(model).__name__}")
     check_partition(model, shard.part)
-    built_width(model.predictor.W1.out_features, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")
-    names, params = zip(*model.named_parameters())
-    if any(p.device != x_local.device for p in params):
-        raise RuntimeError("training needs the model on the compute device: call model.to(device) first")
-    if x_local.shape[0] != shard.n_local or e_local.shape[0] != shard.e_local:
-        raise ValueError(f"x has {x_local.shape[0]} rows for {shard.n_local} local nodes, e has {e_local.shape[0]} rows for {shard.e_local} local edges")
+    names, params = check_step_on(model, shard, x_local, e_local)
     split = PARTITION_SPLIT if split is None else bool(split)
-    return _PartitionedBaselineStep.apply(model, shard, x_local, e_local, list(names), split, *params)
+    step = (draw_masks,   # (the shell hands the sequences shard.views; they read the shard itself)
+            lambda ops, model, views, *rest: _part_step_forward(ops, model, shard, *rest, split),
+            lambda ops, model, views, *rest: _part_step_backward(ops, model, shard, *rest, split))
+    return _BaselineStep.apply(model, shard, x_local, e_local, names, step, *params)

@@ -174,14 +174,6 @@ def unfold(conv, dWp):
     return out
 
 
-def _draw_masks(model, views, x):
-    """One scaled keep-mask per layer with p > 0, drawn once per step: a forward that is run again as bf16x6 drops the same elements."""
-    from . import train
-    H = model.node_encoder.linear2.out_features   # (train.dropout_mask is looked up here, at call time: tests substitute known masks)
-    return [train.dropout_mask(views.num_nodes, H, conv.feat_drop.p, x.device) if conv.feat_drop.p > 0 else None
-            for conv in model.gnn.convs]
-
-
 def _step_forward(ops, model, views, x, e_raw, masks):
     """The train-mode forward on sorted-order e -> (logits[E], what the backward reads)."""
     d = lambda t: t.detach().contiguous()  # noqa: E731
@@ -238,7 +230,7 @@ def _step_backward(ops, model, views, x, e_raw, kept, dlogits):
     return g
 
 
-_STEP = (_draw_masks, _step_forward, _step_backward)
+_STEP = (eb.draw_masks, _step_forward, _step_backward)
 
 
 def train_forward(model, graph, x, e):
@@ -328,22 +320,6 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, directed=True
                           (pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"]))
 
 
-def forward_partitioned(ops, model, prep, part, x_local, e_local, group=None):
-    """engine_baselines.forward_partitioned for this stack: logits that are not all finite left fp16x3's operand range and the forward is
-    run again as bf16x6 - decided on the all-reduced flag (eb._any_rank), so every rank takes the same route."""
-    directed = bool(model.directed)
-    if prep.force_bf16x6:
-        with ops.bf16x6_arithmetic():
-            return run_partitioned(ops, prep, part, x_local, e_local, group, directed)
-    logits = run_partitioned(ops, prep, part, x_local, e_local, group, directed)
-    if getattr(ops, "_TUNING", {}).get(10, 0) == 1 or not getattr(model, "range_check", True):
-        return logits
-    if not eb._any_rank(~torch.isfinite(logits).all(), part, group):
-        return logits
-    with ops.bf16x6_arithmetic():
-        return run_partitioned(ops, prep, part, x_local, e_local, group, directed)
-
-
 def _part_step_forward(ops, model, sh, x, e_raw, masks):
     """_step_forward on a shard -> (logits[E_global], what the backward reads).  Kept per layer: h_d and P for the local rows; A, stats
     and the mask for the owned rows."""
@@ -351,10 +327,9 @@ def _part_step_forward(ops, model, sh, x, e_raw, masks):
     part, views, n_own, n_local = sh.part, sh.views, sh.n_own, sh.n_local
     both = not model.directed
     lists = shard_lists(part)
-    ne, ee = model.node_encoder, model.edge_encoder
-    h = ops.encode(x, d(ne.linear1.weight), d(ne.linear1.bias), d(ne.linear2.weight), d(ne.linear2.bias))
-    e = ops.encode(e_raw, d(ee.linear1.weight), d(ee.linear1.bias), d(ee.linear2.weight), d(ee.linear2.bias), gather=views.srt_eid[:sh.e_own],
-                   rows=sh.e_own)
+    enc_node, enc_edge = eb.live_encoders(model)
+    h = ops.encode(x, *enc_node)
+    e = ops.encode(e_raw, *enc_edge, gather=views.srt_eid[:sh.e_own], rows=sh.e_own)
     H = h.shape[1]
     W = HEADS * H
     layers = []
@@ -375,15 +350,9 @@ def _part_step_forward(ops, model, sh, x, e_raw, masks):
     if layers:
         sh.halo_start(h)
         sh.halo_finish()
-    pred = model.predictor
-    hs = pred.W1.out_features
-    W1 = d(pred.W1.weight)
-    W_nodes = torch.cat([W1[:, :H], W1[:, H:2 * H]], 0).contiguous()
-    b_nodes = torch.cat([torch.zeros_like(pred.W1.bias), pred.W1.bias]).detach().contiguous()
-    z1 = torch.empty((sh.e_own, hs), dtype=torch.float32, device=h.device)
-    logits = eb._score_part(ops, part, sh.group, e, h, (W_nodes, b_nodes, None),
-                            (W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1))),
-                            z1_out=z1)
+    W1, W_nodes, b_nodes, tail = eb.live_predictor(model.predictor, H)
+    z1 = torch.empty((sh.e_own, model.predictor.W1.out_features), dtype=torch.float32, device=h.device)
+    logits = eb._score_part(ops, part, sh.group, e, h, (W_nodes, b_nodes, None), tail, z1_out=z1)
     return logits, dict(h=h, e=e, z1=z1, W1=W1, W_nodes=W_nodes, layers=layers)
 
 
@@ -391,9 +360,9 @@ def _part_step_backward(ops, model, sh, x, e_raw, kept, dlogits):
     """_step_backward on a shard -> {parameter name: this rank's share of the gradient}.  Per layer the head mix's backward on the owned
     rows, the exchange of G = dA's halo rows under the destination phase, the exchange of the halo work rows, the source phase, and dWp, dh
     from the owned rows of dP.  Only the scorer's node gradient returns partial rows to their owners (halo_bwd)."""
-    from .train import encoder_bwd, score_backward_on_shard
+    from .train import score_backward_on_shard
     d = lambda t: t.detach().contiguous()  # noqa: E731
-    views, n_own, n_local, e_own = sh.views, sh.n_own, sh.n_local, sh.e_own
+    n_own, n_local, e_own = sh.n_own, sh.n_local, sh.e_own
     both = not model.directed
     lists = shard_lists(sh.part)
     H = kept["h"].shape[1]
@@ -434,57 +403,17 @@ def _part_step_backward(ops, model, sh, x, e_raw, kept, dlogits):
         if i > 0:                          # h_d > 0 exactly where the ReLU passed and the mask kept
             dY = ops.relu_bwd(dY, h_d)
         kept["layers"][i] = s = None
-    ne, ee = model.node_encoder, model.edge_encoder
-    encoder_bwd(ops, g, dY.contiguous(), x[:n_own], None, n_own, ne.linear1, ne.linear2, "node_encoder.linear1", "node_encoder.linear2")
-    encoder_bwd(ops, g, de, e_raw, views.srt_eid[:e_own], e_own, ee.linear1, ee.linear2, "edge_encoder.linear1", "edge_encoder.linear2")
+    eb.encoders_backward_on_shard(ops, model, sh, g, dY, de, x, e_raw)
     return g
-
-
-class _PartitionedGatStep(torch.autograd.Function):
-    """engine_baselines._PartitionedBaselineStep for GATModel: the step on one rank of a destination-range partition, the range fallback
-    decided on the all-reduced flag, the parameter gradients summed over ranks once at the end."""
-
-    @staticmethod
-    def forward(ctx, model, sh, x, e_raw, names, *params):
-        from . import train
-        ops = sh.ops
-        H = model.node_encoder.linear2.out_features   # feat_drop's masks of the OWNED rows (train.dropout_mask is looked up at call time)
-        masks = [train.dropout_mask(sh.n_own, H, conv.feat_drop.p, x.device) if conv.feat_drop.p > 0 else None for conv in model.gnn.convs]
-        bf16x6 = getattr(ops, "_TUNING", {}).get(10, 0) == 1
-        logits, kept = _part_step_forward(ops, model, sh, x, e_raw, masks)
-        if not bf16x6 and getattr(model, "range_check", True) and eb._any_rank(~torch.isfinite(logits).all(), sh.part, sh.group):
-            bf16x6 = True
-            with ops.bf16x6_arithmetic():
-                logits, kept = _part_step_forward(ops, model, sh, x, e_raw, masks)
-        ctx.model, ctx.sh, ctx.names, ctx.kept, ctx.inputs, ctx.bf16x6 = model, sh, names, kept, (x, e_raw), bf16x6
-        return logits.unsqueeze(1)
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        if ctx.kept is None:
-            raise RuntimeError("the activations of this training step were released by its first backward(); "
-                               "retain_graph=True is not supported - run the forward again")
-        model, sh = ctx.model, ctx.sh
-        ops = sh.ops
-        if ctx.bf16x6:
-            with ops.bf16x6_arithmetic():
-                g = _part_step_backward(ops, model, sh, *ctx.inputs, ctx.kept, dlogits)
-        else:
-            g = _part_step_backward(ops, model, sh, *ctx.inputs, ctx.kept, dlogits)
-        ctx.kept = None
-        return (None, None, None, None, None) + tuple(sh.sum_ranks([g[n].contiguous() for n in ctx.names]))
 
 
 def train_forward_on(model, shard, x_local, e_local):
     """The training step of GATModel over one rank's rows (dist.PartitionShard over the default partition): x_local / e_local are the input
     features of the shard's nodes (owned, then halo) and edges (local edge-id order).  Returns logits[E_global, 1], complete on every
     rank; after backward() every rank holds the whole graph's parameter gradients."""
-    from .train import TRAIN_SCORE_HIDDEN
     check_partition(model, shard.part)
-    eb.built_width(model.predictor.W1.out_features, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")
-    names, params = zip(*model.named_parameters())
-    if any(p.device != x_local.device for p in params):
-        raise RuntimeError("training needs the model on the compute device: call model.to(device) first")
-    if x_local.shape[0] != shard.n_local or e_local.shape[0] != shard.e_local:
-        raise ValueError(f"x has {x_local.shape[0]} rows for {shard.n_local} local nodes, e has {e_local.shape[0]} rows for {shard.e_local} local edges")
-    return _PartitionedGatStep.apply(model, shard, x_local, e_local, list(names), *params)
+    names, params = eb.check_step_on(model, shard, x_local, e_local)
+    step = (eb.draw_masks,   # (the shell hands the sequences shard.views; they read the shard itself)
+            lambda ops, model, views, *rest: _part_step_forward(ops, model, shard, *rest),
+            lambda ops, model, views, *rest: _part_step_backward(ops, model, shard, *rest))
+    return eb._BaselineStep.apply(model, shard, x_local, e_local, names, step, *params)

@@ -40,6 +40,7 @@ class WholeGraph:
     (owned nodes first, then halo; owned in-edges first, then the out-edges that end in the halo)."""
 
     world = 1
+    group = None      # no process group
     alone = True      # no collective is issued (a PartitionShard of one rank under GNNOME_FORCE_COLLECTIVES=1 says False; `world` is 1 for
                       # both, and it is `world` that selects the kernels: the two give the same bits)
 
