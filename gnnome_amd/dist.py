@@ -17,7 +17,13 @@ inference.py:388).  This is the north_star's scheme:
     sorted order; ONE all_gather of the pieces (E*4/G bytes each, padded to the largest) and one index_select
     through a map built with the plan put them into global edge-id order (SURVEY.md 8e "Scorer").
 
-GatedGCNModel runs on the in-edge-only form of the partition (engine_gated.py); GCNModel and SAGEModel on the default one, with one
+GatedGCNModel runs on the in-edge-only form of the partition (engine_gated.py) - with directed=False on the in-edge-only partition of the
+DOUBLED edge list (full_graph.py:47-51; from_global(..., in_edges_only=True, doubled=True) over the original edges): the reverse copy of
+edge k, id E + k, lives with the owner of src[k], both copies carry edge k's features (enc_rows), the stack and bn_e's statistics run over
+the 2E rows, and only the copies with ids below E are scored (score_rows), each by the owner of its dst; a rank all of whose in-edges are
+reverse copies scores nothing and still enters every collective.  Run over gloo and on ranks sharing one GPU - never on two devices.
+Still refused for this model on partitions: CapturedPartitionedForward, training_step = "symmetric", bf16 storage and recompute_gate.
+GCNModel and SAGEModel on the default one, with one
 exchange of h and one forward-direction exchange of its gradient per layer and neighbour sums bit-equal to the single-rank run
 (engine_baselines.py, "destination-range partitions"); GATModel on the default one too, through GATPartitionedRunner: one exchange of h
 per layer forward, the halo rows of the projection made locally, and two forward-direction exchanges per layer backward - dA's halo rows
@@ -140,10 +146,17 @@ class PartitionedGraph:
         self.score_pad = 0          # rows of the padded logits piece every rank contributes to the all_gather
         self.score_index = None     # int64 [E_global]: where global edge id k sits in the flattened [world, score_pad] gather
         self._baseline = {}         # directed -> engine_baselines.PartitionPlan (scales of all local rows, lists, interior / boundary rows)
+        # doubled=True: the plan of GatedGCNModel(directed=False), an in-edge-only partition of engine_gated.doubled_edge_list(src, dst)
+        self.doubled = False
+        self.num_edges_original = 0  # E of the caller's edge list; num_edges_global is then 2E, global id E + k the reverse copy of edge k
+        self.enc_rows = None        # int64 [e_local]  the ORIGINAL edge whose features local edge row r carries (doubled_row_maps' enc_gather)
+        self.score_rows = None      # int64 [n_score_original]  ascending sorted positions of the prefix whose global id is < E (score_gather)
+        self.n_score_original = 0   # how many of them: the edges this rank scores; 0 is legal (every owned in-edge a reverse copy)
+        self.scored = None          # _ScoredRows: the views the scorer and its backward read for score_rows
 
     @classmethod
     def from_global(cls, src, dst, num_nodes, rank, world, device, ops=hip_ops, group=None, node_perm=None, in_edges_only=False,
-                    bounds=None):
+                    bounds=None, doubled=False):
         """Build from the full edge list (every rank holds it in this harness, as inference.py holds the
         whole DGLGraph).  The plan is computed on `device` (masks, unique, searchsorted over the E-sized edge list: 0.9 s per
         rank on the host at 10M edges) + one all_to_all of halo requests.
@@ -153,13 +166,21 @@ class PartitionedGraph:
         in global edge-id order within each destination run, so every owned node's sum has the whole graph's association - and as
         halo the distinct non-owned sources; no out-edge of an owned node into another range is kept, so every local edge is scored
         here (n_score = all of them) and halo nodes have empty in-lists.
-        bounds: the range boundaries [0, ..., N] (the same on every rank) instead of split_by_incident_edges's."""
+        bounds: the range boundaries [0, ..., N] (the same on every rank) instead of split_by_incident_edges's.
+        doubled (with in_edges_only=True only): the plan of GatedGCNModel(directed=False), full_graph.py:47-51.  src, dst stay the ORIGINAL
+        E edges; the plan is the in-edge-only one of engine_gated.doubled_edge_list(src, dst) - edge k goes to the owner of dst[k], its
+        reverse copy E + k to the owner of src[k], default bounds are split_by_incident_edges of the doubled list - and records enc_rows,
+        score_rows and n_score_original; local_edge_rows takes the [E, ...] table of the original edges."""
         self = cls()
         self.in_edges_only = bool(in_edges_only)
+        _check_doubled_flag(doubled, in_edges_only)
         src, dst = torch.as_tensor(src).to(device).long(), torch.as_tensor(dst).to(device).long()
         if node_perm is not None:
             self._set_node_perm(node_perm, num_nodes, device)
             src, dst = self.node_perm[src], self.node_perm[dst]
+        if doubled:
+            self.doubled, self.num_edges_original = True, int(src.numel())
+            src, dst = engine_gated.doubled_edge_list(src, dst)
         self.rank, self.world, self.num_edges_global = rank, world, int(src.numel())
         self.bounds = split_by_incident_edges(src, dst, num_nodes, world) if bounds is None else _checked_bounds(bounds, num_nodes, world)
         lo, hi = self.bounds[rank], self.bounds[rank + 1]
@@ -171,16 +192,21 @@ class PartitionedGraph:
 
     @classmethod
     def from_slices(cls, src_slice, dst_slice, num_nodes, rank, world, device, ops=hip_ops, group=None, node_perm=None, in_edges_only=False,
-                    bounds=None):
+                    bounds=None, doubled=False):
         """Build from a rank's SLICE of the edge list: rank r holds the edges with global ids [off_r, off_r + m_r), the slices in
         rank order making up the whole list (a reader that splits its input file G ways; no rank ever holds all E endpoints).
         Degrees are all-reduced ([N] int64) for the range boundaries, then every edge travels once to the owner of its
         destination and, when that is another rank, once to the owner of its source (one all_to_all of (src, dst, id) triples).
         The ids a rank receives arrive ascending - peer blocks in rank order, each ascending - so the local edge order, and with
         it every later array, equals from_global's.  The same route moves edge features: shuffle_edge_rows(e_slice).
-        in_edges_only, bounds: as for from_global; an edge then travels to the owner of its destination only."""
+        in_edges_only, bounds: as for from_global; an edge then travels to the owner of its destination only.
+        doubled: as for from_global, from slices of the ORIGINAL edge list: edge k travels to the owner of dst[k] and its reverse copy, id
+        E + k, to the owner of src[k].  A peer's block then holds ids below and above E, so the received records are put into ascending
+        id order here; shuffle_edge_rows follows.  global_degrees, and with them local_degree_features, stay the ORIGINAL graph's:
+        full_graph.py computes x before add_edges."""
         self = cls()
         self.in_edges_only = bool(in_edges_only)
+        _check_doubled_flag(doubled, in_edges_only)
         src = torch.as_tensor(src_slice).to(device).long()
         dst = torch.as_tensor(dst_slice).to(device).long()
         if node_perm is not None:   # (as from_global: ranges over renumbered nodes; the permutation itself needs the whole graph once)
@@ -197,15 +223,23 @@ class PartitionedGraph:
         if not alone:
             all_reduce_sum(deg, group)
         self.global_degrees = deg        # [2, N] int64 of the WHOLE graph: what inference.py:416-420 z-scores into x
-        self.bounds = split_by_degree(deg[0] + deg[1], num_nodes, world) if bounds is None else _checked_bounds(bounds, num_nodes, world)
+        incident = (deg[0] + deg[1]) * (2 if doubled else 1)   # (the doubled list: every edge counts at both ends twice)
+        self.bounds = split_by_degree(incident, num_nodes, world) if bounds is None else _checked_bounds(bounds, num_nodes, world)
         bt = torch.tensor(self.bounds[1:-1], device=device, dtype=torch.long)
-        owner_d, owner_s = torch.bucketize(dst, bt, right=True), torch.bucketize(src, bt, right=True)
         gid = torch.arange(offset, offset + src.numel(), device=device)
+        slice_row = torch.arange(src.numel(), device=device)      # the slice row whose features a record carries
+        if doubled:
+            self.doubled, self.num_edges_original = True, self.num_edges_global
+            self.num_edges_global *= 2
+            src, dst = engine_gated.doubled_edge_list(src, dst)
+            gid, slice_row = torch.cat([gid, gid + self.num_edges_original]), torch.cat([slice_row, slice_row])
+        owner_d, owner_s = torch.bucketize(dst, bt, right=True), torch.bucketize(src, bt, right=True)
         second = (owner_s != owner_d) if not self.in_edges_only else torch.zeros_like(owner_s, dtype=torch.bool)
         to_rank = torch.cat([owner_d, owner_s[second]])
         which = torch.cat([torch.arange(src.numel(), device=device), torch.nonzero(second).squeeze(1)])
         order = torch.argsort(to_rank * (self.num_edges_global + 1) + gid[which])     # by receiving rank, then by global id
-        self._slice_rows = which[order]                                                # slice row of every record sent
+        sent = which[order]
+        self._slice_rows = slice_row[sent]                                             # slice row of every record sent
         self._slice_send = torch.bincount(to_rank, minlength=world).tolist()
         sc = torch.tensor(self._slice_send, dtype=torch.int64, device=device)
         rc = torch.empty(world, dtype=torch.int64, device=device)
@@ -214,12 +248,16 @@ class PartitionedGraph:
         else:
             all_to_all_rows(rc, sc, None, None, group)
         self._slice_recv = rc.tolist()
-        triples = torch.stack([src, dst, gid], 1)[self._slice_rows].contiguous()
+        triples = torch.stack([src, dst, gid], 1)[sent].contiguous()
         got = torch.empty((sum(self._slice_recv), 3), dtype=torch.int64, device=device)
         if alone:
             got.copy_(triples)
         else:
             all_to_all_rows(got, triples, self._slice_recv, self._slice_send, group)
+        self._slice_sort = None
+        if doubled:   # a peer's block is ascending below E and again above it: one sort puts the whole list into from_global's order
+            self._slice_sort = torch.argsort(got[:, 2])
+            got = got[self._slice_sort]
         self.edge_gid = got[:, 2].contiguous()
         assert self.edge_gid.numel() < 2 or bool((self.edge_gid[1:] > self.edge_gid[:-1]).all()), "edge ids must arrive ascending"
         return self._build(got[:, 0].contiguous(), got[:, 1].contiguous(), device, ops, group)
@@ -237,6 +275,8 @@ class PartitionedGraph:
             out.copy_(packed)
         else:
             all_to_all_rows(out, packed, self._slice_recv, self._slice_send, self._group)
+        if self._slice_sort is not None:
+            out = out[self._slice_sort]
         return out.reshape((out.shape[0],) + tuple(rows_slice.shape[1:]))
 
     def local_degree_features(self, reverse=False):
@@ -276,6 +316,12 @@ class PartitionedGraph:
         assert self.n_score == int(own_d.sum())
         srt_eid = self.views.srt_eid[:self.n_score].long()
         self.srt_geid = self.edge_gid[srt_eid].int()
+        if self.doubled:
+            E = self.num_edges_original
+            self.enc_rows = torch.where(self.edge_gid >= E, self.edge_gid - E, self.edge_gid)
+            self.score_rows = torch.nonzero(self.srt_geid < E).squeeze(1)
+            self.n_score_original = int(self.score_rows.numel())
+            self.scored = _ScoredRows(ops, self.views, self.score_rows, self.srt_geid, self.n_local)
 
         # halo-exchange plan: tell each owner which of its rows I hold as halo
         bounds_t = torch.tensor(self.bounds, device=halo.device)
@@ -302,18 +348,22 @@ class PartitionedGraph:
         the pieces are all-gathered (padded to the largest) and un-permuted with one index_select.  The map from global
         edge id to its slot in the gathered buffer is exchanged here, once."""
         world = self.world
+        # a doubled plan scores the ORIGINAL edges only: score_rows of the prefix, ids below E, every one on the owner of its destination
+        n_scored, ids, total = self.n_score, self.srt_geid, self.num_edges_global
+        if self.doubled:
+            n_scored, ids, total = self.n_score_original, self.srt_geid[self.score_rows], self.num_edges_original
         if _alone(world):
-            self.score_pad, self.score_index = self.n_score, None
+            self.score_pad, self.score_index = n_scored, None
             return
-        counts = all_gather_rows(torch.tensor([self.n_score], dtype=torch.int64, device=device), world, group).view(-1).tolist()
+        counts = all_gather_rows(torch.tensor([n_scored], dtype=torch.int64, device=device), world, group).view(-1).tolist()
         self.score_pad = pad = max(max(counts), 1)
         mine = torch.full((pad,), -1, dtype=torch.int64, device=device)
-        mine[:self.n_score] = self.srt_geid.long()
+        mine[:n_scored] = ids.long()
         every = all_gather_rows(mine, world, group).view(-1)                 # [world * pad] global edge ids, -1 = padding
         slots = torch.nonzero(every >= 0).squeeze(1)
-        index = torch.full((self.num_edges_global,), -1, dtype=torch.int64, device=device)
+        index = torch.full((total,), -1, dtype=torch.int64, device=device)
         index[every[slots]] = slots
-        assert sum(counts) == self.num_edges_global and int(index.min()) >= 0, "every edge must be scored exactly once"
+        assert sum(counts) == total and (total == 0 or int(index.min()) >= 0), "every edge must be scored exactly once"
         self.score_index = index
 
     def assemble_logits(self, piece, group=None):
@@ -337,7 +387,27 @@ class PartitionedGraph:
         return x_global[gid.to(x_global.device)]
 
     def local_edge_rows(self, e_global):
-        return e_global[self.edge_gid.to(e_global.device)]
+        """Rows of this rank's local edges, in local edge-id order.  A doubled plan takes the table of the ORIGINAL edges, [E, ...], and
+        feeds a row to both copies of its edge (enc_rows)."""
+        return e_global[(self.enc_rows if self.doubled else self.edge_gid).to(e_global.device)]
+
+
+def _check_doubled_flag(doubled, in_edges_only):
+    if doubled and not in_edges_only:
+        raise ValueError("doubled=True is the plan of GatedGCNModel(directed=False), a one-direction model: it needs in_edges_only=True")
+
+
+class _ScoredRows:
+    """The rows a doubled plan scores, as the scorer and its backward read them: `rows` (int32, score_rows), `views` - graph views of
+    the scored edges alone over the local nodes, whose sorted order IS rows' order (the sub-list is already sorted by destination and
+    the sort is stable), so their in- / out-lists segment the scorer's rows - and `score_views`, the same with global edge ids."""
+
+    def __init__(self, ops, views, score_rows, srt_geid, n_local):
+        self.rows = score_rows.int()
+        self.views = ops.GraphViews(views.srt_src[score_rows].contiguous(), views.srt_dst[score_rows].contiguous(), n_local)
+        k = int(score_rows.numel())
+        assert torch.equal(self.views.srt_eid.long().cpu(), torch.arange(k)), "the scored rows must keep their order"
+        self.score_views = _ScoreViews(self.views, srt_geid[score_rows].contiguous())
 
 
 def _staged(t, group):
@@ -478,6 +548,13 @@ class PartitionShard:
         self.e_own, self.e_local = part.n_score, part.views.num_edges
         self.n_global, self.e_global = part.bounds[-1], part.num_edges_global
         self.score_views = _ScoreViews(self.views, part.srt_geid)
+        # what the scorer reads: every owned in-edge as it lies, its node gathers transposed over the local lists - or, on a doubled plan,
+        # the score_rows alone (e_scored of them, possibly none) under the views of those edges; e_own / e_global stay the DOUBLED counts,
+        # the rows bn_e's statistics run over
+        self.score_rows, self.seg_views, self.e_scored = None, self.views, self.e_own
+        if part.doubled:
+            self.score_rows, self.seg_views, self.e_scored = part.scored.rows, part.scored.views, part.n_score_original
+            self.score_views = part.scored.score_views
         self._xchg = HaloExchange(part, ops, group)
 
     def halo_start(self, h):
@@ -544,12 +621,27 @@ def _project(ops, lw, h, n_own, xchg):
     return P
 
 
+def check_doubled(gated, directed, part, what):
+    """Model and plan must agree on the doubled edge list of full_graph.py:47-51: GatedGCNModel(directed=False) runs on a doubled plan and
+    nothing else does.  Raised before anything is allocated or exchanged; `what` names a model that is no GatedGCNModel."""
+    doubled = bool(getattr(part, "doubled", False))
+    if gated and not directed and not doubled:
+        raise NotImplementedError("GatedGCNModel with directed=False runs on a partition of the doubled edge list, and this plan is not one: "
+                                  "build it with PartitionedGraph.from_global(src, dst, ..., in_edges_only=True, doubled=True) over the "
+                                  "original edges")
+    if doubled and not gated:
+        raise ValueError(f"a doubled plan (doubled=True) serves GatedGCNModel with directed=False only; got {what}")
+    if doubled and directed:
+        raise ValueError("a doubled plan (doubled=True) serves GatedGCNModel with directed=False only; this model has directed=True and "
+                         "would run the stack on edges it does not have: build the plan with doubled=False")
+
+
 def _check_partition_kind(prep, part):
-    """True for a GatedGCNModel's weights.  The one-direction model runs on the in-edge-only partition, the symmetric model on the one
-    that also keeps the out-edges of the owned nodes: the other combination would silently drop or double terms, so it raises."""
+    """True for a GatedGCNModel's weights.  The one-direction model runs on the in-edge-only partition - the doubled one with
+    directed=False - the symmetric model on the one that also keeps the out-edges of the owned nodes: any other combination would silently
+    drop or double terms, so it raises."""
     gated = isinstance(prep, engine_gated.Prepared)
-    if gated and not prep.directed:
-        raise NotImplementedError("GatedGCNModel with directed=False is not served on partitions (the doubled edge list is not partitioned)")
+    check_doubled(gated, not gated or prep.directed, part, "a SymGatedGCNModel")
     if gated != bool(getattr(part, "in_edges_only", False)):
         raise ValueError("GatedGCNModel runs on PartitionedGraph.from_global(..., in_edges_only=True), SymGatedGCNModel on the default "
                          f"partition; got in_edges_only={getattr(part, 'in_edges_only', False)}")
@@ -565,7 +657,9 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result
     the forward pass's; the column blocks of P change roles (A2 <-> A3, B1 <-> B2, as engine.layer_step does on a whole graph) and the
     scorer's node halves change places (engine.score_step).
     prep = engine_gated.Prepared (a GatedGCNModel): engine_gated's eval sequence per layer - the [n_local,4H] projection, the same gate,
-    gnnome_node_aggregate_in_f32 over the owned rows - on an in-edge-only partition (PartitionedGraph.from_global(..., in_edges_only=True))."""
+    gnnome_node_aggregate_in_f32 over the owned rows - on an in-edge-only partition (PartitionedGraph.from_global(..., in_edges_only=True)).
+    With directed=False the plan is the doubled one (doubled=True): the same sequence over the local rows of the doubled list, the scorer
+    over part.score_rows alone, logits[E] at the ORIGINAL edge ids."""
     from . import engine_baselines
     if isinstance(prep, engine_baselines.Prepared):   # GCNModel / SAGEModel: engine_baselines' sequence on the default partition
         if reverse:
@@ -602,18 +696,24 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result
     xchg.finish()
     PQ = ops.linear(h, pw["W_nodes"], pw["b_nodes"], planes=pw.get("planes"))
     Ps, Qd = (PQ[:, hs:], PQ[:, :hs]) if reverse else (PQ[:, :hs], PQ[:, hs:])   # x[src'] | x[dst'] = x[dst] | x[src]; b1 enters once either way
-    score_views = _ScoreViews(views, part.srt_geid)
+    score_views, n_score, n_logits = _ScoreViews(views, part.srt_geid), part.n_score, part.num_edges_global
+    if part.doubled:
+        # the ORIGINAL graph is scored (full_graph.py:51): the rows of the prefix with ids below E, gathered as run_stack gathers
+        # score_gather, under views of those edges alone; a rank whose in-edges are all reverse copies scores nothing
+        score_views, n_score, n_logits = part.scored.score_views, part.n_score_original, part.num_edges_original
+        if n_score > 0:
+            e = ops.gather_rows(e, part.scored.rows)
     if _alone(part.world) or not reduce_result:
         # scatter straight to GLOBAL edge ids: a GraphViews-like shim whose srt_eid is the global map
-        logits = (torch.zeros if part.world > 1 else torch.empty)(part.num_edges_global, dtype=torch.float32, device=h.device)
-        if part.n_score > 0:
+        logits = (torch.zeros if part.world > 1 else torch.empty)(n_logits, dtype=torch.float32, device=h.device)
+        if n_score > 0:
             ops.edge_score(e, Ps, Qd, score_views, pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"], logits,
-                           num_edges=part.n_score)
+                           num_edges=n_score)
         return logits
     piece = torch.empty(part.score_pad, dtype=torch.float32, device=h.device)
-    if part.n_score > 0:
+    if n_score > 0:
         ops.edge_score(e, Ps, Qd, score_views, pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"], piece,
-                       num_edges=part.n_score, scatter_to_edge_id=False)
+                       num_edges=n_score, scatter_to_edge_id=False)
     return part.assemble_logits(piece, group)
 
 
@@ -724,6 +824,8 @@ class PartitionedRunner:
         kind = getattr(model, "kind", None)             # GCNModel "gcn", SAGEModel "sage", GATModel "gat" (engine_baselines.py, engine_gat.py)
         self.baseline = kind in engine_baselines.KINDS
         self.gated = isinstance(model, GatedGCNModel)   # (engine_gated.py): the in-edge-only partition, its own kernel sequences
+        if not self.gated:
+            check_doubled(False, True, part, f"a {type(model).__name__}")
         if kind == "gat":
             raise NotImplementedError("GATModel is not served on partitions by PartitionedRunner: its backward makes a second exchange per "
                                       "layer and it takes no split= - use dist.GATPartitionedRunner (same inputs, same forward() / "
@@ -734,8 +836,7 @@ class PartitionedRunner:
         if self.baseline:
             engine_baselines.check_partition(model, part)
         elif self.gated:
-            if not model.directed:
-                raise NotImplementedError("GatedGCNModel with directed=False is not served on partitions (the doubled edge list is not partitioned)")
+            check_doubled(True, bool(model.directed), part, None)
             if not part.in_edges_only:
                 raise ValueError("GatedGCNModel runs on an in-edge-only partition: PartitionedGraph.from_global(..., in_edges_only=True)")
         elif part.in_edges_only:
@@ -823,6 +924,7 @@ class GATPartitionedRunner:
         """x_global / e_global, or x_local / e_local already selected: as for PartitionedRunner.  Every refusal is raised before anything
         is allocated on the device."""
         from . import engine_gat
+        check_doubled(False, True, part, f"a {type(model).__name__}")
         engine_gat.check_partition(model, part)
         self.ops, self.part, self.group, self.model = ops, part, group, model
         self.prep = None if model.training else engine.prepared_for(model, device, engine_gat.Prepared)

@@ -22,8 +22,14 @@ fifth projection block are computed on zeros.  That is the default (`GatedGCNMod
 `training_step = "in_edge"` selects the step of this model's own (train_forward_in_edge, below): a [N,4H] projection, the train-form
 gate, gnnome_node_aggregate_in_raw_f32 forward and gnnome_node_aggregate_in_bwd_f32 backward (csrc/node_aggregate_in_bwd.hip) - no
 A_3, no out-edge half, no Tb / Ub tables - and directed=False on the doubled edge list.  The same step runs one rank's rows of an
-in-edge-only destination-range partition (train_forward_in_edge_on over dist.PartitionShard; directed=True) on the partition forms
+in-edge-only destination-range partition (train_forward_in_edge_on over dist.PartitionShard) on the partition forms
 gnnome_node_aggregate_in_raw_part_f32 / gnnome_node_aggregate_in_bwd_part_f32; eval mode on a partition is dist.run_partitioned.
+
+directed=False on a partition: the doubled graph is again a one-direction problem, so its plan is the in-edge-only partition of the doubled
+edge list (dist.PartitionedGraph.from_global(..., in_edges_only=True, doubled=True)); the partition forms above serve it unchanged.  The
+plan's enc_rows / score_rows are the per-rank counterparts of doubled_row_maps' enc_gather / score_gather: the scorer gathers the
+score_rows and runs under views of those edges alone, as run_stack does with score_gather on a whole graph.  Not served on a partition:
+the captured forward, training_step = "symmetric", bf16 storage and recompute_gate.
 """
 import torch
 import torch.nn.functional as F
@@ -84,7 +90,7 @@ class Prepared:
 
         check_arithmetic(model)
         self.device = device
-        self.directed = bool(getattr(model, "directed", True))   # (dist.run_partitioned refuses directed=False up front)
+        self.directed = bool(getattr(model, "directed", True))   # (dist.run_partitioned: directed=False on a doubled plan only, checked up front)
         self.hidden = built_width(model.node_encoder.linear2.out_features)
         self.enc_node = tuple(dev(t) for t in (model.node_encoder.linear1.weight, model.node_encoder.linear1.bias,
                                                model.node_encoder.linear2.weight, model.node_encoder.linear2.bias))
@@ -385,18 +391,21 @@ class _StepGraph:
 
     @classmethod
     def on_shard(cls, shard):
-        """One rank's rows of an in-edge-only destination-range partition (dist.PartitionShard; directed=True): the stack runs on the
-        local views, every local edge is an owned in-edge and is scored here, into this rank's piece of the logits."""
+        """One rank's rows of an in-edge-only destination-range partition (dist.PartitionShard): the stack runs on the local views, every
+        local edge is an owned in-edge.  directed=True: each is scored here, into this rank's piece of the logits.  directed=False (a doubled
+        plan): the local rows are this rank's share of the 2E doubled ones, e_local already carries every row's original features
+        (PartitionedGraph.enc_rows), and the scorer reads the shard's score_rows - the copies with ids below E, possibly none - under the
+        views of those edges alone."""
         self = object.__new__(cls)
-        self.sh, self.enc_gather, self.score_gather = shard, shard.views.srt_eid, None
-        self.score_views, self.seg_views, self.num_scored = shard.score_views, shard.views, shard.e_own
+        self.sh, self.enc_gather, self.score_gather = shard, shard.views.srt_eid, shard.score_rows
+        self.score_views, self.seg_views, self.num_scored = shard.score_views, shard.seg_views, shard.e_scored
         return self
 
 
 class _InEdgeStep(torch.autograd.Function):
     """One training step of GatedGCNModel (gated_gcn_full.py:182-230 in train mode, full_graph.py:42-53) as ONE autograd node whose inputs
     are the model's parameters - train._TrainStep's shape on the one-direction kernels.  fp32 storage.  A single process (train.WholeGraph),
-    or one rank of an in-edge-only destination-range partition (dist.PartitionShard, directed=True): n_own owned rows first, halo rows of h
+    or one rank of an in-edge-only destination-range partition (dist.PartitionShard; directed=False: of the doubled list): n_own owned rows first, halo rows of h
     refreshed before every projection, BatchNorm statistics over the owned rows merged across ranks, the halo rows of dh - which carry this
     rank's PARTIAL gradients, as do the halo rows of dA2h / dB1h - returned to their owners once per layer, parameter gradients summed over ranks.
     The single-process case issues exactly the calls it issued before shards were served."""
@@ -481,8 +490,8 @@ class _InEdgeStep(torch.autograd.Function):
             sh.halo_finish()
         PQ = ops.linear(h, W_nodes, b_nodes)
         # directed=False: the ORIGINAL graph is scored with the rows of the first E edge ids (full_graph.py:51)
-        e_sc = e if sg.score_gather is None else ops.gather_rows(e, sg.score_gather)
-        E = sg.num_scored
+        E = sg.num_scored   # (0 on a rank of a doubled plan whose in-edges are all reverse copies: it scores nothing and gathers with the others)
+        e_sc = e if sg.score_gather is None else ops.gather_rows(e, sg.score_gather) if E > 0 else e[:0]
         z1 = torch.empty((E, hs), dtype=torch.float32, device=h.device)
         w_tail = (W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1)))
         if sh.alone:
@@ -490,7 +499,8 @@ class _InEdgeStep(torch.autograd.Function):
             ops.edge_score(e_sc, PQ[:, :hs], PQ[:, hs:], sg.score_views, *w_tail, logits, num_edges=E, z1_out=z1)
         else:   # one contiguous piece per rank in sorted order; finish_logits all-gathers and un-permutes them
             piece = torch.empty(sh.part.score_pad, dtype=torch.float32, device=h.device)
-            ops.edge_score(e_sc, PQ[:, :hs], PQ[:, hs:], sg.score_views, *w_tail, piece, num_edges=E, scatter_to_edge_id=False, z1_out=z1)
+            if E > 0:
+                ops.edge_score(e_sc, PQ[:, :hs], PQ[:, hs:], sg.score_views, *w_tail, piece, num_edges=E, scatter_to_edge_id=False, z1_out=z1)
             logits = sh.finish_logits(piece)
         ctx.model, ctx.sg, ctx.names, ctx.saved = model, sg, names, saved
         ctx.tail = dict(h=h, e_sc=e_sc, z1=z1, W1=W1, W_nodes=W_nodes, x=x, e_raw=e_raw)
@@ -520,24 +530,32 @@ class _InEdgeStep(torch.autograd.Function):
         pred = model.predictor
         hs = pred.W1.out_features
         dl = dlogits.reshape(-1).contiguous().float()
-        dz1, dz2, u = ops.score_tail_bwd(tail["z1"], dl, sv, d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)))
-        g["predictor.W2.weight"] = ops.wgrad(dz2, tail["z1"])
-        g["predictor.W2.bias"] = ops.colsum2(dz2)[0]
-        g["predictor.W3.weight"] = ops.colsum2(u)[0].reshape(1, 32)
-        g["predictor.W3.bias"] = (dl if sh.alone else dl[sv.srt_eid.long()]).sum().reshape(1)   # (a shard: the edges scored here)
-        W1 = tail["W1"]
-        de = ops.linear(dz1, W1[:, 2 * H:].t().contiguous(), None)       # d e_final of the scored rows
-        gW1e = ops.wgrad(dz1, tail["e_sc"])
-        seg = sg.seg_views
-        d_ps = ops.segment_sum(dz1, seg.out_ptr, seg.out_pos, n)         # gathered by srt_src in the forward
-        d_qd = ops.segment_sum(dz1, seg.in_ptr, None, n)                 # gathered by srt_dst
-        dPQ = torch.cat([d_ps, d_qd], 1)
-        g["predictor.W1.bias"] = ops.colsum2(d_qd)[0]
-        gWn = ops.wgrad(dPQ, tail["h"])                                  # [2hs, H]
-        g["predictor.W1.weight"] = torch.cat([gWn[:hs], gWn[hs:], gW1e], 1)
-        dh = ops.linear(dPQ, tail["W_nodes"].t().contiguous(), None)     # [N,H]
-        if sg.score_gather is not None:   # directed=False: the scorer's de goes back to the rows it read, the reverse copies get none
-            de = ops.scatter_add_rows(de, sg.score_gather, torch.zeros((E2, H), dtype=torch.float32, device=dev))
+        if sg.num_scored == 0:
+            # a rank of a doubled plan that scored nothing: its share of the predictor's gradients, of de and of dh is zero; the layers
+            # below still run, for the gradients that reach its rows through the peers' halo rows of dh
+            for k, p in pred.named_parameters():
+                g["predictor." + k] = torch.zeros_like(p)
+            de = torch.zeros((E2, H), dtype=torch.float32, device=dev)
+            dh = torch.zeros((n, H), dtype=torch.float32, device=dev)
+        else:
+            dz1, dz2, u = ops.score_tail_bwd(tail["z1"], dl, sv, d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)))
+            g["predictor.W2.weight"] = ops.wgrad(dz2, tail["z1"])
+            g["predictor.W2.bias"] = ops.colsum2(dz2)[0]
+            g["predictor.W3.weight"] = ops.colsum2(u)[0].reshape(1, 32)
+            g["predictor.W3.bias"] = (dl if sh.alone else dl[sv.srt_eid.long()]).sum().reshape(1)   # (a shard: the edges scored here)
+            W1 = tail["W1"]
+            de = ops.linear(dz1, W1[:, 2 * H:].t().contiguous(), None)       # d e_final of the scored rows
+            gW1e = ops.wgrad(dz1, tail["e_sc"])
+            seg = sg.seg_views
+            d_ps = ops.segment_sum(dz1, seg.out_ptr, seg.out_pos, n)         # gathered by srt_src in the forward
+            d_qd = ops.segment_sum(dz1, seg.in_ptr, None, n)                 # gathered by srt_dst
+            dPQ = torch.cat([d_ps, d_qd], 1)
+            g["predictor.W1.bias"] = ops.colsum2(d_qd)[0]
+            gWn = ops.wgrad(dPQ, tail["h"])                                  # [2hs, H]
+            g["predictor.W1.weight"] = torch.cat([gWn[:hs], gWn[hs:], gW1e], 1)
+            dh = ops.linear(dPQ, tail["W_nodes"].t().contiguous(), None)     # [N,H]
+            if sg.score_gather is not None:   # directed=False: the scorer's de goes back to the rows it read, the reverse copies get none
+                de = ops.scatter_add_rows(de, sg.score_gather, torch.zeros((E2, H), dtype=torch.float32, device=dev))
 
         # ---- layers, last to first (gated_gcn_full.py:182-230)
         if saved:
@@ -641,10 +659,14 @@ def train_forward_in_edge_on(model, shard, x_local, e_local):
     """The one-direction step over one rank's rows of an in-edge-only destination-range partition (dist.PartitionShard over
     PartitionedGraph.from_global(..., in_edges_only=True)); x_local / e_local: the input features of the shard's nodes (owned, then halo)
     and edges (local edge-id order).  Returns logits[E_global, 1], complete on every rank; after backward() every rank holds the whole
-    graph's parameter gradients.  directed=True and training_step="in_edge" only (dist.PartitionedRunner.train_forward checks both)."""
+    graph's parameter gradients.  training_step="in_edge" only (dist.PartitionedRunner.train_forward checks it).  directed=False runs on a
+    doubled plan (PartitionedGraph.from_global(..., in_edges_only=True, doubled=True)): the logits are [E, 1] over the ORIGINAL edge ids,
+    e_local the plan's local_edge_rows of the original features; bn_e's statistics run over the 2E rows (the ranks' local rows sum to
+    them through combine_stats), one momentum update per layer; the edge encoder's weight gradient sums both copies' de, each copy on
+    the rank that owns it (sum_ranks)."""
+    from .dist import check_doubled
     _check_in_edge_step(model)
-    if not model.directed:
-        raise NotImplementedError("GatedGCNModel with directed=False is not served on partitions (the doubled edge list is not partitioned)")
+    check_doubled(True, bool(model.directed), shard.part, None)
     if not getattr(shard.part, "in_edges_only", False):
         raise ValueError("GatedGCNModel runs on an in-edge-only partition: build it with PartitionedGraph.from_global(..., in_edges_only=True)")
     names, params = zip(*model.named_parameters())

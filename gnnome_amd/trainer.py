@@ -545,7 +545,12 @@ def _partition_bounds(ctx, gr, src, dst, num_nodes, epoch, phase):
     """The range boundaries of one (masked) graph's plan, or the collective refusal: decided from the edge list every rank holds, before the
     first collective of the plan, so every rank raises the same ValueError and none is left waiting for a peer."""
     bounds = None if ctx.bounds is None else ctx.bounds(src, dst, num_nodes, ctx.world)
-    bounds, nodes, in_edges = _ranks_that_would_be_empty(src, dst, num_nodes, ctx.world, bounds, ctx.in_edges_only)
+    if ctx.doubled:   # the plan is cut over the doubled edge list: a rank's in-edges are the edges INCIDENT to its nodes, counted there
+        from . import engine_gated
+        plan_src, plan_dst = engine_gated.doubled_edge_list(src, dst)
+    else:
+        plan_src, plan_dst = src, dst
+    bounds, nodes, in_edges = _ranks_that_would_be_empty(plan_src, plan_dst, num_nodes, ctx.world, bounds, ctx.in_edges_only)
     for r in range(ctx.world):
         if nodes[r] == 0 or in_edges[r] == 0:
             when = "before epoch 0" if epoch is None else f"{phase} phase of epoch {epoch}"
@@ -558,7 +563,7 @@ def _partition_bounds(ctx, gr, src, dst, num_nodes, epoch, phase):
 def _partition_plan(ctx, src, dst, num_nodes, bounds):
     from . import dist as gdist
     return gdist.PartitionedGraph.from_global(src, dst, num_nodes, ctx.rank, ctx.world, ctx.device, ops=ctx.be.kernels, group=ctx.group,
-                                              in_edges_only=ctx.in_edges_only, bounds=bounds)
+                                              in_edges_only=ctx.in_edges_only, bounds=bounds, doubled=ctx.doubled)
 
 
 def _partition_runner(ctx, model, part, ci):
@@ -679,6 +684,9 @@ def train_partitioned(train_set, valid_set, out=None, hyperparameters=None, over
     is accepted).  bounds: a function (src, dst, num_nodes, world) -> range boundaries [0, ..., N] for the plan of each (masked) graph,
     in place of dist.split_by_incident_edges.
 
+    A GatedGCNModel subclass whose constructor sets directed=False (with training_step = "in_edge") trains on the doubled plan of each graph
+    (PartitionedGraph.from_global(..., in_edges_only=True, doubled=True), full_graph.py:47-51); `bounds` still receives the original edges.
+
     Rank 0 draws every random decision of the loop - the shuffle of the training graphs, the mask fraction, the keep mask - in the order
     `train` draws them and broadcasts it, so one seed gives the graph order and the masks of the single-device loop.  The logits and the
     gradients (summed over ranks) are the same bits on every rank, so the optimizers, the schedulers and the records stay in step.  Only
@@ -703,7 +711,8 @@ def train_partitioned(train_set, valid_set, out=None, hyperparameters=None, over
             raise ValueError(f"num_nodes_per_cluster={hp['num_nodes_per_cluster']} is smaller than the {gr.num_nodes} nodes of graph {gr.name}: "
                              "that is the cluster regime, which trainer.train serves; train_partitioned trains on whole graphs")
     ctx = types.SimpleNamespace(be=be, group=group, rank=rank, world=world, device=device, bounds=bounds, alone=gdist._alone(world),
-                                in_edges_only=isinstance(model, GatedGCNModel))
+                                in_edges_only=isinstance(model, GatedGCNModel),
+                                doubled=isinstance(model, GatedGCNModel) and not model.directed)   # full_graph.py:47-51: the doubled plan
     # the runners' own refusals (a model they do not serve, a training step they do not run) surface here, on every rank, before epoch 0
     model.train()
     first = run.ds_train[0]
