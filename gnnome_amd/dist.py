@@ -17,6 +17,10 @@ inference.py:388).  This is the north_star's scheme:
     sorted order; ONE all_gather of the pieces (E*4/G bytes each, padded to the largest) and one index_select
     through a map built with the plan put them into global edge-id order (SURVEY.md 8e "Scorer").
 
+Every sequence on a partition - eval or training step, whichever model - reads what its rank scores from part.scored (ScoredRows: the rows,
+the views that segment them, the score views, count and total), ends in engine.score_tail (PartitionedGraph.logits_finish says how: alone,
+or padded piece + assembly) and makes its node projection with engine.project_rows; what a partition refuses is check_shard's to say.
+
 GatedGCNModel runs on the in-edge-only form of the partition (engine_gated.py) - with directed=False on the in-edge-only partition of the
 DOUBLED edge list (full_graph.py:47-51; from_global(..., in_edges_only=True, doubled=True) over the original edges): the reverse copy of
 edge k, id E + k, lives with the owner of src[k], both copies carry edge k's features (enc_rows), the stack and bn_e's statistics run over
@@ -152,7 +156,7 @@ class PartitionedGraph:
         self.enc_rows = None        # int64 [e_local]  the ORIGINAL edge whose features local edge row r carries (doubled_row_maps' enc_gather)
         self.score_rows = None      # int64 [n_score_original]  ascending sorted positions of the prefix whose global id is < E (score_gather)
         self.n_score_original = 0   # how many of them: the edges this rank scores; 0 is legal (every owned in-edge a reverse copy)
-        self.scored = None          # _ScoredRows: the views the scorer and its backward read for score_rows
+        self.scored = None          # ScoredRows: what this rank scores, as the scorer, its backward and the assembly read it - every plan has one
 
     @classmethod
     def from_global(cls, src, dst, num_nodes, rank, world, device, ops=hip_ops, group=None, node_perm=None, in_edges_only=False,
@@ -316,12 +320,17 @@ class PartitionedGraph:
         assert self.n_score == int(own_d.sum())
         srt_eid = self.views.srt_eid[:self.n_score].long()
         self.srt_geid = self.edge_gid[srt_eid].int()
+        self.scored = ScoredRows(None, self.views, self.srt_geid, self.num_edges_global)   # the sorted prefix as it lies
         if self.doubled:
+            # the ORIGINAL graph is scored (full_graph.py:51): the rows of the prefix with ids below E, every one on the owner of its destination
             E = self.num_edges_original
             self.enc_rows = torch.where(self.edge_gid >= E, self.edge_gid - E, self.edge_gid)
-            self.score_rows = torch.nonzero(self.srt_geid < E).squeeze(1)
-            self.n_score_original = int(self.score_rows.numel())
-            self.scored = _ScoredRows(ops, self.views, self.score_rows, self.srt_geid, self.n_local)
+            self.score_rows = rows = torch.nonzero(self.srt_geid < E).squeeze(1)
+            self.n_score_original = int(rows.numel())
+            # views of the scored edges alone over the local nodes: the sub-list is already sorted by destination and the sort is stable
+            seg = ops.GraphViews(self.views.srt_src[rows].contiguous(), self.views.srt_dst[rows].contiguous(), self.n_local)
+            assert torch.equal(seg.srt_eid.long().cpu(), torch.arange(self.n_score_original)), "the scored rows must keep their order"
+            self.scored = ScoredRows(rows.int(), seg, self.srt_geid[rows].contiguous(), E)
 
         # halo-exchange plan: tell each owner which of its rows I hold as halo
         bounds_t = torch.tensor(self.bounds, device=halo.device)
@@ -348,10 +357,7 @@ class PartitionedGraph:
         the pieces are all-gathered (padded to the largest) and un-permuted with one index_select.  The map from global
         edge id to its slot in the gathered buffer is exchanged here, once."""
         world = self.world
-        # a doubled plan scores the ORIGINAL edges only: score_rows of the prefix, ids below E, every one on the owner of its destination
-        n_scored, ids, total = self.n_score, self.srt_geid, self.num_edges_global
-        if self.doubled:
-            n_scored, ids, total = self.n_score_original, self.srt_geid[self.score_rows], self.num_edges_original
+        n_scored, ids, total = self.scored.count, self.scored.score_views.srt_eid, self.scored.total
         if _alone(world):
             self.score_pad, self.score_index = n_scored, None
             return
@@ -373,6 +379,13 @@ class PartitionedGraph:
             raise RuntimeError("single rank: the scorer writes edge-id order itself")
         gathered = all_gather_rows(piece, self.world, group).view(-1)
         return gathered.index_select(0, self.score_index)
+
+    def logits_finish(self, group=None):
+        """How engine.score_tail ends on this plan, as its keyword arguments: nothing - a lone process scatters to the edge ids itself -
+        or the padded piece every rank contributes and its assembly."""
+        if _alone(self.world):
+            return {}
+        return dict(pad=self.score_pad, assemble=functools.partial(self.assemble_logits, group=group))
 
     def _set_node_perm(self, node_perm, num_nodes, device):
         self.node_perm = torch.as_tensor(node_perm).to(device=device, dtype=torch.int64)
@@ -397,17 +410,16 @@ def _check_doubled_flag(doubled, in_edges_only):
         raise ValueError("doubled=True is the plan of GatedGCNModel(directed=False), a one-direction model: it needs in_edges_only=True")
 
 
-class _ScoredRows:
-    """The rows a doubled plan scores, as the scorer and its backward read them: `rows` (int32, score_rows), `views` - graph views of
-    the scored edges alone over the local nodes, whose sorted order IS rows' order (the sub-list is already sorted by destination and
-    the sort is stable), so their in- / out-lists segment the scorer's rows - and `score_views`, the same with global edge ids."""
+class ScoredRows:
+    """What a rank scores, the one description the scorer, its backward and the assembly of the logits read (PartitionedGraph._build):
+    `rows` - the sorted positions the scorer reads, int32, or None: the owned in-edges, the sorted prefix as it lies; `views` - graph views
+    whose sorted order IS the scored rows' order, so their in- / out-lists segment the scorer's rows; `score_views` - their srt_src /
+    srt_dst with, as srt_eid, the scored rows' ids in the complete logits; `count` rows are scored here (0 is legal on a doubled plan:
+    every owned in-edge a reverse copy) and the complete logits have `total` entries."""
 
-    def __init__(self, ops, views, score_rows, srt_geid, n_local):
-        self.rows = score_rows.int()
-        self.views = ops.GraphViews(views.srt_src[score_rows].contiguous(), views.srt_dst[score_rows].contiguous(), n_local)
-        k = int(score_rows.numel())
-        assert torch.equal(self.views.srt_eid.long().cpu(), torch.arange(k)), "the scored rows must keep their order"
-        self.score_views = _ScoreViews(self.views, srt_geid[score_rows].contiguous())
+    def __init__(self, rows, views, ids, total):
+        self.rows, self.views, self.score_views = rows, views, _ScoreViews(views, ids)
+        self.count, self.total = int(ids.numel()), int(total)
 
 
 def _staged(t, group):
@@ -517,11 +529,16 @@ class HaloExchange:
         dh[p.n_own:].zero_()
 
 
-def check_shard(part):
-    """What a PartitionShard refuses (GATPartitionedRunner raises the same, in the same words, before it allocates anything).  The PLAN is
-    always the forward orientation's; the reversed pass of SymGatedGCNModel is asked for with reverse=True on that plan."""
+def check_forward_plan(part):
+    """The PLAN is always the forward orientation's; the reversed pass of SymGatedGCNModel is asked for with reverse=True on that plan."""
     if part.views.transposed:
         raise NotImplementedError("partitioned training runs on the forward orientation of the graph")
+
+
+def check_shard(part):
+    """What a PartitionShard refuses; every runner and engine_baselines / engine_gat.check_partition raise the same through here, before
+    they allocate anything."""
+    check_forward_plan(part)
     if part.n_own == 0 or part.n_score == 0:
         raise NotImplementedError("a rank without owned nodes or owned in-edges (graph too small for this world size)")
 
@@ -547,14 +564,13 @@ class PartitionShard:
         self.n_own, self.n_local = part.n_own, part.n_local
         self.e_own, self.e_local = part.n_score, part.views.num_edges
         self.n_global, self.e_global = part.bounds[-1], part.num_edges_global
-        self.score_views = _ScoreViews(self.views, part.srt_geid)
-        # what the scorer reads: every owned in-edge as it lies, its node gathers transposed over the local lists - or, on a doubled plan,
-        # the score_rows alone (e_scored of them, possibly none) under the views of those edges; e_own / e_global stay the DOUBLED counts,
-        # the rows bn_e's statistics run over
-        self.score_rows, self.seg_views, self.e_scored = None, self.views, self.e_own
-        if part.doubled:
-            self.score_rows, self.seg_views, self.e_scored = part.scored.rows, part.scored.views, part.n_score_original
-            self.score_views = part.scored.score_views
+        # what the scorer reads (part.scored): every owned in-edge as it lies, its node gathers transposed over the local lists - or, on a
+        # doubled plan, the score_rows alone (e_scored of them, possibly none) under the views of those edges; e_own / e_global stay the
+        # DOUBLED counts, the rows bn_e's statistics run over
+        sc = part.scored
+        self.score_views, self.score_rows, self.e_scored = sc.score_views, sc.rows, sc.count
+        self.seg_views = sc.views.reversed() if self.reverse else sc.views
+        self.logits_finish = part.logits_finish(group)   # engine.score_tail's ending: {} when alone
         self._xchg = HaloExchange(part, ops, group)
 
     def halo_start(self, h):
@@ -605,20 +621,6 @@ class PartitionShard:
             at += t.numel()
         return out
 
-    def finish_logits(self, piece):
-        """world > 1: this rank's piece (owned in-edges, sorted order) -> the complete logits in edge-id order."""
-        return piece if self.alone else self.part.assemble_logits(piece, self.group)
-
-
-def _project(ops, lw, h, n_own, xchg):
-    """P = h * Wcat^T + bcat; the owned rows are projected while the halo rows are still in flight."""
-    P = torch.empty((h.shape[0], lw.Wcat.shape[0]), dtype=torch.float32, device=h.device)
-    if n_own > 0:
-        engine.project(ops, lw, h[:n_own], out=P[:n_own])
-    xchg.finish()
-    if h.shape[0] > n_own:
-        engine.project(ops, lw, h[n_own:], out=P[n_own:])
-    return P
 
 
 def check_doubled(gated, directed, part, what):
@@ -648,10 +650,9 @@ def _check_partition_kind(prep, part):
     return gated
 
 
-def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result=True, reverse=False):
+def run_partitioned(ops, prep, part, x_local, e_local, group=None, reverse=False):
     """The rank-local kernel sequence.  x_local: [n_local, F] features of owned+halo nodes, e_local:
-    [e_local, F] features of local edges in local edge-id order.  Returns logits[E_global] (complete on
-    every rank after the all_reduce when `reduce_result`).
+    [e_local, F] features of local edges in local edge-id order.  Returns logits[E_global], complete on every rank.
     reverse (SymGatedGCNModel only): the pass over dgl.reverse(g) (gated_gcn_full.py:99,117-127; train.py:165) on the SAME plan - x_local
     then holds the swapped degree columns.  Owned nodes, scored edges (the sorted prefix), halo exchange and the assembly of the logits are
     the forward pass's; the column blocks of P change roles (A2 <-> A3, B1 <-> B2, as engine.layer_step does on a whole graph) and the
@@ -668,8 +669,7 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result
     gated = _check_partition_kind(prep, part)
     if gated and reverse:
         raise NotImplementedError("GatedGCNModel on an in-edge-only partition runs on the forward orientation of the graph")
-    if part.views.transposed:   # (the plan itself is never flipped: reverse= selects the pass)
-        raise NotImplementedError("partitioned training runs on the forward orientation of the graph")
+    check_forward_plan(part)   # (the plan itself is never flipped: reverse= selects the pass)
     views, n_own = (part.views.reversed() if reverse else part.views), part.n_own
     xchg = HaloExchange(part, ops, group)
     H = prep.hidden
@@ -679,7 +679,7 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result
     for li, lw in enumerate(prep.layers):
         if li > 0:
             xchg.start(h)
-        P = _project(ops, lw, h, n_own, xchg)
+        P = engine.project_rows(functools.partial(engine.project, ops, lw), h, n_own, xchg.finish, lw.Wcat.shape[0])
         if gated:   # A1h|A2h|B1h|B2h: no A_3 block, no out-edge half (the halo rows of h' are written by the next exchange)
             A1, A2, B1, B2 = (P[:, i * H:(i + 1) * H] for i in range(4))
             e = engine.gate(ops, lw, views, e, B1, B2, (e_local, prep.enc_edge), scratch)
@@ -696,25 +696,11 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, reduce_result
     xchg.finish()
     PQ = ops.linear(h, pw["W_nodes"], pw["b_nodes"], planes=pw.get("planes"))
     Ps, Qd = (PQ[:, hs:], PQ[:, :hs]) if reverse else (PQ[:, :hs], PQ[:, hs:])   # x[src'] | x[dst'] = x[dst] | x[src]; b1 enters once either way
-    score_views, n_score, n_logits = _ScoreViews(views, part.srt_geid), part.n_score, part.num_edges_global
-    if part.doubled:
-        # the ORIGINAL graph is scored (full_graph.py:51): the rows of the prefix with ids below E, gathered as run_stack gathers
-        # score_gather, under views of those edges alone; a rank whose in-edges are all reverse copies scores nothing
-        score_views, n_score, n_logits = part.scored.score_views, part.n_score_original, part.num_edges_original
-        if n_score > 0:
-            e = ops.gather_rows(e, part.scored.rows)
-    if _alone(part.world) or not reduce_result:
-        # scatter straight to GLOBAL edge ids: a GraphViews-like shim whose srt_eid is the global map
-        logits = (torch.zeros if part.world > 1 else torch.empty)(n_logits, dtype=torch.float32, device=h.device)
-        if n_score > 0:
-            ops.edge_score(e, Ps, Qd, score_views, pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"], logits,
-                           num_edges=n_score)
-        return logits
-    piece = torch.empty(part.score_pad, dtype=torch.float32, device=h.device)
-    if n_score > 0:
-        ops.edge_score(e, Ps, Qd, score_views, pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"], piece,
-                       num_edges=n_score, scatter_to_edge_id=False)
-    return part.assemble_logits(piece, group)
+    # what is scored here: the owned in-edges as they lie - or, on a doubled plan, the ORIGINAL graph (full_graph.py:51): the rows of the
+    # prefix with ids below E, gathered as run_stack gathers score_gather; a rank whose in-edges are all reverse copies scores nothing
+    sc = part.scored
+    return engine.score_tail(ops, engine.scored_rows(ops, e, sc.rows, sc.count), Ps, Qd, engine.tail_weights(pw), sc.score_views,
+                             sc.count, sc.total, **part.logits_finish(group))
 
 
 class CapturedPartitionedForward:
@@ -766,14 +752,11 @@ class CapturedPartitionedForward:
             pw = prep.predictor
             hs = pw["hs"]
             PQ = ops.linear(state["h"], pw["W_nodes"], pw["b_nodes"], planes=pw.get("planes"))
-            sv = _ScoreViews(views, part.srt_geid)
-            if alone:
-                self.piece = torch.empty(part.num_edges_global, dtype=torch.float32, device=dev)
-            else:
-                self.piece = torch.empty(part.score_pad, dtype=torch.float32, device=dev)
-            if part.n_score > 0:
-                ops.edge_score(state["e"], PQ[:, :hs], PQ[:, hs:], sv, pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"], self.piece,
-                               num_edges=part.n_score, scatter_to_edge_id=alone)
+            # the complete logits when alone; otherwise this rank's piece as it is: every replay assembles it (__call__), no collective is recorded
+            sc = part.scored
+            finish = {} if alone else dict(pad=part.score_pad, assemble=lambda piece: piece)
+            self.piece = engine.score_tail(ops, engine.scored_rows(ops, state["e"], sc.rows, sc.count), PQ[:, :hs], PQ[:, hs:],
+                                           engine.tail_weights(pw), sc.score_views, sc.count, sc.total, **finish)
 
         with torch.no_grad():
             for fn in [lambda li=li: layer(li) for li in range(len(prep.layers))] + [score]:
@@ -841,8 +824,8 @@ class PartitionedRunner:
                 raise ValueError("GatedGCNModel runs on an in-edge-only partition: PartitionedGraph.from_global(..., in_edges_only=True)")
         elif part.in_edges_only:
             raise ValueError("an in-edge-only partition serves GatedGCNModel; SymGatedGCNModel needs the out-edges of the owned nodes too")
-        elif part.views.transposed:   # the reversed pass is selected by reverse=, never by flipping the plan (check_shard's words)
-            raise NotImplementedError("partitioned training runs on the forward orientation of the graph")
+        else:   # the reversed pass is selected by reverse=, never by flipping the plan
+            check_forward_plan(part)
         if (x_rev_global is not None or x_rev_local is not None) and (self.baseline or self.gated):
             raise NotImplementedError(f"{type(model).__name__} on a partition runs on the forward orientation of the graph: it takes no x_rev")
         prepared = engine_baselines.Prepared if self.baseline else engine_gated.Prepared if self.gated else engine.Prepared

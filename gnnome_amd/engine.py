@@ -222,6 +222,11 @@ def prepare_predictor(pred, device):
     }
 
 
+def tail_weights(pw):
+    """(W1_e, W2, b2, W3, b3) of a prepared predictor: what edge_score takes after the score views (score_tail's w_tail)."""
+    return pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"]
+
+
 class _StateProbe:
     """Has anything `Prepared` was built from changed?  The question is asked on every forward, and walking module.parameters() + buffers()
     (190 tensors behind generators) cost 0.26 ms of the 0.63 ms a forward spent on the host.  Kept instead: the flat list of (owning dict,
@@ -424,16 +429,12 @@ def score_step(ops, pw, views, h, e, logits, n_edges=None, PQ=None):
     return ops.edge_score(e, Ps, Qd, views, pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"], logits, num_edges=n_edges)
 
 
-def run_stack(ops, prep, views, x, e_raw, exchange=None, n_own=None, n_score=None, logits=None):
-    """Encoders -> L layers -> scorer.  `exchange(h)` (optional) refreshes halo rows before every
-    consumer of h; `n_own` limits the node update to the first rows, `n_score` the scorer to the first
-    sorted positions (both used by the destination-range partition, dist.py).  With PIPELINE_CHUNKS > 1 (off by
-    default: measured slower) every node projection after the first runs under the preceding aggregation on a second
-    stream (aggregate_then_project)."""
-    pipelined = (exchange is None and n_own is None and getattr(ops, "side_stream", None) is not None and PIPELINE_CHUNKS > 1
-                 and views.num_nodes >= PIPELINE_MIN_NODES)
+def run_stack(ops, prep, views, x, e_raw, logits=None):
+    """Encoders -> L layers -> scorer.  With PIPELINE_CHUNKS > 1 (off by default: measured slower) every node projection after the
+    first runs under the preceding aggregation on a second stream (aggregate_then_project)."""
+    pipelined = getattr(ops, "side_stream", None) is not None and PIPELINE_CHUNKS > 1 and views.num_nodes >= PIPELINE_MIN_NODES
     one_call = getattr(ops, "model_forward", None)
-    if (ONE_CALL_FORWARD and one_call is not None and exchange is None and n_own is None and n_score is None and not pipelined
+    if (ONE_CALL_FORWARD and one_call is not None and not pipelined
             and not getattr(ops, "STREAM_AGGREGATE", False) and isinstance(views, ops.GraphViews) and x.is_cuda and x.is_contiguous()
             and e_raw.is_contiguous()):
         # the whole sequence below as ONE call into the library (gnnome_model_forward_f32: the same entries in the same order, same bits)
@@ -447,18 +448,56 @@ def run_stack(ops, prep, views, x, e_raw, exchange=None, n_own=None, n_score=Non
     scratch = {}
     P = None
     for i, lw in enumerate(prep.layers):
-        if exchange is not None:
-            h = exchange(h)
         then = None
         if pipelined:
             then = layer_projection(ops, prep.layers[i + 1]) if i + 1 < len(prep.layers) else predictor_projection(ops, prep.predictor)
-        h, e, P = layer_step(ops, lw, views, h, e, n_out=n_own, raw_edges=(e_raw, prep.enc_edge), scratch=scratch, P=P, then=then)
-    if exchange is not None:
-        h = exchange(h)
+        h, e, P = layer_step(ops, lw, views, h, e, raw_edges=(e_raw, prep.enc_edge), scratch=scratch, P=P, then=then)
     if logits is None:
-        logits = torch.empty(views.num_edges if n_score is None else n_score, dtype=torch.float32, device=h.device)
-    score_step(ops, prep.predictor, views, h, e, logits, n_edges=n_score, PQ=P)
+        logits = torch.empty(views.num_edges, dtype=torch.float32, device=h.device)
+    score_step(ops, prep.predictor, views, h, e, logits, PQ=P)
     return logits
+
+
+# ---------------------------------------------------------------------------------------------------
+# the two pieces every sequence on a destination-range partition shares (dist.py; train.py and the other engines call them too)
+# ---------------------------------------------------------------------------------------------------
+
+def project_rows(product, h, n_own, finish, width):
+    """P [n_local, width] = the node projection of ALL local rows of a shard: the owned rows while the halo rows are in flight, then
+    `finish()` ends the exchange and the halo rows follow.  product(rows, out=) is the caller's own product call (project, or ops.linear
+    on its weights); a whole graph has no halo rows and finish() does nothing."""
+    P = torch.empty((h.shape[0], width), dtype=torch.float32, device=h.device)
+    if n_own > 0:
+        product(h[:n_own], out=P[:n_own])
+    finish()
+    if h.shape[0] > n_own:
+        product(h[n_own:], out=P[n_own:])
+    return P
+
+
+def scored_rows(ops, e, rows, count):
+    """The rows of e the scorer reads: e as it lies (rows = None: the sorted prefix), or e[rows] - `count` of them; a rank that scores
+    nothing launches no gather.  The in-edge step keeps the result for its backward."""
+    if rows is None:
+        return e
+    return ops.gather_rows(e, rows) if count > 0 else e[:0]
+
+
+def score_tail(ops, e, Ps, Qd, w_tail, score_views, count, total, z1_out=None, pad=None, assemble=None):
+    """The scorer's tail (score_predictor.py:12-24) over the `count` rows of e that scored_rows selected -> logits[total] in edge-id order.
+    w_tail = (W1_e, W2, b2, W3, b3); score_views: srt_src / srt_dst of those rows and, as srt_eid, their ids in the complete logits.
+    assemble = None - a whole graph, a lone process: the kernel scatters to the edge ids itself, into empty(total).  Otherwise (one rank
+    of several, dist.PartitionedGraph.logits_finish): the rows are scored in sorted order into piece[pad] and assemble(piece) makes the
+    complete logits; a rank with count = 0 launches nothing and still assembles, because the assembly is a collective."""
+    kw = {} if z1_out is None else dict(z1_out=z1_out)
+    if assemble is None:
+        logits = torch.empty(total, dtype=torch.float32, device=e.device)
+        ops.edge_score(e, Ps, Qd, score_views, *w_tail, logits, num_edges=count, **kw)
+        return logits
+    piece = torch.empty(pad, dtype=torch.float32, device=e.device)
+    if count > 0:
+        ops.edge_score(e, Ps, Qd, score_views, *w_tail, piece, num_edges=count, scatter_to_edge_id=False, **kw)
+    return assemble(piece)
 
 
 # ---------------------------------------------------------------------------------------------------

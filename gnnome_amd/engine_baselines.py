@@ -530,13 +530,11 @@ def plan_for(ops, part, directed, group=None):
 
 def check_partition(model, part):
     """The refusals of GCNModel / SAGEModel on a partition, before anything is allocated."""
+    from .dist import check_shard
     if getattr(part, "in_edges_only", False):
         raise ValueError(f"{type(model).__name__} runs on the default partition, not in_edges_only=True: GraphConv scales every source by its "
                          "OUT-degree and the backward walks the owned nodes' out-lists, which an in-edge-only partition does not hold")
-    if part.views.transposed:
-        raise NotImplementedError(f"{type(model).__name__} on a partition runs on the forward orientation of the graph")
-    if part.n_own == 0 or part.n_score == 0:
-        raise NotImplementedError("a rank without owned nodes or owned in-edges (graph too small for this world size)")
+    check_shard(part)
     built_width(model.node_encoder.linear2.out_features)
 
 
@@ -565,22 +563,15 @@ def _sage_layer_part(ops, plan, n_own, T, both, split, finish):
         T[:, :H], plan.lists, n_own, dscale=plan.din_inv, both=both, out=T[:, H:], rows=rows))
 
 
-def _score_part(ops, part, group, e, h, pw_nodes, w_tail, z1_out=None):
-    """The symmetric model's scorer on the owned in-edges (dist.run_partitioned's tail): h [n_local,H] with its halo rows fetched ->
-    logits[E_global] in edge-id order, complete on every rank."""
-    from .dist import _ScoreViews, _alone
+def score_part(ops, part, group, e, h, pw_nodes, w_tail, z1_out=None):
+    """The symmetric model's scorer on the owned in-edges (engine.score_tail, after the node halves' product): h [n_local,H] with its halo
+    rows fetched, e the encoded scored rows -> logits[E_global] in edge-id order, complete on every rank.  GATModel's sequences end here too."""
     W_nodes, b_nodes, planes = pw_nodes
     hs = W_nodes.shape[0] // 2
     PQ = ops.linear(h, W_nodes, b_nodes, planes=planes)
-    sv = _ScoreViews(part.views, part.srt_geid)
-    kw = {} if z1_out is None else dict(z1_out=z1_out)
-    if _alone(part.world):
-        logits = torch.empty(part.num_edges_global, dtype=torch.float32, device=h.device)
-        ops.edge_score(e, PQ[:, :hs], PQ[:, hs:], sv, *w_tail, logits, num_edges=part.n_score, **kw)
-        return logits
-    piece = torch.empty(part.score_pad, dtype=torch.float32, device=h.device)
-    ops.edge_score(e, PQ[:, :hs], PQ[:, hs:], sv, *w_tail, piece, num_edges=part.n_score, scatter_to_edge_id=False, **kw)
-    return part.assemble_logits(piece, group)
+    sc = part.scored
+    return engine.score_tail(ops, engine.scored_rows(ops, e, sc.rows, sc.count), PQ[:, :hs], PQ[:, hs:], w_tail, sc.score_views,
+                             sc.count, sc.total, z1_out=z1_out, **part.logits_finish(group))
 
 
 def run_partitioned(ops, prep, part, x_local, e_local, group=None, directed=None, split=None):
@@ -629,8 +620,7 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, directed=None
         xchg.start(h)
         xchg.finish()
     pw = prep.predictor
-    return _score_part(ops, part, group, e, h, (pw["W_nodes"], pw["b_nodes"], pw.get("planes")),
-                       (pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"]))
+    return score_part(ops, part, group, e, h, (pw["W_nodes"], pw["b_nodes"], pw.get("planes")), engine.tail_weights(pw))
 
 
 def _any_rank_not_finite(logits, alone, group):
@@ -731,7 +721,7 @@ def _part_step_forward(ops, model, sh, x, e_raw, masks, split):
         sh.halo_finish()
     W1, W_nodes, b_nodes, tail = live_predictor(model.predictor, H)
     z1 = torch.empty((sh.e_own, model.predictor.W1.out_features), dtype=torch.float32, device=h.device)
-    logits = _score_part(ops, part, sh.group, e, h, (W_nodes, b_nodes, None), tail, z1_out=z1)
+    logits = score_part(ops, part, sh.group, e, h, (W_nodes, b_nodes, None), tail, z1_out=z1)
     return logits, dict(h=h, e=e, z1=z1, W1=W1, W_nodes=W_nodes, layers=layers)
 
 

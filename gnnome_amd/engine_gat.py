@@ -280,13 +280,8 @@ def check_partition(model, part):
 
 
 def _project_part(ops, h, Wp, planes, n_own, finish):
-    """P [n_local, 3H + 64] = h Wp^T of ALL local rows: the owned rows while the halo rows of h are in flight, the halo rows after."""
-    P = torch.empty((h.shape[0], Wp.shape[0]), dtype=torch.float32, device=h.device)
-    ops.linear(h[:n_own], Wp, None, out=P[:n_own], planes=planes)
-    finish()
-    if h.shape[0] > n_own:
-        ops.linear(h[n_own:], Wp, None, out=P[n_own:], planes=planes)
-    return P
+    """P [n_local, 3H + 64] = h Wp^T of ALL local rows, the halo rows made locally once they have arrived (engine.project_rows)."""
+    return engine.project_rows(lambda rows, out: ops.linear(rows, Wp, None, out=out, planes=planes), h, n_own, finish, Wp.shape[0])
 
 
 def run_partitioned(ops, prep, part, x_local, e_local, group=None, directed=True):
@@ -316,8 +311,7 @@ def run_partitioned(ops, prep, part, x_local, e_local, group=None, directed=True
         xchg.start(h)
         xchg.finish()
     pw = prep.predictor
-    return eb._score_part(ops, part, group, e, h, (pw["W_nodes"], pw["b_nodes"], pw.get("planes")),
-                          (pw["W1_e"], pw["W2"], pw["b2"], pw["W3"], pw["b3"]))
+    return eb.score_part(ops, part, group, e, h, (pw["W_nodes"], pw["b_nodes"], pw.get("planes")), engine.tail_weights(pw))
 
 
 def _part_step_forward(ops, model, sh, x, e_raw, masks):
@@ -352,7 +346,7 @@ def _part_step_forward(ops, model, sh, x, e_raw, masks):
         sh.halo_finish()
     W1, W_nodes, b_nodes, tail = eb.live_predictor(model.predictor, H)
     z1 = torch.empty((sh.e_own, model.predictor.W1.out_features), dtype=torch.float32, device=h.device)
-    logits = eb._score_part(ops, part, sh.group, e, h, (W_nodes, b_nodes, None), tail, z1_out=z1)
+    logits = eb.score_part(ops, part, sh.group, e, h, (W_nodes, b_nodes, None), tail, z1_out=z1)
     return logits, dict(h=h, e=e, z1=z1, W1=W1, W_nodes=W_nodes, layers=layers)
 
 

@@ -382,7 +382,7 @@ class _StepGraph:
         """doubled, ops: the builder of the doubled graph and the backend (the tests run the step's host logic on a torch backend)."""
         from .train import WholeGraph
         self.score_views = self.seg_views = views   # seg_views: whose in- / out-lists the scorer's node gathers are transposed over
-        self.num_scored = views.num_edges
+        self.num_scored = self.num_logits = views.num_edges   # (num_logits: the length of the complete logits)
         if directed:
             self.sh, self.enc_gather, self.score_gather = WholeGraph(views, ops), views.srt_eid, None
         else:
@@ -399,6 +399,7 @@ class _StepGraph:
         self = object.__new__(cls)
         self.sh, self.enc_gather, self.score_gather = shard, shard.views.srt_eid, shard.score_rows
         self.score_views, self.seg_views, self.num_scored = shard.score_views, shard.seg_views, shard.e_scored
+        self.num_logits = shard.part.scored.total
         return self
 
 
@@ -436,11 +437,7 @@ class _InEdgeStep(torch.autograd.Function):
             else:
                 if li > 0:
                     sh.halo_start(h)
-                P = torch.empty((n, 4 * H), dtype=torch.float32, device=x.device)
-                ops.linear(h[:n_own], Wcat, bcat, out=P[:n_own])    # owned rows while the halo rows are in flight
-                sh.halo_finish()
-                if n > n_own:
-                    ops.linear(h[n_own:], Wcat, bcat, out=P[n_own:])
+                P = engine.project_rows(lambda rows, out: ops.linear(rows, Wcat, bcat, out=out), h, n_own, sh.halo_finish, 4 * H)
             A1, A2, B1, B2 = (P[:, i * H:(i + 1) * H] for i in range(4))
             mean_e = rstd_e = sc_e = sh_e = mean_h = rstd_h = sc_h = sh_h = None
             path, xe, stats = train._raw_gate(sh, conv, e, B1, B2, layer_norm, torch.float32)
@@ -491,17 +488,10 @@ class _InEdgeStep(torch.autograd.Function):
         PQ = ops.linear(h, W_nodes, b_nodes)
         # directed=False: the ORIGINAL graph is scored with the rows of the first E edge ids (full_graph.py:51)
         E = sg.num_scored   # (0 on a rank of a doubled plan whose in-edges are all reverse copies: it scores nothing and gathers with the others)
-        e_sc = e if sg.score_gather is None else ops.gather_rows(e, sg.score_gather) if E > 0 else e[:0]
+        e_sc = engine.scored_rows(ops, e, sg.score_gather, E)
         z1 = torch.empty((E, hs), dtype=torch.float32, device=h.device)
         w_tail = (W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1)))
-        if sh.alone:
-            logits = torch.empty(E, dtype=torch.float32, device=h.device)
-            ops.edge_score(e_sc, PQ[:, :hs], PQ[:, hs:], sg.score_views, *w_tail, logits, num_edges=E, z1_out=z1)
-        else:   # one contiguous piece per rank in sorted order; finish_logits all-gathers and un-permutes them
-            piece = torch.empty(sh.part.score_pad, dtype=torch.float32, device=h.device)
-            if E > 0:
-                ops.edge_score(e_sc, PQ[:, :hs], PQ[:, hs:], sg.score_views, *w_tail, piece, num_edges=E, scatter_to_edge_id=False, z1_out=z1)
-            logits = sh.finish_logits(piece)
+        logits = engine.score_tail(ops, e_sc, PQ[:, :hs], PQ[:, hs:], w_tail, sg.score_views, E, sg.num_logits, z1_out=z1, **sh.logits_finish)
         ctx.model, ctx.sg, ctx.names, ctx.saved = model, sg, names, saved
         ctx.tail = dict(h=h, e_sc=e_sc, z1=z1, W1=W1, W_nodes=W_nodes, x=x, e_raw=e_raw)
         return logits.unsqueeze(1)

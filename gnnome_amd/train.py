@@ -30,6 +30,7 @@ for it with `GNNOME_SCALED_WGRAD=0 GNNOME_SCALED_NODE_WGRAD=0 GNNOME_SCALED_NODE
 """
 import torch
 
+from . import engine
 from . import ops as hip_ops
 from .graph import views_for
 
@@ -43,6 +44,7 @@ class WholeGraph:
     group = None      # no process group
     alone = True      # no collective is issued (a PartitionShard of one rank under GNNOME_FORCE_COLLECTIVES=1 says False; `world` is 1 for
                       # both, and it is `world` that selects the kernels: the two give the same bits)
+    logits_finish = {}   # engine.score_tail's ending: the scorer writes logits[E_global] at the edge ids itself, nothing is assembled
 
     def __init__(self, views, ops=hip_ops):
         self.views, self.ops = views, ops
@@ -73,9 +75,6 @@ class WholeGraph:
 
     def sum_ranks(self, tensors):       # element-wise sum over ranks of a list of tensors (same shapes on every rank)
         return tensors
-
-    def finish_logits(self, logits):    # assemble the per-rank disjoint pieces of logits[E_global]
-        return logits
 
 
 def dropout_mask(rows, cols, p, device):
@@ -307,11 +306,7 @@ class _TrainStep(torch.autograd.Function):
             Wcat, bcat, WcatT, W3T = _cat_layer(conv, ops)
             if li > 0:
                 sh.halo_start(h)        # layer 0's halo rows come straight from the input features
-            P = new(n_local, 5 * H)
-            ops.linear(h[:n_own], Wcat, bcat, out=P[:n_own])    # owned rows while the halo rows are in flight
-            sh.halo_finish()
-            if n_local > n_own:
-                ops.linear(h[n_own:], Wcat, bcat, out=P[n_own:])
+            P = engine.project_rows(lambda rows, out: ops.linear(rows, Wcat, bcat, out=out), h, n_own, sh.halo_finish, 5 * H)
             mean_e = rstd_e = sc_e = sh_e = mean_h = rstd_h = sc_h = sh_h = None
             if layer_norm and storage != torch.float32:
                 raise _no_bf16_storage()
@@ -372,16 +367,10 @@ class _TrainStep(torch.autograd.Function):
         sh.halo_finish()
         PQ = ops.linear(h, W_nodes, b_nodes)
         ps, qd = (PQ[:, hs:], PQ[:, :hs]) if views.transposed else (PQ[:, :hs], PQ[:, hs:])
-        # every edge of the graph is scored once, by the rank that owns its destination
+        # every edge of the graph is scored once, by the rank that owns its destination: the owned in-edges, the sorted prefix as it lies
         z1 = new(e_own, hs)
         w_tail = (W1[:, 2 * H:], d(pred.W2.weight), d(pred.W2.bias), d(pred.W3.weight.reshape(-1)), d(pred.W3.bias.reshape(-1)))
-        if not sh.alone:    # one contiguous piece per rank in sorted order; finish_logits all-gathers and un-permutes them
-            piece = torch.empty(sh.part.score_pad, dtype=torch.float32, device=h.device)
-            ops.edge_score(e, ps, qd, sh.score_views, *w_tail, piece, num_edges=e_own, scatter_to_edge_id=False, z1_out=z1)
-            logits = sh.finish_logits(piece)
-        else:
-            logits = torch.empty(sh.e_global, dtype=torch.float32, device=h.device)
-            ops.edge_score(e, ps, qd, sh.score_views, *w_tail, logits, num_edges=e_own, z1_out=z1)
+        logits = engine.score_tail(ops, e, ps, qd, w_tail, sh.score_views, e_own, sh.e_global, z1_out=z1, **sh.logits_finish)
         ctx.model, ctx.sh, ctx.names, ctx.saved = model, sh, names, saved
         ctx.tail = dict(h=h, e=e, z1=z1, W1=W1, W_nodes=W_nodes, x=x, e_raw=e_raw)
         return logits.unsqueeze(1)
@@ -549,8 +538,7 @@ class _TrainStep(torch.autograd.Function):
 
 def train_forward(model, graph, x, e):
     """`model(graph, x, e)` in train mode with autograd support: logits [E,1] on the compute device."""
-    from .engine import compute_device
-    device = compute_device(x, e)
+    device = engine.compute_device(x, e)
     views = views_for(graph, device, node_order=getattr(model, "node_order", "input"))
     xd = x.detach().to(device=device, dtype=torch.float32).contiguous()
     ed = e.detach().to(device=device, dtype=torch.float32).contiguous()
@@ -564,13 +552,12 @@ def train_forward_on(model, shard, x_local, e_local):
     e_local are the input features of the shard's nodes / edges (local edge-id order).  Returns logits[E_global, 1],
     complete on every rank, differentiable w.r.t. the model's parameters; the parameter gradients that
     `backward()` leaves in `.grad` are already summed over ranks."""
-    from .engine import BUILT_HIDDEN
     H, hs = model.linear2_node.out_features, model.predictor.W1.out_features
     names = [n for n, _ in model.named_parameters()]
     params = [p for _, p in model.named_parameters()]
     if any(p.device != x_local.device for p in params):
         raise RuntimeError("training needs the model on the compute device: call model.to(device) first")
-    if H not in BUILT_HIDDEN or (hs not in TRAIN_SCORE_HIDDEN and hs <= TRAIN_SCORE_HIDDEN[-1]):
+    if H not in engine.BUILT_HIDDEN or (hs not in TRAIN_SCORE_HIDDEN and hs <= TRAIN_SCORE_HIDDEN[-1]):
         return _padded_step(model, shard, x_local, e_local, names, params)
     return _TrainStep.apply(model, shard, x_local, e_local, names, *params)
 
@@ -593,14 +580,13 @@ def _padded_step(model, shard, x_local, e_local, names, params):
     and constant-zero activations (batch mean 0, variance 0, x_hat = 0), so its relu mask is off, every gradient that reaches it is zero, and
     the gradients of the padded tensors arrive at the model's parameters sliced by autograd.  LayerNorm (round 5): the twin's kernels take the
     statistics over the model's own channels (`_gnnome_norm_width`; a padded channel gets xhat = 0, output 0 and dx = 0)."""
-    from .engine import padded_width
     from .models import SymGatedGCNModel
     conv0 = model.gnn.convs[0]
     layer_norm = isinstance(conv0.bn_e, torch.nn.LayerNorm)
     H, hs = model.linear2_node.out_features, model.predictor.W1.out_features
     if hs > TRAIN_SCORE_HIDDEN[-1]:
         raise ValueError(f"train mode at hidden_edge_scores={hs}: the scorer's backward is built for widths up to {TRAIN_SCORE_HIDDEN[-1]}")
-    Hp, hsp = padded_width(H), padded_width(hs, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")
+    Hp, hsp = engine.padded_width(H), engine.padded_width(hs, TRAIN_SCORE_HIDDEN, "hidden_edge_scores")
     dev = params[0].device
     twin = model.__dict__.get("_gnnome_padded_twin")
     if twin is None or next(twin.parameters()).device != dev:
