@@ -164,6 +164,9 @@ SIGNATURES = {
     "gnnome_pr_curve_emit": [_p, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _sz, _p],
     "gnnome_pr_curve_ap": [_p, _p, _l, _p, _p, _sz, _p],
     "gnnome_walk_audit": [_p, _p, _p, _l, _l, _p, _p, _p, _p, _l, _p, _p, _p],
+    "gnnome_interval_union_tile_size": [ctypes.POINTER(_i)],
+    "gnnome_interval_union_workspace_bytes": [_l, ctypes.POINTER(_sz)],
+    "gnnome_interval_union": [_p, _p, _p, _l, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _sz, _p],
 }
 
 ABI_VERSION = 32

@@ -2,7 +2,9 @@
 
     g = gfa.read_gfa("asm.gfa", reads_path="reads.fasta", training=True)     # g["y"]: these labels, computed here
     gt_edge_ids, y = process_graph(g)                                        # y float32[E] in edge-id order
-    merged = interval_union(g)                                               # the strand +1 reads' [start, end] union
+    merged = interval_union(g)                                               # the strand +1 reads' [start, end] union (host)
+    islands = interval_union_device(g, by="chr")                             # the same on the device, per chromosome
+    report = reference_coverage(g, ref_length={1: 4_600_000})                # covered bases, islands, longest island, fraction
 
 An edge (u, v) is correct - a "class edge" - when both reads come from one chromosome and one genome strand and v starts inside u
 (strand +1: start[u] < start[v] < end[u]; strand -1 mirrored).  Per (chromosome, strand) the reference walks the class graph
@@ -105,3 +107,120 @@ def interval_union(g):
         else:
             result.append([s, e])
     return result
+
+
+# ---- the union on the device (csrc/interval_union.hip) ---------------------------------------------------------------------------
+
+def interval_union_tile_size():
+    """Intervals per tile of the scans (csrc/interval_union.hip); results do not depend on it, the tests place their edges by it."""
+    tile = ctypes.c_int(0)
+    _lib.check(_lib.load().gnnome_interval_union_tile_size(ctypes.byref(tile)), "interval_union_tile_size")
+    return int(tile.value)
+
+
+class IntervalUnion:
+    """The islands of one interval_union_device call, in (group, start) order.  group int32[K], start, end int64[K]: the islands;
+    groups int32[G] ascending, covered int64[G] (the sum of end - start over the group's islands), count int64[G] (its islands);
+    head uint8[M]: 1 where a selected read, in sorted order, opens an island.  All on the device."""
+
+    def __init__(self, by, group, start, end, groups, covered, count, head):
+        self.by, self.group, self.start, self.end = by, group, start, end
+        self.groups, self.covered, self.count, self.head = groups, covered, count, head
+
+    def __len__(self):
+        return int(self.start.numel())
+
+    def tolist(self):
+        """by="all": the reference's list of [start, end]; by="chr": [chromosome, start, end] per island.  One copy to the host."""
+        rows = torch.stack([self.group.to(torch.int64), self.start, self.end], 1).tolist()
+        return [r[1:] for r in rows] if self.by == "all" else rows
+
+
+def _as_tensor(t):
+    return t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))
+
+
+def _strand_text(strand):
+    return "no node" if strand is None else f"no strand {int(strand):+d} node"
+
+
+def interval_union_device(g, by="all", strand=1, device=None):
+    """utils/labels.py:5-20 on the device -> IntervalUnion.  by="all" is the reference: the chromosome is ignored and .tolist() equals
+    interval_union(g); by="chr" merges within each read_chr value, groups in ascending chromosome code.  strand: +1 (the reference),
+    -1, or None for the reads of both strands, each interval taken as stored.  An interval opens a new island iff its start lies
+    beyond every end before it in its group; start == that end merges.  Lengths and end >= start are checked on the
+    device before the launch; no selected read raises the host function's IndexError."""
+    if by not in ("all", "chr"):
+        raise ValueError(f"interval_union: by={by!r}: expected 'all' or 'chr'")
+    if strand not in (1, -1, None):
+        raise ValueError(f"interval_union: strand={strand!r}: expected 1, -1 or None")
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    names = ("read_strand", "read_start", "read_end") + (("read_chr",) if by == "chr" else ())
+    cols = [_as_tensor(g[k]).reshape(-1).to(dev, torch.int64) for k in names]
+    for k, t in zip(names[1:], cols[1:]):
+        if t.numel() != cols[0].numel():
+            raise ValueError(f"interval_union: {k} has {t.numel()} entries, read_strand {cols[0].numel()}")
+    if cols[0].numel() >= (1 << 31):
+        raise ValueError(f"interval_union: {cols[0].numel()} nodes: must be below 2^31")
+    node = torch.arange(cols[0].numel(), device=dev) if strand is None else torch.nonzero(cols[0] == strand, as_tuple=True)[0]
+    M = int(node.numel())
+    if M == 0:
+        raise IndexError(f"interval_union: {_strand_text(strand)}")   # the reference's intervals[0] on an empty list
+    start, end = cols[1][node], cols[2][node]
+    bad = torch.nonzero(end < start, as_tuple=True)[0]
+    if bad.numel():
+        i = int(bad[0])
+        raise ValueError(f"interval_union: node {int(node[i])} ends at {int(end[i])}, before its start {int(start[i])}")
+    order = torch.sort(start, stable=True).indices
+    if by == "chr":
+        chrom = cols[3][node]
+        if int(chrom.min()) < _I32[0] or int(chrom.max()) > _I32[1]:
+            raise ValueError("interval_union: read_chr does not fit int32")
+        order = order[torch.sort(chrom[order], stable=True).indices]
+        group = chrom[order].to(torch.int32)
+        G = int(torch.unique_consecutive(group).numel())
+    else:
+        group, G = torch.zeros(M, dtype=torch.int32, device=dev), 1
+    start, end = start[order].contiguous(), end[order].contiguous()
+    head = torch.empty(M, dtype=torch.uint8, device=dev)
+    isl_group = torch.empty(M, dtype=torch.int32, device=dev)
+    isl_start, isl_end = (torch.empty(M, dtype=torch.int64, device=dev) for _ in range(2))
+    grp_code = torch.empty(G, dtype=torch.int32, device=dev)
+    grp_covered, grp_count = (torch.empty(G, dtype=torch.int64, device=dev) for _ in range(2))
+    need = ctypes.c_size_t(0)
+    _lib.check(lib.gnnome_interval_union_workspace_bytes(M, ctypes.byref(need)), "interval_union_workspace_bytes")
+    ws = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+    result = (ctypes.c_int64 * 2)()
+    with _on(dev):
+        _lib.check(lib.gnnome_interval_union(_ptr(start), _ptr(end), _ptr(group), M, _ptr(head), _ptr(isl_group), _ptr(isl_start),
+                                             _ptr(isl_end), G, _ptr(grp_code), _ptr(grp_covered), _ptr(grp_count), result, _ptr(ws),
+                                             ws.numel(), _stream(dev)), "interval_union")
+    K = int(result[0])
+    return IntervalUnion(by, isl_group[:K], isl_start[:K], isl_end[:K], grp_code, grp_covered, grp_count, head)
+
+
+def reference_coverage(g, ref_length=None, device=None):
+    """How much of the reference the strand +1 reads can reconstruct, per chromosome (interval_union_device(g, by="chr")) ->
+    {"chromosomes": {code: {"covered", "islands", "longest_island"[, "fraction"]}}, "covered", "islands", "longest_island"[,
+    "fraction"]}: covered bases (the honest ref_length of calculate_NG50 / quick_evaluation), the number of islands (a lower bound on
+    the contigs of a perfect assembly) and the longest one.  ref_length: an int - the whole reference, giving the total's fraction -
+    or a dict by chromosome code, giving every chromosome's and, over the sum of the dict, the total's.  One copy to the host."""
+    u = interval_union_device(g, by="chr", strand=1, device=device)
+    rank = torch.searchsorted(u.groups.to(torch.int64), u.group.to(torch.int64))
+    longest = torch.zeros_like(u.covered).scatter_reduce_(0, rank, u.end - u.start, "amax", include_self=False)
+    codes, covered, islands, longest = torch.stack([u.groups.to(torch.int64), u.covered, u.count, longest]).tolist()
+    per_chr = isinstance(ref_length, dict)
+    if per_chr:
+        missing = [c for c in codes if c not in ref_length]
+        if missing:
+            raise ValueError(f"reference_coverage: ref_length has no entry for chromosome {missing[0]}")
+    report = {"chromosomes": {}, "covered": sum(covered), "islands": sum(islands), "longest_island": max(longest)}
+    for c, cov, n, lng in zip(codes, covered, islands, longest):
+        row = {"covered": cov, "islands": n, "longest_island": lng}
+        if per_chr:
+            row["fraction"] = cov / ref_length[c]
+        report["chromosomes"][c] = row
+    if ref_length is not None:
+        report["fraction"] = report["covered"] / (sum(ref_length.values()) if per_chr else ref_length)
+    return report

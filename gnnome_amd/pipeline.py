@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import contigs as contigs_mod
-from . import analyze, decode, features, gfa, metrics
+from . import analyze, decode, features, gfa, labels, metrics
 from .graph import views_for
 
 
@@ -159,3 +159,11 @@ def walk_report(g, walks, device=None):
     report.update({k: totals[i] for i, k in enumerate(kinds)})
     report.update({"walks_with_" + k: totals[3 + i] for i, k in enumerate(kinds)})
     return report
+
+
+def coverage_report(g, ref_length=None, device=None):
+    """How much of the reference the simulated reads of a graph with read positions (read_gfa(training=True)) can reconstruct at all:
+    labels.reference_coverage - per chromosome and in total the covered bases, the number of islands and the longest island, and the
+    covered fraction when ref_length (an int, or a dict by chromosome code) is given.  The covered total is the honest ref_length for
+    contigs.calculate_NG50 / quick_evaluation; the island count is a lower bound on the contigs of a perfect assembly."""
+    return labels.reference_coverage(g, ref_length=ref_length, device=device)

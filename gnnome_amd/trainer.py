@@ -217,15 +217,19 @@ class _Graph:
             self.in_deg, self.out_deg = (t.contiguous() for t in be.stored_degrees(self.views))
 
 
-def process(gfa, reads, out_path, device=None, maf=None, maf_chr=None, maf_parser="host"):
+def process(gfa, reads, out_path, device=None, maf=None, maf_chr=None, maf_parser="host", coverage=False):
     """One training graph file: gfa.read_gfa(gfa, reads_path=reads, training=True) with the labels computed on the device and the
     stored degrees (graph_parser.py: ndata in_deg / out_deg) added, written with torch.save to `out_path` (<dir>/<idx>.pt).  maf, maf_chr,
-    maf_parser: the simulator's MAF file as the source of the read positions (read_gfa's keywords; `reads` may then be None)."""
+    maf_parser: the simulator's MAF file as the source of the read positions (read_gfa's keywords; `reads` may then be None).
+    coverage=True also stores labels.reference_coverage(g) under "coverage": what of the reference the reads cover, per chromosome."""
     from .gfa import read_gfa
     g = read_gfa(gfa, reads_path=reads, training=True, labels="device", maf=maf, maf_chr=maf_chr, maf_parser=maf_parser)
     device = device or torch.device("cuda", torch.cuda.current_device())
     views = ops.GraphViews(g["src"].to(device=device, dtype=torch.int32), g["dst"].to(device=device, dtype=torch.int32), g["num_nodes"])
     g["in_deg"], g["out_deg"] = (t.cpu() for t in features.stored_degrees(views))
+    if coverage:
+        from .labels import reference_coverage
+        g["coverage"] = reference_coverage(g, device=device)
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     torch.save(g, out_path)
     return g

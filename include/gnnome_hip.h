@@ -32,7 +32,8 @@ extern "C" {
 /* Raised when an existing entry changes its signature or meaning.  32 also covers gnnome_node_neighbour_sum_part_f32,
  * gnnome_node_neighbour_sum_bwd_part_f32 and the four part entries of the attention sum (gnnome_node_attention_sum_part_f32, _stats_part_f32,
  * _bwd_dst_part_f32, _bwd_src_part_f32), which were ADDED without touching any other entry: a caller built against 32 keeps working, and
- * the Python binding resolves every entry by name when it loads the library, so a library that predates them is refused there, by name. */
+ * the Python binding resolves every entry by name when it loads the library, so a library that predates them is refused there, by name.
+ * The three interval-union entries were added in the same way. */
 #define GNNOME_ABI_VERSION 32
 
 #define GNNOME_OK 0
@@ -1339,6 +1340,31 @@ int gnnome_pr_curve_ap(const double* precision, const double* recall, int64_t nu
 int gnnome_walk_audit(const int32_t* walk_ptr, const int32_t* walk_nodes, const int32_t* walk_id, int64_t num_walks, int64_t num_positions,
                       const int64_t* read_strand, const int64_t* read_start, const int64_t* read_end, const int64_t* read_chr,
                       int64_t num_nodes, uint8_t* flags, int32_t* counts, void* stream);
+
+/* ---- Interval union: the islands of reference that the reads cover, per group -------------------------------------------------------
+ * Replaces utils/labels.py:5-20 (interval_union: a sort and a Python loop over every strand +1 read), as tests/interval_statement.py
+ * states it, with groups added: start, end int64[M] and group int32[M] are ordered by (group, start) - the caller's stable torch sorts;
+ * equal group values must be adjacent, their order is the caller's.  Walking a group in that order with R = the largest end seen so
+ * far in the group, interval i heads a new island iff it is the group's first or start[i] > R (start[i] == R touches and merges); the
+ * island is [start of its head, R at its last member].  For intervals with end >= start - which the caller checks - that R is the
+ * largest end of the island's own members, the reference's result; one group of all intervals is the reference's single line.
+ * Two exact segmented scans over tiles of a fixed number of intervals (running maximum; island, group and length counts), each as a
+ * per-tile reduce, ONE workgroup over the tile summaries and a per-tile apply, five launches: no kernel waits on another workgroup, no
+ * atomics, no floating point, one writer per output slot.
+ * gnnome_interval_union_tile_size: intervals per tile (host, no launch); results do not depend on it.
+ * gnnome_interval_union_workspace_bytes: 0 <= num_intervals < 2^31.
+ * gnnome_interval_union: head uint8[M] (may be NULL): 1 where an island starts.  isl_group int32, isl_start, isl_end int64, each with
+ *   room for M entries: island k in input order, the first K are written.  grp_code int32, grp_covered, grp_count int64, each
+ *   [max_groups]: per group in input order its value of `group`, the sum of (end - start) over its islands (64-bit wrap-around sums:
+ *   exact when the figure fits) and the number of its islands.  SYNCHRONISES `stream` once and fills result_host int64[2] (HOST
+ *   memory): K and the number of groups G.  G > max_groups is an error reported after the fact; only the first max_groups groups
+ *   were written.  M = 0 gives K = G = 0 without a launch. */
+int gnnome_interval_union_tile_size(int* tile_host);
+int gnnome_interval_union_workspace_bytes(int64_t num_intervals, size_t* bytes_host);
+int gnnome_interval_union(const int64_t* start, const int64_t* end, const int32_t* group, int64_t num_intervals, uint8_t* head,
+                          int32_t* isl_group, int64_t* isl_start, int64_t* isl_end, int64_t max_groups, int32_t* grp_code,
+                          int64_t* grp_covered, int64_t* grp_count, int64_t* result_host, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 #ifdef __cplusplus
 }
