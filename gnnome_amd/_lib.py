@@ -167,6 +167,11 @@ SIGNATURES = {
     "gnnome_interval_union_tile_size": [ctypes.POINTER(_i)],
     "gnnome_interval_union_workspace_bytes": [_l, ctypes.POINTER(_sz)],
     "gnnome_interval_union": [_p, _p, _p, _l, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _sz, _p],
+    "gnnome_pagerank_workspace_bytes": [_l, ctypes.POINTER(_sz)],
+    "gnnome_pagerank_steps_f64": [_p, _p, _p, _l, _i, _p, _p, _p, _sz, _p],
+    "gnnome_rw_return_lds_bytes": [_i, ctypes.POINTER(_sz)],
+    "gnnome_rw_return_workspace_bytes": [_l, _i, ctypes.POINTER(_sz)],
+    "gnnome_rw_return_f64": [_p, _p, _p, _l, _i, _i, _p, _i, _p, _p, _p, _sz, _p],
 }
 
 ABI_VERSION = 32

@@ -1896,3 +1896,83 @@ def walk_audit(walk_ptr, walk_nodes, walk_id, read_strand, read_start, read_end,
     counts = torch.zeros((W, 3), dtype=torch.int32, device=dev)
     _call("gnnome_walk_audit", dev, _ptr(walk_ptr), _ptr(walk_nodes), _ptr(walk_id), W, T, *(_ptr(c) for c in cols), N, _ptr(flags), _ptr(counts))
     return flags, counts
+
+
+# ---------------------------------------------------------------------------------------------------
+# positional encodings (include/gnnome_hip.h, "Positional encodings")
+# ---------------------------------------------------------------------------------------------------
+
+RW_DEFAULT_CAPACITY = 1024   # (node, value) pairs of one expansion: 32 KiB of LDS per workgroup, four one-wavefront workgroups per CU
+
+
+def _pe_lists(views):
+    """(in-list ptr, in-list sources, out-list ptr, out-list destinations, in_deg, out_deg) of the graph the views stand for: reversed()
+    views exchange the roles of the two orderings."""
+    ind = (views.in_ptr[1:] - views.in_ptr[:-1]).contiguous()
+    outd = (views.out_ptr[1:] - views.out_ptr[:-1]).contiguous()
+    if views.transposed:
+        return views.out_ptr, views.out_dst, views.in_ptr, views.srt_src, outd, ind
+    return views.in_ptr, views.srt_src, views.out_ptr, views.out_dst, ind, outd
+
+
+def _pe_out(out, shape, dtype, device, name):
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{name}: dtype float32 or float64, got {dtype}")
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}")
+    return out
+
+
+def pagerank_steps(views, pe_dim, dtype=torch.float32, out=None):
+    """gnnome_pagerank_steps_f64 (utils/data_utils.py:74-90) -> [N, pe_dim] in the caller's node numbering: the fp64 table itself for
+    dtype=float64, its one cast for float32.  Nothing synchronises."""
+    n, dev, pe_dim = views.num_nodes, views.device, int(pe_dim)
+    out = _pe_out(out, (n, pe_dim), dtype, dev, "pagerank_steps")
+    in_ptr, in_src, _, _, _, out_deg = _pe_lists(views)
+    table = out if dtype == torch.float64 else torch.empty((n, pe_dim), dtype=torch.float64, device=dev)
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().gnnome_pagerank_workspace_bytes(n, ctypes.byref(need)), "pagerank_workspace_bytes")
+    ws = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+    _call("gnnome_pagerank_steps_f64", dev, _ptr(in_ptr), _ptr(in_src), _ptr(out_deg), n, pe_dim, _ptr(table),
+          _ptr(None if dtype == torch.float64 else out), _ptr(ws), ws.numel())
+    if views.node_perm is not None:
+        out.copy_(out.index_select(0, views.node_perm))
+    return out
+
+
+def rw_return_lds_bytes(capacity):
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().gnnome_rw_return_lds_bytes(int(capacity), ctypes.byref(need)), "rw_return_lds_bytes")
+    return int(need.value)
+
+
+def rw_return(views, pe_dim, dtype=torch.float32, capacity=None, out=None, return_info=False):
+    """gnnome_rw_return_f64 (utils/data_utils.py:59-72) -> [N, pe_dim] in the caller's node numbering (with return_info: and info
+    int32[N, 2], per node of the views' numbering the largest expansion and the steps before its row was empty).  capacity: the (node,
+    value) pairs one expansion of a node's row may hold (default RW_DEFAULT_CAPACITY).  Synchronises once, on the status word: a row
+    that outgrows the capacity raises RuntimeError and `out` is left as it was."""
+    n, dev, pe_dim = views.num_nodes, views.device, int(pe_dim)
+    capacity = RW_DEFAULT_CAPACITY if capacity is None else int(capacity)
+    out = _pe_out(out, (n, pe_dim), dtype, dev, "rw_return")
+    _, _, out_ptr, out_dst, in_deg, _ = _pe_lists(views)
+    result = out if views.node_perm is None else torch.empty_like(out)
+    info = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().gnnome_rw_return_workspace_bytes(n, pe_dim, ctypes.byref(need)), "rw_return_workspace_bytes")
+    ws = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+    _call("gnnome_rw_return_f64", dev, _ptr(out_ptr), _ptr(out_dst), _ptr(in_deg), n, pe_dim, capacity, _ptr(result),
+          int(dtype == torch.float64), _ptr(info), _ptr(status), _ptr(ws), ws.numel())
+    if int(status.item()) != 0:
+        over = info[:, 0] > capacity
+        first = int(torch.nonzero(over)[0])
+        needed = int(info[first, 0])
+        node = first if views.node_gather is None else int(views.node_gather[first])
+        raise RuntimeError(f"rw_return: the row of node {node} needs at least {needed} (node, value) pairs in one step, capacity={capacity} "
+                           f"({int(over.sum())} of {n} nodes overflow); pass a larger capacity= (at most 4096: the row lives in LDS), "
+                           "or a smaller pe_dim")
+    if views.node_perm is not None:
+        out.copy_(result.index_select(0, views.node_perm))
+    return (out, info) if return_info else out

@@ -65,6 +65,8 @@ DEFAULT_HYPERPARAMETERS = {
     "masking": True,
     "mask_frac_low": 80,
     "mask_frac_high": 100,
+    "nb_pos_enc": 0,            # add_positional_encoding (utils/data_utils.py:53-54): 0 = off, as the reference ships it
+    "type_pos_enc": "none",     # 'RW' | 'PR'; anything else sets no pe
 }
 
 CHECKPOINT_KEYS = ("epoch", "model_state_dict", "optim_state_dict", "loss_train", "loss_valid", "scheduler_state_dict", "rng_state")
@@ -154,9 +156,22 @@ def _dataset_files(path):
     return sorted(found)
 
 
-def load_dataset(ds):
+def load_dataset(ds, hyperparameters=None, device=None):
     """A list of graph dicts (as gfa.read_gfa / dgl_io return them, each with y) -> [(name, dict)]; or a directory of <idx>.pt files
-    (torch.save of such a dict; trainer.process writes them), sorted by idx, and of <idx>.dgl files when DGL can be imported."""
+    (torch.save of such a dict; trainer.process writes them), sorted by idx, and of <idx>.dgl files when DGL can be imported.
+    hyperparameters: with nb_pos_enc > 0 every graph goes through positional.add_positional_encoding on `device`, as the reference's
+    dataset class does with every loaded graph (graph_dataset.py:50-52).  At nb_pos_enc = 0, the default, that call would only store the
+    degrees (data_utils.py:50-57), which _Graph counts at load anyway: the graphs are returned exactly as they were read."""
+    named = _read_dataset(ds)
+    hp = hyperparameters_with(hyperparameters)
+    if hp["nb_pos_enc"] > 0:
+        from .positional import add_positional_encoding
+        for _, g in named:
+            add_positional_encoding(g, hp["nb_pos_enc"], hp["type_pos_enc"], device=device)
+    return named
+
+
+def _read_dataset(ds):
     if isinstance(ds, (str, os.PathLike)):
         out = []
         try:
@@ -401,8 +416,8 @@ def _set_up(train_set, valid_set, out, hyperparameters, overfit, dropout, seed, 
     set_seed(seed)
     if out is None:
         out = datetime.now().strftime("%Y-%b-%d-%H-%M-%S")
-    ds_train = [_Graph(n, g, device, be) for n, g in load_dataset(train_set)]
-    ds_valid = ds_train if overfit else [_Graph(n, g, device, be) for n, g in load_dataset(valid_set)]
+    ds_train = [_Graph(n, g, device, be) for n, g in load_dataset(train_set, hp, device)]
+    ds_valid = ds_train if overfit else [_Graph(n, g, device, be) for n, g in load_dataset(valid_set, hp, device)]
     pos_weight = torch.tensor([pos_weight_of([(g.name, g.y) for g in ds_train])], device=device)
     model = model_class(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_ne_features"], hp["num_gnn_layers"],
                         hp["hidden_edge_scores"], hp["normalization"], dropout=dropout).to(device)

@@ -33,7 +33,7 @@ extern "C" {
  * gnnome_node_neighbour_sum_bwd_part_f32 and the four part entries of the attention sum (gnnome_node_attention_sum_part_f32, _stats_part_f32,
  * _bwd_dst_part_f32, _bwd_src_part_f32), which were ADDED without touching any other entry: a caller built against 32 keeps working, and
  * the Python binding resolves every entry by name when it loads the library, so a library that predates them is refused there, by name.
- * The three interval-union entries were added in the same way. */
+ * The three interval-union entries and the five positional-encoding entries were added in the same way. */
 #define GNNOME_ABI_VERSION 32
 
 #define GNNOME_OK 0
@@ -1365,6 +1365,45 @@ int gnnome_interval_union(const int64_t* start, const int64_t* end, const int32_
                           int32_t* isl_group, int64_t* isl_start, int64_t* isl_end, int64_t max_groups, int32_t* grp_code,
                           int64_t* grp_covered, int64_t* grp_count, int64_t* result_host, void* workspace, size_t workspace_bytes,
                           void* stream);
+
+/* ---- Positional encodings: k-step PageRank and random-walk return probabilities ------------------------------------------------------
+ * Replaces the nb_pos_enc > 0 half of utils/data_utils.py:44-92 (add_positional_encoding; the in_deg / out_deg half is read off the
+ * views' CSR pointers), as tests/positional_statement.py states it.  Both are fp64 until one final cast, use no atomics and sum in a
+ * fixed association: the same input gives the same bits on every launch.  num_nodes < 2^31, 1 <= pe_dim <= 1024; num_nodes == 0
+ * returns 0 without a launch.
+ *
+ * gnnome_pagerank_steps_f64 (data_utils.py:74-90): x_0 = 1/n, x_{t+1}[v] = 0.95 * sum_{u -> v} x_t[u] * dinv[u] + (1 - 0.95)/n with
+ *   dinv[u] = 1/(out_deg[u] + 1e-9), 0 where out_deg[u] < 1e-9; table[v, t] = x_{t+1}[v], t = 0 .. pe_dim-1 (double[num_nodes, pe_dim],
+ *   row-major, stays on the device).  in_ptr int32[N+1] / in_src int32[E]: the destination-sorted in-lists of the graph views
+ *   (in_ptr, srt_src); out_deg int32[N].  A parallel edge is one term per copy, a self-loop an ordinary edge.  One launch per step;
+ *   a destination's terms are added in list order, a list longer than 64 by the wavefront (lane l takes entries l, l + 64, ..., the
+ *   64 partial sums meet in the xor butterfly 32 .. 1).  out_f32 float[num_nodes, pe_dim], or NULL to keep the fp64 table only: the
+ *   reference's .float() (:88), one cast of the finished table.  Workspace: gnnome_pagerank_workspace_bytes (two fp64 vectors).
+ *
+ * gnnome_rw_return_f64 (data_utils.py:59-72): PE[i, t-1] = (M^t)[i, i], t = 1 .. pe_dim, M[u, v] = mult(u -> v) / max(in_deg[v], 1).
+ *   Which axis DGL's adjacency_matrix puts the sources on does not matter: the diagonal entry is the sum over the closed walks of
+ *   length t through i of the product of 1/max(in_deg, 1) over the walk's nodes, and the transposed convention sums the same walks
+ *   read backwards.  out_ptr int32[N+1] / out_dst int32[E]: the out-lists of the graph views; in_deg int32[N].  No matrix power is
+ *   formed: the workgroup of node i keeps the sparse row e_i^T M^t as (node id, fp64 value) pairs in LDS and advances it pe_dim
+ *   times through the out-lists - expand, sort the pairs by (node id, row order, edge order), add every run of equal ids left to
+ *   right - reading off the entry of i after each step; an empty row ends the node, its remaining columns are 0.
+ *   capacity: the (node, value) pairs ONE expansion may hold = the sum of the out-degrees over the row's nodes; it costs
+ *   gnnome_rw_return_lds_bytes = 8 * pow2ceil(capacity) + 24 * capacity + 4 bytes of LDS per workgroup, which must fit a CU's
+ *   160 KiB (capacity <= 4096; GNNOME_EINVAL beyond).  A node whose expansion would exceed it stops before writing anything past a
+ *   buffer, stores the size it needed in info and sets status[0] = 1 (zeroed here first).
+ *   info int32[num_nodes, 2]: per node the largest expansion it needed (at least that: a node stops at its first overflow) and the
+ *   number of steps it ran before its row was empty (pe_dim if it never was).
+ *   out: float[num_nodes, pe_dim], or double[...] with out_is_f64 != 0 - written by the last launch from the fp64 table in the
+ *   workspace (one cast, :70) and ONLY if no node overflowed: with status[0] = 1 `out` is untouched.  Nothing synchronises; the
+ *   caller reads status[0] after the stream.  Workspace: gnnome_rw_return_workspace_bytes (1/in_deg and the fp64 table). */
+int gnnome_pagerank_workspace_bytes(int64_t num_nodes, size_t* bytes_host);
+int gnnome_pagerank_steps_f64(const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_deg, int64_t num_nodes, int pe_dim,
+                              double* table, float* out_f32, void* workspace, size_t workspace_bytes, void* stream);
+int gnnome_rw_return_lds_bytes(int capacity, size_t* bytes_host);
+int gnnome_rw_return_workspace_bytes(int64_t num_nodes, int pe_dim, size_t* bytes_host);
+int gnnome_rw_return_f64(const int32_t* out_ptr, const int32_t* out_dst, const int32_t* in_deg, int64_t num_nodes, int pe_dim,
+                         int capacity, void* out, int out_is_f64, int32_t* info, int32_t* status, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
