@@ -172,6 +172,12 @@ SIGNATURES = {
     "gnnome_rw_return_lds_bytes": [_i, ctypes.POINTER(_sz)],
     "gnnome_rw_return_workspace_bytes": [_l, _i, ctypes.POINTER(_sz)],
     "gnnome_rw_return_f64": [_p, _p, _p, _l, _i, _i, _p, _i, _p, _p, _p, _sz, _p],
+    "gnnome_sketch_tile_size": [ctypes.POINTER(_i)],
+    "gnnome_sketch_workspace_bytes": [_l, ctypes.POINTER(_sz)],
+    "gnnome_sketch_reads": [_p, _p, _l, _i, _i, _p, _l, _p, _p, _p, _p, _l, _p, _p, _sz, _p],
+    "gnnome_seed_pairs_workspace_bytes": [_l, ctypes.POINTER(_sz)],
+    "gnnome_seed_pairs": [_p, _p, _p, _p, _l, _p, _l, _i, _i, _p, _p, _l, _p, _p, _sz, _p],
+    "gnnome_chain_overlaps": [_p, _p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p, _p],
 }
 
 ABI_VERSION = 32

@@ -126,6 +126,36 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
     return walks, contigs, stats
 
 
+def assemble_reads_to_fasta(reads_path, model, out_path, len_threshold, nb_paths=100, device=None, scores=None, use_labels=False,
+                            sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, long_overlaps=False, **overlap_kw):
+    """Reads -> overlap graph -> scores -> greedy walks -> contigs -> FASTA at out_path, with no assembler's GFA in between:
+    reads.read_reads_device (every record of the FASTA / FASTQ file, in file order; a repeated id keeps its last record) ->
+    overlapper.overlap_graph (overlap_kw: its k, w, max_occ, band, min_seeds, min_overlap, max_hang, max_pairs, drop_contained) ->
+    assemble_to_fasta on that dict.  -> (walks, contigs, stats, graph dict).  scores: one logit per edge instead of the model.
+    use_labels: the titles carry strand=, start=, end= and chr= (the simulator's), the dict gets the four read_* columns and y, and the
+    labels are the scores (+20 / -20 as logits: the reference's use_labels, whose floor is 1e-9)."""
+    from . import overlapper
+    from .reads import read_reads_device
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    names = list(dict.fromkeys(contigs_mod.read_titles(reads_path)))
+    res = read_reads_device(reads_path, names, device=device, sequences=True, titles=use_labels)
+    annotations = None
+    if use_labels:
+        if bool((res.missing != 0).any()):
+            raise ValueError(f"{reads_path}: use_labels needs strand=, start=, end= and chr= in every title")
+        cols = torch.repeat_interleave(res.ann, 2, dim=0)
+        cols[1::2, 0] = -cols[1::2, 0]
+        annotations = [cols[:, j].contiguous() for j in range(4)]
+    g = overlapper.overlap_graph((res.data, res.off), annotations=annotations, device=device, long_overlaps=long_overlaps, **overlap_kw)
+    g["node_to_read"] = {2 * r + s: n for r, n in enumerate(names) for s in (0, 1)}
+    if use_labels:
+        g["y"] = labels.process_graph(g, device=device)[1]
+        scores = (g["y"] * 2 - 1) * 20
+    walks, contigs, stats = assemble_to_fasta(g, model, out_path, len_threshold, nb_paths=nb_paths, device=device, scores=scores,
+                                              sampler=sampler, line_width=line_width, ref_length=ref_length)
+    return walks, contigs, stats, g
+
+
 def edge_report(g, model=None, scores=None, device=None):
     """The quality figures of a scorer on a labelled graph (a dict with `y`, e.g. read_gfa(training=True)): the confusion counts at
     0.5, the eight figures utils/metrics.py:15-46 derives from them and the two average precisions (:67-80).  `scores` (logits, one

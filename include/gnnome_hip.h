@@ -1405,6 +1405,57 @@ int gnnome_rw_return_f64(const int32_t* out_ptr, const int32_t* out_dst, const i
                          int capacity, void* out, int out_is_f64, int32_t* info, int32_t* status, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- Overlap graph from reads: minimizer sketch, seed pairs, banded chains -----------------------------------------------------------
+ * The step graph_dataset.py:76-186 leaves to hifiasm / raven, as tests/overlap_graph_statement.py states it: integers only, every output
+ * order fixed by a count and an exclusive scan before anything is written, no result depends on the grid or on the order atomics land in
+ * (there are none).  data uint8[total] / off int64[R+1]: the reads as overlap.pack_reads lays them out, data 4-byte aligned, R < 2^30,
+ * every read shorter than 2^30 bases.  1 <= k <= 31.
+ *
+ * The hash: bases A, C, G, T in either case are 0 .. 3, a k-mer's code is the smaller of its forward (first base most significant) and
+ * reverse-complement 2k-bit codes, strand = 1 where that is the reverse complement; a k-mer over any other byte, or equal to its reverse
+ * complement, is invalid.  With m = 2^(2k) - 1 the hash is Thomas Wang's 64-bit mix, every step masked to m (a bijection of [0, m]):
+ *   x = (~x + (x << 21)) & m; x ^= x >> 24; x = (x + (x << 3) + (x << 8)) & m; x ^= x >> 14; x = (x + (x << 2) + (x << 4)) & m;
+ *   x ^= x >> 28; x = (x + (x << 31)) & m.
+ *
+ * gnnome_sketch_reads: position p of a read is a minimizer when some window of w consecutive k-mer starts inside the read has its
+ *   smallest valid hash at p, ties to the leftmost; reads shorter than k + w - 1 give none.  One workgroup per tile of
+ *   gnnome_sketch_tile_size windows of one read; tile_first int64[R+1] (device): the exclusive scan of ceil(windows / tile) over the
+ *   reads, num_tiles = tile_first[R]; k + w - 1 <= 256.  Called twice on one workspace (gnnome_sketch_workspace_bytes(num_tiles)):
+ *   with hash == NULL it counts, scans and SYNCHRONISES `stream` once to fill result_host[0] (HOST memory) with the number of
+ *   minimizers M; with the four outputs (hash uint64, read int32, pos int32, strand uint8, each [capacity], capacity = M) it writes
+ *   them in (read, pos) order and does not synchronise.  The workspace starts with int64[num_tiles + 1]: the first output slot of every
+ *   tile, M last - a read's slice of the output starts at the slot of its first tile.
+ * gnnome_seed_pairs: hash / read / pos / strand [num_seeds]: the sketch sorted STABLY by hash.  A hash with more than max_occ seeds is
+ *   dropped whole; every other gives each pair of its seeds that lie in different reads, a < b their reads: rel = strand_a ^ strand_b,
+ *   pb' = pb if rel == 0 else len_b - k - pb, d = pa - pb'.  Record t is the two sort keys key_ab[t] = a << 32 | b << 1 | rel and
+ *   key_dp[t] = (d + 2^30) << 32 | pa; the order the records are written in is fixed (by the later seed, then by the earlier) and is
+ *   not the sorted order - the caller sorts by (key_ab, key_dp).  Called twice on one workspace (gnnome_seed_pairs_workspace_bytes):
+ *   key_ab == NULL counts, scans and SYNCHRONISES once to fill result_host[0] with the exact number of records P - nothing is
+ *   written anywhere but the workspace; with key_ab / key_dp int64[capacity], capacity = P, it writes them.  1 <= max_occ <= 2^20.
+ * gnnome_chain_overlaps: key_ab / key_dp [num_records] sorted by (key_ab, key_dp); group_start int64[num_groups + 1]: where each run
+ *   of equal key_ab starts, num_records last.  One wavefront per group walks it in order: a band starts at a record and takes every
+ *   following record whose d is at most `band` above the band's first d, the next band starts at the first record left out; per band
+ *   n_seeds, span_beg = min pa, span_end = max pa + k, d_beg = the d at the smallest pa (ties: smallest d), d_end = the d at the largest
+ *   pa (ties: largest d); the group's overlap is the band with the most seeds, ties to the first.  In the frame where a is forward and
+ *   b' is b (rel = 0) or its reverse complement, As = max(0, d_beg), Ae = min(len_a, len_b + d_end), and kind is, first match wins:
+ *   5 n_seeds < min_seeds; 0 (internal match) span_beg - As > max_hang or Ae - span_end > max_hang; 1 (b contained) d_beg >= 0 and
+ *   len_b + d_end <= len_a; 2 (a contained) d_beg <= 0 and len_a <= len_b + d_end; 3 (a -> b', edge (2a, 2b + rel)) d_beg > 0,
+ *   overlap_length = min(len_a - d_beg, len_b); 4 (b' -> a, edge (2b + rel, 2a)) the rest, overlap_length = min(len_b + d_beg, len_a);
+ *   a kind 3 or 4 with overlap_length < min_overlap becomes 6.  out int32[10, num_groups], one plane per field: a, b, rel, kind, d_beg,
+ *   d_end, n_seeds, span_beg, span_end, overlap_length (0 unless kind is 3, 4 or 6).  No workspace, no synchronisation. */
+int gnnome_sketch_tile_size(int* tile_host);
+int gnnome_sketch_workspace_bytes(int64_t num_tiles, size_t* bytes_host);
+int gnnome_sketch_reads(const uint8_t* data, const int64_t* off, int64_t num_reads, int k, int w, const int64_t* tile_first,
+                        int64_t num_tiles, uint64_t* hash, int32_t* read, int32_t* pos, uint8_t* strand, int64_t capacity,
+                        int64_t* result_host, void* workspace, size_t workspace_bytes, void* stream);
+int gnnome_seed_pairs_workspace_bytes(int64_t num_seeds, size_t* bytes_host);
+int gnnome_seed_pairs(const uint64_t* hash, const int32_t* read, const int32_t* pos, const uint8_t* strand, int64_t num_seeds,
+                      const int64_t* off, int64_t num_reads, int k, int max_occ, int64_t* key_ab, int64_t* key_dp, int64_t capacity,
+                      int64_t* result_host, void* workspace, size_t workspace_bytes, void* stream);
+int gnnome_chain_overlaps(const int64_t* key_ab, const int64_t* key_dp, int64_t num_records, const int64_t* group_start,
+                          int64_t num_groups, const int64_t* off, int64_t num_reads, int k, int band, int min_seeds, int min_overlap,
+                          int max_hang, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

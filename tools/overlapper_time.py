@@ -1,0 +1,119 @@
+"""Times gnnome_amd.overlapper on synthetic reads: a random genome read at 20x by error-free reads of one length on both strands
+(default 10 000 reads x 15 000 bases).  Every figure is a host clock around a call that ends in a device synchronise, after a warm-up
+call of the same shapes; the median of --repeats calls is reported.
+
+    python tools/overlapper_time.py [--reads 10000 --length 15000 --k 19 --w 10 --repeats 5 --statement-reads 200]
+
+Sketch: input bytes per second of the whole sketch_reads call, and the share of the HBM figure the project uses (8 TB/s) that the
+kernel's own traffic - every base twice, once per launch - amounts to.  A further pass with stats= takes device-event times of every
+stage (the median over the repeats): for the sketch the count stage (count launch, scan, size read-back) and the write launch alone - the
+write launch's bytes per second is the one figure that is a single kernel's; for find_overlaps the record kernel and the chain kernel
+as records per second, and torch's sorts beside them.  The only baseline is the NumPy / Python statement
+(tests/overlap_graph_statement.py) on the first --statement-reads reads of the same input, a host wall time labelled as such.
+Prints one JSON line."""
+import argparse
+import hashlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+HBM_BYTES_PER_S = 8e12
+_COMP = np.arange(256, dtype=np.uint8)
+for _a, _b in zip(b"ACGT", b"TGCA"):
+    _COMP[_a] = _b
+
+
+def make_reads(n, length, coverage, seed):
+    rng = np.random.default_rng(seed)
+    genome = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, max(n * length // coverage, 2 * length))]
+    start = rng.integers(0, len(genome) - length + 1, n)
+    flip = rng.integers(0, 2, n).astype(bool)
+    data = np.empty(n * length, dtype=np.uint8)
+    for i, (s, f) in enumerate(zip(start.tolist(), flip.tolist())):
+        piece = genome[s:s + length]
+        data[i * length:(i + 1) * length] = _COMP[piece[::-1]] if f else piece
+    return torch.from_numpy(data), torch.arange(n + 1, dtype=torch.int64) * length
+
+
+def timed(fn, repeats):
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    return statistics.median(times), min(times), max(times), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=10000)
+    ap.add_argument("--length", type=int, default=15000)
+    ap.add_argument("--coverage", type=int, default=20)
+    ap.add_argument("--k", type=int, default=19)
+    ap.add_argument("--w", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--statement-reads", type=int, default=200)
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("overlapper_time: no GPU - nothing is measured without one")
+    from gnnome_amd import overlapper
+    dev = torch.device("cuda", 0)
+    data, off = make_reads(a.reads, a.length, a.coverage, a.seed)
+    reads = (data.to(dev), off.to(dev))
+    nbytes = int(data.numel())
+    sk_t, sk_lo, sk_hi, sk = timed(lambda: overlapper.sketch_reads(reads, a.k, a.w), a.repeats)
+    ov_t, ov_lo, ov_hi, ov = timed(lambda: overlapper.find_overlaps(reads, sk), a.repeats)
+    P, kept = int(ov.records[0].numel()), len(ov)
+    sk_stats, ov_stats = [], []
+    for _ in range(a.repeats):
+        sk_stats.append({})
+        ov_stats.append({})
+        overlapper.find_overlaps(reads, overlapper.sketch_reads(reads, a.k, a.w, stats=sk_stats[-1]), stats=ov_stats[-1])
+    stage = lambda runs: {key: statistics.median(r[key] for r in runs) for key in runs[0] if key.endswith("_ms")}   # noqa: E731
+    sk_ms, ov_ms = stage(sk_stats), stage(ov_stats)
+    from gnnome_amd import _lib
+    with open(_lib.LIB_PATH, "rb") as f:
+        so_sha16 = hashlib.sha256(f.read()).hexdigest()[:16]
+    out = {"commit": subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip(),
+           "so_sha16": so_sha16,
+           "reads": a.reads, "length": a.length, "k": a.k, "w": a.w, "input_bytes": nbytes, "minimizers": len(sk), "seed_pairs": P,
+           "overlaps_kept": kept,
+           "sketch_call_s": sk_t, "sketch_call_s_min_max": [sk_lo, sk_hi], "sketch_input_bytes_per_s": nbytes / sk_t,
+           "sketch_share_of_hbm_2_reads_per_base": 2 * nbytes / sk_t / HBM_BYTES_PER_S,
+           "sketch_stage_ms": sk_ms, "sketch_write_launch_bytes_per_s": nbytes / (sk_ms["write_ms"] * 1e-3),
+           "sketch_write_launch_share_of_hbm": nbytes / (sk_ms["write_ms"] * 1e-3) / HBM_BYTES_PER_S,
+           "find_overlaps_stage_ms": ov_ms, "groups": ov_stats[0]["groups"],
+           "pair_kernel_records_per_s": P / (ov_ms["pairs_write_ms"] * 1e-3), "chain_kernel_records_per_s": P / (ov_ms["chain_ms"] * 1e-3),
+           "find_overlaps_call_s": ov_t, "find_overlaps_call_s_min_max": [ov_lo, ov_hi], "find_overlaps_records_per_s": P / ov_t}
+    del ov, sk
+    if a.statement_reads:
+        import overlap_graph_statement as st
+        n = min(a.statement_reads, a.reads)
+        host = data[:n * a.length].numpy().tobytes()
+        sub = [host[i * a.length:(i + 1) * a.length] for i in range(n)]
+        t0 = time.perf_counter()
+        st.sketch(sub, a.k, a.w)
+        t1 = time.perf_counter()
+        st.overlaps(sub, k=a.k, w=a.w)
+        t2 = time.perf_counter()
+        out.update(statement_reads=n, statement_sketch_wall_s=t1 - t0, statement_overlaps_wall_s=t2 - t1,
+                   statement_sketch_bytes_per_s=n * a.length / (t1 - t0))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
