@@ -121,10 +121,10 @@ class ReadStore:
         restriction is one gnnome_gfa_pack over the kept lengths; nothing visits the host."""
         if keep is None:
             return cls(data, off)
-        from .gfa import _pack
+        from .textscan import pack
         mask = _keep_mask(keep, int(off.numel()) - 1)
         lengths = (off[1:] - off[:-1]) * torch.from_numpy(mask).to(off.device)
-        kept, kept_off = _pack(_lib.load(), data, off[:-1], lengths, data.device)
+        kept, kept_off = pack(_lib.load(), data, off[:-1], lengths, data.device)
         return cls(kept, kept_off, ~mask)
 
     def sequence(self, node):

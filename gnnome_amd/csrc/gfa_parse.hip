@@ -2,7 +2,7 @@
 //
 //   gnnome_gfa_mark          elementwise over the file's bytes: field starts, field ends, line starts; the first byte >= 0x80 and
 //                            the first '\r' that no '\n' follows
-//   (compaction of the marks and the field index of every line: torch nonzero / searchsorted in gnnome_amd/gfa.py)
+//   (compaction of the marks and the field index of every line: torch nonzero / searchsorted in gnnome_amd/textscan.py tokenise)
 //   gnnome_gfa_classify      one thread per line: kind, byte ranges of the names, LN, overlap, orientation case, SI:f: tag
 //   gnnome_gfa_names_insert  the S names into an open-addressing table (32-bit compare-and-swap per slot)
 //   gnnome_gfa_links         both names of every L line looked up; the line's two events (sr, dr), (sv, dv)
@@ -15,7 +15,7 @@
 // or that this parser does not reproduce (see include/gnnome_hip.h) sets a per-line code, and the smallest such line is kept
 // with an integer atomicMin: the caller reads it after one synchronisation.  No float is produced here: a tag's value stays
 // text (the host converts all of them in one vectorised cast).  All byte offsets are int64.
-#include "common.h"
+#include "text_fields.h"   // the line descriptors, fields, digits, the line flag and the name hash: shared with the other text readers
 
 namespace gnnome {
 
@@ -27,7 +27,6 @@ constexpr int kPackChunks = 4;                                       // 16-byte 
 constexpr int64_t kPackTile = (int64_t)kPackThreads * 16 * kPackChunks;
 constexpr int kLineThreads = 256;
 constexpr int kRec = 8;                                              // int64 words per line record
-constexpr int kMaxDigits = 18;
 constexpr int kTagMax = 31;
 
 enum { kMarkStart = 1, kMarkEnd = 2, kMarkLine = 4 };
@@ -40,12 +39,6 @@ enum {
 };
 
 __device__ __forceinline__ bool is_ws(unsigned c) { return (c >= 0x09u && c <= 0x0du) || (c >= 0x1cu && c <= 0x20u); }
-__device__ __forceinline__ bool is_digit(unsigned c) { return c >= '0' && c <= '9'; }
-
-__device__ __forceinline__ void flag_line(int32_t* err, int32_t* first_bad, int64_t line, int code) {
-    atomicCAS(&err[line], 0, code);   // the first stage that objects names the reason; stages are separate launches
-    atomicMin(first_bad, (int32_t)line);
-}
 
 __global__ __launch_bounds__(kTokThreads) void k_gfa_mark(const uint8_t* __restrict__ buf, int64_t n, uint8_t* __restrict__ marks,
                                                           unsigned long long* bad_pos, int aligned) {
@@ -90,63 +83,22 @@ __global__ __launch_bounds__(kTokThreads) void k_gfa_mark(const uint8_t* __restr
     if (cr >= 0) atomicMin(&bad_pos[1], (unsigned long long)cr);
 }
 
-struct LineArgs {
-    const uint8_t* buf;
-    int64_t n;
-    const int64_t* fs;   // first byte of every field
-    const int64_t* fe;   // last byte of every field
-    int64_t F;
-    const int64_t* ff;   // [L+1] index of the first field at or after every line start; ff[L] = F
-    int64_t L;
-    int32_t* kind;
-    int64_t* rec;
-    int32_t* err;
-    int32_t* first_bad;
-};
-
-// field k as [b, e); false when the descriptors are not what gnnome_gfa_mark produces
-__device__ __forceinline__ bool field(const LineArgs& a, int64_t k, int64_t& b, int64_t& e) {
-    if (k < 0 || k >= a.F) return false;
-    b = a.fs[k];
-    e = a.fe[k] + 1;
-    return b >= 0 && b < e && e <= a.n;
-}
-
-__device__ __forceinline__ bool has_prefix(const uint8_t* buf, int64_t b, int64_t e, const char* p, int len) {
-    if (e - b < len) return false;
-    for (int j = 0; j < len; ++j)
-        if (buf[b + j] != (uint8_t)p[j]) return false;
-    return true;
-}
-
-// 1-18 plain digits in [b, e) -> value; false otherwise
-__device__ __forceinline__ bool parse_uint(const uint8_t* buf, int64_t b, int64_t e, int64_t& value) {
-    if (e - b < 1 || e - b > kMaxDigits) return false;
-    int64_t v = 0;
-    for (int64_t p = b; p < e; ++p) {
-        if (!is_digit(buf[p])) return false;
-        v = v * 10 + (buf[p] - '0');
-    }
-    value = v;
-    return true;
-}
-
 // [+-]? (digits [. digits*] | . digits) ([eE] [+-]? digits)? : text that float() and numpy's cast read alike
 __device__ __forceinline__ bool is_decimal(const uint8_t* buf, int64_t b, int64_t e) {
     int64_t p = b;
     if (p < e && (buf[p] == '+' || buf[p] == '-')) ++p;
     int64_t d = 0;
-    while (p < e && is_digit(buf[p])) ++p, ++d;
+    while (p < e && text_is_digit(buf[p])) ++p, ++d;
     if (p < e && buf[p] == '.') {
         ++p;
-        while (p < e && is_digit(buf[p])) ++p, ++d;
+        while (p < e && text_is_digit(buf[p])) ++p, ++d;
     }
     if (d == 0) return false;
     if (p < e && (buf[p] == 'e' || buf[p] == 'E')) {
         ++p;
         if (p < e && (buf[p] == '+' || buf[p] == '-')) ++p;
         int64_t x = 0;
-        while (p < e && is_digit(buf[p])) ++p, ++x;
+        while (p < e && text_is_digit(buf[p])) ++p, ++x;
         if (x == 0) return false;
     }
     return p == e;
@@ -155,14 +107,14 @@ __device__ __forceinline__ bool is_decimal(const uint8_t* buf, int64_t b, int64_
 // the hifiasm id of a 7-field link: everything before the LAST ":<digit>-" (gfa.py _HIFIASM_ID, greedy); false without one
 __device__ __forceinline__ bool trim_suffix(const uint8_t* buf, int64_t b, int64_t& e) {
     for (int64_t p = e - 3; p >= b; --p)
-        if (buf[p] == ':' && is_digit(buf[p + 1]) && buf[p + 2] == '-') {
+        if (buf[p] == ':' && text_is_digit(buf[p + 1]) && buf[p + 2] == '-') {
             e = p;
             return true;
         }
     return false;
 }
 
-__global__ __launch_bounds__(kLineThreads) void k_gfa_classify(const LineArgs a) {
+__global__ __launch_bounds__(kLineThreads) void k_gfa_classify(const TextLineArgs a, int32_t* __restrict__ kinds, int64_t* __restrict__ rec) {
     const int64_t l = (int64_t)blockIdx.x * kLineThreads + threadIdx.x;
     if (l >= a.L) return;
     int64_t r[kRec] = {-1, -1, -1, -1, 0, 0, -1, -1};
@@ -172,32 +124,32 @@ __global__ __launch_bounds__(kLineThreads) void k_gfa_classify(const LineArgs a)
     if (nf < 0 || f0 < 0 || f1 > a.F) {
         code = kGfaDescriptor;
     } else if (nf > 0) {
-        if (!field(a, f0, b, e)) {
+        if (!text_field(a, f0, b, e)) {
             code = kGfaDescriptor;
         } else if (e - b == 1 && a.buf[b] == 'S') {
             kind = kKindS;
             int64_t lb = 0, le = 0;
             if (nf < 4) {
                 code = kGfaSFields;
-            } else if (!field(a, f0 + 1, r[0], r[1]) || !field(a, f0 + 2, r[2], r[3]) || !field(a, f0 + 3, lb, le)) {
+            } else if (!text_field(a, f0 + 1, r[0], r[1]) || !text_field(a, f0 + 2, r[2], r[3]) || !text_field(a, f0 + 3, lb, le)) {
                 code = kGfaDescriptor;
             } else {
-                if (!parse_uint(a.buf, lb + 5 < le ? lb + 5 : le, le, r[4])) code = kGfaLength;   // int(length[5:])
-                r[5] = (r[3] - r[2] == 1 && a.buf[r[2]] == '*' ? 1 : 0) | (has_prefix(a.buf, r[0], r[1], "utg", 3) ? 2 : 0);
+                if (text_uint(a.buf, lb + 5 < le ? lb + 5 : le, le, r[4]) != kTextUintRead) code = kGfaLength;   // int(length[5:])
+                r[5] = (r[3] - r[2] == 1 && a.buf[r[2]] == '*' ? 1 : 0) | (text_has_prefix(a.buf, r[0], r[1], "utg", 3) ? 2 : 0);
             }
         } else if (e - b == 1 && a.buf[b] == 'A') {
             kind = kKindA;   // whether it belongs to a segment is decided over the kinds of its neighbours (gfa.py)
-            if (nf >= 5 && (!field(a, f0 + 4, r[0], r[1]) || !field(a, f0 + 3, r[2], r[3]))) code = kGfaDescriptor;
+            if (nf >= 5 && (!text_field(a, f0 + 4, r[0], r[1]) || !text_field(a, f0 + 3, r[2], r[3]))) code = kGfaDescriptor;
         } else if (e - b == 1 && a.buf[b] == 'L') {
             kind = kKindL;
             bool tagged = false;
             int64_t tb = -1, te = -1;
             for (int64_t k = f0 + 6; k < f1; ++k) {
-                if (!field(a, k, b, e)) {
+                if (!text_field(a, k, b, e)) {
                     code = kGfaDescriptor;
                     break;
                 }
-                if (has_prefix(a.buf, b, e, "SI:f:", 5)) {
+                if (text_has_prefix(a.buf, b, e, "SI:f:", 5)) {
                     tagged = true;
                     tb = b + 5, te = e;   // the first one is the tag
                     break;
@@ -209,8 +161,8 @@ __global__ __launch_bounds__(kLineThreads) void k_gfa_classify(const LineArgs a)
                 for (int j = 0; j < 6 && j < nf; ++j) kept[j] = f0 + j;
             } else {
                 for (int64_t k = f0; k < f1 && code == kGfaOk; ++k) {   // every SI:f: field is dropped, wherever it stands
-                    if (!field(a, k, b, e)) code = kGfaDescriptor;
-                    else if (!has_prefix(a.buf, b, e, "SI:f:", 5)) {
+                    if (!text_field(a, k, b, e)) code = kGfaDescriptor;
+                    else if (!text_has_prefix(a.buf, b, e, "SI:f:", 5)) {
                         if (count < 6) kept[count] = k;
                         ++count;
                     }
@@ -218,11 +170,11 @@ __global__ __launch_bounds__(kLineThreads) void k_gfa_classify(const LineArgs a)
             }
             int64_t ob[2] = {0, 0}, oe[2] = {0, 0}, cb = 0, ce = 0;
             if (code == kGfaOk && (count < 6 || count > 8)) code = kGfaLFields;
-            if (code == kGfaOk && !(field(a, kept[1], r[0], r[1]) && field(a, kept[3], r[2], r[3]) && field(a, kept[2], ob[0], oe[0]) &&
-                                    field(a, kept[4], ob[1], oe[1]) && field(a, kept[5], cb, ce)))
+            if (code == kGfaOk && !(text_field(a, kept[1], r[0], r[1]) && text_field(a, kept[3], r[2], r[3]) && text_field(a, kept[2], ob[0], oe[0]) &&
+                                    text_field(a, kept[4], ob[1], oe[1]) && text_field(a, kept[5], cb, ce)))
                 code = kGfaDescriptor;
             if (code == kGfaOk && count == 7 && !(trim_suffix(a.buf, r[0], r[1]) && trim_suffix(a.buf, r[2], r[3]))) code = kGfaSuffix;
-            if (code == kGfaOk && !parse_uint(a.buf, cb, ce - 1, r[4])) code = kGfaOverlap;   // int(cigar[:-1])
+            if (code == kGfaOk && text_uint(a.buf, cb, ce - 1, r[4]) != kTextUintRead) code = kGfaOverlap;   // int(cigar[:-1])
             if (code == kGfaOk) {
                 const bool p1 = oe[0] - ob[0] == 1 && a.buf[ob[0]] == '+', m1 = oe[0] - ob[0] == 1 && a.buf[ob[0]] == '-';
                 const bool p2 = oe[1] - ob[1] == 1 && a.buf[ob[1]] == '+', m2 = oe[1] - ob[1] == 1 && a.buf[ob[1]] == '-';
@@ -235,10 +187,10 @@ __global__ __launch_bounds__(kLineThreads) void k_gfa_classify(const LineArgs a)
             }
         }
     }
-    a.kind[l] = kind;
+    kinds[l] = kind;
     a.err[l] = code;
 #pragma unroll
-    for (int j = 0; j < kRec; ++j) a.rec[l * kRec + j] = r[j];
+    for (int j = 0; j < kRec; ++j) rec[l * kRec + j] = r[j];
     if (code != kGfaOk) atomicMin(a.first_bad, (int32_t)l);
 }
 
@@ -254,12 +206,6 @@ struct TableArgs {
     int64_t L;
     int32_t* first_bad;
 };
-
-__device__ __forceinline__ uint32_t name_hash(const uint8_t* buf, int64_t b, int64_t e) {   // FNV-1a
-    uint32_t h = 2166136261u;
-    for (int64_t p = b; p < e; ++p) h = (h ^ buf[p]) * 16777619u;
-    return h ^ (h >> 15);
-}
 
 __device__ __forceinline__ bool seg_name(const TableArgs& t, int64_t k, int64_t& b, int64_t& e) {
     if (k < 0 || k >= t.R) return false;
@@ -283,7 +229,7 @@ __global__ __launch_bounds__(kLineThreads) void k_gfa_names_insert(const TableAr
     if (k >= t.R) return;
     int64_t b, e;
     if (!seg_name(t, k, b, e)) return;   // an S line without a name field: flagged by the classifier
-    const uint32_t h = name_hash(t.buf, b, e);
+    const uint32_t h = text_hash(t.buf, b, e);
     for (int64_t probe = 0; probe < t.cap; ++probe) {
         const int64_t slot = (h + probe) & (t.cap - 1);
         const int32_t prev = atomicCAS(&t.table[slot], -1, (int32_t)k);
@@ -292,17 +238,16 @@ __global__ __launch_bounds__(kLineThreads) void k_gfa_names_insert(const TableAr
             const int32_t old = atomicMin(&t.table[slot], (int32_t)k);
             const int64_t loser = old > k ? old : k;
             const int64_t line = loser < t.R ? t.seg_line[loser] : -1;
-            if (line >= 0 && line < t.L) flag_line(t.err, t.first_bad, line, kGfaDuplicate);
+            text_flag(t.err, t.first_bad, line, t.L, kGfaDuplicate);
             return;
         }
     }
-    const int64_t line = t.seg_line[k];
-    if (line >= 0 && line < t.L) flag_line(t.err, t.first_bad, line, kGfaTableFull);
+    text_flag(t.err, t.first_bad, t.seg_line[k], t.L, kGfaTableFull);
 }
 
 // S index of the name in [b, e), or -1
 __device__ __forceinline__ int64_t lookup(const TableArgs& t, int64_t b, int64_t e) {
-    const uint32_t h = name_hash(t.buf, b, e);
+    const uint32_t h = text_hash(t.buf, b, e);
     for (int64_t probe = 0; probe < t.cap; ++probe) {
         const int32_t k = t.table[(h + probe) & (t.cap - 1)];
         if (k == -1) return -1;
@@ -323,9 +268,9 @@ __global__ __launch_bounds__(kLineThreads) void k_gfa_links(const TableArgs t, c
         r[2] <= r[3] && r[3] <= t.n) {   // a zero overlap is dropped before its names are looked at (gfa.py:161-163)
         const int64_t a = lookup(t, r[0], r[1]), b = lookup(t, r[2], r[3]);
         if (a < 0 || b < 0) {
-            flag_line(t.err, t.first_bad, line, kGfaUnknown);
+            text_flag(t.err, t.first_bad, line, t.L, kGfaUnknown);
         } else if (t.seg_line[a] > line || t.seg_line[b] > line) {
-            flag_line(t.err, t.first_bad, line, kGfaLater);
+            text_flag(t.err, t.first_bad, line, t.L, kGfaLater);
         } else {
             const int64_t a0 = 2 * a, a1 = 2 * a + 1, b0 = 2 * b, b1 = 2 * b + 1;
             switch ((int)r[5]) {   // graph_parser.py:302-321
@@ -435,12 +380,12 @@ extern "C" int gnnome_gfa_classify(const uint8_t* buf, int64_t num_bytes, const 
                                    int32_t* err, int32_t* first_bad, void* stream) {
     using namespace gnnome;
     if (num_lines == 0) return GNNOME_OK;
-    GN_REQUIRE(num_lines > 0 && num_fields >= 0 && num_bytes >= 0, "gfa_classify: negative size");
-    GN_REQUIRE(num_lines < ((int64_t)1 << 31) && num_fields < ((int64_t)1 << 31), "gfa_classify: line and field counts are int32");
-    GN_REQUIRE(line_field && kind && rec && err && first_bad && (num_fields == 0 || (buf && field_start && field_end)),
-               "gfa_classify: null pointer");
-    LineArgs a{buf, num_bytes, field_start, field_end, num_fields, line_field, num_lines, kind, rec, err, first_bad};
-    hipLaunchKernelGGL(k_gfa_classify, dim3((unsigned)blocks_for(num_lines, kLineThreads)), dim3(kLineThreads), 0, (hipStream_t)stream, a);
+    const TextLineArgs a{buf, num_bytes, field_start, field_end, num_fields, line_field, nullptr, num_lines, err, first_bad};
+    const int rc = text_line_args_ok(a, "gfa_classify");
+    if (rc != GNNOME_OK) return rc;
+    GN_REQUIRE(kind && rec, "gfa_classify: null pointer");
+    hipLaunchKernelGGL(k_gfa_classify, dim3((unsigned)blocks_for(num_lines, kLineThreads)), dim3(kLineThreads), 0, (hipStream_t)stream, a,
+                       kind, rec);
     GN_LAUNCH_CHECK();
     return GNNOME_OK;
 }

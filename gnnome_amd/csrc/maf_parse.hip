@@ -1,74 +1,27 @@
 // pbsim3 MAF files on the device (generate_data.py:43-60, change_description_pbsim: start and size from the reference line of every
 // alignment block, the strand from the read line; gnnome_amd/maf.py is the statement here).
 //
-//   (gnnome_gfa_mark tokenises the bytes unchanged: a 50 kb alignment text is two marks; compactions and the scans that group the s
-//    lines under the nearest a line are torch operators in gnnome_amd/maf.py; the wanted names go through gnnome_reads_names_insert /
-//    gnnome_reads_match as they are)
+//   (gnnome_amd/textscan.py tokenise: gnnome_gfa_mark marks the bytes - a 50 kb alignment text is two marks - and torch operators compact
+//    the marks into text_fields.h's descriptors; the scans that group the s lines under the nearest a line are torch operators in
+//    gnnome_amd/maf.py; the wanted names go through gnnome_reads_names_insert / gnnome_reads_match as they are: textscan.lookup_names)
 //   gnnome_maf_lines        one thread per line: blank / comment / a / s / other; an s line's name, start, size, strand and text range
 //   gnnome_maf_text_check   one wavefront per s line: the bytes of its text that are not '-' counted and compared with its size - the
 //                           only pass over the alignment texts
 //
 // Every byte range is checked against the buffer before it is read; a line this path does not serve gets a per-line code and the
 // smallest such line is kept with an integer atomicMin (gnnome_amd/maf.py _DECLINED names the codes).  No float is produced here.
-#include "common.h"
+#include "text_fields.h"   // the line descriptors, fields, digits and the line flag: shared with the other text readers
 
 namespace gnnome {
 
 constexpr int kMafThreads = 256;
-constexpr int kMafMaxDigits = 18;
 constexpr int kMafRec = 8;   // int64 words per s-line record
 
 // per-line codes (gnnome_amd/maf.py _DECLINED)
 enum { kMafOk = 0, kMafFields = 1, kMafNumber = 2, kMafDigits = 3, kMafStrand = 4, kMafOtherLine = 5, kMafSize = 9 };
 enum { kMafBlank = 0, kMafComment = 1, kMafA = 2, kMafS = 3, kMafOther = 4 };
 
-__device__ __forceinline__ void maf_flag(int32_t* err, int32_t* first_bad, int64_t line, int64_t L, int code) {
-    if (line < 0 || line >= L) return;
-    atomicCAS(&err[line], 0, code);
-    atomicMin(first_bad, (int32_t)line);
-}
-
-struct MafLineArgs {
-    const uint8_t* buf;
-    int64_t n;
-    const int64_t* fs;   // first byte of every field
-    const int64_t* fe;   // last byte of every field
-    int64_t F;
-    const int64_t* ff;   // [L+1] index of the first field at or after every line start; ff[L] = F
-    int64_t L;
-    int32_t* err;
-    int32_t* first_bad;
-};
-
-// field k as [b, e); false when the descriptors are not what gnnome_gfa_mark produces
-__device__ __forceinline__ bool maf_field(const MafLineArgs& a, int64_t k, int64_t& b, int64_t& e) {
-    if (k < 0 || k >= a.F) return false;
-    b = a.fs[k];
-    e = a.fe[k] + 1;
-    return b >= 0 && b < e && e <= a.n;
-}
-
-__device__ __forceinline__ bool maf_is(const uint8_t* buf, int64_t b, int64_t e, const char* word, int len) {
-    if (e - b != len) return false;
-    for (int j = 0; j < len; ++j)
-        if (buf[b + j] != (uint8_t)word[j]) return false;
-    return true;
-}
-
-// plain digits in [b, e) -> value.  0 read, kMafNumber a byte that is no digit, kMafDigits more than 18 of them
-__device__ __forceinline__ int maf_uint(const uint8_t* buf, int64_t b, int64_t e, int64_t& value) {
-    int64_t v = 0;
-    for (int64_t p = b; p < e; ++p) {
-        const unsigned c = buf[p];
-        if (c < '0' || c > '9') return kMafNumber;
-        if (p - b < kMafMaxDigits) v = v * 10 + (c - '0');
-    }
-    if (e - b > kMafMaxDigits) return kMafDigits;
-    value = v;
-    return kMafOk;
-}
-
-__global__ __launch_bounds__(kMafThreads) void k_maf_lines(const MafLineArgs a, int32_t* __restrict__ kind, int64_t* __restrict__ rec) {
+__global__ __launch_bounds__(kMafThreads) void k_maf_lines(const TextLineArgs a, int32_t* __restrict__ kind, int64_t* __restrict__ rec) {
     const int64_t l = (int64_t)blockIdx.x * kMafThreads + threadIdx.x;
     if (l >= a.L) return;
     int64_t r[kMafRec] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -76,27 +29,27 @@ __global__ __launch_bounds__(kMafThreads) void k_maf_lines(const MafLineArgs a, 
     const int64_t f0 = a.ff[l], f1 = a.ff[l + 1];
     int64_t b = 0, e = 0;
     if (f0 >= 0 && f0 < f1 && f1 <= a.F) {
-        if (!maf_field(a, f0, b, e)) {
+        if (!text_field(a, f0, b, e)) {
             k = kMafOther, code = kMafOtherLine;
-        } else if (a.buf[b] == '#' || maf_is(a.buf, b, e, "track", 5)) {
+        } else if (a.buf[b] == '#' || text_equals(a.buf, b, e, "track", 5)) {
             k = kMafComment;
-        } else if (maf_is(a.buf, b, e, "a", 1)) {
+        } else if (text_equals(a.buf, b, e, "a", 1)) {
             k = kMafA;
-        } else if (maf_is(a.buf, b, e, "s", 1)) {
+        } else if (text_equals(a.buf, b, e, "s", 1)) {
             k = kMafS;
             int64_t nb[7], ne[7];
             bool ok = f1 - f0 == 7;
-            for (int j = 0; ok && j < 7; ++j) ok = maf_field(a, f0 + j, nb[j], ne[j]);
+            for (int j = 0; ok && j < 7; ++j) ok = text_field(a, f0 + j, nb[j], ne[j]);
             if (!ok) {
                 code = kMafFields;
             } else {
                 int64_t start = 0, size = 0, src_size = 0;
-                const int rc[3] = {maf_uint(a.buf, nb[2], ne[2], start), maf_uint(a.buf, nb[3], ne[3], size),
-                                   maf_uint(a.buf, nb[5], ne[5], src_size)};
+                const int rc[3] = {text_uint(a.buf, nb[2], ne[2], start), text_uint(a.buf, nb[3], ne[3], size),
+                                   text_uint(a.buf, nb[5], ne[5], src_size)};
                 const unsigned sign = a.buf[nb[4]];
-                if (rc[0] == kMafNumber || rc[1] == kMafNumber || rc[2] == kMafNumber) code = kMafNumber;
+                if (rc[0] == kTextUintNoNumber || rc[1] == kTextUintNoNumber || rc[2] == kTextUintNoNumber) code = kMafNumber;
                 else if (ne[4] - nb[4] != 1 || (sign != '+' && sign != '-')) code = kMafStrand;
-                else if (rc[0] != kMafOk || rc[1] != kMafOk || rc[2] != kMafOk) code = kMafDigits;
+                else if (rc[0] != kTextUintRead || rc[1] != kTextUintRead || rc[2] != kTextUintRead) code = kMafDigits;
                 if (code == kMafOk) {
                     r[0] = nb[1], r[1] = ne[1], r[2] = start, r[3] = size, r[4] = sign == '+' ? 1 : -1, r[5] = nb[6], r[6] = ne[6], r[7] = 1;
                 }
@@ -105,7 +58,7 @@ __global__ __launch_bounds__(kMafThreads) void k_maf_lines(const MafLineArgs a, 
             k = kMafOther, code = kMafOtherLine;
         }
     }
-    if (code != kMafOk) maf_flag(a.err, a.first_bad, l, a.L, code);
+    if (code != kMafOk) text_flag(a.err, a.first_bad, l, a.L, code);
     kind[l] = k;
 #pragma unroll
     for (int j = 0; j < kMafRec; ++j) rec[l * kMafRec + j] = r[j];
@@ -144,7 +97,7 @@ __global__ __launch_bounds__(kMafThreads) void k_maf_text_check(const uint8_t* _
     }
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) dashes += __shfl_xor(dashes, o);
-    if (lane == 0 && (te - tb) - dashes != r[3]) maf_flag(err, first_bad, rec_line[s], L, kMafSize);
+    if (lane == 0 && (te - tb) - dashes != r[3]) text_flag(err, first_bad, rec_line[s], L, kMafSize);
 }
 
 }  // namespace gnnome
@@ -154,10 +107,10 @@ extern "C" int gnnome_maf_lines(const uint8_t* buf, int64_t num_bytes, const int
                                 void* stream) {
     using namespace gnnome;
     if (num_lines == 0) return GNNOME_OK;
-    GN_REQUIRE(num_lines > 0 && num_fields >= 0 && num_bytes > 0, "maf_lines: negative or zero size");
-    GN_REQUIRE(num_lines < ((int64_t)1 << 31) && num_fields < ((int64_t)1 << 31), "maf_lines: line and field counts are int32");
-    GN_REQUIRE(buf && line_field && kind && rec && err && first_bad && (num_fields == 0 || (field_start && field_end)), "maf_lines: null pointer");
-    MafLineArgs a{buf, num_bytes, field_start, field_end, num_fields, line_field, num_lines, err, first_bad};
+    const TextLineArgs a{buf, num_bytes, field_start, field_end, num_fields, line_field, nullptr, num_lines, err, first_bad};
+    const int rc = text_line_args_ok(a, "maf_lines");
+    if (rc != GNNOME_OK) return rc;
+    GN_REQUIRE(kind && rec, "maf_lines: null pointer");
     hipLaunchKernelGGL(k_maf_lines, dim3((unsigned)((num_lines + kMafThreads - 1) / kMafThreads)), dim3(kMafThreads), 0, (hipStream_t)stream, a,
                        kind, rec);
     GN_LAUNCH_CHECK();

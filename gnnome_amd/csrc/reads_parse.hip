@@ -1,7 +1,7 @@
 // FASTA / FASTQ reads files on the device (graph_parser.py:121-136 the titles, :213-272 the positions in them, :341-366 the sequences;
 // gnnome_amd/contigs.py _records / read_sequences / read_titles and gfa.py _annotation are their statement here).
 //
-//   (gnnome_gfa_mark tokenises the bytes unchanged; compaction of its marks and the field index of every line are torch operators)
+//   (gnnome_amd/textscan.py tokenise: gnnome_gfa_mark marks the bytes, torch operators compact the marks into text_fields.h's descriptors)
 //   gnnome_reads_records_fasta   one thread per line: header ('>' as the line's first byte) or sequence line; id, title, sequence ranges
 //   gnnome_reads_records_fastq   one thread per record over the non-blank lines: the four-line form checked, id, title, sequence ranges
 //   gnnome_reads_names_insert    the wanted names into an open-addressing table; equal names share a slot
@@ -22,83 +22,46 @@
 //
 // Every byte range is checked against the buffer before it is read; a line this path does not serve gets a per-line code and the
 // smallest such line is kept with an integer atomicMin (gnnome_amd/reads.py _DECLINED names the codes).  No float is produced here.
-#include "common.h"
+#include "text_fields.h"   // the line descriptors, fields, lines, digits, the line flag and the name hash: shared with the other text readers
 
 namespace gnnome {
 
 constexpr int kReadsThreads = 256;
-constexpr int kReadsMaxDigits = 18;
 
 // per-line codes (gnnome_amd/reads.py _DECLINED)
 enum { kReadsOk = 0, kReadsFields = 1, kReadsFourLine = 2, kReadsDigits = 3, kReadsChrMixed = 4 };
 enum { kLineBlank = 0, kLineHeader = 1, kLineSequence = 2 };
 
-__device__ __forceinline__ bool rd_is_digit(unsigned c) { return c >= '0' && c <= '9'; }
-
-__device__ __forceinline__ void rd_flag(int32_t* err, int32_t* first_bad, int64_t line, int64_t L, int code) {
-    if (line < 0 || line >= L) return;
-    atomicCAS(&err[line], 0, code);
-    atomicMin(first_bad, (int32_t)line);
-}
-
-struct ReadsLineArgs {
-    const uint8_t* buf;
-    int64_t n;
-    const int64_t* fs;   // first byte of every field
-    const int64_t* fe;   // last byte of every field
-    int64_t F;
-    const int64_t* ff;   // [L+1] index of the first field at or after every line start; ff[L] = F
-    const int64_t* ls;   // [L] first byte of every line
-    int64_t L;
-    int32_t* err;
-    int32_t* first_bad;
-};
-
-// field k as [b, e); false when the descriptors are not what gnnome_gfa_mark produces
-__device__ __forceinline__ bool rd_field(const ReadsLineArgs& a, int64_t k, int64_t& b, int64_t& e) {
-    if (k < 0 || k >= a.F) return false;
-    b = a.fs[k];
-    e = a.fe[k] + 1;
-    return b >= 0 && b < e && e <= a.n;
-}
-
-// fields [f0, f1) of line l; false when the line is outside the arrays
-__device__ __forceinline__ bool rd_line(const ReadsLineArgs& a, int64_t l, int64_t& start, int64_t& f0, int64_t& f1) {
-    if (l < 0 || l >= a.L) return false;
-    start = a.ls[l], f0 = a.ff[l], f1 = a.ff[l + 1];
-    return start >= 0 && start < a.n && f0 >= 0 && f0 <= f1 && f1 <= a.F;
-}
-
 // A header line that starts at `start` with its marker byte: id = the first whitespace-separated token of line[1:], title =
 // line[1:].rstrip(), both as [b, e).  out[0..3] = id_b, id_e, title_b, title_e.
-__device__ __forceinline__ bool rd_header(const ReadsLineArgs& a, int64_t start, int64_t f0, int64_t f1, int64_t* out) {
+__device__ __forceinline__ bool rd_header(const TextLineArgs& a, int64_t start, int64_t f0, int64_t f1, int64_t* out) {
     int64_t b = 0, e = 0, lb = 0, le = 0;
-    if (f1 <= f0 || !rd_field(a, f0, b, e) || b != start || !rd_field(a, f1 - 1, lb, le)) return false;
+    if (f1 <= f0 || !text_field(a, f0, b, e) || b != start || !text_field(a, f1 - 1, lb, le)) return false;
     out[2] = start + 1;
     out[3] = le > start + 1 ? le : start + 1;
     if (e - b > 1) {                                   // ">id ..."
         out[0] = start + 1, out[1] = e;
     } else if (f1 - f0 >= 2) {                         // "> id ...": the marker alone is the first field
-        if (!rd_field(a, f0 + 1, out[0], out[1])) return false;
+        if (!text_field(a, f0 + 1, out[0], out[1])) return false;
     } else {
         out[0] = out[1] = start + 1;                   // nothing behind the marker: the empty id
     }
     return true;
 }
 
-__global__ __launch_bounds__(kReadsThreads) void k_reads_records_fasta(const ReadsLineArgs a, const int64_t* __restrict__ first_header,
+__global__ __launch_bounds__(kReadsThreads) void k_reads_records_fasta(const TextLineArgs a, const int64_t* __restrict__ first_header,
                                                                        int32_t* __restrict__ kind, int64_t* __restrict__ rec) {
     const int64_t l = (int64_t)blockIdx.x * kReadsThreads + threadIdx.x;
     if (l >= a.L) return;
     int64_t r[4] = {0, 0, 0, 0};
     int k = kLineBlank;
     int64_t start = 0, f0 = 0, f1 = 0;
-    if (rd_line(a, l, start, f0, f1) && f1 > f0) {
+    if (text_line(a, l, start, f0, f1) && f1 > f0) {
         if (a.buf[start] == '>') {
             if (rd_header(a, start, f0, f1, r)) k = kLineHeader;
-        } else if (rd_field(a, f0, r[0], r[1])) {
+        } else if (text_field(a, f0, r[0], r[1])) {
             k = kLineSequence;
-            if (f1 - f0 > 1 && l > *first_header) rd_flag(a.err, a.first_bad, l, a.L, kReadsFields);   // above the first header: no record's
+            if (f1 - f0 > 1 && l > *first_header) text_flag(a.err, a.first_bad, l, a.L, kReadsFields);   // above the first header: no record's
         }
     }
     kind[l] = k;
@@ -106,7 +69,7 @@ __global__ __launch_bounds__(kReadsThreads) void k_reads_records_fasta(const Rea
     for (int j = 0; j < 4; ++j) rec[l * 4 + j] = r[j];
 }
 
-__global__ __launch_bounds__(kReadsThreads) void k_reads_records_fastq(const ReadsLineArgs a, const int64_t* __restrict__ nonblank, int64_t Q,
+__global__ __launch_bounds__(kReadsThreads) void k_reads_records_fastq(const TextLineArgs a, const int64_t* __restrict__ nonblank, int64_t Q,
                                                                        int64_t K, int64_t* __restrict__ rec) {
     const int64_t k = (int64_t)blockIdx.x * kReadsThreads + threadIdx.x;
     if (k >= K) return;
@@ -120,20 +83,20 @@ __global__ __launch_bounds__(kReadsThreads) void k_reads_records_fastq(const Rea
         bool ok = true;
         for (int j = 0; j < 4; ++j) {
             line[j] = nonblank[4 * k + j];
-            ok = ok && rd_line(a, line[j], start[j], f0[j], f1[j]) && f1[j] > f0[j];
+            ok = ok && text_line(a, line[j], start[j], f0[j], f1[j]) && f1[j] > f0[j];
         }
         int64_t qb = 0, qe = 0;
         if (!ok) bad = l0;
         else if (a.buf[start[0]] != '@' || !rd_header(a, start[0], f0[0], f1[0], r)) bad = line[0];
-        else if (a.buf[start[1]] == '+' || !rd_field(a, f0[1], r[4], r[5])) bad = line[1];
+        else if (a.buf[start[1]] == '+' || !text_field(a, f0[1], r[4], r[5])) bad = line[1];
         else if (f1[1] - f0[1] != 1) bad = -2 - line[1];
         else if (a.buf[start[2]] != '+') bad = line[2];
-        else if (!rd_field(a, f0[3], qb, qe)) bad = line[3];
+        else if (!text_field(a, f0[3], qb, qe)) bad = line[3];
         else if (f1[3] - f0[3] != 1) bad = -2 - line[3];
         else if (qe - qb != r[5] - r[4]) bad = line[3];
     }
-    if (bad <= -2) rd_flag(a.err, a.first_bad, -2 - bad, a.L, kReadsFields);
-    else if (bad >= 0) rd_flag(a.err, a.first_bad, bad, a.L, kReadsFourLine);
+    if (bad <= -2) text_flag(a.err, a.first_bad, -2 - bad, a.L, kReadsFields);
+    else if (bad >= 0) text_flag(a.err, a.first_bad, bad, a.L, kReadsFourLine);
     if (bad != -1) r[0] = r[1] = r[2] = r[3] = r[4] = r[5] = 0;
 #pragma unroll
     for (int j = 0; j < 6; ++j) rec[k * 6 + j] = r[j];
@@ -147,12 +110,6 @@ struct NamesArgs {
     int32_t* table;
     int64_t cap;               // a power of two; fewer slots than distinct names: the insert reports it
 };
-
-__device__ __forceinline__ uint32_t rd_hash(const uint8_t* p, int64_t b, int64_t e) {   // FNV-1a, as gfa_parse.hip
-    uint32_t h = 2166136261u;
-    for (int64_t q = b; q < e; ++q) h = (h ^ p[q]) * 16777619u;
-    return h ^ (h >> 15);
-}
 
 __device__ __forceinline__ bool rd_name(const NamesArgs& t, int64_t r, int64_t& b, int64_t& e) {
     if (r < 0 || r >= t.R) return false;
@@ -175,7 +132,7 @@ __device__ __forceinline__ bool rd_same(const NamesArgs& t, int64_t r, const uin
 // Kept out of line on purpose: with this loop inlined into the kernel (a break under `claimed || same bytes`), the code hipcc generated
 // for gfx950 lost the slot on the same-bytes path - every repeated name came back as -1 on the MI355X - while this form returns it.
 __device__ __noinline__ int32_t rd_claim(const NamesArgs& t, int64_t r, int64_t b, int64_t e) {
-    const uint32_t h = rd_hash(t.names, b, e);
+    const uint32_t h = text_hash(t.names, b, e);
     for (int64_t probe = 0; probe < t.cap; ++probe) {
         const int64_t slot = (h + probe) & (t.cap - 1);
         const int32_t prev = atomicCAS(&t.table[slot], -1, (int32_t)r);
@@ -201,7 +158,7 @@ __global__ __launch_bounds__(kReadsThreads) void k_reads_match(const NamesArgs t
     if (k >= K) return;
     const int64_t b = rec[k * stride], e = rec[k * stride + 1];
     if (b < 0 || b > e || e > n) return;
-    const uint32_t h = rd_hash(buf, b, e);
+    const uint32_t h = text_hash(buf, b, e);
     for (int64_t probe = 0; probe < t.cap; ++probe) {
         const int64_t slot = (h + probe) & (t.cap - 1);
         const int32_t r = t.table[slot];
@@ -223,7 +180,7 @@ __device__ __forceinline__ int64_t rd_find(const uint8_t* buf, int64_t from, int
     return -1;
 }
 
-__device__ __forceinline__ bool rd_is_chr(unsigned c) { return rd_is_digit(c) || c == 'X' || c == 'Y' || c == 'M'; }
+__device__ __forceinline__ bool rd_is_chr(unsigned c) { return text_is_digit(c) || c == 'X' || c == 'Y' || c == 'M'; }
 
 // key followed by a run of digits: the first such place in [b, e), as re.search(key + r"(\d+)") finds it.  0 found, 1 missing, 2 the
 // run has more than 18 digits
@@ -232,14 +189,14 @@ __device__ __forceinline__ int rd_number(const uint8_t* buf, int64_t b, int64_t 
         const int64_t p = rd_find(buf, from, e, key, len);
         if (p < 0) return 1;
         int64_t q = p + len;
-        if (!rd_is_digit(buf[q])) {
+        if (!text_is_digit(buf[q])) {
             from = p + 1;
             continue;
         }
         int64_t v = 0;
         int digits = 0;
-        for (; q < e && rd_is_digit(buf[q]); ++q) {
-            if (++digits > kReadsMaxDigits) return 2;
+        for (; q < e && text_is_digit(buf[q]); ++q) {
+            if (++digits > kTextMaxDigits) return 2;
             v = v * 10 + (buf[q] - '0');
         }
         value = v;
@@ -279,8 +236,8 @@ __global__ __launch_bounds__(kReadsThreads) void k_reads_annotations(const uint8
                 int64_t q = p + 4, value = 0;
                 int digits = 0, letters = 0;
                 for (; q < e && rd_is_chr(buf[q]); ++q) {
-                    if (rd_is_digit(buf[q])) {
-                        if (++digits <= kReadsMaxDigits) value = value * 10 + (buf[q] - '0');
+                    if (text_is_digit(buf[q])) {
+                        if (++digits <= kTextMaxDigits) value = value * 10 + (buf[q] - '0');
                     } else {
                         ++letters;
                     }
@@ -288,10 +245,10 @@ __global__ __launch_bounds__(kReadsThreads) void k_reads_annotations(const uint8
                 const unsigned c = buf[p + 4];
                 if (letters == 1 && digits == 0) v[3] = c == 'X' ? -1 : c == 'Y' ? -2 : -3;
                 else if (letters != 0) code = kReadsChrMixed;      // the host's int() raises on it
-                else if (digits > kReadsMaxDigits) code = kReadsDigits;
+                else if (digits > kTextMaxDigits) code = kReadsDigits;
                 else v[3] = value;
             }
-            if (code != kReadsOk) rd_flag(err, first_bad, rec_line[k], L, code);
+            if (code != kReadsOk) text_flag(err, first_bad, rec_line[k], L, code);
         }
     }
 #pragma unroll
@@ -300,15 +257,6 @@ __global__ __launch_bounds__(kReadsThreads) void k_reads_annotations(const uint8
 }
 
 static inline int64_t reads_blocks(int64_t items) { return (items + kReadsThreads - 1) / kReadsThreads; }
-
-static int reads_line_args_ok(const uint8_t* buf, int64_t num_bytes, const int64_t* field_start, const int64_t* field_end, int64_t num_fields,
-                              const int64_t* line_field, const int64_t* line_start, int64_t num_lines, const int32_t* err,
-                              const int32_t* first_bad, const char* who) {
-    GN_REQUIRE(num_lines > 0 && num_fields >= 0 && num_bytes > 0, "%s: negative or zero size", who);
-    GN_REQUIRE(num_lines < ((int64_t)1 << 31) && num_fields < ((int64_t)1 << 31), "%s: line and field counts are int32", who);
-    GN_REQUIRE(buf && line_field && line_start && err && first_bad && (num_fields == 0 || (field_start && field_end)), "%s: null pointer", who);
-    return GNNOME_OK;
-}
 
 static int reads_names_ok(const uint8_t* names, int64_t names_bytes, const int64_t* name_off, int64_t num_names, const int32_t* table,
                           int64_t capacity, const char* who) {
@@ -327,11 +275,10 @@ extern "C" int gnnome_reads_records_fasta(const uint8_t* buf, int64_t num_bytes,
                                           void* stream) {
     using namespace gnnome;
     if (num_lines == 0) return GNNOME_OK;
-    const int rc = reads_line_args_ok(buf, num_bytes, field_start, field_end, num_fields, line_field, line_start, num_lines, err, first_bad,
-                                      "reads_records_fasta");
+    const TextLineArgs a{buf, num_bytes, field_start, field_end, num_fields, line_field, line_start, num_lines, err, first_bad};
+    const int rc = text_line_args_ok(a, "reads_records_fasta");
     if (rc != GNNOME_OK) return rc;
-    GN_REQUIRE(first_header && kind && rec, "reads_records_fasta: null pointer");
-    ReadsLineArgs a{buf, num_bytes, field_start, field_end, num_fields, line_field, line_start, num_lines, err, first_bad};
+    GN_REQUIRE(line_start && first_header && kind && rec, "reads_records_fasta: null pointer");
     hipLaunchKernelGGL(k_reads_records_fasta, dim3((unsigned)reads_blocks(num_lines)), dim3(kReadsThreads), 0, (hipStream_t)stream, a,
                        first_header, kind, rec);
     GN_LAUNCH_CHECK();
@@ -344,14 +291,13 @@ extern "C" int gnnome_reads_records_fastq(const uint8_t* buf, int64_t num_bytes,
                                           void* stream) {
     using namespace gnnome;
     if (num_nonblank == 0) return GNNOME_OK;
-    const int rc = reads_line_args_ok(buf, num_bytes, field_start, field_end, num_fields, line_field, line_start, num_lines, err, first_bad,
-                                      "reads_records_fastq");
+    const TextLineArgs a{buf, num_bytes, field_start, field_end, num_fields, line_field, line_start, num_lines, err, first_bad};
+    const int rc = text_line_args_ok(a, "reads_records_fastq");
     if (rc != GNNOME_OK) return rc;
     GN_REQUIRE(num_nonblank > 0 && num_nonblank <= num_lines, "reads_records_fastq: %lld non-blank lines of %lld", (long long)num_nonblank,
                (long long)num_lines);
-    GN_REQUIRE(nonblank && rec, "reads_records_fastq: null pointer");
+    GN_REQUIRE(line_start && nonblank && rec, "reads_records_fastq: null pointer");
     const int64_t K = (num_nonblank + 3) / 4;
-    ReadsLineArgs a{buf, num_bytes, field_start, field_end, num_fields, line_field, line_start, num_lines, err, first_bad};
     hipLaunchKernelGGL(k_reads_records_fastq, dim3((unsigned)reads_blocks(K)), dim3(kReadsThreads), 0, (hipStream_t)stream, a, nonblank,
                        num_nonblank, K, rec);
     GN_LAUNCH_CHECK();

@@ -47,13 +47,14 @@ read_gfa_device / read_gfa(parser="device" | "auto") is a second implementation 
 "reads" - the S-line sequences packed as overlap.pack_reads packs them.  What it declines (GfaDeviceError names the line) is
 listed at _DECLINED; parser="auto" then runs the host parser, which returns or raises as it always did."""
 import gzip
-import os
 import re
 import warnings
 from collections import Counter
 
 import numpy as np
 import torch
+
+from .textscan import DeviceDecline, first_decline, pack, read_bytes, texts, tokenise
 
 _HIFIASM_ID = re.compile(r"(.*):\d-\d*")
 # Bio.Seq.reverse_complement's table (IUPAC ambiguity codes, both cases) - the same one gnnome_amd/overlap.py hands the device
@@ -294,13 +295,12 @@ def write_similarity_tags(gfa_in, gfa_out, similarity):
             o.write(raw)
 
 
-# ---- the device parser (csrc/gfa_parse.hip) ---------------------------------------------------------------------------------------
+# ---- the device parser (csrc/gfa_parse.hip; the bytes, their tokens and the rule for the reported decline: textscan.py) ----------------
 
 TOKENISE_TILE = 4096    # bytes one workgroup of gnnome_gfa_mark covers (gnnome_gfa_tile_sizes reports the library's own)
 PACK_TILE = 16384       # output bytes one workgroup of gnnome_gfa_pack writes
 TAG_SLOT = 32           # bytes of the slot an SI:f: value is packed into (the value itself: at most 31)
 _REC = 8
-_NONZERO_CHUNK = 1 << 30
 
 # What the device parser declines, by the code gnnome_gfa_classify / _names_insert / _links leave on the line
 _DECLINED = {
@@ -322,12 +322,9 @@ _DECLINED = {
 }
 
 
-class GfaDeviceError(ValueError):
+class GfaDeviceError(DeviceDecline):
     """The device parser declines the file: .line (1-based) and .reason; read_gfa's host parser takes any GFA."""
-
-    def __init__(self, path, line, reason):
-        super().__init__(f"{path}: line {line}: {reason} - not served by the device parser (read_gfa(parser='host') or 'auto')")
-        self.line, self.reason = line, reason
+    SERVED_BY = "the device parser (read_gfa(parser='host') or 'auto')"
 
 
 def assemble_edges(u, v, overlap, tag, num_nodes):
@@ -349,88 +346,23 @@ def assemble_edges(u, v, overlap, tag, num_nodes):
     return u[first_ev], v[first_ev], overlap[last_ev], tag[last_ev]
 
 
-def _positions(marks, bit):
-    """int64 positions of the bytes that carry `bit`, in rising order (nonzero in pieces: a file may exceed 2^31 bytes)."""
-    n = int(marks.numel())
-    parts = [torch.nonzero(marks[a:a + _NONZERO_CHUNK] & bit).squeeze(1) + a for a in range(0, n, _NONZERO_CHUNK)]
-    return parts[0] if len(parts) == 1 else torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=marks.device)
-
-
-def _pack(lib, src, src_beg, lengths, device):
-    """(uint8[total], int64[R+1]): src[src_beg[r] : src_beg[r] + lengths[r]] for every r, concatenated (gnnome_gfa_pack)."""
-    from .ops import _on, _ptr, _stream
-    R = int(lengths.numel())
-    off = torch.zeros(R + 1, dtype=torch.int64, device=device)
-    torch.cumsum(lengths, 0, out=off[1:])
-    total = int(off[-1]) if R else 0
-    out = torch.empty(total, dtype=torch.uint8, device=device)
-    src_beg = src_beg.contiguous()
-    if total:
-        with _on(device):
-            _lib_check(lib.gnnome_gfa_pack(_ptr(src), int(src.numel()), _ptr(src_beg), _ptr(off), R, _ptr(out), total, _stream(device)),
-                       "gfa_pack")
-    return out, off
-
-
-def _lib_check(rc, what):
-    from . import _lib
-    _lib.check(rc, what)
-
-
-def _texts(lib, buf, beg, end, device):
-    """The fields [beg, end) as a list of str: one blob, the fields joined by '\\n', one copy to the host, one split."""
-    k = int(beg.numel())
-    if k == 0:
-        return []
-    blob, off = _pack(lib, buf, beg, end - beg + 1, device)   # one byte more than the field: the whitespace behind it
-    blob[off[1:] - 1] = 10
-    return blob.cpu().numpy().tobytes().decode("ascii").split("\n")[:-1]
-
-
-def _read_bytes(path):
-    if str(path).endswith(".gz"):
-        with gzip.open(path, "rb") as f:
-            return np.frombuffer(f.read(), dtype=np.uint8).copy()
-    with open(path, "rb") as f:
-        data = np.empty(os.fstat(f.fileno()).st_size, dtype=np.uint8)
-        got = 0
-        while got < data.size:
-            k = f.readinto(memoryview(data)[got:])
-            if not k:
-                break
-            got += k
-        return data[:got]
-
-
 def _parse_on_device(data, device, path="<bytes>", table_capacity=None):
     """uint8 bytes of a GFA (numpy or tensor) -> the device-side parse: dict(num_nodes, src, dst, overlap_length, tag_begin, tag_length
     per edge, read_length, buf, seg / arun records for the names, reads).  Raises GfaDeviceError for what _DECLINED lists."""
     from . import _lib
     from .ops import _on, _ptr, _stream
     lib = _lib.load()
-    buf = (torch.from_numpy(data) if isinstance(data, np.ndarray) else data).to(device).contiguous()
-    n = int(buf.numel())
+    tok = tokenise(data, device)
+    buf, n, ff, L, first_bad = tok.buf, tok.n, tok.ff, tok.L, tok.first_bad
+    err = tok.err[:L]   # no line, no pointer: the library refuses the empty file (the parsers' callers get RuntimeError), as it always did
     i64 = dict(dtype=torch.int64, device=device)
     i32 = dict(dtype=torch.int32, device=device)
-    marks = torch.empty(n, dtype=torch.uint8, device=device)
-    bad_pos = torch.full((2,), torch.iinfo(torch.int64).max, **i64)
-    first_bad = torch.full((1,), torch.iinfo(torch.int32).max, **i32)
-    with _on(device):
-        _lib.check(lib.gnnome_gfa_mark(_ptr(buf), n, _ptr(marks), _ptr(bad_pos), _stream(device)), "gfa_mark")
-    fs, fe, ls = _positions(marks, 1), _positions(marks, 2), _positions(marks, 4)
-    del marks
-    F, L = int(fs.numel()), int(ls.numel())
-    ff = torch.empty(L + 1, **i64)
-    ff[:L] = torch.searchsorted(fs, ls)
-    ff[L] = F
     kind = torch.zeros(L, **i32)
     rec = torch.empty(L, _REC, **i64)
-    err = torch.zeros(L, **i32)
     with _on(device):
-        _lib.check(lib.gnnome_gfa_classify(_ptr(buf), n, _ptr(fs), _ptr(fe), F, _ptr(ff), L, _ptr(kind), _ptr(rec), _ptr(err),
-                                           _ptr(first_bad), _stream(device)), "gfa_classify")
+        _lib.check(lib.gnnome_gfa_classify(*tok.line_args(), _ptr(kind), _ptr(rec), _ptr(err), _ptr(first_bad), _stream(device)),
+                   "gfa_classify")
     nf = ff[1:] - ff[:-1]
-    del fs, fe
     s_line = torch.nonzero(kind == 1).squeeze(1)
     l_line = torch.nonzero(kind == 2).squeeze(1)
     R, M = int(s_line.numel()), int(l_line.numel())
@@ -453,20 +385,10 @@ def _parse_on_device(data, device, path="<bytes>", table_capacity=None):
     a_line = torch.nonzero(in_run).squeeze(1)
     a_short = a_line[nf[a_line] < 5]
     big = torch.iinfo(torch.int64).max
-    report = torch.stack([first_bad[0].long(), a_short.min() if a_short.numel() else first_bad.new_tensor(big, dtype=torch.int64),
-                          bad_pos[0], bad_pos[1]]).cpu().tolist()     # the one synchronisation that reports
-    bad_line, a_bad, hi_pos, cr_pos = report
-    cands = []
-    for pos, code in ((hi_pos, 12), (cr_pos, 13)):
-        if pos != big:
-            cands.append((int(torch.searchsorted(ls, ls.new_tensor([pos]), right=True)) - 1, 0, code))
-    if bad_line != torch.iinfo(torch.int32).max:
-        cands.append((bad_line, 1, int(err[bad_line])))
-    if a_bad != big:
-        cands.append((a_bad, 2, 8))
-    if cands:
-        line, _, code = min(cands)
-        raise GfaDeviceError(path, line + 1, _DECLINED.get(code, f"code {code}"))
+    found, _ = first_decline(tok, 12, 13, extra_scalars=(a_short.min() if a_short.numel() else a_short.new_tensor(big),),
+                             extra_candidates=lambda a_bad: [(a_bad, 2, 8)] if a_bad != big else [])
+    if found is not None:
+        raise GfaDeviceError(path, found[0] + 1, _DECLINED.get(found[1], f"code {found[1]}"))
     valid = ev_u >= 0
     ev = torch.nonzero(valid).squeeze(1)
     u, v = ev_u[ev], ev_v[ev]
@@ -478,7 +400,7 @@ def _parse_on_device(data, device, path="<bytes>", table_capacity=None):
            "buf": buf, "lib": lib, "seg_rec": srec, "arun_rec": rec[a_line], "reads": None}
     out["arun_owner"] = (torch.cumsum((kind == 1).long(), 0) - 1)[above[a_line]] if L else a_line
     if R and not bool((srec[:, 5] & 1).any()):
-        out["reads"] = _pack(lib, buf, srec[:, 2], srec[:, 3] - srec[:, 2], device)
+        out["reads"] = pack(lib, buf, srec[:, 2], srec[:, 3] - srec[:, 2], device)
     elif R == 0:
         out["reads"] = (torch.zeros(0, dtype=torch.uint8, device=device), torch.zeros(1, **i64))
     return out
@@ -487,7 +409,7 @@ def _parse_on_device(data, device, path="<bytes>", table_capacity=None):
 def _names(p, device):
     """read_to_node, node_to_read, read_to_node2 from the parse (host dicts; per-item Python only over the utg* segments)."""
     lib, buf, srec, arec = p["lib"], p["buf"], p["seg_rec"], p["arun_rec"]
-    names = _texts(lib, buf, srec[:, 0], srec[:, 1], device)
+    names = texts(lib, buf, srec[:, 0], srec[:, 1], device)
     R = len(names)
     pairs = list(zip(range(0, 2 * R, 2), range(1, 2 * R, 2)))
     read_to_node = dict(zip(names, pairs))
@@ -495,8 +417,8 @@ def _names(p, device):
     read_to_node2 = {}
     utg = torch.nonzero((srec[:, 5] & 2) != 0).squeeze(1).cpu().tolist() if R else []
     if utg:
-        a_reads = _texts(lib, buf, arec[:, 0], arec[:, 1], device)
-        a_orient = _texts(lib, buf, arec[:, 2], arec[:, 3], device)
+        a_reads = texts(lib, buf, arec[:, 0], arec[:, 1], device)
+        a_orient = texts(lib, buf, arec[:, 2], arec[:, 3], device)
         owner = p["arun_owner"].cpu().numpy()
         count = np.bincount(owner, minlength=R) if owner.size else np.zeros(R, dtype=np.int64)
         first = np.concatenate([[0], np.cumsum(count)])
@@ -533,7 +455,7 @@ def read_gfa_device(path, similarity="auto", device=None, keep_names=True, long_
     if similarity not in ("auto", "device", None, False):
         raise ValueError(f"similarity={similarity!r}: expected 'auto', 'device', None or False")
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    p = _parse_on_device(_read_bytes(path), device, path=str(path))
+    p = _parse_on_device(read_bytes(path), device, path=str(path))
     src, dst, ol = p["src"], p["dst"], p["overlap_length"]
     out = {"src": src, "dst": dst, "num_nodes": p["num_nodes"], "overlap_length": ol,
            "prefix_length": (p["read_length"][src] - ol) if src.numel() else ol.clone(), "read_length": p["read_length"],

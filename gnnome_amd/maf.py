@@ -41,10 +41,10 @@ suffix is looked up only in the file given with that c; a name without one must 
 numbering per run, which is why the reference appends the suffix) - found in several, ValueError.
 
 The device reader (parser="device") is a second implementation of this statement and nothing else.  The bytes go to the device once,
-gnnome_gfa_mark tokenises them, gnnome_maf_lines reads every line's fields (one thread per line), torch scans group the `s` lines under
+textscan.tokenise finds their fields and lines, gnnome_maf_lines reads every line's fields (one thread per line), torch scans group the `s` lines under
 the nearest `a` line and check "exactly two" and "equal text lengths", gnnome_maf_text_check counts the bytes of every text that are not
-`-` (one wavefront per `s` line: the only pass over the alignment texts), and the wanted names go through reads_parse.hip's table
-(gnnome_reads_names_insert / gnnome_reads_match, integer atomicMax: the last block of an id wins).  What it cannot serve it declines
+`-` (one wavefront per `s` line: the only pass over the alignment texts), and the wanted names go through textscan.lookup_names
+(reads_parse.hip's table, integer atomicMax: the last block of an id wins).  What it cannot serve it declines
 (MafDeviceError names the line; _DECLINED lists the cases); parser="auto" then runs the host statement, which returns or raises as it
 says.  Synchronisations per file: the three compactions of the tokeniser, the `s`-line and `a`-line lists, and ONE that reports."""
 import os
@@ -54,8 +54,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gfa import _CHR_CODES, _positions, _read_bytes
-from .reads import _default_max_bytes, _pack_names, combine_annotations, wanted_reads
+from .gfa import _CHR_CODES
+from .reads import combine_annotations, wanted_reads
+from .textscan import DeviceDecline, first_decline, load_within, lookup_names, read_bytes, tokenise
 
 # What is at fault in a MAF, by the code left on the line: 1-5 by gnnome_maf_lines, 6-8 by the block scans, 9 by gnnome_maf_text_check.
 # The host statement raises ValueError for 1, 2 and 4-9 (3 it reads, Python's ints being as long as they need); the device reader
@@ -80,13 +81,9 @@ _INT64_MAX = 2 ** 63 - 1
 _DIGITS = re.compile(r"[0-9]+")
 
 
-class MafDeviceError(ValueError):
+class MafDeviceError(DeviceDecline):
     """The device reader declines the file: .line (1-based; 0 where no line is at fault) and .reason; the host statement takes any file."""
-
-    def __init__(self, path, line, reason):
-        where = f"line {line}: " if line else ""
-        super().__init__(f"{path}: {where}{reason} - not served by the device reader (parser='host' or 'auto')")
-        self.line, self.reason = line, reason
+    SERVED_BY = "the device reader (parser='host' or 'auto')"
 
 
 def parse_chr(chr):
@@ -119,7 +116,7 @@ def _s_line(fields):
 def read_maf_blocks(path):
     """The host statement: -> (ids, start, end, strand), one entry per alignment block in file order (list of str, three lists of int),
     or ValueError naming the earliest line at fault (see the module docstring)."""
-    text = _read_bytes(path).tobytes().decode("ascii", "surrogateescape")   # a byte >= 0x80 stays one character and is no whitespace
+    text = read_bytes(path).tobytes().decode("ascii", "surrogateescape")   # a byte >= 0x80 stays one character and is no whitespace
     faults = []                       # (line index, code, reason)
     blocks, current = [], None        # a block: (its a line, [(line, s-line entry)])
     orphans = []
@@ -249,66 +246,26 @@ def _read_uploaded(path, names, device, max_bytes, table_capacity):
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     names = list(names)
     R = len(names)
-    if max_bytes is None:
-        max_bytes = _default_max_bytes(device)
-    if not str(path).endswith(".gz") and os.path.getsize(path) > max_bytes:
-        raise MafDeviceError(path, 0, f"{_DECLINED[13]} ({os.path.getsize(path)} > {max_bytes})")
-    data = _read_bytes(path)
-    if data.size > max_bytes:
-        raise MafDeviceError(path, 0, f"{_DECLINED[13]} ({data.size} > {max_bytes})")
+    data = load_within(path, max_bytes, device, lambda sizes: MafDeviceError(path, 0, f"{_DECLINED[13]} {sizes}"))
     lib = _lib.load()
-    name_bytes, name_off = _pack_names(names)
     i64 = dict(dtype=torch.int64, device=device)
     i32 = dict(dtype=torch.int32, device=device)
-    buf = torch.from_numpy(data).to(device).contiguous()
-    n = int(buf.numel())
-    marks = torch.empty(n, dtype=torch.uint8, device=device)
-    bad_pos = torch.full((2,), torch.iinfo(torch.int64).max, **i64)
-    first_bad = torch.full((1,), torch.iinfo(torch.int32).max, **i32)
-    with _on(device):
-        _lib.check(lib.gnnome_gfa_mark(_ptr(buf), n, _ptr(marks), _ptr(bad_pos), _stream(device)), "gfa_mark")
-    fs, fe, ls = _positions(marks, 1), _positions(marks, 2), _positions(marks, 4)
-    del marks
-    F, L = int(fs.numel()), int(ls.numel())
-    ff = torch.empty(L + 1, **i64)
-    ff[:L] = torch.searchsorted(fs, ls)
-    ff[L] = F
-    err = torch.zeros(max(L, 1), **i32)
+    tok = tokenise(data, device)
+    buf, n, L, err, first_bad = tok.buf, tok.n, tok.L, tok.err, tok.first_bad
     kind = torch.zeros(L, **i32)
     lrec = torch.zeros(L, 8, **i64)
     with _on(device):
-        _lib.check(lib.gnnome_maf_lines(_ptr(buf), n, _ptr(fs), _ptr(fe), F, _ptr(ff), L, _ptr(kind), _ptr(lrec), _ptr(err), _ptr(first_bad),
-                                        _stream(device)), "maf_lines")
+        _lib.check(lib.gnnome_maf_lines(*tok.line_args(), _ptr(kind), _ptr(lrec), _ptr(err), _ptr(first_bad), _stream(device)), "maf_lines")
     brec, srec, s_line = assemble_blocks(kind, lrec, err, first_bad)
     s_line = s_line.contiguous()
     S, B = int(s_line.numel()), int(brec.shape[0])
     with _on(device):
         _lib.check(lib.gnnome_maf_text_check(_ptr(buf), n, _ptr(srec), _ptr(s_line), S, _ptr(err), L, _ptr(first_bad), _stream(device)),
                    "maf_text_check")
-    # the wanted names into the table, every block's read id looked up in it
-    cap = int(table_capacity) if table_capacity is not None else max(2, 1 << (2 * R).bit_length())
-    names_dev, off_dev = torch.from_numpy(name_bytes).to(device), torch.from_numpy(name_off).to(device)
-    table = torch.full((cap,), -1, **i32)
-    match = torch.full((cap,), -1, **i32)
-    slot_of = torch.full((R,), -1, **i32)
-    full = torch.zeros(1, **i32)
-    name_args = (_ptr(names_dev), int(names_dev.numel()), _ptr(off_dev), R, _ptr(table), cap)
-    with _on(device):
-        _lib.check(lib.gnnome_reads_names_insert(*name_args, _ptr(slot_of), _ptr(full), _stream(device)), "reads_names_insert")
-        _lib.check(lib.gnnome_reads_match(_ptr(buf), n, _ptr(brec), 8, B, *name_args, _ptr(match), _stream(device)), "reads_match")
-    slot = slot_of.long()
-    last = torch.where(slot >= 0, match[slot.clamp(min=0)].long(), slot) if R else slot
-    big = torch.iinfo(torch.int64).max
-    bad_line, hi_pos, cr_pos, table_full = torch.cat([first_bad.long(), bad_pos, full.long()]).cpu().tolist()   # the one synchronisation that reports
-    cands = []
-    for pos, code in ((hi_pos, 10), (cr_pos, 11)):
-        if pos != big:
-            cands.append((int(torch.searchsorted(ls, ls.new_tensor([pos]), right=True)) - 1, 0, code))
-    if bad_line != torch.iinfo(torch.int32).max:
-        cands.append((bad_line, 1, int(err[bad_line])))
-    if cands:
-        line, _, code = min(cands)
-        return MafDeviceError(path, line + 1, _DECLINED.get(code, f"code {code}"))
+    last, full = lookup_names(lib, tok, names, brec, 8, B, table_capacity)   # every block's read id looked up among the wanted names
+    found, (table_full,) = first_decline(tok, 10, 11, extra_scalars=(full,))
+    if found is not None:
+        return MafDeviceError(path, found[0] + 1, _DECLINED.get(found[1], f"code {found[1]}"))
     if table_full:
         return MafDeviceError(path, 0, _DECLINED[12])
     cols = torch.zeros(R, 3, **i64)

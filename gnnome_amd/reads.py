@@ -8,7 +8,7 @@
 
 This is a second implementation of the statement the host code makes - contigs._records, _record_id, read_sequences and read_titles,
 gfa._annotation and gfa._node_annotations - and nothing else: wherever it accepts a file it returns what they return.  The file's
-bytes go to the device once (.gz is decompressed on the host, as gfa._read_bytes does), gnnome_gfa_mark tokenises them, one thread per
+bytes go to the device once (.gz is decompressed on the host) and textscan.tokenise finds their fields and lines, one thread per
 line (FASTA) or per record (FASTQ) finds the id, title and sequence ranges, the wanted names sit in an open-addressing table that every
 record looks its id up in (integer atomicMax on the record index: the last record of an id wins, like the host's dict), one thread per
 matched record searches its title, and gnnome_gfa_pack copies the sequence lines - FASTQ quality bytes are never copied.  What the
@@ -18,14 +18,12 @@ runs the host code, which returns or raises as it always did.
 Synchronisations per file: one for each compaction whose size the host must know (field starts, field ends and line starts of the
 tokeniser, the header / sequence-line or non-blank-line lists), ONE that reports (the earliest declined line, the two byte checks and
 the table), and with sequences one for the number of pack items and one for the packed size."""
-import os
-
 import numpy as np
 import torch
 
 from . import _lib
 from .contigs import reads_file_type
-from .gfa import _pack, _positions, _read_bytes
+from .textscan import DeviceDecline, first_decline, load_within, lookup_names, pack, pack_names as _pack_names, tokenise  # noqa: F401
 
 # What the device reader declines: codes 1-4 are left on the line by the kernels of csrc/reads_parse.hip, 5 and 6 come from
 # gnnome_gfa_mark's byte checks, 7 from the name table, 8 is decided before the upload.  7 and 8 belong to no line: .line is 0.
@@ -40,16 +38,11 @@ _DECLINED = {
     8: "a file above max_bytes",
 }
 _FIELDS = ("strand=", "start=", "end=", "chr=")
-_MEMORY_SHARE = 6    # default max_bytes = free device memory / 6: the bytes, their marks, one mask and the int64 positions of the compactions
 
 
-class ReadsDeviceError(ValueError):
+class ReadsDeviceError(DeviceDecline):
     """The device reader declines the file: .line (1-based; 0 where no line is at fault) and .reason; the host code takes any file."""
-
-    def __init__(self, path, line, reason):
-        where = f"line {line}: " if line else ""
-        super().__init__(f"{path}: {where}{reason} - not served by the device reader (parser='host' or 'auto')")
-        self.line, self.reason = line, reason
+    SERVED_BY = "the device reader (parser='host' or 'auto')"
 
 
 class DeviceReads:
@@ -69,22 +62,6 @@ def record_title(res, k):
         raise IndexError(k)
     b, e = res._rec[k, 2:4].cpu().tolist()
     return res._buf[b:e].cpu().numpy().tobytes().decode("ascii")
-
-
-def _pack_names(names):
-    """list of str -> (uint8 numpy, int64[R+1] numpy): the names one after the other.  A name that is not ASCII cannot be in a file this
-    reader serves; it is encoded as UTF-8 and simply matches nothing."""
-    blob = "".join(names)
-    try:
-        raw = blob.encode("ascii")
-        lengths = np.fromiter(map(len, names), dtype=np.int64, count=len(names))
-    except UnicodeEncodeError:
-        enc = [s.encode("utf-8") for s in names]
-        raw = b"".join(enc)
-        lengths = np.fromiter(map(len, enc), dtype=np.int64, count=len(enc))
-    off = np.zeros(len(names) + 1, dtype=np.int64)
-    np.cumsum(lengths, out=off[1:])
-    return np.frombuffer(raw, dtype=np.uint8).copy(), off
 
 
 def pack_items(last, keep, seq_first, item_beg, item_len):
@@ -146,10 +123,6 @@ def combine_annotations(owner, sign, ann, num_owners):
     return out
 
 
-def _default_max_bytes(device):
-    return torch.cuda.mem_get_info(device)[0] // _MEMORY_SHARE
-
-
 def read_reads_device(path, names, device=None, sequences=True, titles=False, max_bytes=None, keep=None, table_capacity=None):
     """-> DeviceReads for the wanted ids `names` (a list of str; a repeated name is legal) from the FASTA / FASTQ file `path` (plain or
     .gz; the type by suffix as contigs.reads_file_type).  sequences: pack the sequence of every name's last record (keep: bool numpy
@@ -169,33 +142,14 @@ def _read_uploaded(path, names, device, sequences, titles, max_bytes, keep, tabl
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     names = list(names)
     R = len(names)
-    if max_bytes is None:
-        max_bytes = _default_max_bytes(device)
-    if not str(path).endswith(".gz") and os.path.getsize(path) > max_bytes:
-        raise ReadsDeviceError(path, 0, f"{_DECLINED[8]} ({os.path.getsize(path)} > {max_bytes})")
-    data = _read_bytes(path)
-    if data.size > max_bytes:
-        raise ReadsDeviceError(path, 0, f"{_DECLINED[8]} ({data.size} > {max_bytes})")
+    data = load_within(path, max_bytes, device, lambda sizes: ReadsDeviceError(path, 0, f"{_DECLINED[8]} {sizes}"))
     lib = _lib.load()
-    name_bytes, name_off = _pack_names(names)
     i64 = dict(dtype=torch.int64, device=device)
     i32 = dict(dtype=torch.int32, device=device)
-    buf = torch.from_numpy(data).to(device).contiguous()
-    n = int(buf.numel())
+    tok = tokenise(data, device)
+    buf, n, ls, ff, L, err, first_bad = tok.buf, tok.n, tok.ls, tok.ff, tok.L, tok.err, tok.first_bad
     res = DeviceReads(str(path), R)
-    marks = torch.empty(n, dtype=torch.uint8, device=device)
-    bad_pos = torch.full((2,), torch.iinfo(torch.int64).max, **i64)
-    first_bad = torch.full((1,), torch.iinfo(torch.int32).max, **i32)
-    with _on(device):
-        _lib.check(lib.gnnome_gfa_mark(_ptr(buf), n, _ptr(marks), _ptr(bad_pos), _stream(device)), "gfa_mark")
-    fs, fe, ls = _positions(marks, 1), _positions(marks, 2), _positions(marks, 4)
-    del marks
-    F, L = int(fs.numel()), int(ls.numel())
-    ff = torch.empty(L + 1, **i64)
-    ff[:L] = torch.searchsorted(fs, ls)
-    ff[L] = F
-    err = torch.zeros(max(L, 1), **i32)
-    line_args = (_ptr(buf), n, _ptr(fs), _ptr(fe), F, _ptr(ff), _ptr(ls), L)
+    line_args = tok.line_args(with_line_starts=True)
     if kind_of_file == "fasta":
         stride = 4
         kind = torch.zeros(L, **i32)
@@ -226,42 +180,22 @@ def _read_uploaded(path, names, device, sequences, titles, max_bytes, keep, tabl
         seq_first = torch.arange(K + 1, **i64)
         item_beg, item_len = rec[:, 4], rec[:, 5] - rec[:, 4]
     res.num_records, res._buf, res._rec = K, buf, rec
-    # the wanted names into the table, every record's id looked up in it
-    cap = int(table_capacity) if table_capacity is not None else max(2, 1 << (2 * R).bit_length())
-    names_dev, off_dev = torch.from_numpy(name_bytes).to(device), torch.from_numpy(name_off).to(device)
-    table = torch.full((cap,), -1, **i32)
-    match = torch.full((cap,), -1, **i32)
-    slot_of = torch.full((R,), -1, **i32)
-    full = torch.zeros(1, **i32)
-    name_args = (_ptr(names_dev), int(names_dev.numel()), _ptr(off_dev), R, _ptr(table), cap)
-    with _on(device):
-        _lib.check(lib.gnnome_reads_names_insert(*name_args, _ptr(slot_of), _ptr(full), _stream(device)), "reads_names_insert")
-        _lib.check(lib.gnnome_reads_match(_ptr(buf), n, _ptr(rec), stride, K, *name_args, _ptr(match), _stream(device)), "reads_match")
-    slot = slot_of.long()
-    res.last = torch.where(slot >= 0, match[slot.clamp(min=0)].long(), slot) if R else slot
+    res.last, full = lookup_names(lib, tok, names, rec, stride, K, table_capacity)   # every record's id looked up among the wanted names
     if titles:
         res.ann = torch.zeros(R, 4, **i64)
         res.missing = torch.full((R,), 15, **i32)
         with _on(device):
             _lib.check(lib.gnnome_reads_annotations(_ptr(buf), n, _ptr(rec), stride, K, _ptr(rec_line), _ptr(res.last), R, _ptr(res.ann),
                                                     _ptr(res.missing), _ptr(err), L, _ptr(first_bad), _stream(device)), "reads_annotations")
-    big = torch.iinfo(torch.int64).max
-    bad_line, hi_pos, cr_pos, table_full = torch.cat([first_bad.long(), bad_pos, full.long()]).cpu().tolist()   # the one synchronisation that reports
-    cands = []
-    for pos, code in ((hi_pos, 5), (cr_pos, 6)):
-        if pos != big:
-            cands.append((int(torch.searchsorted(ls, ls.new_tensor([pos]), right=True)) - 1, 0, code))
-    if bad_line != torch.iinfo(torch.int32).max:
-        cands.append((bad_line, 1, int(err[bad_line])))
-    if cands:
-        line, _, code = min(cands)
-        return ReadsDeviceError(path, line + 1, _DECLINED.get(code, f"code {code}"))
+    found, (table_full,) = first_decline(tok, 5, 6, extra_scalars=(full,))
+    if found is not None:
+        return ReadsDeviceError(path, found[0] + 1, _DECLINED.get(found[1], f"code {found[1]}"))
     if table_full:
         return ReadsDeviceError(path, 0, _DECLINED[7])
     if sequences:
         keep_dev = None if keep is None else torch.from_numpy(np.ascontiguousarray(keep, dtype=bool)).to(device)
         src_beg, lengths, first = pack_items(res.last, keep_dev, seq_first, item_beg, item_len)
-        res.data, item_off = _pack(lib, buf, src_beg, lengths, device)
+        res.data, item_off = pack(lib, buf, src_beg, lengths, device)
         res.off = item_off[first]
     return res
 
