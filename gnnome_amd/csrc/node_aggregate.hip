@@ -331,11 +331,34 @@ __device__ __forceinline__ int opaque_(int v) {
     return v;
 }
 
-template <int H, int U = (H == 256 ? 8 : 4)>
+// EXACT (the default; false = the loop as it was, tuning variant 17): a round issues loads only for the slots that hold an item.  A round is
+// G * U slots (U per lane group).  The fixed-width loop issues all of them in every round, a dead slot repeating a live one's address, and
+// restarts the out-edge pass on the G * U grid, so that up to G * U - 1 leading slots of its first round hold in-edge items: a node with 10
+// in- and 10 out-edges at H = 128 issues 32 slots for 20 items.  Here a pass runs full rounds (U loads per group, unconditional, a uniform
+// trip count) while more than G * (U - 1) items remain and then ONE round of U' = ceil(remaining / G) loads per group, a body instantiated for every
+// U' < U and chosen by a scalar switch; the out-edge pass starts at m_in / G * G.  At most G - 1 dead slots are left at each end of a pass
+// (they keep the repeated address: no branch around a load).  An item's lane group is still (index in the batch) % G and a group still adds
+// its items in ascending order: the same bits.
+template <int N>
+struct Slots {
+    static constexpr int value = N;
+};
+template <int U, class F>
+__device__ __forceinline__ void partial_round(int slots, F&& f) {   // slots in [1, U)
+    switch (slots) {
+        case 1: f(Slots<1>{}); break;
+        case 2: if constexpr (U > 2) f(Slots<2>{}); break;
+        case 3: if constexpr (U > 3) f(Slots<3>{}); break;
+        default: break;
+    }
+}
+
+template <int H, int U, bool EXACT>
 __device__ __forceinline__ void accumulate_items_lean(const float* __restrict__ e, const float* __restrict__ A2h, const float* __restrict__ A3h,
                                                       int ldn, const int32_t* __restrict__ srt_src, const int32_t* __restrict__ out_pos,
                                                       const int32_t* __restrict__ out_dst, int ib, int din, int ob, int lo, int hi, int lane,
                                                       int group, int c, f32x4& nf, f32x4& df, f32x4& nb, f32x4& db, uint32_t a32_rows) {
+    static_assert(!EXACT || U <= 4, "partial_round dispatches up to 3 slots (the launches use U = 4, and 2 at H = 256)");
     constexpr int LPR = H / 4, G = 64 / LPR;
     constexpr uint32_t kPosLimit = (uint32_t)((1ull << 32) / (H * 4));
     const uint32_t lc = (uint32_t)c * 4, lg = (uint32_t)group * (H * 4) + lc;
@@ -359,12 +382,14 @@ __device__ __forceinline__ void accumulate_items_lean(const float* __restrict__ 
         }
         const int m = min(64, hi - base);
         const int m_in = min(m, max(din - base, 0));   // items [0, m_in) of this batch are in-edges
-        for (int j0 = 0; j0 < m_in; j0 += G * U) {
+        // one round of in-edges: UP slots per lane group from item j0 on
+        auto in_round = [&](auto up, int j0) {
+            constexpr int UP = decltype(up)::value;
             const char* xb = reinterpret_cast<const char*>(e + (int64_t)(ib + base + j0) * H);
-            f32x4 x[U], a[U];
-            bool live[U];
+            f32x4 x[UP], a[UP];
+            bool live[UP];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
+            for (int u = 0; u < UP; ++u) {
                 live[u] = j0 + u * G + group < m_in;
                 x[u] = *reinterpret_cast<const f32x4*>(xb + (size_t)(live[u] ? lg + (uint32_t)(u * G * H * 4) : lc));   // (a dead slot reads item j0)
             }
@@ -372,55 +397,71 @@ __device__ __forceinline__ void accumulate_items_lean(const float* __restrict__ 
             if (__ballot(nn >= a32_rows) == 0) {
                 const uint32_t no = nn * (uint32_t)(ldn * 4);
 #pragma unroll
-                for (int u = 0; u < U; ++u) a[u] = row32(A2h, pick(no, live[u] ? j0 + u * G + group : j0));
+                for (int u = 0; u < UP; ++u) a[u] = row32(A2h, pick(no, live[u] ? j0 + u * G + group : j0));
             } else {
 #pragma unroll
-                for (int u = 0; u < U; ++u) a[u] = row64(A2h, pick(nn, live[u] ? j0 + u * G + group : j0), ldn);
+                for (int u = 0; u < UP; ++u) a[u] = row64(A2h, pick(nn, live[u] ? j0 + u * G + group : j0), ldn);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
+            for (int u = 0; u < UP; ++u) {
                 if (live[u]) {
                     const f32x4 s = sigmoid4_(x[u]);
                     nf += s * a[u];
                     df += s;
                 }
             }
+        };
+        if (EXACT) {
+            int j0 = 0;
+            for (; j0 + G * (U - 1) < m_in; j0 += G * U) in_round(Slots<U>{}, j0);   // (a round that needs all U slots, its last one maybe in part)
+            if (j0 < m_in) partial_round<U>((m_in - j0 + G - 1) / G, [&](auto up) { in_round(up, j0); });
+        } else {
+            for (int j0 = 0; j0 < m_in; j0 += G * U) in_round(Slots<U>{}, j0);
         }
         if (m_in < m) {
             const uint32_t pp = (uint32_t)my_p, nn = (uint32_t)my_n;
             const bool fit = __ballot(pp >= kPosLimit || nn >= a32_rows) == 0;
             const uint32_t po = pp * (uint32_t)(H * 4), no = nn * (uint32_t)(ldn * 4);
-            for (int j0 = m_in / (G * U) * (G * U); j0 < m; j0 += G * U) {
-                f32x4 x[U], a[U];
-                bool live[U];
-                int it[U];
+            // one round of out-edges: UP slots per lane group from item j0 on (j0 <= m_in in a pass's first round)
+            auto out_round = [&](auto up, int j0) {
+                constexpr int UP = decltype(up)::value;
+                f32x4 x[UP], a[UP];
+                bool live[UP];
+                int it[UP];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
+                for (int u = 0; u < UP; ++u) {
                     const int item = j0 + u * G + group;
                     live[u] = item >= m_in && item < m;
                     it[u] = live[u] ? item : m_in;   // (m_in < m here: a valid out-item)
                 }
                 if (fit) {
 #pragma unroll
-                    for (int u = 0; u < U; ++u) {
+                    for (int u = 0; u < UP; ++u) {
                         x[u] = row32(e, pick(po, it[u]));
                         a[u] = row32(A3h, pick(no, it[u]));
                     }
                 } else {
 #pragma unroll
-                    for (int u = 0; u < U; ++u) {
+                    for (int u = 0; u < UP; ++u) {
                         x[u] = row64(e, pick(pp, it[u]), H);
                         a[u] = row64(A3h, pick(nn, it[u]), ldn);
                     }
                 }
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
+                for (int u = 0; u < UP; ++u) {
                     if (live[u]) {
                         const f32x4 s = sigmoid4_(x[u]);
                         nb += s * a[u];
                         db += s;
                     }
                 }
+            };
+            if (EXACT) {
+                int j0 = m_in / G * G;   // the G-wide grid cell that holds the first out-item: at most G - 1 leading dead slots
+                for (; j0 + G * (U - 1) < m; j0 += G * U) out_round(Slots<U>{}, j0);
+                if (j0 < m) partial_round<U>((m - j0 + G - 1) / G, [&](auto up) { out_round(up, j0); });
+            } else {
+                for (int j0 = m_in / (G * U) * (G * U); j0 < m; j0 += G * U) out_round(Slots<U>{}, j0);
             }
         }
     }
@@ -490,9 +531,9 @@ __global__ __launch_bounds__(kAggThreads, (WPS > 0 ? WPS : 1)) void k_node_aggre
     const float* __restrict__ hub_partials, int64_t node0, int norm_width, const int32_t* __restrict__ records = nullptr,
     uint32_t a32_rows = 0) {
     constexpr int LPR = H / 4;
-    // SPLIT == 6 (the default item loop, accumulate_items_lean): the wave index read as a scalar, so that the node and everything loaded
+    // SPLIT >= 6 (the default item loop, accumulate_items_lean; 7 = its fixed-width rounds, variant 17): the wave index read as a scalar, so that the node and everything loaded
     // through it (list bounds, counts) live in scalar registers
-    const int lane = threadIdx.x & 63, wave = SPLIT == 6 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = SPLIT >= 6 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     int64_t node;
     int hub_slot = -1;
     if (HUBFIN) {
@@ -539,18 +580,20 @@ __global__ __launch_bounds__(kAggThreads, (WPS > 0 ? WPS : 1)) void k_node_aggre
             }
         }
     } else {
-        if (SPLIT == 2)   // MEASUREMENT ONLY (variant 7, wrong results): the out-edges alone - what the aggregation would cost if the in-edge half
+        if constexpr (SPLIT == 2)   // MEASUREMENT ONLY (variant 7, wrong results): the out-edges alone - what the aggregation would cost if the in-edge half
                           // were done elsewhere (inside the gate's store waves); see DESIGN.md, round 3
             accumulate_items_split<H, U>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, 0, ob, 0, cnt - din, lane, group, c, nf, df, nb, db);
-        else if (SPLIT == 4)   // variant 14: nontemporal out-edge loads of e'
+        else if constexpr (SPLIT == 4)   // variant 14: nontemporal out-edge loads of e'
             accumulate_items_split<H, U, false, true>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db);
-        else if (SPLIT == 5)   // variant 15, MEASUREMENT ONLY (wrong results): every table row of a node replaced by one L1-resident row - the kernel without its gathers' L1 misses
+        else if constexpr (SPLIT == 5)   // variant 15, MEASUREMENT ONLY (wrong results): every table row of a node replaced by one L1-resident row - the kernel without its gathers' L1 misses
             accumulate_items_split<H, U, false, false, true>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db);
-        else if (SPLIT == 3)   // variant 8: the split loop without branches around dead items
+        else if constexpr (SPLIT == 3)   // variant 8: the split loop without branches around dead items
             accumulate_items_split<H, U, true>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db);
-        else if (SPLIT == 6)
-            accumulate_items_lean<H, U>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db, a32_rows);
-        else if (SPLIT == 1)   // the item loop up to round 6, kept as tuning variant 16: the oracle of tests/test_aggregate_issue_forms.py
+        else if constexpr (SPLIT == 6)
+            accumulate_items_lean<H, U, true>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db, a32_rows);
+        else if constexpr (SPLIT == 7)   // the default loop with fixed-width rounds, kept as tuning variant 17: the A/B partner and second witness of tests/test_aggregate_exact_rounds.py
+            accumulate_items_lean<H, U, false>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db, a32_rows);
+        else if constexpr (SPLIT == 1)   // the item loop up to round 6, kept as tuning variant 16: the oracle of tests/test_aggregate_issue_forms.py
             accumulate_items_split<H, U>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db, recv, rec_small);
         else
             accumulate_items<H, U>(e, A2h, A3h, ldn, srt_src, out_pos, out_dst, ib, din, ob, 0, cnt, lane, group, c, nf, df, nb, db);
@@ -607,8 +650,9 @@ __global__ __launch_bounds__(kAggThreads, (WPS > 0 ? WPS : 1)) void k_node_aggre
 }
 
 // Round 4 experiment (tuning key 7 = 9, H = 128, the fused inference update): TWO NODES PER WAVE.  The kernel above gives a wave one node and
-// lets its two 32-lane groups take alternate items of that node's list: a list of 10 + 10 items costs four rounds of 8 row slots (62 % of
-// them live) and a cross-group reduction.  Here each 32-lane group owns a node of its own (consecutive nodes: mates 2r / 2r + 1 on an
+// lets its two 32-lane groups take alternate items of that node's list: a list of 10 + 10 items cost four rounds of 8 row slots (62 % of
+// them live) in the fixed-width loop this was measured against (today's tuning variant 17; the default's exact-width rounds issue 20 slots
+// for that node) and a cross-group reduction.  Here each 32-lane group owns a node of its own (consecutive nodes: mates 2r / 2r + 1 on an
 // assembly graph, with lists of equal length): three rounds of 4 slots per direction and node (83 % live), half as many waves, no
 // cross-lane sums - every node's items are added in list order by one lane group, so the result is a function of the graph alone here
 // too (another association than the kernel above: equal to fp32 rounding, not bit for bit).
@@ -820,16 +864,21 @@ static int launch_agg(const float* e, int64_t n_out, const float* A1h, const flo
     hipLaunchKernelGGL((k_node_aggregate<H, NORM_, MODE_, FIN_, U_, WPS_, SPLIT_>), dim3((unsigned)(GRID_)), dim3(kAggThreads), (FIN_) ? 0 : dyn, s, e, \
                        (FIN_) ? n_out : node_end, A1h, A2h, A3h, ldn, in_ptr, ss, out_ptr, out_pos, od, h_in, ldh, h_out, scale, shift,   \
                        (int)blocks, aux0, aux1, aux2, aux3, hub_count, hub_nodes, hub_partials, (FIN_) ? (int64_t)0 : node0, norm_width, nullptr, a32_rows)
-    // the regular launch of every mode: accumulate_items_lean (SPLIT 6); tuning variant 16 keeps the split loop it replaced (SPLIT 1) - the same bits
+    // the regular launch of every mode: accumulate_items_lean with exact-width rounds (SPLIT 6); tuning variant 17 keeps its fixed-width rounds
+    // (SPLIT 7) and variant 16 the split loop before it (SPLIT 1) - the same bits
 #define GN_AGG_LAUNCH(NORM_, MODE_, FIN_, U_, WPS_, GRID_)                                \
     do {                                                                                  \
         constexpr int kLoop = (!(FIN_) && (WPS_) == 0 && (U_) == UD) ? 6 : 1;             \
+        constexpr int kFixed = kLoop == 6 ? 7 : 1;   /* (no SPLIT 7 kernel for the other forms) */ \
         if (kLoop == 6 && prev_loop)                                                      \
             GN_AGG_LAUNCH_S(NORM_, MODE_, FIN_, U_, WPS_, GRID_, 1);                      \
+        else if (kLoop == 6 && fixed_rounds)                                              \
+            GN_AGG_LAUNCH_S(NORM_, MODE_, FIN_, U_, WPS_, GRID_, kFixed);                 \
         else                                                                              \
             GN_AGG_LAUNCH_S(NORM_, MODE_, FIN_, U_, WPS_, GRID_, kLoop);                  \
     } while (0)
-    // The regular launches run the split item loop (accumulate_items_split: 0.2207 -> 0.2103 ms per launch at configs[1], whole forward
+    // History of the loop (every figure below was measured with fixed-width rounds, G U slots in every round: today's variants 16 / 17).
+    // The regular launches ran the split item loop (accumulate_items_split: 0.2207 -> 0.2103 ms per launch at configs[1], whole forward
     // 4.89 -> 4.78 ms, the same bits, the same 782 MB fetched); variant 6 keeps the single loop for A/B.  (A single loop with a
     // wave-uniform fast path for steps of in-edges only - one round fewer, the overlap only when a node has >= G U in-edges - measured
     // the same as the split form: 4.875 against 4.881 ms.)
@@ -841,7 +890,7 @@ static int launch_agg(const float* e, int64_t n_out, const float* A1h, const flo
     // H = 256 (one 1 KB row per load instruction): 2 since round 4 - measured inside the 2.5M-edge forward 1.036 (U = 8) / 0.980 (2) / 0.969 ms (1) per launch,
     // the same bits (one lane group: the items are added in list order whatever U)
     constexpr int UD = H == 256 ? 2 : 4;
-    const bool prev_loop = tuning(kTuneAggVariant) == 16;
+    const bool prev_loop = tuning(kTuneAggVariant) == 16, fixed_rounds = tuning(kTuneAggVariant) == 17;
     // table rows below this index are addressed with 32-bit byte offsets (accumulate_items_lean); gnnome_set_tuning(11, 1): none are
     const uint32_t a32_rows = tuning(kTuneAggAddr64) == 1 ? 0u : (uint32_t)((1ull << 32) / ((uint64_t)ldn * 4));
     constexpr int kFinGrid = kHubCap / (kAggThreads / 64);

@@ -77,7 +77,9 @@ const char* gnnome_last_error(void);
  *   key 10 forward arithmetic : 0 fp16x3 on the f16 matrix cores for the forward's dense products at H = 128 / 256 (round 4; see
  *                             gnnome_linear_f32), 1 bf16x6 everywhere (round 3's arithmetic; the plane-form kernels at H = 256)
  *   key 7 also: 9 / 10 two nodes per wave (U = 4 / 2), 11-13 persistent contiguous chunks (measured negatives),
- *                             16 the item loop before the lean one (accumulate_items_split; the same bits, every mode)
+ *                             16 the item loop before the lean one (accumulate_items_split; the same bits, every mode),
+ *                             17 the lean loop with fixed-width rounds (G * U row-load slots in every round, as before the exact-width
+ *                             rounds; the same bits, every mode) - the A/B partner and bit oracle of tests/test_aggregate_exact_rounds.py
  *   key 11 aggregation addressing: 1 = row addresses in 64 bits per item at every size (default: 32-bit byte offsets wherever a step's
  *                             rows lie below 4 GiB; the same bits)
  *   key 12 node projection schedule (gnnome_linear_planes_f32 at K = 128): 0 the shipped default, 1 the schedule before it (plain stores for P, where the
