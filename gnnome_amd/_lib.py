@@ -178,6 +178,10 @@ SIGNATURES = {
     "gnnome_seed_pairs_workspace_bytes": [_l, ctypes.POINTER(_sz)],
     "gnnome_seed_pairs": [_p, _p, _p, _p, _l, _p, _l, _i, _i, _p, _p, _l, _p, _p, _sz, _p],
     "gnnome_chain_overlaps": [_p, _p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p, _p],
+    "gnnome_transitive_tile_size": [ctypes.POINTER(_i)],
+    "gnnome_transitive_edges": [_p, _p, _p, _p, _l, _l, _i, _p, _p],
+    "gnnome_tip_nodes_workspace_bytes": [_l, ctypes.POINTER(_sz)],
+    "gnnome_tip_nodes": [_p, _p, _p, _p, _p, _p, _l, _i, _p, _p, _sz, _p],
 }
 
 ABI_VERSION = 32

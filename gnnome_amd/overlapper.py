@@ -8,7 +8,8 @@
 hash, minimizer rule, pair records, bands, classification, every output order - is in include/gnnome_hip.h and, executable, in
 tests/overlap_graph_statement.py; the kernels are csrc/overlap_graph.hip.  torch does the plumbing between them: the
 stable sort of the seeds by hash, the sort of the pair records, the starts of the (a, b, rel) groups, the compaction of the kept overlaps
-and gfa.assemble_edges.  The graph is the raw dovetail graph: no transitive reduction, no tip or bubble removal, no unitigs; a read set
+and gfa.assemble_edges.  The graph is the raw dovetail graph unless overlap_graph(simplify=) hands it to simplify.simplify_graph
+(transitive edges, tips, the reads left without an edge); no bubble removal, no unitigs; a read set
 whose seed pairs do not fit the device at once is refused (ValueError naming max_occ and max_pairs), not processed in blocks."""
 import ctypes
 
@@ -219,13 +220,18 @@ def find_overlaps(reads, sk=None, k=19, w=10, max_occ=64, band=500, min_seeds=3,
 
 
 def overlap_graph(reads, sk=None, k=19, w=10, max_occ=64, band=500, min_seeds=3, min_overlap=1000, max_hang=1000, max_pairs=None,
-                  similarity=True, drop_contained=True, annotations=None, device=None, long_overlaps=False):
+                  similarity=True, drop_contained=True, annotations=None, device=None, long_overlaps=False, simplify=None):
     """-> the dict gfa.read_gfa_device returns (src, dst, num_nodes = 2R, overlap_length, prefix_length, read_length, overlap_similarity or
     None, reads = the packed reads; the name tables are None), tensors on the device, plus `contained` bool[R] and `overlaps`.  Node 2r
     is read r, 2r + 1 its reverse complement; overlap j gives the events 2j (its real edge) and 2j + 1 (the mate (v ^ 1, u ^ 1)) to
     gfa.assemble_edges.  similarity: overlap.overlap_similarity on every edge (long_overlaps is handed to it).  drop_contained: contained
     reads keep their node numbers and lose their edges.  annotations: (read_strand, read_start, read_end, read_chr), int64[2R] as
-    reads.node_annotations_device gives them - the dict then carries them and labels.process_graph(g) works on it."""
+    reads.node_annotations_device gives them - the dict then carries them and labels.process_graph(g) works on it.  simplify: True, or a
+    dict of simplify.simplify_graph's keywords (fuzz, max_tip, tips, compact, check_mates, stats) - the graph is handed through it before
+    it is returned (transitive edges and tips dropped; with compact the reads left without an edge removed, `kept_reads` naming the
+    others); None, the default, returns the raw dovetail graph."""
+    if simplify is not None and simplify is not True and not isinstance(simplify, dict):
+        raise ValueError(f"simplify={simplify!r}: expected None, True or a dict of simplify_graph's keywords")
     data, off = _packed(reads, device)
     dev = data.device
     ov = find_overlaps((data, off), sk, k, w, max_occ, band, min_seeds, min_overlap, max_hang, max_pairs, dev)
@@ -249,4 +255,7 @@ def overlap_graph(reads, sk=None, k=19, w=10, max_occ=64, band=500, min_seeds=3,
         if len(cols) != 4 or any(c.numel() != 2 * R for c in cols):
             raise ValueError(f"annotations: expected read_strand, read_start, read_end, read_chr with {2 * R} entries each")
         g.update(zip(("read_strand", "read_start", "read_end", "read_chr"), cols))
+    if simplify is not None:
+        from .simplify import simplify_graph
+        g = simplify_graph(g, device=dev, **(simplify if isinstance(simplify, dict) else {}))
     return g

@@ -46,15 +46,36 @@ def _read(path, similarity, parser, device, long_overlaps=False):
     return gfa.read_gfa(path, similarity=similarity, long_overlaps=long_overlaps)
 
 
+def _simplified(g, simplify, device, renumber=True):
+    """g through simplify.simplify_graph when `simplify` is True or a dict of its keywords; None leaves g alone.  renumber=False: the
+    read sequences come from a source that knows the reads by their old numbers, so the reads keep them (compact=False; asking for
+    compact=True there is refused)."""
+    if simplify is None:
+        return g
+    if simplify is not True and not isinstance(simplify, dict):
+        raise ValueError(f"simplify={simplify!r}: expected None, True or a dict of simplify_graph's keywords")
+    from .simplify import simplify_graph
+    kw = dict(simplify) if isinstance(simplify, dict) else {}
+    if not renumber:
+        if kw.get("compact"):
+            raise ValueError("simplify: compact=True renumbers the reads, and the sequences of this call (the GFA file's S lines, or a "
+                             "ReadStore) go by the old numbers; pass compact=False")
+        kw["compact"] = False
+    return simplify_graph(g, device=device, **kw)
+
+
 def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto", device=None, scores=None, sampler=None, parser="host",
-             long_overlaps=False, early_stopping=False, p_threshold=0.06, random_walks=False, seed=None):
+             long_overlaps=False, early_stopping=False, p_threshold=0.06, random_walks=False, seed=None, simplify=None):
     """-> (walks, scores, graph dict).  `scores` overrides the model (inference.py:426-432: saved predictions / labels).
     parser: how a GFA path is read (gfa.read_gfa's parser=; with "device" the graph's tensors stay on the device).
     long_overlaps: gfa.read_gfa's keyword - True lets a GFA with overlaps beyond 65 536 bases (ultra-long ONT reads) through.
     early_stopping, p_threshold, random_walks, seed: decode.decode_contigs' keywords (the reference's decoder switches,
-    inference.py:26-28); the ablation's constant scores are scores=decode.constant_scores(g)."""
+    inference.py:26-28); the ablation's constant scores are scores=decode.constant_scores(g).
+    simplify: True or a dict of simplify.simplify_graph's keywords - the graph is simplified (transitive edges, tips, the reads left
+    without an edge) before it is scored; the returned dict, and `scores` if given, are of the simplified graph."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     g = gfa_or_graph if isinstance(gfa_or_graph, dict) else _read(gfa_or_graph, similarity, parser, device, long_overlaps)
+    g = _simplified(g, simplify, device)
     if scores is None:
         scores = score_graph(g, model, device)
     prefix = g["prefix_length"].masked_fill(g["prefix_length"] < 0, 0)      # inference.py:461
@@ -66,7 +87,7 @@ def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto"
 
 def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, nb_paths=100, similarity="auto", device=None, scores=None,
                       sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, parser="host", reads_parser="host",
-                      long_overlaps=False, early_stopping=False, p_threshold=0.06, random_walks=False, seed=None):
+                      long_overlaps=False, early_stopping=False, p_threshold=0.06, random_walks=False, seed=None, simplify=None):
     """GFA -> scores -> greedy walks -> contigs spelled on the device -> FASTA at out_path (inference.py:411-489).
     -> (walks, contigs, stats); stats = quick_evaluation's figures as a dict (ref_length from the caller: NG50 and the
     reconstructed fraction are -1 without it).  Sequences: the GFA's S lines if it carries them, else `reads` (a FASTA / FASTQ
@@ -74,7 +95,8 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
     uploaded.  The prefixes are masked as pipeline.assemble masks them (inference.py:461).  parser="device" / "auto": the GFA is read
     once, by gfa.read_gfa_device, and its sequences are the packed reads that parse left on the device, restricted to the touched ones.
     reads_parser: how a `reads` file is read (ReadStore.from_reads_file's parser=).  long_overlaps, early_stopping, p_threshold,
-    random_walks, seed: as in assemble."""
+    random_walks, seed, simplify: as in assemble; where the sequences come from the GFA file's S lines (parser="host") or from a
+    ReadStore the reads keep their numbers (compact=False)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     gfa_path = None if isinstance(gfa_or_graph, dict) else gfa_or_graph
     if gfa_path is not None and parser != "host":
@@ -99,6 +121,7 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
     else:
         raise ValueError("no read sequences: the GFA's S lines say '*' (or a graph dict was passed) and no `reads` was given")
     g = gfa_or_graph if isinstance(gfa_or_graph, dict) else gfa.read_gfa(gfa_or_graph, similarity=similarity, long_overlaps=long_overlaps)
+    g = _simplified(g, simplify, device, renumber=source not in ("store", "gfa"))
     walks, scores, g = assemble(g, model, len_threshold, nb_paths=nb_paths, similarity=similarity, device=device, scores=scores,
                                 sampler=sampler, early_stopping=early_stopping, p_threshold=p_threshold, random_walks=random_walks, seed=seed)
     touched = sorted({v >> 1 for w in walks for v in w})
@@ -130,7 +153,8 @@ def assemble_reads_to_fasta(reads_path, model, out_path, len_threshold, nb_paths
                             sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, long_overlaps=False, **overlap_kw):
     """Reads -> overlap graph -> scores -> greedy walks -> contigs -> FASTA at out_path, with no assembler's GFA in between:
     reads.read_reads_device (every record of the FASTA / FASTQ file, in file order; a repeated id keeps its last record) ->
-    overlapper.overlap_graph (overlap_kw: its k, w, max_occ, band, min_seeds, min_overlap, max_hang, max_pairs, drop_contained) ->
+    overlapper.overlap_graph (overlap_kw: its k, w, max_occ, band, min_seeds, min_overlap, max_hang, max_pairs, drop_contained, simplify;
+    with simplify's compact the names follow the dict's kept_reads) ->
     assemble_to_fasta on that dict.  -> (walks, contigs, stats, graph dict).  scores: one logit per edge instead of the model.
     use_labels: the titles carry strand=, start=, end= and chr= (the simulator's), the dict gets the four read_* columns and y, and the
     labels are the scores (+20 / -20 as logits: the reference's use_labels, whose floor is 1e-9)."""
@@ -147,7 +171,8 @@ def assemble_reads_to_fasta(reads_path, model, out_path, len_threshold, nb_paths
         cols[1::2, 0] = -cols[1::2, 0]
         annotations = [cols[:, j].contiguous() for j in range(4)]
     g = overlapper.overlap_graph((res.data, res.off), annotations=annotations, device=device, long_overlaps=long_overlaps, **overlap_kw)
-    g["node_to_read"] = {2 * r + s: n for r, n in enumerate(names) for s in (0, 1)}
+    kept = g["kept_reads"].tolist() if "kept_reads" in g else range(len(names))
+    g["node_to_read"] = {2 * i + s: names[r] for i, r in enumerate(kept) for s in (0, 1)}
     if use_labels:
         g["y"] = labels.process_graph(g, device=device)[1]
         scores = (g["y"] * 2 - 1) * 20

@@ -1458,6 +1458,35 @@ int gnnome_chain_overlaps(const int64_t* key_ab, const int64_t* key_dp, int64_t 
                           int64_t num_groups, const int64_t* off, int64_t num_reads, int k, int band, int min_seeds, int min_overlap,
                           int max_hang, int32_t* out, void* stream);
 
+/* ---- Overlap-graph simplification: transitive edges and tips ------------------------------------------------------------------------
+ * As tests/graph_simplify_statement.py states them, on a graph that follows the complement convention (node v ^ 1 is the reverse
+ * complement of v, edge (u, v) has the mate (v ^ 1, u ^ 1)); p(e) is the edge's prefix length.  Integers only, no atomics; every decision
+ * reads only the inputs and every flag stored is 1, so no result depends on the grid or on timing.  num_nodes, num_edges < 2^31.
+ *
+ * gnnome_transitive_edges: the edges sorted by (src, dst) - row_ptr int64[N + 1]: node v's out-edges are the positions
+ *   row_ptr[v] .. row_ptr[v + 1]; dst, prefix, edge_id int32[E] per position (edge_id: where the edge's flag goes) - and mark uint8[E],
+ *   zeroed here.  A simultaneous rule on the input graph (raven's; not Myers' sequential marking): mark[e] = 1 for e = (v, x) iff there
+ *   are a node w, w != v and w != x, and edges e1 = (v, w), e2 = (w, x) with |p(e1) + p(e2) - p(e)| <= fuzz (fuzz >= 0, an absolute
+ *   number of bases; parallel edges are separate edges).  p(e1) + p(e2) - p(e) = len(w) - ol(e1) - ol(e2) + ol(e) is the same for the
+ *   mates, so an edge is marked iff its mate is.  One wavefront per v; out(v) is staged in LDS gnnome_transitive_tile_size entries at a
+ *   time, and a longer row is done tile by tile.  No workspace, no synchronisation.
+ * gnnome_tip_nodes: in_deg, out_deg int32[N]; succ, succ_prefix int32[N]: the target and the p of a node's out-edge where out_deg
+ *   is 1 (not read elsewhere); in_ptr int64[N + 1] / in_src int32[E]: the sources of every node's in-edges; tip uint8[N], zeroed
+ *   here; N even.  A tip start is a node of in-degree 0 and out-degree 1.  From c0 = s the unique out-edges are followed; the node
+ *   reached next is, in this order: the junction j if its in-degree is >= 2 (the chain ends); the end of a chain that is no tip if
+ *   its out-degree is not 1; else the next chain node.  The chain c0 .. c(m-1) is a candidate iff it reached a junction with
+ *   m <= max_tip (>= 1); its weight is the sum of p over its m edges.  At a junction with an in-edge that does not come from the
+ *   last node of one of its candidates every candidate is a tip; where all in-edges do, all but one are: the heaviest, ties to the
+ *   smallest c(m-1), survives.  tip[c] = tip[c ^ 1] = 1 for every node c of a tip.  Two launches, one lane per node; the
+ *   workspace (gnnome_tip_nodes_workspace_bytes) holds the candidates.  No synchronisation. */
+int gnnome_transitive_tile_size(int* tile_host);
+int gnnome_transitive_edges(const int64_t* row_ptr, const int32_t* dst, const int32_t* prefix, const int32_t* edge_id, int64_t num_nodes,
+                            int64_t num_edges, int fuzz, uint8_t* mark, void* stream);
+int gnnome_tip_nodes_workspace_bytes(int64_t num_nodes, size_t* bytes_host);
+int gnnome_tip_nodes(const int32_t* in_deg, const int32_t* out_deg, const int32_t* succ, const int32_t* succ_prefix,
+                     const int64_t* in_ptr, const int32_t* in_src, int64_t num_nodes, int max_tip, uint8_t* tip, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,9 @@ Sketch: input bytes per second of the whole sketch_reads call, and the share of 
 kernel's own traffic - every base twice, once per launch - amounts to.  A further pass with stats= takes device-event times of every
 stage (the median over the repeats): for the sketch the count stage (count launch, scan, size read-back) and the write launch alone - the
 write launch's bytes per second is the one figure that is a single kernel's; for find_overlaps the record kernel and the chain kernel
-as records per second, and torch's sorts beside them.  The only baseline is the NumPy / Python statement
+as records per second, and torch's sorts beside them; for simplify.simplify_graph on the graph of these overlaps the edge and node
+counts before and after and its stages (mates check, the sort and the mark kernel of the transitive rule, the lists and the two launches
+of the tips, the compaction).  The only baseline is the NumPy / Python statement
 (tests/overlap_graph_statement.py) on the first --statement-reads reads of the same input, a host wall time labelled as such.
 Prints one JSON line."""
 import argparse
@@ -99,7 +101,22 @@ def main():
            "find_overlaps_stage_ms": ov_ms, "groups": ov_stats[0]["groups"],
            "pair_kernel_records_per_s": P / (ov_ms["pairs_write_ms"] * 1e-3), "chain_kernel_records_per_s": P / (ov_ms["chain_ms"] * 1e-3),
            "find_overlaps_call_s": ov_t, "find_overlaps_call_s_min_max": [ov_lo, ov_hi], "find_overlaps_records_per_s": P / ov_t}
-    del ov, sk
+    del ov
+    # the graph of these overlaps and simplify.simplify_graph on it: its stages by device events, the whole call by the host clock
+    from gnnome_amd import simplify
+    g = overlapper.overlap_graph(reads, sk, similarity=False)
+    del sk
+    g.pop("overlaps")
+    sg_t, sg_lo, sg_hi, sg = timed(lambda: simplify.simplify_graph(g), a.repeats)
+    sg_stats = []
+    for _ in range(a.repeats):
+        sg_stats.append({})
+        simplify.simplify_graph(g, stats=sg_stats[-1])
+    out.update(graph_edges=int(g["src"].numel()), graph_nodes=int(g["num_nodes"]), graph_max_out_degree=int(torch.bincount(g["src"]).max()),
+               simplified_edges=int(sg["src"].numel()), simplified_nodes=int(sg["num_nodes"]), simplify_removed=sg["removed"],
+               simplified_max_out_degree=int(torch.bincount(sg["src"]).max()) if sg["src"].numel() else 0,
+               simplify_stage_ms=stage(sg_stats), simplify_call_s=sg_t, simplify_call_s_min_max=[sg_lo, sg_hi])
+    del g, sg
     if a.statement_reads:
         import overlap_graph_statement as st
         n = min(a.statement_reads, a.reads)
