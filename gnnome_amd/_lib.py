@@ -182,6 +182,10 @@ SIGNATURES = {
     "gnnome_transitive_edges": [_p, _p, _p, _p, _l, _l, _i, _p, _p],
     "gnnome_tip_nodes_workspace_bytes": [_l, ctypes.POINTER(_sz)],
     "gnnome_tip_nodes": [_p, _p, _p, _p, _p, _p, _l, _i, _p, _p, _sz, _p],
+    "gnnome_unitig_links": [_p, _p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _p],
+    "gnnome_unitig_rank_workspace_bytes": [_l, ctypes.POINTER(_sz)],
+    "gnnome_unitig_rank": [_p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _i, _p, _p, _sz, _p],
+    "gnnome_unitig_scatter": [_p, _p, _p, _l, _l, _p, _p],
 }
 
 ABI_VERSION = 32

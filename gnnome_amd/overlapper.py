@@ -9,7 +9,7 @@ hash, minimizer rule, pair records, bands, classification, every output order - 
 tests/overlap_graph_statement.py; the kernels are csrc/overlap_graph.hip.  torch does the plumbing between them: the
 stable sort of the seeds by hash, the sort of the pair records, the starts of the (a, b, rel) groups, the compaction of the kept overlaps
 and gfa.assemble_edges.  The graph is the raw dovetail graph unless overlap_graph(simplify=) hands it to simplify.simplify_graph
-(transitive edges, tips, the reads left without an edge); no bubble removal, no unitigs; a read set
+(transitive edges, tips, the reads left without an edge) and overlap_graph(unitigs=) to unitigs.compact_unitigs; no bubble removal; a read set
 whose seed pairs do not fit the device at once is refused (ValueError naming max_occ and max_pairs), not processed in blocks."""
 import ctypes
 
@@ -220,7 +220,7 @@ def find_overlaps(reads, sk=None, k=19, w=10, max_occ=64, band=500, min_seeds=3,
 
 
 def overlap_graph(reads, sk=None, k=19, w=10, max_occ=64, band=500, min_seeds=3, min_overlap=1000, max_hang=1000, max_pairs=None,
-                  similarity=True, drop_contained=True, annotations=None, device=None, long_overlaps=False, simplify=None):
+                  similarity=True, drop_contained=True, annotations=None, device=None, long_overlaps=False, simplify=None, unitigs=False):
     """-> the dict gfa.read_gfa_device returns (src, dst, num_nodes = 2R, overlap_length, prefix_length, read_length, overlap_similarity or
     None, reads = the packed reads; the name tables are None), tensors on the device, plus `contained` bool[R] and `overlaps`.  Node 2r
     is read r, 2r + 1 its reverse complement; overlap j gives the events 2j (its real edge) and 2j + 1 (the mate (v ^ 1, u ^ 1)) to
@@ -229,9 +229,14 @@ def overlap_graph(reads, sk=None, k=19, w=10, max_occ=64, band=500, min_seeds=3,
     reads.node_annotations_device gives them - the dict then carries them and labels.process_graph(g) works on it.  simplify: True, or a
     dict of simplify.simplify_graph's keywords (fuzz, max_tip, tips, compact, check_mates, stats) - the graph is handed through it before
     it is returned (transitive edges and tips dropped; with compact the reads left without an edge removed, `kept_reads` naming the
-    others); None, the default, returns the raw dovetail graph."""
+    others); None, the default, returns the raw dovetail graph.  unitigs: True, or a dict of unitigs.compact_unitigs' keywords (stats) -
+    after `simplify`, the graph's non-branching paths are merged and the unitig graph is returned in its place (its `reads` are the
+    unitig sequences, its name tables read_gfa's unitig form; `contained`, `overlaps` and the read_* columns are not carried); False,
+    the default, changes nothing."""
     if simplify is not None and simplify is not True and not isinstance(simplify, dict):
         raise ValueError(f"simplify={simplify!r}: expected None, True or a dict of simplify_graph's keywords")
+    if unitigs is not False and unitigs is not True and not isinstance(unitigs, dict):
+        raise ValueError(f"unitigs={unitigs!r}: expected False, True or a dict of compact_unitigs' keywords")
     data, off = _packed(reads, device)
     dev = data.device
     ov = find_overlaps((data, off), sk, k, w, max_occ, band, min_seeds, min_overlap, max_hang, max_pairs, dev)
@@ -258,4 +263,7 @@ def overlap_graph(reads, sk=None, k=19, w=10, max_occ=64, band=500, min_seeds=3,
     if simplify is not None:
         from .simplify import simplify_graph
         g = simplify_graph(g, device=dev, **(simplify if isinstance(simplify, dict) else {}))
+    if unitigs is not False:
+        from .unitigs import compact_unitigs
+        g = compact_unitigs(g, device=dev, **(unitigs if isinstance(unitigs, dict) else {}))
     return g

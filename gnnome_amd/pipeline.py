@@ -65,29 +65,40 @@ def _simplified(g, simplify, device, renumber=True):
 
 
 def assemble(gfa_or_graph, model, len_threshold, nb_paths=100, similarity="auto", device=None, scores=None, sampler=None, parser="host",
-             long_overlaps=False, early_stopping=False, p_threshold=0.06, random_walks=False, seed=None, simplify=None):
+             long_overlaps=False, early_stopping=False, p_threshold=0.06, random_walks=False, seed=None, simplify=None, isolated=False):
     """-> (walks, scores, graph dict).  `scores` overrides the model (inference.py:426-432: saved predictions / labels).
     parser: how a GFA path is read (gfa.read_gfa's parser=; with "device" the graph's tensors stay on the device).
     long_overlaps: gfa.read_gfa's keyword - True lets a GFA with overlaps beyond 65 536 bases (ultra-long ONT reads) through.
     early_stopping, p_threshold, random_walks, seed: decode.decode_contigs' keywords (the reference's decoder switches,
     inference.py:26-28); the ablation's constant scores are scores=decode.constant_scores(g).
     simplify: True or a dict of simplify.simplify_graph's keywords - the graph is simplified (transitive edges, tips, the reads left
-    without an edge) before it is scored; the returned dict, and `scores` if given, are of the simplified graph."""
+    without an edge) before it is scored; the returned dict, and `scores` if given, are of the simplified graph.
+    isolated: for a unitig graph - the decoder starts its walks from edges, so a segment that no walk reaches (one without edges above
+    all) is never a contig; True appends a one-node walk for every even node of at least len_threshold bases that the walks leave
+    untouched on both strands, in node order."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     g = gfa_or_graph if isinstance(gfa_or_graph, dict) else _read(gfa_or_graph, similarity, parser, device, long_overlaps)
     g = _simplified(g, simplify, device)
+    if scores is None and isolated and int(torch.as_tensor(g["src"]).numel()) == 0:
+        scores = torch.zeros(0)
     if scores is None:
         scores = score_graph(g, model, device)
     prefix = g["prefix_length"].masked_fill(g["prefix_length"] < 0, 0)      # inference.py:461
     dg = decode.DecodeGraph(g["src"], g["dst"], g["num_nodes"], prefix, g["read_length"], device=device).set_scores(scores)
     walks = decode.decode_contigs(dg, len_threshold, nb_paths=nb_paths, sampler=sampler, early_stopping=early_stopping,
                                   p_threshold=p_threshold, random_walks=random_walks, seed=seed)
+    if isolated:
+        free = torch.ones(int(g["num_nodes"]), dtype=torch.bool)
+        free[torch.tensor([v ^ s for w in walks for v in w for s in (0, 1)], dtype=torch.long)] = False
+        long_enough = torch.as_tensor(g["read_length"]).reshape(-1).cpu() >= len_threshold
+        walks = walks + [[v] for v in torch.nonzero(free & long_enough).squeeze(1).tolist() if v % 2 == 0]
     return walks, scores, g
 
 
 def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, nb_paths=100, similarity="auto", device=None, scores=None,
                       sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, parser="host", reads_parser="host",
-                      long_overlaps=False, early_stopping=False, p_threshold=0.06, random_walks=False, seed=None, simplify=None):
+                      long_overlaps=False, early_stopping=False, p_threshold=0.06, random_walks=False, seed=None, simplify=None,
+                      isolated=False):
     """GFA -> scores -> greedy walks -> contigs spelled on the device -> FASTA at out_path (inference.py:411-489).
     -> (walks, contigs, stats); stats = quick_evaluation's figures as a dict (ref_length from the caller: NG50 and the
     reconstructed fraction are -1 without it).  Sequences: the GFA's S lines if it carries them, else `reads` (a FASTA / FASTQ
@@ -95,7 +106,7 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
     uploaded.  The prefixes are masked as pipeline.assemble masks them (inference.py:461).  parser="device" / "auto": the GFA is read
     once, by gfa.read_gfa_device, and its sequences are the packed reads that parse left on the device, restricted to the touched ones.
     reads_parser: how a `reads` file is read (ReadStore.from_reads_file's parser=).  long_overlaps, early_stopping, p_threshold,
-    random_walks, seed, simplify: as in assemble; where the sequences come from the GFA file's S lines (parser="host") or from a
+    random_walks, seed, simplify, isolated: as in assemble; where the sequences come from the GFA file's S lines (parser="host") or from a
     ReadStore the reads keep their numbers (compact=False)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     gfa_path = None if isinstance(gfa_or_graph, dict) else gfa_or_graph
@@ -123,7 +134,8 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
     g = gfa_or_graph if isinstance(gfa_or_graph, dict) else gfa.read_gfa(gfa_or_graph, similarity=similarity, long_overlaps=long_overlaps)
     g = _simplified(g, simplify, device, renumber=source not in ("store", "gfa"))
     walks, scores, g = assemble(g, model, len_threshold, nb_paths=nb_paths, similarity=similarity, device=device, scores=scores,
-                                sampler=sampler, early_stopping=early_stopping, p_threshold=p_threshold, random_walks=random_walks, seed=seed)
+                                sampler=sampler, early_stopping=early_stopping, p_threshold=p_threshold, random_walks=random_walks, seed=seed,
+                                isolated=isolated)
     touched = sorted({v >> 1 for w in walks for v in w})
     if source == "store":
         store = reads
@@ -150,14 +162,20 @@ def assemble_to_fasta(gfa_or_graph, model, out_path, len_threshold, reads=None, 
 
 
 def assemble_reads_to_fasta(reads_path, model, out_path, len_threshold, nb_paths=100, device=None, scores=None, use_labels=False,
-                            sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, long_overlaps=False, **overlap_kw):
+                            sampler=None, line_width=contigs_mod.FASTA_WRAP, ref_length=None, long_overlaps=False, unitigs=False, **overlap_kw):
     """Reads -> overlap graph -> scores -> greedy walks -> contigs -> FASTA at out_path, with no assembler's GFA in between:
     reads.read_reads_device (every record of the FASTA / FASTQ file, in file order; a repeated id keeps its last record) ->
     overlapper.overlap_graph (overlap_kw: its k, w, max_occ, band, min_seeds, min_overlap, max_hang, max_pairs, drop_contained, simplify;
     with simplify's compact the names follow the dict's kept_reads) ->
     assemble_to_fasta on that dict.  -> (walks, contigs, stats, graph dict).  scores: one logit per edge instead of the model.
     use_labels: the titles carry strand=, start=, end= and chr= (the simulator's), the dict gets the four read_* columns and y, and the
-    labels are the scores (+20 / -20 as logits: the reference's use_labels, whose floor is 1e-9)."""
+    labels are the scores (+20 / -20 as logits: the reference's use_labels, whose floor is 1e-9).
+    unitigs: True, or a dict of unitigs.compact_unitigs' keywords - the graph (named and, with use_labels, labelled as a read graph
+    first) is compacted, and the decoder walks the unitig graph with the unitig sequences as the read store; `scores`, if given, are per
+    edge of the unitig graph; unitigs that no walk reaches become contigs of their own (assemble's isolated=True).  The returned dict is
+    the unitig graph."""
+    if unitigs is not False and unitigs is not True and not isinstance(unitigs, dict):
+        raise ValueError(f"unitigs={unitigs!r}: expected False, True or a dict of compact_unitigs' keywords")
     from . import overlapper
     from .reads import read_reads_device
     device = device or torch.device("cuda", torch.cuda.current_device())
@@ -175,9 +193,13 @@ def assemble_reads_to_fasta(reads_path, model, out_path, len_threshold, nb_paths
     g["node_to_read"] = {2 * i + s: names[r] for i, r in enumerate(kept) for s in (0, 1)}
     if use_labels:
         g["y"] = labels.process_graph(g, device=device)[1]
+    if unitigs is not False:
+        from .unitigs import compact_unitigs
+        g = compact_unitigs(g, device=device, **(unitigs if isinstance(unitigs, dict) else {}))
+    if use_labels:
         scores = (g["y"] * 2 - 1) * 20
     walks, contigs, stats = assemble_to_fasta(g, model, out_path, len_threshold, nb_paths=nb_paths, device=device, scores=scores,
-                                              sampler=sampler, line_width=line_width, ref_length=ref_length)
+                                              sampler=sampler, line_width=line_width, ref_length=ref_length, isolated=unitigs is not False)
     return walks, contigs, stats, g
 
 

@@ -10,7 +10,7 @@ the mate (v ^ 1, u ^ 1) - as overlapper.overlap_graph, gfa.read_gfa / read_gfa_d
 prefix_length are read (simplify_graph gathers the other columns).  The rules are stated in include/gnnome_hip.h and, executable, in
 tests/graph_simplify_statement.py; the kernels are csrc/graph_simplify.hip.  torch does the plumbing: the sort of the edges by
 (src, dst) and the row pointer for the mark kernel; degrees, the unique successor and the in-edge lists of the kept edges for the tip
-kernels; the gathers and the renumbering.  Not here: bubbles, unitig compaction, a GFA writer."""
+kernels; the gathers and the renumbering.  Unitig compaction and the GFA writer are unitigs.py; not here: bubbles."""
 import ctypes
 
 import torch

@@ -1487,6 +1487,46 @@ int gnnome_tip_nodes(const int32_t* in_deg, const int32_t* out_deg, const int32_
                      const int64_t* in_ptr, const int32_t* in_src, int64_t num_nodes, int max_tip, uint8_t* tip, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- Unitig compaction: links, chains and their ranking -----------------------------------------------------------------------------
+ * As tests/unitig_statement.py states it, on a graph that follows the complement convention, whose edge multiset is closed under
+ * mates and whose prefixes are p(e) = read_length[src] - overlap_length (the caller checks all three before any launch).
+ *
+ * The rule.  Degrees count parallel edges.  Edge (u, v) is a link iff out_deg(u) == 1, in_deg(v) == 1 and u >> 1 != v >> 1; the last
+ * clause keeps self-loops and hairpins u -> u ^ 1 out, and an edge is a link iff its mate is.  A chain is a maximal path over links;
+ * every node is in exactly one chain, a node without links is a chain of one, and under mate closure no chain holds both v and v ^ 1,
+ * so the complement of a chain (reversed, every node ^ 1) is another chain.  A component all of whose edges are links has no head:
+ * with r its smallest read, the cycle that holds node 2r starts at 2r and the cycle that holds 2r + 1 ends at 2r + 1; the link that
+ * enters the start is the cut link and is not internal.  Of a chain and its complement the forward one has the smaller head; the
+ * pairs are numbered q = 0, 1, .. by ascending forward head, unitig node 2q is the forward chain and 2q + 1 its complement.  A node's
+ * rank is its 0-based place in its chain, its offset the summed p of the links before it, a chain's length offset[tail] +
+ * read_length[tail] (equal for 2q and 2q + 1 by the prefix identity).  Every edge that is not internal runs from a chain's tail to a
+ * chain's head and becomes the edge (unitig[u], unitig[v]) of the unitig graph, a cut link thereby a self-edge; compaction of that
+ * graph changes nothing.
+ *
+ * gnnome_unitig_links: src, dst, prefix int64[E]; out_deg, in_deg int32[N].  link uint8[E] = the link flag of every edge; succ, pred
+ *   int32[N] (-1: none), weight int32[N] (the p of the node's out-link) and succ_edge int32[N] (its edge id) are initialised here
+ *   and written by the links - one writer per slot.  Node ids outside [0, N) make no link.  No synchronisation.
+ * gnnome_unitig_rank: list ranking by pointer jumping over those tables, N even.  head int32[N], rank int32[N], offset int64[N] per
+ *   node; cyc uint8[N] = 1 for the nodes of cycles; succ, pred and link are UPDATED where a cycle is cut.  No atomics, integers
+ *   only, double-buffered 16-byte records (ancestor, hops, bases): every byte is the same on every call and for every `grid` (the
+ *   workgroups per launch; 0: by size).  One jump per node and launch, so a chain of n nodes takes ceil(log2 n) launches; after each
+ *   the number of unfinished nodes is read back (the entry SYNCHRONISES `stream`; not capturable).  When that number stops falling
+ *   the rest are cycles: their smallest reads are found by the same doubling until the jump distance reaches the number of leftover
+ *   nodes, the cycles are cut and the leftover ranked.  rounds_host int64[4] (or NULL): jump launches on the paths, minimum launches,
+ *   jump launches after the cut, nodes on cycles - a graph without cycles reports 0 for the last three and launches nothing for them.
+ *   Every index read from a table is range-checked before use.  workspace: gnnome_unitig_rank_workspace_bytes.
+ * gnnome_unitig_scatter: chain_nodes[chain_off[unitig[v]] + rank[v]] = v for every node v (unitig, rank int32[N], chain_off
+ *   int64[U + 1], chain_nodes int32[N], preset to -1); an index outside its table is skipped.  No synchronisation. */
+int gnnome_unitig_links(const int64_t* src, const int64_t* dst, const int64_t* prefix, const int32_t* out_deg, const int32_t* in_deg,
+                        int64_t num_nodes, int64_t num_edges, int32_t* succ, int32_t* pred, int32_t* weight, int32_t* succ_edge,
+                        uint8_t* link, void* stream);
+int gnnome_unitig_rank_workspace_bytes(int64_t num_nodes, size_t* bytes_host);
+int gnnome_unitig_rank(int32_t* succ, int32_t* pred, const int32_t* weight, const int32_t* succ_edge, int64_t num_nodes,
+                       int64_t num_edges, uint8_t* link, uint8_t* cyc, int32_t* head, int32_t* rank, int64_t* offset, int grid,
+                       int64_t* rounds_host, void* workspace, size_t workspace_bytes, void* stream);
+int gnnome_unitig_scatter(const int32_t* unitig, const int32_t* rank, const int64_t* chain_off, int64_t num_nodes, int64_t num_unitigs,
+                          int32_t* chain_nodes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,10 @@ stage (the median over the repeats): for the sketch the count stage (count launc
 write launch's bytes per second is the one figure that is a single kernel's; for find_overlaps the record kernel and the chain kernel
 as records per second, and torch's sorts beside them; for simplify.simplify_graph on the graph of these overlaps the edge and node
 counts before and after and its stages (mates check, the sort and the mark kernel of the transitive rule, the lists and the two launches
-of the tips, the compaction).  The only baseline is the NumPy / Python statement
+of the tips, the compaction); for unitigs.compact_unitigs on the simplified graph its stages (checks and degrees, the link kernel, the
+ranking with its round count, the numbering, the scatter kernel, the edge gathers, the spelling, the host name tables) and, beside the
+ranking, the same pointer jumping written as torch gathers (torch_pointer_jumping below: one record per node, one jump per round, the
+same count read back per round), whose ranks must equal the kernel's.  The only baseline is the NumPy / Python statement
 (tests/overlap_graph_statement.py) on the first --statement-reads reads of the same input, a host wall time labelled as such.
 Prints one JSON line."""
 import argparse
@@ -57,6 +60,27 @@ def timed(fn, repeats):
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
     return statistics.median(times), min(times), max(times), out
+
+
+def torch_pointer_jumping(pred, weight):
+    """The ranking of csrc/unitigs.hip as torch gathers, for comparison: pred int64[N] (-1: a head), weight int64[N] (the p of a node's
+    out-link) -> (head, rank, offset, rounds).  Paths only: a cycle leaves unfinished nodes and raises."""
+    node = torch.arange(pred.numel(), device=pred.device)
+    has = pred >= 0
+    anc = torch.where(has, pred, node)
+    hops = has.long()
+    bases = torch.where(has, weight[anc], torch.zeros_like(weight))
+    done = pred[anc] < 0
+    left, rounds = int((~done).sum()), 0
+    while left:
+        hops = torch.where(done, hops, hops + hops[anc])
+        bases = torch.where(done, bases, bases + bases[anc])
+        anc = torch.where(done, anc, anc[anc])
+        done = pred[anc] < 0
+        before, left, rounds = left, int((~done).sum()), rounds + 1
+        if left >= before:
+            raise SystemExit("torch_pointer_jumping: the count of unfinished nodes stopped falling: the graph has a cycle")
+    return anc, hops, bases, rounds
 
 
 def main():
@@ -116,7 +140,28 @@ def main():
                simplified_edges=int(sg["src"].numel()), simplified_nodes=int(sg["num_nodes"]), simplify_removed=sg["removed"],
                simplified_max_out_degree=int(torch.bincount(sg["src"]).max()) if sg["src"].numel() else 0,
                simplify_stage_ms=stage(sg_stats), simplify_call_s=sg_t, simplify_call_s_min_max=[sg_lo, sg_hi])
-    del g, sg
+    # unitigs.compact_unitigs on the simplified graph, and the ranking once more as torch gathers
+    from gnnome_amd import unitigs
+    ug_t, ug_lo, ug_hi, ug = timed(lambda: unitigs.compact_unitigs(sg), a.repeats)
+    ug_stats = []
+    for _ in range(a.repeats):
+        ug_stats.append({})
+        unitigs.compact_unitigs(sg, stats=ug_stats[-1])
+    src, dst, p, N = sg["src"], sg["dst"], sg["prefix_length"], sg["num_nodes"]
+    link = (torch.bincount(src, minlength=N)[src] == 1) & (torch.bincount(dst, minlength=N)[dst] == 1) & ((src >> 1) != (dst >> 1))
+    pred, weight = torch.full((N,), -1, dtype=torch.int64, device=dev), torch.zeros(N, dtype=torch.int64, device=dev)
+    pred[dst[link]] = src[link]
+    weight[src[link]] = p[link]
+    tj_t, tj_lo, tj_hi, (_, tj_rank, tj_offset, tj_rounds) = timed(lambda: torch_pointer_jumping(pred, weight), a.repeats)
+    chains = unitigs.unitig_chains(sg)
+    sizes = chains["chain_off"][1:] - chains["chain_off"][:-1]
+    out.update(unitig_nodes=int(ug["num_nodes"]), unitig_edges=int(ug["src"].numel()), unitig_links=int(chains["link"].sum()),
+               unitig_longest_chain=int(sizes.max()) if sizes.numel() else 0, unitig_circular=int(ug["circular"].sum()),
+               unitig_rank_rounds=ug_stats[0]["rank_rounds"], unitig_stage_ms=stage(ug_stats), unitig_call_s=ug_t,
+               unitig_call_s_min_max=[ug_lo, ug_hi], torch_rank_wall_ms=tj_t * 1e3, torch_rank_wall_ms_min_max=[tj_lo * 1e3, tj_hi * 1e3],
+               torch_rank_rounds=tj_rounds,
+               torch_rank_matches=bool(torch.equal(tj_rank.int(), chains["rank"]) and torch.equal(tj_offset, chains["offset"])))
+    del g, sg, ug
     if a.statement_reads:
         import overlap_graph_statement as st
         n = min(a.statement_reads, a.reads)
