@@ -186,6 +186,10 @@ SIGNATURES = {
     "gnnome_unitig_rank_workspace_bytes": [_l, ctypes.POINTER(_sz)],
     "gnnome_unitig_rank": [_p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _i, _p, _p, _sz, _p],
     "gnnome_unitig_scatter": [_p, _p, _p, _l, _l, _p, _p],
+    "gnnome_bubble_tile_size": [ctypes.POINTER(_i)],
+    "gnnome_bubble_arms": [_p, _p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _i, _p],
+    "gnnome_bubble_judge": [_p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _p, _i, _p],
+    "gnnome_bubble_mark": [_p, _p, _l, _l, _p, _i, _p],
 }
 
 ABI_VERSION = 32

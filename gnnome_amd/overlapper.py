@@ -9,7 +9,8 @@ hash, minimizer rule, pair records, bands, classification, every output order - 
 tests/overlap_graph_statement.py; the kernels are csrc/overlap_graph.hip.  torch does the plumbing between them: the
 stable sort of the seeds by hash, the sort of the pair records, the starts of the (a, b, rel) groups, the compaction of the kept overlaps
 and gfa.assemble_edges.  The graph is the raw dovetail graph unless overlap_graph(simplify=) hands it to simplify.simplify_graph
-(transitive edges, tips, the reads left without an edge) and overlap_graph(unitigs=) to unitigs.compact_unitigs; no bubble removal; a read set
+(transitive edges, tips, with bubbles= the simple bubbles, the reads left without an edge) and overlap_graph(unitigs=) to
+unitigs.compact_unitigs; a read set
 whose seed pairs do not fit the device at once is refused (ValueError naming max_occ and max_pairs), not processed in blocks."""
 import ctypes
 
@@ -227,7 +228,7 @@ def overlap_graph(reads, sk=None, k=19, w=10, max_occ=64, band=500, min_seeds=3,
     gfa.assemble_edges.  similarity: overlap.overlap_similarity on every edge (long_overlaps is handed to it).  drop_contained: contained
     reads keep their node numbers and lose their edges.  annotations: (read_strand, read_start, read_end, read_chr), int64[2R] as
     reads.node_annotations_device gives them - the dict then carries them and labels.process_graph(g) works on it.  simplify: True, or a
-    dict of simplify.simplify_graph's keywords (fuzz, max_tip, tips, compact, check_mates, stats) - the graph is handed through it before
+    dict of simplify.simplify_graph's keywords (fuzz, max_tip, tips, bubbles, compact, check_mates, stats) - the graph is handed through it before
     it is returned (transitive edges and tips dropped; with compact the reads left without an edge removed, `kept_reads` naming the
     others); None, the default, returns the raw dovetail graph.  unitigs: True, or a dict of unitigs.compact_unitigs' keywords (stats) -
     after `simplify`, the graph's non-branching paths are merged and the unitig graph is returned in its place (its `reads` are the

@@ -4,13 +4,15 @@ decodes on them.
     mark = transitive_edges(g, fuzz=10)                  # bool[E]: the edges a two-hop path explains
     tip = tip_nodes(g, keep=~mark, max_tip=4)            # bool[N]: short dead ends at a junction, and their complements
     s = simplify_graph(g)                                # both, the edges dropped, the reads left without an edge removed and renumbered
+    s = simplify_graph(g, bubbles=True)                  # and the simple bubbles of what is kept popped (bubbles.py), off by default
 
 `g`: any graph dict of this package that follows the complement convention - node v ^ 1 is the reverse complement of v, edge (u, v) has
 the mate (v ^ 1, u ^ 1) - as overlapper.overlap_graph, gfa.read_gfa / read_gfa_device, synth and decode do; src, dst, num_nodes,
 prefix_length are read (simplify_graph gathers the other columns).  The rules are stated in include/gnnome_hip.h and, executable, in
 tests/graph_simplify_statement.py; the kernels are csrc/graph_simplify.hip.  torch does the plumbing: the sort of the edges by
 (src, dst) and the row pointer for the mark kernel; degrees, the unique successor and the in-edge lists of the kept edges for the tip
-kernels; the gathers and the renumbering.  Unitig compaction and the GFA writer are unitigs.py; not here: bubbles."""
+kernels; the gathers and the renumbering.  Unitig compaction and the GFA writer are unitigs.py; simple bubbles are bubbles.py, which
+simplify_graph(bubbles=) runs after the tips."""
 import ctypes
 
 import torch
@@ -153,32 +155,10 @@ def _renumber_table(table, new_node):
     return out
 
 
-def simplify_graph(g, fuzz=10, max_tip=4, tips=True, compact=True, check_mates=True, device=None, stats=None):
-    """-> a new graph dict: the transitive edges (transitive_edges(g, fuzz)) and, with tips=True, the tip nodes of what is kept
-    (tip_nodes(g, ~mark, max_tip)) are found, and every marked edge and every edge at a tip node is dropped; the edges keep their
-    relative order.  compact=True also removes the reads both of whose nodes are left without an edge (contained reads, clipped tips,
-    reads that never overlapped) and renumbers the others 2r', 2r' + 1 in the old order; compact=False keeps num_nodes.  Gathered
-    where present: src, dst, overlap_length, prefix_length, overlap_similarity, y per edge; read_length and every other tensor-valued
-    read_* column per node; contained per read; reads = the packed (data, off); the name tables (node_to_read, read_to_node,
-    read_to_node2, read_seqs).  Any other key is carried over as it is.  New keys: kept_reads int64[R'] (the old read of each new
-    one), edge_origin int64[E'] (the old edge of each new one), removed = {"transitive_edges", "tip_nodes", "reads"} (counts).
-    check_mates: ValueError when the input's edges, or the kept ones, are not closed under mates.  stats: a dict that receives the
-    device-event times mates_ms, transitive_sort_ms, transitive_mark_ms, tip_lists_ms, tip_mark_ms, compact_ms."""
-    src, dst, p, N, dev = _graph(g, device)
+def _kept_graph(g, src, dst, N, keep, removed, compact, check_mates, dev):
+    """The tail simplify_graph and bubbles.pop_bubbles share: the edges of `keep` (bool[E]) in their old order, with compact the reads
+    left without an edge removed and the others renumbered, every column of `g` gathered -> the new dict; `removed` gains "reads"."""
     E, R = int(src.numel()), N // 2
-    stages = _Stages(stats, dev)
-    if check_mates:
-        if not mates_closed(src, dst, N):
-            raise ValueError("the edge set is not closed under mates: some edge (u, v) lacks (v ^ 1, u ^ 1)")
-        stages.mark("mates")
-    mark = _transitive(src, dst, p, N, fuzz, stages)
-    if tips:
-        tip = _tips(src, dst, p, N, ~mark, max_tip, stages)
-    else:
-        if int(max_tip) != max_tip or max_tip < 1:
-            raise ValueError(f"max_tip={max_tip}: an int >= 1")
-        tip = torch.zeros(N, dtype=torch.bool, device=dev)
-    keep = ~mark & ~tip[src] & ~tip[dst]
     origin = torch.nonzero(keep).squeeze(1)
     src, dst = src[origin], dst[origin]
     if check_mates and not mates_closed(src, dst, N):
@@ -195,8 +175,7 @@ def simplify_graph(g, fuzz=10, max_tip=4, tips=True, compact=True, check_mates=T
     nodes = torch.stack([2 * reads, 2 * reads + 1], 1).reshape(-1)
     out = dict(g)
     out.update(src=2 * new_read[src >> 1] + (src & 1), dst=2 * new_read[dst >> 1] + (dst & 1), num_nodes=2 * int(reads.numel()),
-               kept_reads=reads, edge_origin=origin,
-               removed={"transitive_edges": int(mark.sum()), "tip_nodes": int(tip.sum()), "reads": R - int(reads.numel())})
+               kept_reads=reads, edge_origin=origin, removed=dict(removed, reads=R - int(reads.numel())))
 
     def gather(value, index, count):
         t = torch.as_tensor(value)
@@ -224,6 +203,57 @@ def simplify_graph(g, fuzz=10, max_tip=4, tips=True, compact=True, check_mates=T
         for f in ("node_to_read", "read_to_node", "read_to_node2", "read_seqs"):
             if isinstance(g.get(f), dict):
                 out[f] = _renumber_table(g[f], new_node)
+    return out
+
+
+def simplify_graph(g, fuzz=10, max_tip=4, tips=True, compact=True, check_mates=True, device=None, stats=None, bubbles=None):
+    """-> a new graph dict: the transitive edges (transitive_edges(g, fuzz)) and, with tips=True, the tip nodes of what is kept
+    (tip_nodes(g, ~mark, max_tip)) are found, and every marked edge and every edge at a tip node is dropped; the edges keep their
+    relative order.  compact=True also removes the reads both of whose nodes are left without an edge (contained reads, clipped tips,
+    reads that never overlapped) and renumbers the others 2r', 2r' + 1 in the old order; compact=False keeps num_nodes.  Gathered
+    where present: src, dst, overlap_length, prefix_length, overlap_similarity, y per edge; read_length and every other tensor-valued
+    read_* column per node; contained per read; reads = the packed (data, off); the name tables (node_to_read, read_to_node,
+    read_to_node2, read_seqs).  Any other key is carried over as it is.  New keys: kept_reads int64[R'] (the old read of each new
+    one), edge_origin int64[E'] (the old edge of each new one), removed = {"transitive_edges", "tip_nodes", "reads"} (counts).
+    check_mates: ValueError when the input's edges, or the kept ones, are not closed under mates.  bubbles: True, or a dict of
+    bubbles.bubble_nodes' keywords (weight, max_dist, max_diff, grid) and `rounds` - after the tips the simple bubbles of what is kept
+    are popped (bubbles.pop_bubbles' rounds; the dict then needs overlap_length and read_length), before the one compaction, and
+    `removed` gains "bubble_nodes" and "bubble_rounds"; None, the default, changes nothing.  stats: a dict that receives the
+    device-event times mates_ms, transitive_sort_ms, transitive_mark_ms, tip_lists_ms, tip_mark_ms, compact_ms, and with bubbles
+    pop_bubbles' entries."""
+    if bubbles is not None and bubbles is not True and not isinstance(bubbles, dict):
+        raise ValueError(f"bubbles={bubbles!r}: expected None, True or a dict of bubble_nodes' keywords and rounds")
+    src, dst, p, N, dev = _graph(g, device)
+    if bubbles is None:
+        stages = _Stages(stats, dev)
+    else:
+        from . import bubbles as bubbles_mod
+        from .unitigs import _columns
+        kw = {"rounds": 4, "weight": None, "max_dist": 50000, "max_diff": 1000, "grid": 0}
+        given = bubbles if isinstance(bubbles, dict) else {}
+        if set(given) - set(kw):
+            raise ValueError(f"bubbles: unknown keywords {sorted(set(given) - set(kw))}; expected some of {sorted(kw)}")
+        kw.update(given)
+        ol, rl = _columns(g, dev)[3:5]
+        stages = bubbles_mod._SummedStages(stats, dev)
+    if check_mates:
+        if not mates_closed(src, dst, N):
+            raise ValueError("the edge set is not closed under mates: some edge (u, v) lacks (v ^ 1, u ^ 1)")
+        stages.mark("mates")
+    mark = _transitive(src, dst, p, N, fuzz, stages)
+    if tips:
+        tip = _tips(src, dst, p, N, ~mark, max_tip, stages)
+    else:
+        if int(max_tip) != max_tip or max_tip < 1:
+            raise ValueError(f"max_tip={max_tip}: an int >= 1")
+        tip = torch.zeros(N, dtype=torch.bool, device=dev)
+    keep = ~mark & ~tip[src] & ~tip[dst]
+    removed = {"transitive_edges": int(mark.sum()), "tip_nodes": int(tip.sum())}
+    if bubbles is not None:
+        popped, rounds, keep = bubbles_mod._pop(src, dst, p, ol, rl, N, keep, kw["rounds"], kw["weight"], kw["max_dist"], kw["max_diff"],
+                                                stages, kw["grid"])
+        removed.update(bubble_nodes=int(popped.sum()), bubble_rounds=rounds)
+    out = _kept_graph(g, src, dst, N, keep, removed, compact, check_mates, dev)
     stages.mark("compact")
     stages.finish()
     return out

@@ -11,7 +11,7 @@ anything else is a ValueError before a kernel is launched.  The rule is stated i
 tests/unitig_statement.py; the kernels are csrc/unitigs.hip: the link decision with the successor, predecessor and link-weight tables,
 the list ranking (pointer jumping over 16-byte records, O(log n) launches for a chain of n nodes) and the scatter of the chain members.
 torch does the plumbing: degrees, the mates check, the numbering of the chains (a scan over the heads), the gathers.  The sequences are
-spelled by contigs.spell_contigs with the chains as walks.  Not here: bubbles."""
+spelled by contigs.spell_contigs with the chains as walks.  Simple bubbles are popped by bubbles.py, on these chains."""
 import ctypes
 
 import torch

@@ -1527,6 +1527,48 @@ int gnnome_unitig_rank(int32_t* succ, int32_t* pred, const int32_t* weight, cons
 int gnnome_unitig_scatter(const int32_t* unitig, const int32_t* rank, const int64_t* chain_off, int64_t num_nodes, int64_t num_unitigs,
                           int32_t* chain_nodes, void* stream);
 
+/* ---- Simple bubbles: arms, their judgement and the node mark ------------------------------------------------------------------------
+ * As tests/bubble_statement.py states it, on the kept edges of a graph that follows the complement convention, closed under mates and
+ * with p(e) = read_length[src] - overlap_length (the caller checks all three before any launch); degrees count parallel edges.
+ *
+ * The rule.  An arm is a chain a_1 .. a_k (k >= 1) of the unitig ranking on the kept edges that is not circular, whose head has
+ * in-degree 1 and whose tail has out-degree 1 (every node of it then has both), whose one in-edge comes from a node s of out-degree
+ * >= 2 and whose one out-edge goes to a node t of in-degree >= 2, with t != s and t != s ^ 1.  s -> a_1 and a_k -> t are no links,
+ * so an arm is one whole chain; a direct edge s -> t is no arm (the transitive rule's case), and parallel edges s -> a_1 make a_1 a
+ * join.  Three integers, equal for an arm and for its mate arm a_k ^ 1 .. a_1 ^ 1 from t ^ 1 to s ^ 1: weight = the sum of a
+ * caller's weight[a_i] (weight[v] == weight[v ^ 1]); overlap = the sum of overlap_length over the arm's k + 1 edges; dist = the sum
+ * of read_length[a_i] - overlap, the bases between the end of s and the start of t (it may be negative; the summed p would differ
+ * between an arm and its mate by len(s) - len(t)).  A bubble is the arms that share (s, t), when there are at least two; its winner
+ * has the largest (weight, overlap, -min(a_1, a_k ^ 1)), a triple that is equal for an arm and its mate and differs between two
+ * arms of one bubble.  Another arm of the bubble is a loser iff dist(winner) <= max_dist, dist(arm) <= max_dist and
+ * |dist(arm) - dist(winner)| <= max_diff (absolute numbers of bases).  The nodes of every loser and their complements are marked;
+ * all bubbles are judged on the input at once: s and t are no arm nodes, arms are disjoint, and an arm whose complement lay in an arm
+ * of the same bubble would need t == s ^ 1, so the mark is the same on both strands, the kept edges stay closed under mates and s
+ * still reaches t.  Bubbles with a direct-edge arm, bubbles whose arms branch and t == s ^ 1 are left alone.
+ *
+ * gnnome_bubble_arms: src, dst, overlap int64[E] (the kept edges); in_deg, out_deg int32[N]; chain_off int64[U + 1], chain_nodes
+ *   int32[N], circular uint8[U], length int64[U] as the unitig entries and their caller give them; cum_weight, cum_length int64[N + 1]:
+ *   the exclusive prefix sums of weight and read_length in chain_nodes' order.  in_edge, out_edge int32[N] are set here: the id of a
+ *   node's one in-edge / out-edge where that degree is 1, else -1.  arms: U records of 40 bytes {int32 s, t, key, nodes; int64 weight,
+ *   overlap, dist}, s = -1 where the chain is no arm.  Two launches, one lane per edge, then one per chain; no lane walks a chain.
+ * gnnome_bubble_judge: row_ptr int64[N + 1] / dst int32[E]: the kept edges sorted by (src, dst), as for gnnome_transitive_edges;
+ *   unitig, rank int32[N]; loser uint8[U], zeroed here, = 1 for every losing arm's chain.  One wavefront per source of out-degree >= 2;
+ *   its row is staged in LDS gnnome_bubble_tile_size entries at a time, a longer row is done tile by tile and in passes of 64 arms.
+ * gnnome_bubble_mark: mark uint8[N], every entry written: loser[unitig[v]] | loser[unitig[v ^ 1]]; N even.
+ * Integers only, no atomics, one writer per slot or every writer storing the same 1: the bytes are the same on every call and for every
+ * `grid` (the workgroups per launch; 0: by size).  Every index read from a table is range-checked before use.  No workspace, no
+ * synchronisation. */
+int gnnome_bubble_tile_size(int* tile_host);
+int gnnome_bubble_arms(const int64_t* src, const int64_t* dst, const int64_t* overlap, const int32_t* in_deg, const int32_t* out_deg,
+                       int64_t num_nodes, int64_t num_edges, const int64_t* chain_off, const int32_t* chain_nodes, const uint8_t* circular,
+                       const int64_t* length, const int64_t* cum_weight, const int64_t* cum_length, int64_t num_unitigs, int32_t* in_edge,
+                       int32_t* out_edge, void* arms, int grid, void* stream);
+int gnnome_bubble_judge(const int64_t* row_ptr, const int32_t* dst, const int32_t* unitig, const int32_t* rank, const void* arms,
+                        int64_t num_nodes, int64_t num_edges, int64_t num_unitigs, int64_t max_dist, int64_t max_diff, uint8_t* loser,
+                        int grid, void* stream);
+int gnnome_bubble_mark(const int32_t* unitig, const uint8_t* loser, int64_t num_nodes, int64_t num_unitigs, uint8_t* mark, int grid,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

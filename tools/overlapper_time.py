@@ -13,7 +13,9 @@ counts before and after and its stages (mates check, the sort and the mark kerne
 of the tips, the compaction); for unitigs.compact_unitigs on the simplified graph its stages (checks and degrees, the link kernel, the
 ranking with its round count, the numbering, the scatter kernel, the edge gathers, the spelling, the host name tables) and, beside the
 ranking, the same pointer jumping written as torch gathers (torch_pointer_jumping below: one record per node, one jump per round, the
-same count read back per round), whose ranks must equal the kernel's.  The only baseline is the NumPy / Python statement
+same count read back per round), whose ranks must equal the kernel's; with --bubbles SITES the reads come from two haplotypes that differ
+at SITES places and bubbles.pop_bubbles on the simplified graph is timed as well (its stages added up over the rounds, the arms, what is
+removed, the share of the ranking in the stage times) - without the flag nothing changes.  The only baseline is the NumPy / Python statement
 (tests/overlap_graph_statement.py) on the first --statement-reads reads of the same input, a host wall time labelled as such.
 Prints one JSON line."""
 import argparse
@@ -38,14 +40,24 @@ for _a, _b in zip(b"ACGT", b"TGCA"):
     _COMP[_a] = _b
 
 
-def make_reads(n, length, coverage, seed):
+def make_reads(n, length, coverage, seed, sites=0, site_length=2000):
+    """sites > 0: a second haplotype that differs from the first in `sites` evenly spaced stretches of site_length random bases - longer
+    than max_hang, so reads of different haplotypes do not dovetail across a site - and a haplotype bit per read, drawn after everything
+    else."""
     rng = np.random.default_rng(seed)
     genome = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, max(n * length // coverage, 2 * length))]
     start = rng.integers(0, len(genome) - length + 1, n)
     flip = rng.integers(0, 2, n).astype(bool)
+    haplotypes, hap = [genome], np.zeros(n, dtype=np.int64)
+    if sites:
+        other = genome.copy()
+        for at in np.linspace(0, len(genome) - site_length, sites + 2)[1:-1].astype(np.int64).tolist():
+            other[at:at + site_length] = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, site_length)]
+        haplotypes.append(other)
+        hap = rng.integers(0, 2, n)
     data = np.empty(n * length, dtype=np.uint8)
     for i, (s, f) in enumerate(zip(start.tolist(), flip.tolist())):
-        piece = genome[s:s + length]
+        piece = haplotypes[hap[i]][s:s + length]
         data[i * length:(i + 1) * length] = _COMP[piece[::-1]] if f else piece
     return torch.from_numpy(data), torch.arange(n + 1, dtype=torch.int64) * length
 
@@ -93,12 +105,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--statement-reads", type=int, default=200)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--bubbles", type=int, default=0, metavar="SITES",
+                    help="read a diploid genome whose haplotypes differ at SITES places and time the bubble stages too (0: off)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("overlapper_time: no GPU - nothing is measured without one")
     from gnnome_amd import overlapper
     dev = torch.device("cuda", 0)
-    data, off = make_reads(a.reads, a.length, a.coverage, a.seed)
+    data, off = make_reads(a.reads, a.length, a.coverage, a.seed, a.bubbles)
     reads = (data.to(dev), off.to(dev))
     nbytes = int(data.numel())
     sk_t, sk_lo, sk_hi, sk = timed(lambda: overlapper.sketch_reads(reads, a.k, a.w), a.repeats)
@@ -161,6 +175,22 @@ def main():
                unitig_call_s_min_max=[ug_lo, ug_hi], torch_rank_wall_ms=tj_t * 1e3, torch_rank_wall_ms_min_max=[tj_lo * 1e3, tj_hi * 1e3],
                torch_rank_rounds=tj_rounds,
                torch_rank_matches=bool(torch.equal(tj_rank.int(), chains["rank"]) and torch.equal(tj_offset, chains["offset"])))
+    if a.bubbles:
+        # bubbles.pop_bubbles on the simplified graph: its stages by device events, added up over the rounds, and the ranking's share
+        from gnnome_amd import bubbles
+        bb_t, bb_lo, bb_hi, bb = timed(lambda: bubbles.pop_bubbles(sg), a.repeats)
+        bb_stats = []
+        for _ in range(a.repeats):
+            bb_stats.append({})
+            bubbles.pop_bubbles(sg, stats=bb_stats[-1])
+        bb_ms = stage(bb_stats)
+        arms = bubbles.bubble_arms(sg)
+        out.update(bubble_sites=a.bubbles, bubble_arms=int(arms["first"].numel()), bubble_longest_arm=int(arms["nodes"].max()) if arms["first"].numel() else 0,
+                   bubble_removed=bb["removed"], bubble_edges_left=int(bb["src"].numel()),
+                   bubble_max_out_degree_left=int(torch.bincount(bb["src"]).max()) if bb["src"].numel() else 0,
+                   bubble_rank_rounds=bb_stats[0]["rank_rounds"], bubble_stage_ms=bb_ms, bubble_call_s=bb_t, bubble_call_s_min_max=[bb_lo, bb_hi],
+                   bubble_ranking_share=sum(v for k, v in bb_ms.items() if k.startswith("unitig_")) / sum(bb_ms.values()))
+        del bb
     del g, sg, ug
     if a.statement_reads:
         import overlap_graph_statement as st
